@@ -21,9 +21,15 @@ collective (weak scaling); the only collectives are the barriers of the timing p
 of the elapsed time.
 
 Timing: W warm-up steps, then blocks of EXACTLY K steps, each block bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  One block is the contract; the
-block is repeated until --min-seconds of timed work have run (so that utilisation sampling from outside
-sees a busy GPU) and the line reports the MEDIAN block (`blocks_ms_per_step` lists the first eight).
+torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  One block is the contract: by
+default the headline runs exactly K timed steps and `ms_per_step` is that block's time / K.  With
+--min-seconds S > 0 the block is repeated until S seconds of timed work have run (so that utilisation
+sampling from outside sees a busy GPU) and the line reports the MEDIAN block (`blocks_ms_per_step` lists the first eight).
+
+--dump-outputs DIR: after the timed steps, what the headline's last step computed (the arrays its caller receives) is
+written as DIR/<name>.npy, float32 / float64, at most DUMP_BYTES in all (a fixed, seeded sample of rows of a larger
+output).  Inputs are generated from fixed seeds and every block starts from the same pristine state, so two builds run
+with the same arguments can be compared output for output.
 
 ONE JSON line is printed by rank 0, kept under ~6 KB so that it survives the driver's tail buffer.  Every BASELINE
 config and SURVEY 8(f) row measured in the same processes with the same protocol is summarised inside
@@ -70,6 +76,8 @@ CONFIG_KEY = {"fft4096": "#2", "rfft2048": "#3", "stft1024": "#4", "c64_2p20": "
 INPLACE_SCALE = 1e-18        # the in-place batch starts at 1e-18 x uniform(-1, 1) ...
 INPLACE_MAX_STEPS = 30       # ... and is restored at the latest after this many forward steps (64^30 x 1e-18 = 1.5e36)
 LINE_BUDGET = 6000           # bytes of the JSON line the driver's tail buffer is known to keep
+DUMP_BYTES = 48 << 20        # --dump-outputs: array data written in all (under 64 MB with the .npy headers)
+DUMP_SEED = 0x6B6F666674     # --dump-outputs: which rows of a larger output are written
 
 
 def parse(argv=None):
@@ -82,8 +90,8 @@ def parse(argv=None):
                          "(measured: per-launch time falls 1.17 -> 0.81 ms over the first ~40 ms of load)")
     ap.add_argument("--workload", default="fft4096", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch (debug only; invalidates the metric)")
-    ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="repeat the K-step block until this much timed work has run (0: exactly one block)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step block until this much timed work has run (default 0: exactly one block, K timed steps)")
     ap.add_argument("--all-workloads", dest="extras", action="store_true", default=None,
                     help="also measure the other BASELINE configs into `workloads` (default at --workload fft4096)")
     ap.add_argument("--no-extra-workloads", dest="extras", action="store_false")
@@ -95,6 +103,9 @@ def parse(argv=None):
     ap.add_argument("--no-multi-ab", action="store_true", help="N > 1: skip rank 0's single-process RCCL-vs-direct gather A/B of config #4")
     ap.add_argument("--detail-file", default=None, help="where the full per-workload objects go (default gpurun_out/bench_detail_n<N>.json)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU work for the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (float32 / float64; "
+                         "a fixed, seeded sample of rows where the output exceeds the dump budget)")
     ap.add_argument("--extras-timeout", type=float, default=None,
                     help="seconds the extra workloads may take before rank 0 prints the headline alone and exits "
                          "(0 = no limit; default 240 at N > 1, where a hanging collective cannot be caught, none at N = 1)")
@@ -106,7 +117,10 @@ def parse(argv=None):
     ap.add_argument("--dry-protocol", action="store_true",
                     help="with --dry-launch: the ranks also rendezvous (gloo, CPU), run the barrier / all-reduce steps of the timing "
                          "protocol, and rank 0 prints ONE line with the real line's keys (values null): the N-rank contract without a GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -407,6 +421,7 @@ class Workload:
         self.allgather = None
         self.block_prep = None  # untimed restore before every block (and at the latest every max_steps_per_restore steps)
         self.max_steps_per_restore = 0
+        self.outputs = {}  # name -> device tensor: what the caller of one step receives (--dump-outputs)
         if name == "fft4096":
             n, batch = 4096, batch_override or 65536
             form = getattr(args, "form", "inplace")
@@ -433,6 +448,7 @@ class Workload:
             self.dtype, self.scaling = "f32", "weak"
             self.kernels_per_step = 1
             self._finite_probe = buf
+            self.outputs = {"fft4096_spectrum": buf}
             src, dst = pristine, buf
         elif name == "rfft2048":
             n, batch = 2048, batch_override or (1 << 20)
@@ -447,6 +463,7 @@ class Workload:
             self.cfg = {"workload": WORKLOADS[name], "n": n, "batch_per_gpu": batch, "sharding": f"batch x{world}, no collective"}
             self.dtype, self.scaling = "f32", "weak"
             self.kernels_per_step = 1
+            self.outputs = {"rfft2048_spectrum": dst}
         elif name == "c64_2p20":
             n, batch = 1 << 20, batch_override or 1024
             src = torch.empty((batch, n, 2), dtype=torch.float64, device=dev).uniform_(-1.0, 1.0, generator=gen)
@@ -460,6 +477,7 @@ class Workload:
                         "passes_over_hbm": 2}
             self.dtype, self.scaling = "f64", "weak"
             self.kernels_per_step = None  # several kernels per step: see roofline.kernels_per_step in the line
+            self.outputs = {"c64_2p20_spectrum": dst}
         elif name in ("istft1024", "magnitudes1024"):
             total_len, win_len, hop = 28_800_000, 1024, 256
             frames = -(-total_len // hop)
@@ -493,6 +511,7 @@ class Workload:
                 self.cfg = {"workload": WORKLOADS[name], "frames": frames, "win_len": win_len, "hop": hop, "out_len": out_len,
                             "kernels": "istft_fused_kernel (inverse transform + overlap-add in one pass) + seam / tail overlap-add, no atomics"}
                 self._keep = (sig, win, spec, work, out, scratch)
+                self.outputs = {"istft1024_signal": out, "istft1024_frames": work}
             else:
                 bins = win_len // 2
                 mags = torch.empty((frames, bins), dtype=torch.float32, device=dev)
@@ -506,6 +525,7 @@ class Workload:
                             "bins_per_frame": bins, "kernels": "one: STFT with the magnitude and the running maximum fused into the store"}
                 self.kernels_per_step = 1
                 self._keep = (sig, mags, mx)
+                self.outputs = {"magnitudes1024_magnitudes": mags, "magnitudes1024_max": mx}
             return
         elif name == "fft2d_4096":
             rows = cols = 4096
@@ -520,10 +540,18 @@ class Workload:
                 fft32.fftnd_dev(img.data_ptr(), 1, rows, cols, state["inv"])
                 state["inv"] = not state["inv"]
             self.launch = launch2d
+            pristine = img.clone()
+
+            def restore2d():  # untimed, before every block: the last step's output does not depend on how many steps ran before
+                img.copy_(pristine)
+                state["inv"] = False
+            self.block_prep = restore2d
+            self.max_steps_per_restore = 1 << 62  # the values stay bounded: no restore inside a block
             self.cfg = {"workload": WORKLOADS[name], "rows": rows, "cols": cols, "direction": "forward / inverse alternating, in place",
                         "passes_over_hbm": "2: rows + the columns' first two stages, then one column-tile pass (DESIGN 5.7)"}
             self.dtype, self.scaling, self.kernels_per_step = "f32", "weak", None
-            self._keep = (img,)
+            self._keep = (img, pristine)
+            self.outputs = {"fft2d_4096_image": img}
             return
         elif name == "bluestein1000":
             n, batch = 1000, batch_override or 65536
@@ -538,6 +566,7 @@ class Workload:
                         "kernels": "one: both 2048-pt transforms and the three pointwise products in registers + LDS"}
             self.dtype, self.scaling, self.kernels_per_step = "f32", "weak", 1
             self._keep = (src, dst)
+            self.outputs = {"bluestein1000_spectrum": dst}
             return
         else:
             total_len, win_len, hop = 28_800_000, 1024, 256
@@ -563,6 +592,7 @@ class Workload:
             self.dtype, self.scaling = "f32", "strong"
             self.kernels_per_step = 1
             self._gather = (frames_total, win_len, count, dst)
+            self.outputs = {"stft1024_spectrogram": dst}
         self._keep = (src, dst) if name != "stft1024" else (sig, win, dst)
 
     def shard_kernel_ms(self, fft32, stream, dev, worlds=(1, 2, 4, 8), reps=200):
@@ -764,6 +794,30 @@ def measure(w: Workload, steps, warmup, ramp_ms, min_seconds, dev, stream, barri
     }
 
 
+def dump_outputs(outputs: dict, out_dir: Path) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy in its own dtype (float32 / float64).  An array larger than its share of
+    DUMP_BYTES is written as the rows (first axis) picked by a generator seeded with DUMP_SEED, in ascending order: the same rows
+    in every run with the same arguments."""
+    import numpy as np
+    import torch
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // len(outputs)
+    for name, t in outputs.items():
+        rows = t.shape[0]
+        row_bytes = t.element_size() * (t[0].numel() if t.dim() > 1 else 1)
+        keep = min(rows, share // row_bytes)
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: one row of {name} ({row_bytes} B) exceeds the dump budget")
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(out_dir / f"{name}.npy", a)
+        print(f"# dump: {out_dir / name}.npy {a.dtype} {list(a.shape)} ({keep} of {rows} rows)", file=sys.stderr, flush=True)
+
+
 def sig(x, digits=5):
     """x rounded to `digits` significant digits (the line is size-limited)."""
     if x is None or isinstance(x, (str, bool)) or x == 0:
@@ -962,6 +1016,8 @@ def run_rank(args) -> None:
     launches: list[int] = []
     w = Workload(args.workload, args, rank, world, dev, stream, fft32, fft64, args.batch)
     head = measure(w, args.steps, args.warmup, args.ramp_ms, args.min_seconds, dev, stream, barrier, reduce_max, reduce_sum, launches)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w.outputs, Path(args.dump_outputs))  # the buffers still hold the last timed step's results
     allgather = w.time_allgather(dist, dev, world, barrier) if (args.workload == "stft1024" and world > 1) else None
     del w
     torch.cuda.empty_cache()

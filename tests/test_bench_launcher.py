@@ -86,3 +86,27 @@ def test_dry_protocol_eight_ranks_one_line_with_every_workload_key():
     assert res1.returncode == 0, res1.stderr[-2000:]
     line1 = json.loads([ln for ln in res1.stdout.splitlines() if ln.startswith("{")][-1])
     assert list(line1["workloads"]) == ["stft1024", "rfft2048", "c64_2p20", "istft1024", "magnitudes1024", "fft2d_4096", "bluestein1000"]
+
+
+def test_dump_outputs_writes_a_seeded_sample_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float arrays as <name>.npy, the whole dump under the budget, and an array larger than its share written as the
+    same ascending rows in every run (two builds are compared output for output)."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    outputs = {"spectrum": torch.arange(4096 * 64 * 2, dtype=torch.float32).reshape(4096, 64, 2),
+               "signal": torch.arange(300_000, dtype=torch.float64), "max": torch.ones(1, dtype=torch.float32)}
+    for run in ("a", "b"):
+        bench.dump_outputs(outputs, tmp_path / run)
+    for name, t in outputs.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == t.numpy().dtype and a.shape[1:] == tuple(t.shape[1:]) and a.tobytes() == b.tobytes(), name
+        rows = a.reshape(a.shape[0], -1)[:, 0] / (a[0].size if a.ndim > 1 else 1)  # each row's index in the full array
+        assert np.all(np.diff(rows) > 0) and np.array_equal(rows, np.round(rows)), name
+        assert a.nbytes <= (1 << 20) // len(outputs), name
+    assert np.load(tmp_path / "a" / "spectrum.npy").shape[0] < 4096 and np.load(tmp_path / "a" / "max.npy").shape == (1,)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < (1 << 20) + 1024

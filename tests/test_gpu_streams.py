@@ -318,3 +318,29 @@ def test_bench_single_rank_line_is_compact_and_complete():
     for v in line.values():  # the driver truncates long strings: keep every one short
         if isinstance(v, str):
             assert len(v) <= 120, v
+
+
+def test_bench_steps_are_the_timed_steps_and_dumps_repeat(tmp_path):
+    """`--steps K` times exactly K steps of the headline (one block by default) and `--dump-outputs DIR` writes what the last of them
+    computed: float32 arrays under 64 MB, the same bytes in two runs with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--ramp-ms", "20",
+                              "--no-extra-workloads", "--no-twin", "--no-cpu-baseline", "--detail-file", str(tmp_path / f"detail_{run}.json"),
+                              "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["blocks"] == 1 and line["ms_per_step"] > 0 and line["values_finite"] is True, line
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["fft4096_spectrum.npy"], files
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64_000_000
+    a, b = np.load(tmp_path / "a" / files[0]), np.load(tmp_path / "b" / files[0])
+    assert a.dtype == np.float32 and a.shape[1:] == (4096, 2) and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert bits_equal(a, b)
