@@ -90,12 +90,14 @@ int kofft_hip_big_probe_info(kofft_hip_ctx *ctx, float *first_us, float *total_u
 /* ---- tables: the planner recipes, on the host --------------------------------
  * kofft_hip_twiddles_*: FftPlanner::get_twiddles(n) (fft.rs:370-408), n/2 complex.
  * kofft_hip_rfft_table_*: build_twiddle_table(m) (rfft.rs:172-183), m complex.
- * kofft_hip_hann_f32: window::hann(len) (window.rs:24-28). */
+ * kofft_hip_hann_f32: window::hann(len) (window.rs:24-28).
+ * kofft_hip_dct2_table_f32: DctPlanner's (cos, sin) of PI * k / (2n), k < n (dct.rs:50-58, 89-92), n pairs. */
 int kofft_hip_twiddles_f32(size_t n, float *out);
 int kofft_hip_twiddles_f64(size_t n, double *out);
 int kofft_hip_rfft_table_f32(size_t m, float *out);
 int kofft_hip_rfft_table_f64(size_t m, double *out);
 int kofft_hip_hann_f32(size_t len, float *out);
+int kofft_hip_dct2_table_f32(size_t n, float *cs);
 
 /* ---- complex FFT --------------------------------------------------------------
  * FftImpl::fft / FftImpl::ifft (fft.rs:467-468; ScalarFftImpl fft.rs:1054-1082,
@@ -167,6 +169,23 @@ int kofft_hip_rfft_f64_dev(kofft_hip_ctx *ctx, const double *d_in, double *d_out
 int kofft_hip_irfft_f64(kofft_hip_ctx *ctx, const double *in, double *out, size_t n, size_t batch);
 int kofft_hip_irfft_f64_dev(kofft_hip_ctx *ctx, const double *d_in, double *d_out, size_t n,
                             size_t batch);
+
+/* ---- DCT-II -------------------------------------------------------------------
+ * DctPlanner::plan_dct2 (dct.rs:16-105), f32 only like the reference, on `batch`
+ * contiguous rows of n reals; out: batch * n reals.  Each row is mirrored into 2n
+ * reals, rfft_direct'ed (rfft.rs:425-465, inner complex length n) and twisted:
+ *   out[k] = 0.5 * (spec[k].re * cos(a_k) + spec[k].im * sin(a_k)),  a_k = PI * k / (2n).
+ * The reference's MismatchedLengths (output length != n, dct.rs:68-70) is the
+ * caller's to check: both lengths are n here.  batch == 0 -> KOFFT_OK; n == 0 ->
+ * EMPTY_INPUT (from the rfft); n beyond the complex transform's range (2^26 for
+ * powers of two, 2^25 otherwise) -> KOFFT_ERR_UNSUPPORTED.  _dev: device pointers,
+ * asynchronous on the context's stream.  Powers of two 32 .. 4096 run one fused kernel
+ * (8-byte aligned input); kofft_hip_set_dct_fused(ctx, 0) sends every length of that
+ * context through the composed route instead (mirror, n-point transform, post-pass:
+ * the same bytes; A/B measurements and tests).  Same results either way. */
+int kofft_hip_dct2_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_dct2_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_set_dct_fused(kofft_hip_ctx *ctx, int on);
 
 /* ---- STFT ---------------------------------------------------------------------
  * stft::stft (stft.rs:76-105): out = frames * win_len complex, contiguous (the

@@ -11,6 +11,7 @@
 //   kofft::batch / batch_inverse / multi_channel fft.rs:2156-2191
 //   kofft::stft / istft / parallel / frame / StftStream  stft.rs:76-156, 232-263, 355-372, 160-206
 //   kofft::hann                                  window.rs:24-28
+//   kofft::HipFftImpl<float>::dct2               DctPlanner::plan_dct2, dct.rs:61-105
 //
 // Result<(), FftError> becomes kofft::Result (is_ok / is_err / unwrap / unwrap_err).  A negative C-ABI status
 // (HIP failure, unsupported length) has no FftError variant: it throws kofft::DeviceError, the C++ analogue of
@@ -22,6 +23,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kofft_hip.h"
@@ -253,6 +255,16 @@ public:
     {
         std::vector<C> scratch(output.size() / 2);
         return irfft_with_scratch(input, output, scratch);
+    }
+    // DctPlanner::plan_dct2 (dct.rs:61-105), f32 only like the reference: `batch` contiguous rows of n reals in and out.
+    // Checks in dct2_with_table's order: MismatchedLengths (dct.rs:68-70), then the rfft's EmptyInput (rfft.rs:434).
+    Result dct2(const std::vector<float> &input, std::vector<float> &output, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "dct2 is f32-only (dct.rs:6)");
+        if (batch == 0 || input.size() % batch != 0 || output.size() != input.size()) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = input.size() / batch;
+        if (n == 0) return Result::Err(FftError::EmptyInput);
+        return st(kofft_hip_dct2_f32(ctx_, input.data(), output.data(), n, batch));
     }
 
     // added: contiguous batch (fft::batch over one buffer)

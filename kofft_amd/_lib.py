@@ -43,6 +43,7 @@ SIGNATURES = {
     "kofft_hip_rfft_table_f32": (C.c_int, [_sz, C.c_void_p]),
     "kofft_hip_rfft_table_f64": (C.c_int, [_sz, C.c_void_p]),
     "kofft_hip_hann_f32": (C.c_int, [_sz, C.c_void_p]),
+    "kofft_hip_dct2_table_f32": (C.c_int, [_sz, C.c_void_p]),
     "kofft_hip_fft_c32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_int]),
     "kofft_hip_fft_c64": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_int]),
     "kofft_hip_fft_c32_dev": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_int]),
@@ -67,6 +68,9 @@ SIGNATURES = {
     "kofft_hip_rfft_f64_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_irfft_f64": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_irfft_f64_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dct2_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dct2_f32_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_dct_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_stft_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_parallel_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_frame_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p]),

@@ -38,6 +38,7 @@ struct kofft_hip_ctx {
     int num_cus = 256;
     bool use_persist = true;  // KOFFT_HIP_NO_PERSIST=1 forces the generic kernels (A/B measurements, tests)
     bool istft_fused = true;  // KOFFT_HIP_ISTFT_FUSED=0: ISTFT always as inverse transforms + the overlap-add kernel
+    bool dct_fused = true;    // kofft_hip_set_dct_fused(ctx, 0): DCT-II of every length through the composed route (mirror, fft_dev, post-pass; A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
@@ -71,7 +72,7 @@ struct kofft_hip_ctx {
     bool use_split = true;     // KOFFT_HIP_SPLIT=0: n = 8192 on the block-synchronised persistent kernel instead of the wave-split one (A/B)
     std::string last_error;
     // planner caches: (kind, n) -> device table.  kind 0/1 = FftPlanner twiddles f32/f64,
-    // 2/3 = RfftPlanner post-pass table f32/f64.
+    // 2/3 = RfftPlanner post-pass table f32/f64, 13 = DctPlanner (cos, sin) table f32.
     std::map<std::pair<int, size_t>, void *> tables;
     // staging for the host-pointer entry points
     void *stage[3] = {nullptr, nullptr, nullptr};
@@ -119,7 +120,7 @@ inline int ilog2(size_t n)
 }
 
 template <typename T> struct Kind;
-template <> struct Kind<float> { static constexpr int tw = 0, rt = 2; };
+template <> struct Kind<float> { static constexpr int tw = 0, rt = 2, dct2 = 13; };  // (4 .. 12: k_stft.hip, complex_impl.hip.h)
 template <> struct Kind<double> { static constexpr int tw = 1, rt = 3; };
 
 template <typename T>
@@ -131,10 +132,14 @@ int get_table(kofft_hip_ctx *ctx, int kind, size_t n, const cpx<T> **out)
         *out = static_cast<const cpx<T> *>(it->second);
         return KOFFT_OK;
     }
-    const bool is_rfft = kind >= 2;
-    const size_t entries = is_rfft ? n : n / 2;
+    const bool is_dct2 = kind == 13;  // Kind<float>::dct2: (cos, sin) of DctPlanner, n pairs
+    const bool is_rfft = kind == 2 || kind == 3;
+    const size_t entries = (is_rfft || is_dct2) ? n : n / 2;
     std::vector<T> host(2 * (entries ? entries : 1));
-    if (is_rfft) {
+    if (is_dct2) {
+        if constexpr (sizeof(T) == 4) kofft_tables::dct2_table_f32(n, (float *)host.data());
+        else return KOFFT_ERR_UNSUPPORTED;  // the reference's DCT is f32-only (dct.rs:6)
+    } else if (is_rfft) {
         if constexpr (sizeof(T) == 4) kofft_tables::rfft_table_f32(n, (float *)host.data());
         else kofft_tables::rfft_table_f64(n, (double *)host.data());
     } else {
@@ -675,6 +680,7 @@ template <typename T>
 int rfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, size_t n, size_t batch);  // k_real_f32/f64.hip
 template <typename T>
 int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch);
+int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

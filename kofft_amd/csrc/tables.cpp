@@ -153,4 +153,17 @@ void hann_f32(size_t len, float *out)
     const float pi = 3.14159265358979323846f;
     for (size_t i = 0; i < len; ++i) out[i] = 0.5f - 0.5f * cosf(2.0f * pi * (float)i / (float)len);
 }
+// DctPlanner::get_cos_table (dct.rs:50-58) and the sine of dct2_with_table (dct.rs:89-92): the angle
+// PI * (k as f32) / (2.0 * (n as f32)), then f32::cos and f32::sin -- two separate libm calls in the reference, so two
+// here (glibc's sincosf returns the same bits as the pair; tests/test_dct_tables.py checks against cosf / sinf).
+void dct2_table_f32(size_t n, float *cs)
+{
+    const float pi = 3.14159265358979323846f;
+    const float den = 2.0f * (float)n;
+    for (size_t k = 0; k < n; ++k) {
+        const float a = (pi * (float)k) / den;
+        cs[2 * k] = cosf(a);
+        cs[2 * k + 1] = sinf(a);
+    }
+}
 }  // namespace kofft_tables
