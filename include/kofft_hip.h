@@ -187,6 +187,24 @@ int kofft_hip_dct2_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n
 int kofft_hip_dct2_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
 int kofft_hip_set_dct_fused(kofft_hip_ctx *ctx, int on);
 
+/* ---- analytic signal ------------------------------------------------------------
+ * hilbert::hilbert_analytic (hilbert.rs:13-47), f32 only like the reference, on `batch`
+ * contiguous rows of n reals; out: batch * n complex (2 * batch * n floats, interleaved),
+ * 8-byte aligned.  Per row: freq = fft((x, +0)); bins 1 .. n/2-1 get re *= 2, im *= 2,
+ * bins n/2+1 .. n-1 become (+0, +0); out = ifft(freq) (conj, fft, conj, * 1/n; n == 1:
+ * (x[0], +0)).  Checks, in this order and before the context is touched: batch == 0 ->
+ * KOFFT_OK; n == 0 -> EMPTY_INPUT; n not a power of two -> NON_POWER_OF_TWO_NO_STD (the
+ * reference rejects it; no Bluestein arm here); n > 2^26 -> KOFFT_ERR_UNSUPPORTED; a null
+ * pointer or context -> KOFFT_ERR_NULL.  _dev: device pointers, asynchronous on the
+ * context's stream; in and out must not overlap (the composed route uses out as its
+ * workspace).  Powers of two 32 .. 4096 run one fused kernel (4-byte aligned input);
+ * kofft_hip_set_hilbert_fused(ctx, 0) sends every length of that context through the
+ * composed route instead (expand, n-point transform, mask, inverse transform: the same
+ * bytes; A/B measurements and tests). */
+int kofft_hip_hilbert_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_hilbert_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_set_hilbert_fused(kofft_hip_ctx *ctx, int on);
+
 /* ---- STFT ---------------------------------------------------------------------
  * stft::stft (stft.rs:76-105): out = frames * win_len complex, contiguous (the
  * reference's &mut [Vec<Complex32>] flattened).  hop == 0 -> INVALID_HOP_SIZE;
