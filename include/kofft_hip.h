@@ -205,6 +205,25 @@ int kofft_hip_hilbert_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_
 int kofft_hip_hilbert_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
 int kofft_hip_set_hilbert_fused(kofft_hip_ctx *ctx, int on);
 
+/* ---- real cepstrum --------------------------------------------------------------
+ * cepstrum::real_cepstrum (cepstrum.rs:12-33), f32 only like the reference, on `batch`
+ * contiguous rows of n reals; out: batch * n reals, the input's bytes.  Per row: freq =
+ * fft((x, +0)); every bin becomes (logf(sqrtf(re * re + im * im) + 1e-12f), +0) with the
+ * libm crate's logf; out = the real parts of ifft(freq) (conj, fft, conj, * 1/n; n == 1:
+ * the early return).  Checks, in this order and before the context is touched: batch == 0
+ * -> KOFFT_OK; n == 0 -> EMPTY_INPUT; n not a power of two -> NON_POWER_OF_TWO_NO_STD (the
+ * reference rejects it; no Bluestein arm here); n > 2^26 -> KOFFT_ERR_UNSUPPORTED; a null
+ * pointer or context -> KOFFT_ERR_NULL.  _dev: device pointers, asynchronous on the
+ * context's stream; in == out is allowed (every route reads a row before it writes it), a
+ * partial overlap is undefined.  Powers of two 32 .. 4096 run one fused kernel (4-byte
+ * aligned input); kofft_hip_set_cepstrum_fused(ctx, 0) sends every length of that context
+ * through the composed route instead (expand, n-point transform, log-magnitude, inverse
+ * transform, real parts, through the context's scratch: the same bytes; A/B measurements
+ * and tests). */
+int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_set_cepstrum_fused(kofft_hip_ctx *ctx, int on);
+
 /* ---- STFT ---------------------------------------------------------------------
  * stft::stft (stft.rs:76-105): out = frames * win_len complex, contiguous (the
  * reference's &mut [Vec<Complex32>] flattened).  hop == 0 -> INVALID_HOP_SIZE;

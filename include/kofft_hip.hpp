@@ -13,6 +13,7 @@
 //   kofft::hann                                  window.rs:24-28
 //   kofft::HipFftImpl<float>::dct2               DctPlanner::plan_dct2, dct.rs:61-105
 //   kofft::HipFftImpl<float>::hilbert_analytic   hilbert::hilbert_analytic, hilbert.rs:13-47
+//   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
 //
 // Result<(), FftError> becomes kofft::Result (is_ok / is_err / unwrap / unwrap_err).  A negative C-ABI status
 // (HIP failure, unsupported length) has no FftError variant: it throws kofft::DeviceError, the C++ analogue of
@@ -278,6 +279,18 @@ public:
         if (n == 0) return Result::Err(FftError::EmptyInput);
         if (n & (n - 1)) return Result::Err(FftError::NonPowerOfTwoNoStd);
         return st(kofft_hip_hilbert_f32(ctx_, input.data(), reinterpret_cast<float *>(output.data()), n, batch));
+    }
+    // cepstrum::real_cepstrum (cepstrum.rs:12-33), f32 only like the reference: `batch` contiguous rows of n reals in, rows of n reals
+    // out.  MismatchedLengths for rows that do not divide the input or an output of another size; then the reference's EmptyInput and
+    // NonPowerOfTwoNoStd (cepstrum.rs:13-18).  input and output may be the same vector.
+    Result real_cepstrum(const std::vector<float> &input, std::vector<float> &output, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "real_cepstrum is f32-only (cepstrum.rs:12)");
+        if (batch == 0 || input.size() % batch != 0 || output.size() != input.size()) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = input.size() / batch;
+        if (n == 0) return Result::Err(FftError::EmptyInput);
+        if (n & (n - 1)) return Result::Err(FftError::NonPowerOfTwoNoStd);
+        return st(kofft_hip_cepstrum_f32(ctx_, input.data(), output.data(), n, batch));
     }
 
     // added: contiguous batch (fft::batch over one buffer)

@@ -74,6 +74,9 @@ SIGNATURES = {
     "kofft_hip_hilbert_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_hilbert_f32_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_hilbert_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_cepstrum_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_cepstrum_f32_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_cepstrum_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_stft_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_parallel_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_frame_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p]),

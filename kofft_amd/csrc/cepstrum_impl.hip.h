@@ -1,0 +1,163 @@
+// cepstrum_impl.hip.h -- cepstrum::real_cepstrum (cepstrum.rs:12-33) on device pointers, f32 only like the reference.
+//
+// For a row of n reals (n a power of two; anything else is the reference's NonPowerOfTwoNoStd) the reference computes
+//   freq = fft((x, +0));  every bin: mag = sqrtf(re * re + im * im), re = logf(mag + 1e-12f), im = +0;  out = ifft(freq).re
+// with ifft = conj (im = -im), fft, conj, * (1 / n) and an early return at n == 1 (fft.rs:1134-1174).  The magnitude is the sum of
+// squares as written (two multiplies and an add, unfused, then a correctly rounded root: not hypotf), and logf is the libm crate's
+// (libm_logf.hip.h).  The pointwise step is the same for every bin, so no bin position enters it.  Two routes, the same operations
+// per element:
+//  * fused (powers of two n = 32 .. 4096): cepstrum_fused_kernel<L>, one pass over HBM.  hilbert_fused_kernel's shape, with its
+//    geometry and forward transform (HilbertGeom, hilbert_forward): rows load as (x, +0) through one buffer descriptor per
+//    workgroup, the forward transform runs, the last pass's registers take log-magnitude + conj, one LDS exchange puts them back
+//    into pass-0 input order, the same forward transform runs again and the store writes re * scale only, 4 bytes per point;
+//  * composed (n <= 16, 8192 .. 2^26, inputs that are not 4-byte aligned, and every n after kofft_hip_set_cepstrum_fused(ctx, 0)):
+//    the output holds only n floats per row, so the context's real scratch is the workspace, in row chunks of 512 MiB at most --
+//    hilbert_expand_kernel writes (x, +0), fft_dev transforms in place, cepstrum_logmag_kernel, fft_dev(inverse) runs the
+//    reference's ifft in place, cepstrum_real_kernel takes the real parts into the output.
+// Both routes read all of a row before they write any of it: in == out is allowed; a partial overlap is undefined.
+#pragma once
+
+#include "hilbert_impl.hip.h"
+#include "libm_logf.hip.h"
+
+namespace kofft {
+namespace host {
+
+// cepstrum.rs:27-29 on one bin: the log-magnitude, as (re, im = +0)
+__device__ __forceinline__ float cepstrum_log_mag(const cpx<float> c)
+{
+    const float mag = sqrtf(c.re * c.re + c.im * c.im);
+    return libm_logf(mag + 1e-12f);  // 1e-12f: 0x2b8cbccc
+}
+
+// ---- composed route ---------------------------------------------------------------------------------------------------------
+// Flat grid-stride grids over the whole chunk, as hilbert_mask_kernel: every bin takes the same operations.
+__global__ __launch_bounds__(256) void cepstrum_logmag_kernel(cpx<float> *__restrict__ z, const size_t total)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) z[i] = mk<float>(cepstrum_log_mag(z[i]), 0.0f);
+}
+
+// cepstrum.rs:32: the real parts
+__global__ __launch_bounds__(256) void cepstrum_real_kernel(const cpx<float> *__restrict__ z, float *__restrict__ out, const size_t total)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) st_stream(out + i, z[i].re);
+}
+
+inline int cepstrum_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    // rows per chunk as dct2_composed_dev: 512 MiB of scratch at most
+    size_t chunk = (size_t(512) << 20) / (n * sizeof(cpx<float>));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    int rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<float>));
+    if (rc) return rc;
+    float *zf = static_cast<float *>(ctx->real_tmp);
+    cpx<float> *z = static_cast<cpx<float> *>(ctx->real_tmp);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk, total = n * nb;
+        const dim3 grid(hilbert_flat_blocks(ctx, total));
+        hipLaunchKernelGGL(hilbert_expand_kernel, grid, dim3(256), 0, ctx->stream, d_in + b0 * n, z, total);  // cepstrum.rs:20-23
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+        if (n > 1) {  // (n == 1: the transform is nothing, fft.rs:1059)
+            rc = fft_dev<float>(ctx, zf, zf, n, nb, 0);  // cepstrum.rs:25
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(cepstrum_logmag_kernel, grid, dim3(256), 0, ctx->stream, z, total);
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+        if (n > 1) {  // (n == 1: ifft returns early, fft.rs:1139)
+            rc = fft_dev<float>(ctx, zf, zf, n, nb, 1);  // cepstrum.rs:31: conj, fft, conj * (1 / n)
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(cepstrum_real_kernel, grid, dim3(256), 0, ctx->stream, z, d_out + b0 * n, total);
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+    }
+    return KOFFT_OK;
+}
+
+// ---- fused route: powers of two n = 2^L, L = 5 .. 12 ------------------------------------------------------------------------
+template <int L>
+__global__ __launch_bounds__(256) void cepstrum_fused_kernel(const float *__restrict__ x, float *__restrict__ out, const cpx<float> *__restrict__ tw,
+                                                             const size_t batch, const float scale)
+{
+    using Geo = HilbertGeom<L>;
+    constexpr int N = Geo::N, R = Geo::R, TPT = Geo::TPT, XPB = Geo::XPB;
+    using G0 = WgGeom<L, Geo::RL, 0>;
+    using GL = WgGeom<L, Geo::RL, Geo::NP - 1>;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x, tau = tid % TPT, slot = tid / TPT;
+    const size_t row0 = (size_t)blockIdx.x * XPB;  // < batch (grid = ceil(batch / XPB))
+    const size_t cnt = batch - row0 < (size_t)XPB ? batch - row0 : (size_t)XPB;
+    // One descriptor over the workgroup's rows, cut at the end of the batch: the rows past it read zeros and store nothing, with no
+    // per-lane test.  Pass 0's register u of thread tau holds sample in_index(0, u) + tau of its row.
+    cpx<float> v[R];
+    {
+        const rsrc_t d = make_rsrc(x + row0 * N, (unsigned)(cnt * N * sizeof(float)));
+        const int lane_bytes = (slot * N + tau) * (int)sizeof(float);
+        float raw[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) raw[u] = buf_load_f32<AUX_NT>(d, lane_bytes, G0::in_index(0, u) * (int)sizeof(float));
+#pragma unroll
+        for (int u = 0; u < R; ++u) v[u] = mk<float>(raw[u], 0.0f);  // cepstrum.rs:21-23
+    }
+    hilbert_forward<L>(v, smem_raw, tw, tau, slot);
+    // every bin: (log-magnitude, +0), then ifft's conj (fft.rs:1163-1165): (l, -0)
+#pragma unroll
+    for (int u = 0; u < R; ++u) v[u] = mk<float>(cepstrum_log_mag(v[u]), -0.0f);
+    {   // last pass's output order -> pass 0's input order, through the row's exchange slot
+        cpx<float> *buf = reinterpret_cast<cpx<float> *>(smem_raw) + (size_t)slot * lds_elems(N);
+        __syncthreads();  // every gather of the transform's last exchange is done
+#pragma unroll
+        for (int u = 0; u < R; ++u) buf[lds_pad(GL::out_index(tau, u))] = v[u];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < R; ++u) v[u] = buf[lds_pad(G0::in_index(tau, u))];
+        __syncthreads();  // (the second transform's first exchange scatters into the same cells)
+    }
+    hilbert_forward<L>(v, smem_raw, tw, tau, slot);
+    // ifft's conj leaves the real part alone; * scale (fft.rs:1168-1172), real part only; bin out_index(0, u) | tau of the row
+    const rsrc_t d = make_rsrc(out + row0 * N, (unsigned)(cnt * N * sizeof(float)));
+    const int lane_bytes = (slot * N + tau) * (int)sizeof(float);
+#pragma unroll
+    for (int u = 0; u < R; ++u) buf_store_f32(v[u].re * scale, d, lane_bytes, GL::out_index(0, u) * (int)sizeof(float));
+}
+
+template <int L>
+int launch_cepstrum_fused(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const cpx<float> *tw, size_t batch)
+{
+    using Geo = HilbertGeom<L>;
+    constexpr size_t lds = Geo::lds_bytes();
+    static_assert(lds <= 64 * 1024, "LDS budget");
+    const size_t blocks = (batch + Geo::XPB - 1) / Geo::XPB;
+    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    const float scale = 1.0f / (float)Geo::N;  // fft.rs:1167
+    hipLaunchKernelGGL(cepstrum_fused_kernel<L>, dim3((unsigned)blocks), dim3(Geo::BLOCK), lds, ctx->stream, d_in, d_out, tw, batch, scale);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
+// (the kernel's loads are 4 bytes wide: an input that is not 4-byte aligned takes the composed route)
+inline bool cepstrum_fused_ok(const kofft_hip_ctx *ctx, const float *d_in, size_t n)
+{
+    return ctx->cepstrum_fused && n >= 32 && n <= 4096 && (reinterpret_cast<size_t>(d_in) & 3) == 0;
+}
+
+inline int cepstrum_fused_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    const cpx<float> *tw = nullptr;
+    const int rc = get_table<float>(ctx, Kind<float>::tw, n, &tw);  // get_twiddles(n), the table of the n-point transform
+    if (rc) return rc;
+    switch (ilog2(n)) {
+    case 5: return launch_cepstrum_fused<5>(ctx, d_in, d_out, tw, batch);
+    case 6: return launch_cepstrum_fused<6>(ctx, d_in, d_out, tw, batch);
+    case 7: return launch_cepstrum_fused<7>(ctx, d_in, d_out, tw, batch);
+    case 8: return launch_cepstrum_fused<8>(ctx, d_in, d_out, tw, batch);
+    case 9: return launch_cepstrum_fused<9>(ctx, d_in, d_out, tw, batch);
+    case 10: return launch_cepstrum_fused<10>(ctx, d_in, d_out, tw, batch);
+    case 11: return launch_cepstrum_fused<11>(ctx, d_in, d_out, tw, batch);
+    case 12: return launch_cepstrum_fused<12>(ctx, d_in, d_out, tw, batch);
+    default: return KOFFT_ERR_UNSUPPORTED;  // (never: cepstrum_fused_ok)
+    }
+}
+
+}  // namespace host
+}  // namespace kofft

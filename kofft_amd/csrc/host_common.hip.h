@@ -40,6 +40,7 @@ struct kofft_hip_ctx {
     bool istft_fused = true;  // KOFFT_HIP_ISTFT_FUSED=0: ISTFT always as inverse transforms + the overlap-add kernel
     bool dct_fused = true;    // kofft_hip_set_dct_fused(ctx, 0): DCT-II of every length through the composed route (mirror, fft_dev, post-pass; A/B, tests)
     bool hilbert_fused = true; // kofft_hip_set_hilbert_fused(ctx, 0): analytic signals of every length through the composed route (expand, fft_dev, mask, inverse fft_dev; A/B, tests)
+    bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
@@ -683,6 +684,7 @@ template <typename T>
 int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch);
 int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
 int hilbert_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: hilbert::hilbert_analytic
+int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_cepstrum_f32.hip: cepstrum::real_cepstrum
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

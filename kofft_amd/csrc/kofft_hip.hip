@@ -353,6 +353,50 @@ int hilbert_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size
     return KOFFT_OK;
 }
 
+// cepstrum::real_cepstrum on host rows: hilbert_host's staging (zero-copy for small calls, the upload / kernel / download pipeline
+// for large ones); rows of n reals in, rows of n reals out -- the input's bytes
+int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (!is_pow2(n)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
+    if (n > (size_t(1) << max_log2_big<float>())) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !in || !out) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = batch * n * sizeof(float);
+    if (ctx->zero_copy && bytes <= kZeroCopyMax && ensure_pinned(ctx, 2 * bytes + 256) == KOFFT_OK) {
+        const size_t o_out = (bytes + 255) & ~size_t(255);
+        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
+        std::memcpy(h, in, bytes);
+        int zrc = cepstrum_dev(ctx, reinterpret_cast<const float *>(dd), reinterpret_cast<float *>(dd + o_out), n, batch);
+        if (zrc) return zrc;
+        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(out, h + o_out, bytes);
+        return KOFFT_OK;
+    }
+    int rc = ensure_stage(ctx, 0, bytes);
+    if (rc) return rc;
+    rc = ensure_stage(ctx, 1, bytes);
+    if (rc) return rc;
+    float *d_in = static_cast<float *>(ctx->stage[0]), *d_out = static_cast<float *>(ctx->stage[1]);
+    if (use_host_pipeline(ctx, 2 * bytes, batch, n * sizeof(float))) {
+        const size_t chunk = host_chunk_rows(ctx, batch);
+        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
+        const int prc = pipeline_chunks(
+            ctx, (batch + chunk - 1) / chunk,
+            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * n, in + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyHostToDevice, st); },
+            [&](size_t c) { return cepstrum_dev(ctx, d_in + c * chunk * n, d_out + c * chunk * n, n, rows(c)); },
+            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * n, d_out + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyDeviceToHost, st); });
+        if (prc != KOFFT_ERR_ALLOC) return prc;
+    }
+    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = cepstrum_dev(ctx, d_in, d_out, n, batch);
+    if (rc) return rc;
+    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KOFFT_OK;
+}
+
 template <typename T>
 int irfft_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t n, size_t batch)
 {
@@ -845,6 +889,20 @@ int kofft_hip_hilbert_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_
 int kofft_hip_hilbert_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     return hilbert_dev(ctx, d_in, d_out, n, batch);
+}
+int kofft_hip_set_cepstrum_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->cepstrum_fused = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
+{
+    return cepstrum_host(ctx, in, out, n, batch);
+}
+int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    return cepstrum_dev(ctx, d_in, d_out, n, batch);
 }
 int kofft_hip_rfft_f64(kofft_hip_ctx *ctx, const double *in, double *out, const double *window, size_t n,
                        size_t batch)
