@@ -224,6 +224,52 @@ int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size
 int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
 int kofft_hip_set_cepstrum_fused(kofft_hip_ctx *ctx, int on);
 
+/* ---- direct DCT-I..IV and DST-I..IV ---------------------------------------------
+ * dct::dct1 .. dct4 (dct.rs:108-176) and dst::dst1 .. dst4 (dst.rs:89-146), f32 only like
+ * the reference (there is no f64 direct transform), on `batch` contiguous rows of n reals;
+ * out: batch * n reals.  These are the naive O(n^2) sums: kofft_hip_dct_direct_f32(ctx, 2,
+ * ..) is dct::dct2, NOT DctPlanner::plan_dct2 (kofft_hip_dct2_f32, FFT-based), and the two do
+ * not return the same bytes.  Per output k: sum = init, then sum += x'[i] * C[i][k] for
+ * every i of the kind's range in increasing order, one f32 multiply and one f32 add per term
+ * (never fused), C[i][k] = glibc cosf / sinf of the reference's f32 angle:
+ *   DCT-I   init x0 + x[n-1] (k even) / x0 + (-x[n-1]) (k odd), [2 * x0] at n == 1; i = 1 ..
+ *           n-2; x' = 2 * x; angle (PI / (n - 1) * i) * k                   (dct.rs:108-131)
+ *   DCT-II  init +0; i = 0 .. n-1; angle (PI / n * (i + 0.5)) * k           (dct.rs:134-146)
+ *   DCT-III init x0 / 2; i = 1 .. n-1; angle (PI / n * i) * (k + 0.5)       (dct.rs:149-161)
+ *   DCT-IV  init +0; i = 0 .. n-1; angle (PI / n * (i + 0.5)) * (k + 0.5)   (dct.rs:164-176)
+ *   DST-I   init +0; i = 0 .. n-1; angle ((i + 1) * (k + 1)) * (PI / (n + 1)) (dst.rs:89-101)
+ *   DST-II  init +0; i = 0 .. n-1; angle (PI / n * (i + 0.5)) * (k + 1)     (dst.rs:104-116)
+ *   DST-III init x0 / 2; i = 1 .. n-1; angle (PI / n * (k + 0.5)) * i       (dst.rs:119-131)
+ *   DST-IV  init +0; i = 0 .. n-1; angle (PI / n * (i + 0.5)) * (k + 0.5)   (dst.rs:134-146)
+ * Checks, in this order and before the context or the device is touched: type not 1 .. 4 ->
+ * INVALID_VALUE; batch == 0 -> KOFFT_OK; n == 0 -> KOFFT_OK (an empty result, as the
+ * reference), but EMPTY_INPUT for type 3 (dct3 / dst3 index input[0] unchecked: the reference
+ * panics); n > 4096 -> KOFFT_ERR_UNSUPPORTED (the bound of the n x n table, 64 MiB at 4096);
+ * a null pointer or context -> KOFFT_ERR_NULL.  The host form allows in == out (the
+ * reference's batch_* work in place).  _dev: device pointers, asynchronous on the context's
+ * stream; in and out must not overlap (the tiles of one row run in different workgroups): an
+ * overlap returns INVALID_VALUE.  The first call of a (context, kind, n) builds the table on
+ * the host (up to 16 threads; about 64 MiB of cosf / sinf at n = 4096) and keeps it on the
+ * device until the context is destroyed.  kofft_hip_set_direct_tiled(ctx, 0) sends every call
+ * of that context to the simple kernel (one lane per output) instead of the tiled one: the
+ * same bytes (A/B measurements and tests). */
+int kofft_hip_dct_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_dct_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_dst_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_dst_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on);
+/* The tables of the direct transforms, host only (tests): C = n * n floats, C[i * n + k] as
+ * above; rows outside the kind's i range are +0.  type not 1 .. 4 -> INVALID_VALUE; n == 0 ->
+ * KOFFT_OK; n > 4096 -> KOFFT_ERR_UNSUPPORTED; C null -> KOFFT_ERR_NULL. */
+int kofft_hip_dct_direct_table_f32(int type, size_t n, float *C);
+int kofft_hip_dst_direct_table_f32(int type, size_t n, float *C);
+/* DstPlanner::plan_dst2 / 3 / 4 (dst.rs:41-77), host only: out[i] = sin(factor * (i + off)),
+ * factor = pi / n, i < n, off = 0.5 (types 2, 4) or 0.0 (type 3).  f32: glibc sinf of f32
+ * arithmetic; f64: glibc sin, with i and n converted through f32 as T::from_f32(i as f32)
+ * does.  type not 2 .. 4 -> INVALID_VALUE; n == 0 -> KOFFT_OK; out null -> KOFFT_ERR_NULL. */
+int kofft_hip_dst_planner_table_f32(int type, size_t n, float *out);
+int kofft_hip_dst_planner_table_f64(int type, size_t n, double *out);
+
 /* ---- STFT ---------------------------------------------------------------------
  * stft::stft (stft.rs:76-105): out = frames * win_len complex, contiguous (the
  * reference's &mut [Vec<Complex32>] flattened).  hop == 0 -> INVALID_HOP_SIZE;

@@ -14,6 +14,8 @@
 //   kofft::HipFftImpl<float>::dct2               DctPlanner::plan_dct2, dct.rs:61-105
 //   kofft::HipFftImpl<float>::hilbert_analytic   hilbert::hilbert_analytic, hilbert.rs:13-47
 //   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
+//   kofft::HipFftImpl<float>::dct_direct         dct::dct1..dct4, dct.rs:108-176 (the direct sums)
+//   kofft::HipFftImpl<float>::dst_direct         dst::dst1..dst4, dst.rs:89-146
 //
 // Result<(), FftError> becomes kofft::Result (is_ok / is_err / unwrap / unwrap_err).  A negative C-ABI status
 // (HIP failure, unsupported length) has no FftError variant: it throws kofft::DeviceError, the C++ analogue of
@@ -291,6 +293,30 @@ public:
         if (n == 0) return Result::Err(FftError::EmptyInput);
         if (n & (n - 1)) return Result::Err(FftError::NonPowerOfTwoNoStd);
         return st(kofft_hip_cepstrum_f32(ctx_, input.data(), output.data(), n, batch));
+    }
+    // dct::dct1 .. dct4 (dct.rs:108-176; type 1 .. 4), the direct sums, f32 only like the reference: `batch` contiguous rows of n reals
+    // in, rows of n reals out.  MismatchedLengths for rows that do not divide the input or an output of another size; InvalidValue for
+    // a type outside 1 .. 4; n == 0 is an empty result except for type 3 (EmptyInput: dct3 indexes input[0] unchecked); n > 4096
+    // throws DeviceError (the table bound).  input and output may be the same vector.  Type 2 is dct::dct2, not plan_dct2 (dct2).
+    Result dct_direct(int type, const std::vector<float> &input, std::vector<float> &output, size_t batch = 1) const
+    {
+        return direct(kofft_hip_dct_direct_f32, type, input, output, batch);
+    }
+    // dst::dst1 .. dst4 (dst.rs:89-146; type 1 .. 4): as dct_direct (dst3: EmptyInput at n == 0).
+    Result dst_direct(int type, const std::vector<float> &input, std::vector<float> &output, size_t batch = 1) const
+    {
+        return direct(kofft_hip_dst_direct_f32, type, input, output, batch);
+    }
+
+    Result direct(int (*fn)(kofft_hip_ctx *, int, const float *, float *, size_t, size_t), int type, const std::vector<float> &input,
+                  std::vector<float> &output, size_t batch) const
+    {
+        static_assert(std::is_same<T, float>::value, "the direct DCT / DST are f32-only (dct.rs / dst.rs)");
+        if (type < 1 || type > 4) return Result::Err(FftError::InvalidValue);
+        if (batch == 0 || input.size() % batch != 0 || output.size() != input.size()) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = input.size() / batch;
+        if (n == 0) return type == 3 ? Result::Err(FftError::EmptyInput) : Result::Ok();
+        return st(fn(ctx_, type, input.data(), output.data(), n, batch));
     }
 
     // added: contiguous batch (fft::batch over one buffer)

@@ -41,6 +41,7 @@ struct kofft_hip_ctx {
     bool dct_fused = true;    // kofft_hip_set_dct_fused(ctx, 0): DCT-II of every length through the composed route (mirror, fft_dev, post-pass; A/B, tests)
     bool hilbert_fused = true; // kofft_hip_set_hilbert_fused(ctx, 0): analytic signals of every length through the composed route (expand, fft_dev, mask, inverse fft_dev; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
+    bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
@@ -74,7 +75,8 @@ struct kofft_hip_ctx {
     bool use_split = true;     // KOFFT_HIP_SPLIT=0: n = 8192 on the block-synchronised persistent kernel instead of the wave-split one (A/B)
     std::string last_error;
     // planner caches: (kind, n) -> device table.  kind 0/1 = FftPlanner twiddles f32/f64,
-    // 2/3 = RfftPlanner post-pass table f32/f64, 13 = DctPlanner (cos, sin) table f32.
+    // 2/3 = RfftPlanner post-pass table f32/f64, 13 = DctPlanner (cos, sin) table f32, 20 .. 27 = the direct DCT / DST tables
+    // (direct_impl.hip.h).
     std::map<std::pair<int, size_t>, void *> tables;
     // staging for the host-pointer entry points
     void *stage[3] = {nullptr, nullptr, nullptr};
@@ -685,6 +687,10 @@ int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batc
 int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
 int hilbert_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: hilbert::hilbert_analytic
 int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_cepstrum_f32.hip: cepstrum::real_cepstrum
+// k_direct_f32.hip: dct::dct1..4 (family 0) / dst::dst1..4 (family 1), the direct sums; direct_check: the argument checks alone
+constexpr size_t kDirectMaxN = 4096;  // the longest row: the n x n table is 64 MiB there
+int direct_check(int family, int type, size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
+int direct_dev(kofft_hip_ctx *ctx, int family, int type, const float *d_in, float *d_out, size_t n, size_t batch);
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

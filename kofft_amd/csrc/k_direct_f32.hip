@@ -1,0 +1,39 @@
+// k_direct_f32.hip -- dct::dct1..dct4 (dct.rs:108-176) and dst::dst1..dst4 (dst.rs:89-146) on float rows: every kernel instance of
+// the family (direct_impl.hip.h).
+#include "direct_impl.hip.h"
+
+namespace kofft {
+namespace host {
+// Checks in the order of include/kofft_hip.h, all before the context or the device is touched: the type, batch == 0, n == 0 (the
+// reference returns an empty result, except DCT-III / DST-III, which index input[0] unchecked: EMPTY_INPUT here), the table bound,
+// then the pointers.
+int direct_check(int family, int type, size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
+{
+    (void)family;
+    if (type < 1 || type > 4) return KOFFT_ERR_INVALID_VALUE;
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return type == 3 ? KOFFT_ERR_EMPTY_INPUT : KOFFT_OK;
+    if (n > kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !in || !out) return KOFFT_ERR_NULL;
+    return KOFFT_OK;
+}
+
+int direct_dev(kofft_hip_ctx *ctx, int family, int type, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    int rc = direct_check(family, type, n, batch, d_in, d_out, ctx);
+    if (rc || batch == 0 || n == 0) return rc;
+    // tiles of one row run in different workgroups: an output that overlaps the input would be read after it is written
+    if (d_in < d_out + batch * n && d_out < d_in + batch * n) return KOFFT_ERR_INVALID_VALUE;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const float *table = nullptr;
+    rc = get_direct_table(ctx, family, type, n, &table);
+    if (rc) return rc;
+    size_t ib, ie;
+    kofft_tables::direct_range(family, type, n, &ib, &ie);
+    if (family == 0 && type == 1) return launch_direct<DIR_DCT1>(ctx, d_in, d_out, table, n, batch, ib, ie);
+    if (type == 3) return launch_direct<DIR_HALF>(ctx, d_in, d_out, table, n, batch, ib, ie);
+    return launch_direct<DIR_ZERO>(ctx, d_in, d_out, table, n, batch, ib, ie);
+}
+
+}  // namespace host
+}  // namespace kofft

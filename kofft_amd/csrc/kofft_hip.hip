@@ -397,6 +397,37 @@ int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, siz
     return KOFFT_OK;
 }
 
+// dct::dct1..4 / dst::dst1..4 on host rows: zero-copy for small calls, else one upload / kernel / download through the stages.  The
+// whole input is on the device before any output is written back, so in == out works (the reference's batch_* are in place).
+int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float *out, size_t n, size_t batch)
+{
+    int rc = direct_check(family, type, n, batch, in, out, ctx);
+    if (rc || batch == 0 || n == 0) return rc;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = batch * n * sizeof(float);
+    if (ctx->zero_copy && bytes <= kZeroCopyMax && ensure_pinned(ctx, 2 * bytes + 256) == KOFFT_OK) {
+        const size_t o_out = (bytes + 255) & ~size_t(255);
+        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
+        std::memcpy(h, in, bytes);
+        rc = direct_dev(ctx, family, type, reinterpret_cast<const float *>(dd), reinterpret_cast<float *>(dd + o_out), n, batch);
+        if (rc) return rc;
+        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(out, h + o_out, bytes);
+        return KOFFT_OK;
+    }
+    rc = ensure_stage(ctx, 0, bytes);
+    if (rc) return rc;
+    rc = ensure_stage(ctx, 1, bytes);
+    if (rc) return rc;
+    float *d_in = static_cast<float *>(ctx->stage[0]), *d_out = static_cast<float *>(ctx->stage[1]);
+    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = direct_dev(ctx, family, type, d_in, d_out, n, batch);
+    if (rc) return rc;
+    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KOFFT_OK;
+}
+
 template <typename T>
 int irfft_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t n, size_t batch)
 {
@@ -780,6 +811,33 @@ int kofft_hip_dct2_table_f32(size_t n, float *cs)
     kofft_tables::dct2_table_f32(n, cs);
     return KOFFT_OK;
 }
+static int direct_table(int family, int type, size_t n, float *c)
+{
+    if (type < 1 || type > 4) return KOFFT_ERR_INVALID_VALUE;
+    if (n == 0) return KOFFT_OK;
+    if (n > kofft::host::kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!c) return KOFFT_ERR_NULL;
+    kofft_tables::direct_table_f32(family, type, n, n, c);
+    return KOFFT_OK;
+}
+int kofft_hip_dct_direct_table_f32(int type, size_t n, float *c) { return direct_table(0, type, n, c); }
+int kofft_hip_dst_direct_table_f32(int type, size_t n, float *c) { return direct_table(1, type, n, c); }
+int kofft_hip_dst_planner_table_f32(int type, size_t n, float *out)
+{
+    if (type < 2 || type > 4) return KOFFT_ERR_INVALID_VALUE;
+    if (n == 0) return KOFFT_OK;
+    if (!out) return KOFFT_ERR_NULL;
+    kofft_tables::dst_planner_f32(type, n, out);
+    return KOFFT_OK;
+}
+int kofft_hip_dst_planner_table_f64(int type, size_t n, double *out)
+{
+    if (type < 2 || type > 4) return KOFFT_ERR_INVALID_VALUE;
+    if (n == 0) return KOFFT_OK;
+    if (!out) return KOFFT_ERR_NULL;
+    kofft_tables::dst_planner_f64(type, n, out);
+    return KOFFT_OK;
+}
 int kofft_hip_hann_f32(size_t len, float *out)
 {
     if (!out && len) return KOFFT_ERR_NULL;
@@ -903,6 +961,28 @@ int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size
 int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     return cepstrum_dev(ctx, d_in, d_out, n, batch);
+}
+int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->direct_tiled = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_dct_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch)
+{
+    return direct_host(ctx, 0, type, in, out, n, batch);
+}
+int kofft_hip_dct_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    return direct_dev(ctx, 0, type, d_in, d_out, n, batch);
+}
+int kofft_hip_dst_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch)
+{
+    return direct_host(ctx, 1, type, in, out, n, batch);
+}
+int kofft_hip_dst_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    return direct_dev(ctx, 1, type, d_in, d_out, n, batch);
 }
 int kofft_hip_rfft_f64(kofft_hip_ctx *ctx, const double *in, double *out, const double *window, size_t n,
                        size_t batch)

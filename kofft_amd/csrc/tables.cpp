@@ -167,3 +167,93 @@ void dct2_table_f32(size_t n, float *cs)
     }
 }
 }  // namespace kofft_tables
+
+// ---- direct DCT / DST tables ---------------------------------------------------------------------------------------------------
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+namespace {
+// C[i][k] of one kind: the angle in the reference's order of f32 operations (`i as f32` is exact for n <= 2^24), then ONE libm
+// call.  Rust's f32::cos / f32::sin are glibc's cosf / sinf on linux-gnu; each loop of the reference calls only one of them.
+void direct_rows(int family, int type, size_t n, size_t ldc, float *c, size_t r0, size_t r1, size_t ib, size_t ie)
+{
+    const float pi = 3.14159265358979323846f;  // core::f32::consts::PI
+    const float nf = (float)n;
+    for (size_t i = r0; i < r1; ++i) {
+        float *row = c + i * ldc;
+        std::fill(row, row + ldc, 0.0f);
+        if (i < ib || i >= ie) continue;
+        const float fi = (float)i;
+        for (size_t k = 0; k < n; ++k) {
+            const float fk = (float)k;
+            float v;
+            if (family == 0) {
+                switch (type) {
+                case 1: v = cosf((pi / (nf - 1.0f) * fi) * fk); break;            // dct.rs:116, 126
+                case 2: v = cosf((pi / nf * (fi + 0.5f)) * fk); break;            // dct.rs:137, 141
+                case 3: v = cosf((pi / nf * fi) * (fk + 0.5f)); break;            // dct.rs:152, 156
+                default: v = cosf((pi / nf * (fi + 0.5f)) * (fk + 0.5f)); break;  // dct.rs:167, 171
+                }
+            } else {
+                switch (type) {
+                case 1: v = sinf(((fi + 1.0f) * (fk + 1.0f)) * (pi / (nf + 1.0f))); break;  // dst.rs:92, 96: the product first
+                case 2: v = sinf((pi / nf * (fi + 0.5f)) * (fk + 1.0f)); break;            // dst.rs:107, 111
+                case 3: v = sinf((pi / nf * (fk + 0.5f)) * fi); break;                     // dst.rs:122, 126: k first
+                default: v = sinf((pi / nf * (fi + 0.5f)) * (fk + 0.5f)); break;           // dst.rs:137, 141
+                }
+            }
+            row[k] = v;
+        }
+    }
+}
+
+template <typename T>
+void dst_planner(int type, size_t n, T *out)
+{
+    const float off = type == 3 ? 0.0f : 0.5f;
+    const T factor = Num<T>::pi() / (T)(float)n;
+    for (size_t i = 0; i < n; ++i) {
+        const T angle = factor * ((T)(float)i + (T)off);
+        if constexpr (sizeof(T) == 4) out[i] = sinf(angle);
+        else out[i] = ::sin(angle);
+    }
+}
+}  // namespace
+
+namespace kofft_tables {
+void direct_range(int family, int type, size_t n, size_t *i_begin, size_t *i_end)
+{
+    if (family == 0 && type == 1) {  // dct.rs:125: input.iter().take(n - 1).enumerate().skip(1)
+        *i_begin = 1;
+        *i_end = n >= 2 ? n - 1 : 1;
+    } else if (type == 3) {  // dct.rs:155 / dst.rs:125: .skip(1)
+        *i_begin = 1;
+        *i_end = n >= 1 ? n : 1;
+    } else {
+        *i_begin = 0;
+        *i_end = n;
+    }
+}
+void direct_table_f32(int family, int type, size_t n, size_t ldc, float *c)
+{
+    size_t ib, ie;
+    direct_range(family, type, n, &ib, &ie);
+    // at most 16 threads, and none for tables of fewer than 2^16 entries (n = 4096: 16.7 M libm calls)
+    size_t threads = std::min<size_t>({size_t(16), std::max<size_t>(1, std::thread::hardware_concurrency()), std::max<size_t>(1, n * n >> 16)});
+    if (threads <= 1) {
+        direct_rows(family, type, n, ldc, c, 0, n, ib, ie);
+        return;
+    }
+    std::vector<std::thread> pool;
+    const size_t per = (n + threads - 1) / threads;
+    for (size_t t = 0; t < threads; ++t) {
+        const size_t r0 = t * per, r1 = std::min(n, r0 + per);
+        if (r0 >= r1) break;
+        pool.emplace_back(direct_rows, family, type, n, ldc, c, r0, r1, ib, ie);
+    }
+    for (auto &th : pool) th.join();
+}
+void dst_planner_f32(int type, size_t n, float *out) { dst_planner<float>(type, n, out); }
+void dst_planner_f64(int type, size_t n, double *out) { dst_planner<double>(type, n, out); }
+}  // namespace kofft_tables
