@@ -6,10 +6,11 @@
 // squares as written (two multiplies and an add, unfused, then a correctly rounded root: not hypotf), and logf is the libm crate's
 // (libm_logf.hip.h).  The pointwise step is the same for every bin, so no bin position enters it.  Two routes, the same operations
 // per element:
-//  * fused (powers of two n = 32 .. 4096): cepstrum_fused_kernel<L>, one pass over HBM.  hilbert_fused_kernel's shape, with its
-//    geometry and forward transform (HilbertGeom, hilbert_forward): rows load as (x, +0) through one buffer descriptor per
-//    workgroup, the forward transform runs, the last pass's registers take log-magnitude + conj, one LDS exchange puts them back
-//    into pass-0 input order, the same forward transform runs again and the store writes re * scale only, 4 bytes per point;
+//  * fused (powers of two n = 32 .. 4096): cepstrum_fused_kernel<L>, one pass over HBM.  hilbert_fused_kernel's body
+//    (fused_two_transforms, hilbert_impl.hip.h) with the policy CepstrumFused: rows load as (x, +0) through one buffer
+//    descriptor per workgroup, the forward transform runs, the last pass's registers take log-magnitude + conj, one LDS exchange
+//    puts them back into pass-0 input order, the same forward transform runs again and the store writes re * scale only, 4 bytes
+//    per point;
 //  * composed (n <= 16, 8192 .. 2^26, inputs that are not 4-byte aligned, and every n after kofft_hip_set_cepstrum_fused(ctx, 0)):
 //    the output holds only n floats per row, so the context's real scratch is the workspace, in row chunks of 512 MiB at most --
 //    hilbert_expand_kernel writes (x, +0), fft_dev transforms in place, cepstrum_logmag_kernel, fft_dev(inverse) runs the
@@ -75,88 +76,23 @@ inline int cepstrum_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d
 }
 
 // ---- fused route: powers of two n = 2^L, L = 5 .. 12 ------------------------------------------------------------------------
+// every bin: (log-magnitude, +0), then ifft's conj (fft.rs:1163-1165): (l, -0); the store: ifft's conj leaves the real part
+// alone, * scale (fft.rs:1168-1172), real part only
+struct CepstrumFused {
+    using Out = float;
+    template <int N>
+    static __device__ __forceinline__ void point(cpx<float> &v, int, int) { v = mk<float>(cepstrum_log_mag(v), -0.0f); }
+    static __device__ __forceinline__ void store(const cpx<float> v, const float scale, const rsrc_t d, const int lane_bytes, const int off)
+    {
+        buf_store_f32(v.re * scale, d, lane_bytes, off);
+    }
+};
+
 template <int L>
 __global__ __launch_bounds__(256) void cepstrum_fused_kernel(const float *__restrict__ x, float *__restrict__ out, const cpx<float> *__restrict__ tw,
                                                              const size_t batch, const float scale)
 {
-    using Geo = HilbertGeom<L>;
-    constexpr int N = Geo::N, R = Geo::R, TPT = Geo::TPT, XPB = Geo::XPB;
-    using G0 = WgGeom<L, Geo::RL, 0>;
-    using GL = WgGeom<L, Geo::RL, Geo::NP - 1>;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int tid = threadIdx.x, tau = tid % TPT, slot = tid / TPT;
-    const size_t row0 = (size_t)blockIdx.x * XPB;  // < batch (grid = ceil(batch / XPB))
-    const size_t cnt = batch - row0 < (size_t)XPB ? batch - row0 : (size_t)XPB;
-    // One descriptor over the workgroup's rows, cut at the end of the batch: the rows past it read zeros and store nothing, with no
-    // per-lane test.  Pass 0's register u of thread tau holds sample in_index(0, u) + tau of its row.
-    cpx<float> v[R];
-    {
-        const rsrc_t d = make_rsrc(x + row0 * N, (unsigned)(cnt * N * sizeof(float)));
-        const int lane_bytes = (slot * N + tau) * (int)sizeof(float);
-        float raw[R];
-#pragma unroll
-        for (int u = 0; u < R; ++u) raw[u] = buf_load_f32<AUX_NT>(d, lane_bytes, G0::in_index(0, u) * (int)sizeof(float));
-#pragma unroll
-        for (int u = 0; u < R; ++u) v[u] = mk<float>(raw[u], 0.0f);  // cepstrum.rs:21-23
-    }
-    hilbert_forward<L>(v, smem_raw, tw, tau, slot);
-    // every bin: (log-magnitude, +0), then ifft's conj (fft.rs:1163-1165): (l, -0)
-#pragma unroll
-    for (int u = 0; u < R; ++u) v[u] = mk<float>(cepstrum_log_mag(v[u]), -0.0f);
-    {   // last pass's output order -> pass 0's input order, through the row's exchange slot
-        cpx<float> *buf = reinterpret_cast<cpx<float> *>(smem_raw) + (size_t)slot * lds_elems(N);
-        __syncthreads();  // every gather of the transform's last exchange is done
-#pragma unroll
-        for (int u = 0; u < R; ++u) buf[lds_pad(GL::out_index(tau, u))] = v[u];
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < R; ++u) v[u] = buf[lds_pad(G0::in_index(tau, u))];
-        __syncthreads();  // (the second transform's first exchange scatters into the same cells)
-    }
-    hilbert_forward<L>(v, smem_raw, tw, tau, slot);
-    // ifft's conj leaves the real part alone; * scale (fft.rs:1168-1172), real part only; bin out_index(0, u) | tau of the row
-    const rsrc_t d = make_rsrc(out + row0 * N, (unsigned)(cnt * N * sizeof(float)));
-    const int lane_bytes = (slot * N + tau) * (int)sizeof(float);
-#pragma unroll
-    for (int u = 0; u < R; ++u) buf_store_f32(v[u].re * scale, d, lane_bytes, GL::out_index(0, u) * (int)sizeof(float));
-}
-
-template <int L>
-int launch_cepstrum_fused(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const cpx<float> *tw, size_t batch)
-{
-    using Geo = HilbertGeom<L>;
-    constexpr size_t lds = Geo::lds_bytes();
-    static_assert(lds <= 64 * 1024, "LDS budget");
-    const size_t blocks = (batch + Geo::XPB - 1) / Geo::XPB;
-    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-    const float scale = 1.0f / (float)Geo::N;  // fft.rs:1167
-    hipLaunchKernelGGL(cepstrum_fused_kernel<L>, dim3((unsigned)blocks), dim3(Geo::BLOCK), lds, ctx->stream, d_in, d_out, tw, batch, scale);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
-}
-
-// (the kernel's loads are 4 bytes wide: an input that is not 4-byte aligned takes the composed route)
-inline bool cepstrum_fused_ok(const kofft_hip_ctx *ctx, const float *d_in, size_t n)
-{
-    return ctx->cepstrum_fused && n >= 32 && n <= 4096 && (reinterpret_cast<size_t>(d_in) & 3) == 0;
-}
-
-inline int cepstrum_fused_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
-{
-    const cpx<float> *tw = nullptr;
-    const int rc = get_table<float>(ctx, Kind<float>::tw, n, &tw);  // get_twiddles(n), the table of the n-point transform
-    if (rc) return rc;
-    switch (ilog2(n)) {
-    case 5: return launch_cepstrum_fused<5>(ctx, d_in, d_out, tw, batch);
-    case 6: return launch_cepstrum_fused<6>(ctx, d_in, d_out, tw, batch);
-    case 7: return launch_cepstrum_fused<7>(ctx, d_in, d_out, tw, batch);
-    case 8: return launch_cepstrum_fused<8>(ctx, d_in, d_out, tw, batch);
-    case 9: return launch_cepstrum_fused<9>(ctx, d_in, d_out, tw, batch);
-    case 10: return launch_cepstrum_fused<10>(ctx, d_in, d_out, tw, batch);
-    case 11: return launch_cepstrum_fused<11>(ctx, d_in, d_out, tw, batch);
-    case 12: return launch_cepstrum_fused<12>(ctx, d_in, d_out, tw, batch);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: cepstrum_fused_ok)
-    }
+    fused_two_transforms<L, CepstrumFused>(x, out, tw, batch, scale);
 }
 
 }  // namespace host

@@ -5,11 +5,11 @@
 // with ifft = conj (im = -im), fft, conj, * (1 / n) and an early return at n == 1 (fft.rs:1134-1174).  The mask is two real
 // multiplies (an Inf stays an Inf; a complex multiply by (2, 0) would make NaNs), and the conj is a negation, so a zeroed bin
 // enters the second transform as (+0, -0).  Two routes, the same operations per element:
-//  * fused (powers of two n = 32 .. 4096): hilbert_fused_kernel<L>, one pass over HBM.  The register-pass machinery of
-//    fft_wg.hip.h (WgGeom, reg_pass, wg_exchange, lds_pad) with rl_for's geometry: rows load as (x, +0) through one buffer
-//    descriptor per workgroup, the forward transform runs, the last pass's registers -- whose bins the geometry names at
-//    compile time up to the thread's low bits -- take mask + conj, one LDS exchange puts them back into pass-0 input order, the
-//    same forward transform runs again and the store applies conj * scale;
+//  * fused (powers of two n = 32 .. 4096): hilbert_fused_kernel<L>, one pass over HBM, whose body (fused_two_transforms) the
+//    cepstrum's fused kernel shares.  The register-pass machinery of fft_wg.hip.h (WgGeom, reg_pass, wg_exchange, lds_pad) with
+//    rl_for's geometry: rows load as (x, +0) through one buffer descriptor per workgroup, the forward transform runs, the last
+//    pass's registers -- whose bins the geometry names at compile time up to the thread's low bits -- take mask + conj, one LDS
+//    exchange puts them back into pass-0 input order, the same forward transform runs again and the store applies conj * scale;
 //  * composed (n <= 16, whose transforms are the reference's straight-line kernels, powers of two above 4096, inputs that are not
 //    4-byte aligned, and every n after kofft_hip_set_hilbert_fused(ctx, 0)): the caller's output is the workspace --
 //    hilbert_expand_kernel writes (x, +0), fft_dev transforms in place, hilbert_mask_kernel masks, fft_dev(inverse) runs the
@@ -17,6 +17,8 @@
 #pragma once
 
 #include "host_common.hip.h"
+
+#include <type_traits>
 
 namespace kofft {
 namespace host {
@@ -92,12 +94,21 @@ __device__ __forceinline__ void hilbert_forward(cpx<float> *v, char *smem, const
     if constexpr (NP > 3) { wg_exchange<float, L, RL, 2, false, false, XPB>(v, smem, tau, slot); wg_compute<float, L, RL, 3>(v, plain, tw, 0, tau); }
 }
 
-template <int L>
-__global__ __launch_bounds__(256) void hilbert_fused_kernel(const float *__restrict__ x, cpx<float> *__restrict__ out,
-                                                            const cpx<float> *__restrict__ tw, const size_t batch, const float scale)
+// The fused kernels' shared body (hilbert_fused_kernel, cepstrum_fused_kernel): rows of n = 2^L reals in, rows of P::Out out.  The
+// policy P supplies
+//   P::Out                                  the output element, one per point;
+//   P::point<N>(v, hi, tau)                 the pointwise step, in place, on the first transform's bin hi | tau (hi =
+//                                           GL::out_index(0, u), a compile-time value once unrolled), ifft's conj included;
+//   P::store(v, scale, d, lane_bytes, off)  ifft's conj and * scale (fft.rs:1168-1172) on the second transform's bin, and the
+//                                           store.
+// (No __restrict__ here: the kernels' own parameters carry it.  Restrict-qualified parameters on this inlined body change the
+// compiler's schedule and register counts.)
+template <int L, class P>
+__device__ __forceinline__ void fused_two_transforms(const float *x, typename P::Out *out, const cpx<float> *tw, const size_t batch,
+                                                     const float scale)
 {
     using Geo = HilbertGeom<L>;
-    constexpr int N = Geo::N, H = N / 2, R = Geo::R, TPT = Geo::TPT, XPB = Geo::XPB;
+    constexpr int N = Geo::N, R = Geo::R, TPT = Geo::TPT, XPB = Geo::XPB;
     using G0 = WgGeom<L, Geo::RL, 0>;
     using GL = WgGeom<L, Geo::RL, Geo::NP - 1>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -114,23 +125,12 @@ __global__ __launch_bounds__(256) void hilbert_fused_kernel(const float *__restr
 #pragma unroll
         for (int u = 0; u < R; ++u) raw[u] = buf_load_f32<AUX_NT>(d, lane_bytes, G0::in_index(0, u) * (int)sizeof(float));
 #pragma unroll
-        for (int u = 0; u < R; ++u) v[u] = mk<float>(raw[u], 0.0f);  // hilbert.rs:21-23
+        for (int u = 0; u < R; ++u) v[u] = mk<float>(raw[u], 0.0f);  // hilbert.rs:21-23, cepstrum.rs:21-23
     }
     hilbert_forward<L>(v, smem_raw, tw, tau, slot);
-    // Register u of thread tau holds bin out_index(0, u) | tau: its top bit -- upper half or not -- is a compile-time fact.
+    // Register u of thread tau holds bin out_index(0, u) | tau: its top bits are a compile-time fact.
 #pragma unroll
-    for (int u = 0; u < R; ++u) {
-        const int hi = GL::out_index(0, u);
-        if (hi >= H) {
-            // n/2 itself (tau == 0 of the register whose other bits are zero): conj only; above it Complex32::zero(), conj'ed
-            const bool half = hi == H && tau == 0;
-            v[u] = half ? mk<float>(v[u].re, -v[u].im) : mk<float>(0.0f, -0.0f);
-        } else {
-            const bool dc = hi == 0 && tau == 0;
-            const float re2 = v[u].re * 2.0f, im2 = v[u].im * 2.0f;  // hilbert.rs:29-30
-            v[u] = dc ? mk<float>(v[u].re, -v[u].im) : mk<float>(re2, -im2);  // then ifft's conj (fft.rs:1163-1165)
-        }
-    }
+    for (int u = 0; u < R; ++u) P::template point<N>(v[u], GL::out_index(0, u), tau);
     {   // last pass's output order -> pass 0's input order, through the row's exchange slot
         cpx<float> *buf = reinterpret_cast<cpx<float> *>(smem_raw) + (size_t)slot * lds_elems(N);
         __syncthreads();  // every gather of the transform's last exchange is done
@@ -142,18 +142,52 @@ __global__ __launch_bounds__(256) void hilbert_fused_kernel(const float *__restr
         __syncthreads();  // (the second transform's first exchange scatters into the same cells)
     }
     hilbert_forward<L>(v, smem_raw, tw, tau, slot);
-    // ifft's conj, then * scale (fft.rs:1168-1172); bin out_index(0, u) | tau of the row
-    const rsrc_t d = make_rsrc(out + row0 * N, (unsigned)(cnt * N * sizeof(cpx<float>)));
-    const int lane_bytes = (slot * N + tau) * (int)sizeof(cpx<float>);
+    // bin out_index(0, u) | tau of the row
+    using Out = typename P::Out;
+    const rsrc_t d = make_rsrc(out + row0 * N, (unsigned)(cnt * N * sizeof(Out)));
+    const int lane_bytes = (slot * N + tau) * (int)sizeof(Out);
 #pragma unroll
-    for (int u = 0; u < R; ++u) {
-        const float im = -v[u].im;
-        buf_store_cpx<float>(mk<float>(v[u].re * scale, im * scale), d, lane_bytes, GL::out_index(0, u) * (int)sizeof(cpx<float>));
-    }
+    for (int u = 0; u < R; ++u) P::store(v[u], scale, d, lane_bytes, GL::out_index(0, u) * (int)sizeof(Out));
 }
 
+struct HilbertFused {
+    using Out = cpx<float>;
+    template <int N>
+    static __device__ __forceinline__ void point(cpx<float> &v, const int hi, const int tau)
+    {
+        if (hi >= N / 2) {
+            // n/2 itself (tau == 0 of the register whose other bits are zero): conj only; above it Complex32::zero(), conj'ed
+            const bool half = hi == N / 2 && tau == 0;
+            v = half ? mk<float>(v.re, -v.im) : mk<float>(0.0f, -0.0f);
+        } else {
+            const bool dc = hi == 0 && tau == 0;
+            const float re2 = v.re * 2.0f, im2 = v.im * 2.0f;  // hilbert.rs:29-30
+            v = dc ? mk<float>(v.re, -v.im) : mk<float>(re2, -im2);  // then ifft's conj (fft.rs:1163-1165)
+        }
+    }
+    static __device__ __forceinline__ void store(const cpx<float> v, const float scale, const rsrc_t d, const int lane_bytes, const int off)
+    {
+        const float im = -v.im;
+        buf_store_cpx<float>(mk<float>(v.re * scale, im * scale), d, lane_bytes, off);
+    }
+};
+
 template <int L>
-int launch_hilbert_fused(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const cpx<float> *tw, size_t batch)
+__global__ __launch_bounds__(256) void hilbert_fused_kernel(const float *__restrict__ x, cpx<float> *__restrict__ out,
+                                                            const cpx<float> *__restrict__ tw, const size_t batch, const float scale)
+{
+    fused_two_transforms<L, HilbertFused>(x, out, tw, batch, scale);
+}
+
+// (the kernels' loads are 4 bytes wide: an input that is not 4-byte aligned takes the composed route; `enabled` is the context's
+// switch, kofft_hip_set_hilbert_fused / kofft_hip_set_cepstrum_fused)
+inline bool fused_ok(const bool enabled, const float *d_in, size_t n)
+{
+    return enabled && n >= 32 && n <= 4096 && (reinterpret_cast<size_t>(d_in) & 3) == 0;
+}
+
+template <int L, class P, class Kernel>
+int launch_fused(kofft_hip_ctx *ctx, Kernel kern, const float *d_in, float *d_out, const cpx<float> *tw, size_t batch)
 {
     using Geo = HilbertGeom<L>;
     constexpr size_t lds = Geo::lds_bytes();
@@ -161,33 +195,31 @@ int launch_hilbert_fused(kofft_hip_ctx *ctx, const float *d_in, float *d_out, co
     const size_t blocks = (batch + Geo::XPB - 1) / Geo::XPB;
     if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     const float scale = 1.0f / (float)Geo::N;  // fft.rs:1167
-    hipLaunchKernelGGL(hilbert_fused_kernel<L>, dim3((unsigned)blocks), dim3(Geo::BLOCK), lds, ctx->stream, d_in,
-                       reinterpret_cast<cpx<float> *>(d_out), tw, batch, scale);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Geo::BLOCK), lds, ctx->stream, d_in,
+                       reinterpret_cast<typename P::Out *>(d_out), tw, batch, scale);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
 }
 
-// (the kernel's loads are 4 bytes wide: an input that is not 4-byte aligned takes the composed route)
-inline bool hilbert_fused_ok(const kofft_hip_ctx *ctx, const float *d_in, size_t n)
-{
-    return ctx->hilbert_fused && n >= 32 && n <= 4096 && (reinterpret_cast<size_t>(d_in) & 3) == 0;
-}
-
-inline int hilbert_fused_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+// The fused route of policy P for n = 32 .. 4096 (fused_ok): kernel_of(std::integral_constant<int, L>{}) is P's __global__ entry
+// point for n = 2^L.
+template <class P, class KernelOf>
+int fused_dev(kofft_hip_ctx *ctx, KernelOf kernel_of, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     const cpx<float> *tw = nullptr;
     const int rc = get_table<float>(ctx, Kind<float>::tw, n, &tw);  // get_twiddles(n), the table of the n-point transform
     if (rc) return rc;
+    using std::integral_constant;
     switch (ilog2(n)) {
-    case 5: return launch_hilbert_fused<5>(ctx, d_in, d_out, tw, batch);
-    case 6: return launch_hilbert_fused<6>(ctx, d_in, d_out, tw, batch);
-    case 7: return launch_hilbert_fused<7>(ctx, d_in, d_out, tw, batch);
-    case 8: return launch_hilbert_fused<8>(ctx, d_in, d_out, tw, batch);
-    case 9: return launch_hilbert_fused<9>(ctx, d_in, d_out, tw, batch);
-    case 10: return launch_hilbert_fused<10>(ctx, d_in, d_out, tw, batch);
-    case 11: return launch_hilbert_fused<11>(ctx, d_in, d_out, tw, batch);
-    case 12: return launch_hilbert_fused<12>(ctx, d_in, d_out, tw, batch);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: hilbert_fused_ok)
+    case 5: return launch_fused<5, P>(ctx, kernel_of(integral_constant<int, 5>{}), d_in, d_out, tw, batch);
+    case 6: return launch_fused<6, P>(ctx, kernel_of(integral_constant<int, 6>{}), d_in, d_out, tw, batch);
+    case 7: return launch_fused<7, P>(ctx, kernel_of(integral_constant<int, 7>{}), d_in, d_out, tw, batch);
+    case 8: return launch_fused<8, P>(ctx, kernel_of(integral_constant<int, 8>{}), d_in, d_out, tw, batch);
+    case 9: return launch_fused<9, P>(ctx, kernel_of(integral_constant<int, 9>{}), d_in, d_out, tw, batch);
+    case 10: return launch_fused<10, P>(ctx, kernel_of(integral_constant<int, 10>{}), d_in, d_out, tw, batch);
+    case 11: return launch_fused<11, P>(ctx, kernel_of(integral_constant<int, 11>{}), d_in, d_out, tw, batch);
+    case 12: return launch_fused<12, P>(ctx, kernel_of(integral_constant<int, 12>{}), d_in, d_out, tw, batch);
+    default: return KOFFT_ERR_UNSUPPORTED;  // (never: fused_ok)
     }
 }
 

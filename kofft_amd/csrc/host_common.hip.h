@@ -686,7 +686,7 @@ template <typename T>
 int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch);
 int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
 int hilbert_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: hilbert::hilbert_analytic
-int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_cepstrum_f32.hip: cepstrum::real_cepstrum
+int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: cepstrum::real_cepstrum
 // k_direct_f32.hip: dct::dct1..4 (family 0) / dst::dst1..4 (family 1), the direct sums; direct_check: the argument checks alone
 constexpr size_t kDirectMaxN = 4096;  // the longest row: the n x n table is 64 MiB there
 int direct_check(int family, int type, size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);

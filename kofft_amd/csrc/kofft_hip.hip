@@ -2,6 +2,7 @@
 // include/kofft_hip.h.  The kernels live in the k_*.hip translation units (host_common.hip.h).
 #include "host_common.hip.h"
 
+#include <algorithm>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -117,7 +118,8 @@ int pipeline_chunks(kofft_hip_ctx *ctx, size_t nchunks, Up up, Run run, Down dow
     return rc;
 }
 
-// does a host batch of `bytes` (both directions together) in `batch` independent rows go through the pipeline?
+// does a host batch of `bytes` (both directions together) in `batch` independent rows, `row_bytes` in the smaller of the input and
+// output row, go through the pipeline?
 inline bool use_host_pipeline(const kofft_hip_ctx *ctx, size_t bytes, size_t batch, size_t row_bytes)
 {
     return ctx->host_pipeline && bytes >= (size_t(128) << 20) && batch >= 16 && row_bytes <= (size_t(8) << 20);
@@ -128,6 +130,63 @@ inline size_t host_chunk_rows(const kofft_hip_ctx *ctx, size_t batch)
     return (batch + parts - 1) / parts;
 }
 
+// One host-pointer call over `batch` independent rows: in_row elements of T per input row, out_row per output row (in_place: one
+// device buffer for both), and an optional side input of side_len elements that every row reads (rfft's window), uploaded once.
+// dev(d_in, d_out, d_side, rows) enqueues the device work for `rows` rows on ctx->stream.  Three ways through:
+//  * zero-copy, when zero_copy_ok and neither direction (input + side input up, output down) is above kZeroCopyMax: the rows go
+//    through the pinned, device-mapped buffer as [input | side | output], 256-byte aligned pieces;
+//  * pipelined (use_host_pipeline, when pipeline_ok): pipeline_chunks over the stages, the side input uploaded ahead of the chunks;
+//  * serial: upload, device work, download through the stages.
+template <typename T, class Dev>
+int rows_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t batch, size_t in_row, size_t out_row, bool in_place, const T *side,
+              size_t side_len, bool zero_copy_ok, bool pipeline_ok, Dev dev)
+{
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t in_bytes = batch * in_row * sizeof(T), out_bytes = batch * out_row * sizeof(T);
+    const size_t side_bytes = side ? side_len * sizeof(T) : 0;
+    if (zero_copy_ok && ctx->zero_copy && std::max(in_bytes + side_bytes, out_bytes) <= kZeroCopyMax) {
+        const size_t o_side = (in_bytes + 255) & ~size_t(255);
+        const size_t o_out = in_place ? 0 : (o_side + side_bytes + 255) & ~size_t(255);
+        if (ensure_pinned(ctx, in_place ? in_bytes : o_out + out_bytes) == KOFFT_OK) {
+            char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
+            std::memcpy(h, in, in_bytes);
+            if (side) std::memcpy(h + o_side, side, side_bytes);
+            const T *d_side = side ? reinterpret_cast<const T *>(dd + o_side) : nullptr;
+            int zrc = dev(reinterpret_cast<T *>(dd), reinterpret_cast<T *>(dd + o_out), d_side, batch);
+            if (zrc) return zrc;
+            KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            std::memcpy(out, h + o_out, out_bytes);
+            return KOFFT_OK;
+        }
+    }
+    int rc = ensure_stage(ctx, 0, in_bytes);
+    if (rc) return rc;
+    if (!in_place && (rc = ensure_stage(ctx, 1, out_bytes))) return rc;
+    T *d_in = static_cast<T *>(ctx->stage[0]), *d_out = in_place ? d_in : static_cast<T *>(ctx->stage[1]);
+    const T *d_side = nullptr;
+    if (side) {
+        if ((rc = ensure_stage(ctx, 2, side_bytes))) return rc;
+        d_side = static_cast<const T *>(ctx->stage[2]);
+        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[2], side, side_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (pipeline_ok && use_host_pipeline(ctx, in_bytes + out_bytes, batch, std::min(in_row, out_row) * sizeof(T))) {
+        const size_t chunk = host_chunk_rows(ctx, batch);
+        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
+        const int prc = pipeline_chunks(
+            ctx, (batch + chunk - 1) / chunk,
+            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * in_row, in + c * chunk * in_row, rows(c) * in_row * sizeof(T), hipMemcpyHostToDevice, st); },
+            [&](size_t c) { return dev(d_in + c * chunk * in_row, d_out + c * chunk * out_row, d_side, rows(c)); },
+            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * out_row, d_out + c * chunk * out_row, rows(c) * out_row * sizeof(T), hipMemcpyDeviceToHost, st); });
+        if (prc != KOFFT_ERR_ALLOC) return prc;  // (no helper thread: serial path below)
+    }
+    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = dev(d_in, d_out, d_side, batch);
+    if (rc) return rc;
+    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KOFFT_OK;
+}
+
 template <typename T>
 int fft_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inverse)
 {
@@ -136,35 +195,8 @@ int fft_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inverse)
     if (n > (size_t(1) << (is_pow2(n) ? max_log2_big<T>() : max_log2_big<T>() - 1))) return KOFFT_ERR_UNSUPPORTED;
     if (n == 1) return KOFFT_OK;
     if (!ctx || !data) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = batch * n * 2 * sizeof(T);
-    if (ctx->zero_copy && bytes <= kZeroCopyMax && is_pow2(n) && ensure_pinned(ctx, bytes) == KOFFT_OK) {
-        std::memcpy(ctx->pinned, data, bytes);
-        int zrc = fft_dev<T>(ctx, static_cast<T *>(ctx->pinned_dev), static_cast<T *>(ctx->pinned_dev), n, batch, inverse);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(data, ctx->pinned, bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, bytes);
-    if (rc) return rc;
-    T *d = static_cast<T *>(ctx->stage[0]);
-    if (use_host_pipeline(ctx, 2 * bytes, batch, n * 2 * sizeof(T))) {
-        const size_t chunk = host_chunk_rows(ctx, batch), row = n * 2;
-        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
-        const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d + c * chunk * row, data + c * chunk * row, rows(c) * row * sizeof(T), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return fft_dev<T>(ctx, d + c * chunk * row, d + c * chunk * row, n, rows(c), inverse); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(data + c * chunk * row, d + c * chunk * row, rows(c) * row * sizeof(T), hipMemcpyDeviceToHost, st); });
-        if (prc != KOFFT_ERR_ALLOC) return prc;  // (no helper thread: serial path below)
-    }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = fft_dev<T>(ctx, d, d, n, batch, inverse);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return rows_host<T>(ctx, data, data, batch, 2 * n, 2 * n, true, nullptr, 0, is_pow2(n), true,
+                        [&](T *d_in, T *d_out, const T *, size_t rows) { return fft_dev<T>(ctx, d_in, d_out, n, rows, inverse); });
 }
 
 // ScalarFftImpl::fft_radix4 on a host buffer (fft_radix4.hip.h); inverse: FftPlan::ifft's loop around it (fft.rs:2040-2055)
@@ -220,97 +252,22 @@ int rfft_host(kofft_hip_ctx *ctx, const T *in, T *out, const T *window, size_t n
     const size_t m = n / 2;
     if (!complex_len_ok(m)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_bytes = batch * n * sizeof(T), out_bytes = batch * (m + 1) * 2 * sizeof(T);
-    if (ctx->zero_copy && in_bytes + out_bytes + n * sizeof(T) <= kZeroCopyMax &&
-        ensure_pinned(ctx, in_bytes + out_bytes + n * sizeof(T) + 512) == KOFFT_OK) {
-        // [input | window | output] in the pinned, device-mapped buffer (256-byte aligned pieces)
-        const size_t o_win = (in_bytes + 255) & ~size_t(255), o_out = (o_win + n * sizeof(T) + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        std::memcpy(h, in, in_bytes);
-        if (window) std::memcpy(h + o_win, window, n * sizeof(T));
-        int zrc = rfft_dev<T>(ctx, reinterpret_cast<const T *>(dd), reinterpret_cast<T *>(dd + o_out),
-                              window ? reinterpret_cast<const T *>(dd + o_win) : nullptr, n, batch);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, out_bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, in_bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, out_bytes);
-    if (rc) return rc;
-    T *d_win = nullptr;
-    if (window) {
-        rc = ensure_stage(ctx, 2, n * sizeof(T));
-        if (rc) return rc;
-        d_win = static_cast<T *>(ctx->stage[2]);
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_win, window, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (use_host_pipeline(ctx, in_bytes + out_bytes, batch, n * sizeof(T))) {
-        const size_t chunk = host_chunk_rows(ctx, batch), orow = (m + 1) * 2;
-        T *d_in = static_cast<T *>(ctx->stage[0]), *d_out = static_cast<T *>(ctx->stage[1]);
-        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
-        const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * n, in + c * chunk * n, rows(c) * n * sizeof(T), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return rfft_dev<T>(ctx, d_in + c * chunk * n, d_out + c * chunk * orow, d_win, n, rows(c)); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * orow, d_out + c * chunk * orow, rows(c) * orow * sizeof(T), hipMemcpyDeviceToHost, st); });
-        if (prc != KOFFT_ERR_ALLOC) return prc;
-    }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[0], in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = rfft_dev<T>(ctx, static_cast<const T *>(ctx->stage[0]), static_cast<T *>(ctx->stage[1]), d_win, n, batch);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->stage[1], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return rows_host<T>(ctx, in, out, batch, n, (m + 1) * 2, false, window, n, true, true,
+                        [&](T *d_in, T *d_out, const T *d_win, size_t rows) { return rfft_dev<T>(ctx, d_in, d_out, d_win, n, rows); });
 }
 
-// DctPlanner::plan_dct2 on host rows: the staging of rfft_host (zero-copy for small calls, the upload / kernel / download
-// pipeline for large ones), rows of n reals in and out
+// DctPlanner::plan_dct2 on host rows of n reals in and out
 int dct2_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
 {
     if (batch == 0) return KOFFT_OK;
     if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = batch * n * sizeof(float);
-    if (ctx->zero_copy && 2 * bytes <= kZeroCopyMax && ensure_pinned(ctx, 2 * bytes + 256) == KOFFT_OK) {
-        const size_t o_out = (bytes + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        std::memcpy(h, in, bytes);
-        int zrc = dct2_dev(ctx, reinterpret_cast<const float *>(dd), reinterpret_cast<float *>(dd + o_out), n, batch);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, bytes);
-    if (rc) return rc;
-    float *d_in = static_cast<float *>(ctx->stage[0]), *d_out = static_cast<float *>(ctx->stage[1]);
-    if (use_host_pipeline(ctx, 2 * bytes, batch, n * sizeof(float))) {
-        const size_t chunk = host_chunk_rows(ctx, batch);
-        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
-        const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * n, in + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return dct2_dev(ctx, d_in + c * chunk * n, d_out + c * chunk * n, n, rows(c)); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * n, d_out + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyDeviceToHost, st); });
-        if (prc != KOFFT_ERR_ALLOC) return prc;
-    }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = dct2_dev(ctx, d_in, d_out, n, batch);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, true,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return dct2_dev(ctx, d_in, d_out, n, rows); });
 }
 
-// hilbert::hilbert_analytic on host rows: dct2_host's staging (zero-copy for small calls, the upload / kernel / download pipeline
-// for large ones); rows of n reals in, rows of n complex out -- twice the input's bytes
+// hilbert::hilbert_analytic on host rows of n reals in, n complex out
 int hilbert_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
 {
     if (batch == 0) return KOFFT_OK;
@@ -318,43 +275,11 @@ int hilbert_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size
     if (!is_pow2(n)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
     if (n > (size_t(1) << max_log2_big<float>())) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_bytes = batch * n * sizeof(float), out_bytes = 2 * in_bytes;
-    if (ctx->zero_copy && out_bytes <= kZeroCopyMax && ensure_pinned(ctx, in_bytes + out_bytes + 256) == KOFFT_OK) {
-        const size_t o_out = (in_bytes + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        std::memcpy(h, in, in_bytes);
-        int zrc = hilbert_dev(ctx, reinterpret_cast<const float *>(dd), reinterpret_cast<float *>(dd + o_out), n, batch);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, out_bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, in_bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, out_bytes);
-    if (rc) return rc;
-    float *d_in = static_cast<float *>(ctx->stage[0]), *d_out = static_cast<float *>(ctx->stage[1]);
-    if (use_host_pipeline(ctx, in_bytes + out_bytes, batch, n * sizeof(float))) {
-        const size_t chunk = host_chunk_rows(ctx, batch), orow = 2 * n;
-        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
-        const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * n, in + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return hilbert_dev(ctx, d_in + c * chunk * n, d_out + c * chunk * orow, n, rows(c)); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * orow, d_out + c * chunk * orow, rows(c) * orow * sizeof(float), hipMemcpyDeviceToHost, st); });
-        if (prc != KOFFT_ERR_ALLOC) return prc;
-    }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = hilbert_dev(ctx, d_in, d_out, n, batch);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return rows_host<float>(ctx, in, out, batch, n, 2 * n, false, nullptr, 0, true, true,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return hilbert_dev(ctx, d_in, d_out, n, rows); });
 }
 
-// cepstrum::real_cepstrum on host rows: hilbert_host's staging (zero-copy for small calls, the upload / kernel / download pipeline
-// for large ones); rows of n reals in, rows of n reals out -- the input's bytes
+// cepstrum::real_cepstrum on host rows of n reals in and out
 int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
 {
     if (batch == 0) return KOFFT_OK;
@@ -362,70 +287,19 @@ int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, siz
     if (!is_pow2(n)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
     if (n > (size_t(1) << max_log2_big<float>())) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = batch * n * sizeof(float);
-    if (ctx->zero_copy && bytes <= kZeroCopyMax && ensure_pinned(ctx, 2 * bytes + 256) == KOFFT_OK) {
-        const size_t o_out = (bytes + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        std::memcpy(h, in, bytes);
-        int zrc = cepstrum_dev(ctx, reinterpret_cast<const float *>(dd), reinterpret_cast<float *>(dd + o_out), n, batch);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, bytes);
-    if (rc) return rc;
-    float *d_in = static_cast<float *>(ctx->stage[0]), *d_out = static_cast<float *>(ctx->stage[1]);
-    if (use_host_pipeline(ctx, 2 * bytes, batch, n * sizeof(float))) {
-        const size_t chunk = host_chunk_rows(ctx, batch);
-        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
-        const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * n, in + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return cepstrum_dev(ctx, d_in + c * chunk * n, d_out + c * chunk * n, n, rows(c)); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * n, d_out + c * chunk * n, rows(c) * n * sizeof(float), hipMemcpyDeviceToHost, st); });
-        if (prc != KOFFT_ERR_ALLOC) return prc;
-    }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = cepstrum_dev(ctx, d_in, d_out, n, batch);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, true,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return cepstrum_dev(ctx, d_in, d_out, n, rows); });
 }
 
-// dct::dct1..4 / dst::dst1..4 on host rows: zero-copy for small calls, else one upload / kernel / download through the stages.  The
-// whole input is on the device before any output is written back, so in == out works (the reference's batch_* are in place).
+// dct::dct1..4 / dst::dst1..4 on host rows of n reals in and out
 int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float *out, size_t n, size_t batch)
 {
     int rc = direct_check(family, type, n, batch, in, out, ctx);
     if (rc || batch == 0 || n == 0) return rc;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = batch * n * sizeof(float);
-    if (ctx->zero_copy && bytes <= kZeroCopyMax && ensure_pinned(ctx, 2 * bytes + 256) == KOFFT_OK) {
-        const size_t o_out = (bytes + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        std::memcpy(h, in, bytes);
-        rc = direct_dev(ctx, family, type, reinterpret_cast<const float *>(dd), reinterpret_cast<float *>(dd + o_out), n, batch);
-        if (rc) return rc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, bytes);
-        return KOFFT_OK;
-    }
-    rc = ensure_stage(ctx, 0, bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, bytes);
-    if (rc) return rc;
-    float *d_in = static_cast<float *>(ctx->stage[0]), *d_out = static_cast<float *>(ctx->stage[1]);
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = direct_dev(ctx, family, type, d_in, d_out, n, batch);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    // No pipeline: the whole input is on the device before any output is written back, so in == out works (the reference's
+    // batch_* are in place).
+    return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, false,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return direct_dev(ctx, family, type, d_in, d_out, n, rows); });
 }
 
 template <typename T>
@@ -437,39 +311,8 @@ int irfft_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t n, size_t batch)
     const size_t m = n / 2;
     if (!complex_len_ok(m)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_bytes = batch * (m + 1) * 2 * sizeof(T), out_bytes = batch * n * sizeof(T);
-    if (ctx->zero_copy && in_bytes + out_bytes <= kZeroCopyMax && ensure_pinned(ctx, in_bytes + out_bytes + 256) == KOFFT_OK) {
-        const size_t o_out = (in_bytes + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        std::memcpy(h, in, in_bytes);
-        int zrc = irfft_dev<T>(ctx, reinterpret_cast<const T *>(dd), reinterpret_cast<T *>(dd + o_out), n, batch);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, out_bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, in_bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, out_bytes);
-    if (rc) return rc;
-    if (use_host_pipeline(ctx, in_bytes + out_bytes, batch, n * sizeof(T))) {
-        const size_t chunk = host_chunk_rows(ctx, batch), irow = (m + 1) * 2;
-        T *d_in = static_cast<T *>(ctx->stage[0]), *d_out = static_cast<T *>(ctx->stage[1]);
-        auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
-        const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * irow, in + c * chunk * irow, rows(c) * irow * sizeof(T), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return irfft_dev<T>(ctx, d_in + c * chunk * irow, d_out + c * chunk * n, n, rows(c)); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * n, d_out + c * chunk * n, rows(c) * n * sizeof(T), hipMemcpyDeviceToHost, st); });
-        if (prc != KOFFT_ERR_ALLOC) return prc;
-    }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[0], in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = irfft_dev<T>(ctx, static_cast<const T *>(ctx->stage[0]), static_cast<T *>(ctx->stage[1]), n, batch);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->stage[1], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return rows_host<T>(ctx, in, out, batch, (m + 1) * 2, n, false, nullptr, 0, true, true,
+                        [&](T *d_in, T *d_out, const T *, size_t rows) { return irfft_dev<T>(ctx, d_in, d_out, n, rows); });
 }
 
 // Host-pointer STFT of frames starting at start0, start0+hop, ...: uploads only the samples

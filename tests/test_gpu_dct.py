@@ -125,18 +125,27 @@ def test_dct2_non_pow2(fft32, oracle, n):
         _check(fft32, x, what=f"n={n} batch={batch}")
 
 
-def test_dct2_host_equals_dev(fft32, oracle):
-    """The host entry point and the device-pointer entry point give the same bytes (zero-copy, staged and chunked sizes)."""
+def test_dct2_host_equals_dev(fft32, oracle, monkeypatch):
+    """The host entry point and the device-pointer entry point give the same bytes: zero-copy (400 KiB each way at n = 1024, batch
+    100: the per-direction limit), staged, and (in a context with the host pipeline on) a batch of 128 MiB each way that goes up
+    and down in eight chunks."""
     import torch
+    import kofft_amd
 
-    for n, batch in [(8, 5), (1024, 300), (100, 70), (4096, 20000)]:
+    monkeypatch.setenv("KOFFT_HIP_HOST_PIPELINE", "1")  # read when the context is created
+    piped = kofft_amd.HipFftImpl(np.float32)
+    cases = [(fft32, 8, 5), (fft32, 1024, 100), (fft32, 1024, 300), (fft32, 100, 70), (fft32, 4096, 20000), (piped, 4096, 8192 + 5)]
+    for f, n, batch in cases:
         x = seeded(6700 + n).uniform(-1, 1, (batch, n)).astype(np.float32)
-        host = fft32.dct2_batch(x)
+        host = f.dct2_batch(x)
         d_in = torch.from_numpy(x).cuda()
         d_out = torch.empty_like(d_in)
-        fft32.dct2_dev(d_in.data_ptr(), d_out.data_ptr(), n, batch)
-        fft32.synchronize()
+        f.dct2_dev(d_in.data_ptr(), d_out.data_ptr(), n, batch)
+        f.synchronize()
         assert bits_equal(d_out.cpu().numpy(), host), f"n={n} batch={batch}"
+        r = _rows(batch)
+        assert bits_equal(host[r], dct2_ref(x[r])), f"n={n} batch={batch}"
+    piped.close()
 
 
 def test_dct2_planner(oracle):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal, rand_c, seeded
+from dct_oracle import dct2_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -205,6 +206,37 @@ def test_host_pipeline_on_every_entry_point(oracle, monkeypatch):
     assert bits_equal(yz, oracle.fft(xz)) and bits_equal(iz, oracle.ifft(yz))
     assert bits_equal(rw, oracle.rfft(xr, win)) and bits_equal(rp, oracle.rfft(xr))
     assert bits_equal(back, oracle.irfft(rp, 4096)) and bits_equal(rd, oracle.rfft(xd))
+
+
+def test_zero_copy_up_to_the_limit_in_each_direction(fft32, oracle):
+    """kZeroCopyMax is per direction: a host call whose upload (input + window) and download are each at most 512 KiB goes through
+    the pinned, device-mapped buffer even when the two together are more.  dct2, rfft (with a row window) and irfft at n = 1024,
+    batch 100 -- about 400 KiB each way -- byte for byte against the device-pointer form and the oracle."""
+    import torch
+
+    n, batch = 1024, 100
+    rng = seeded(4343)
+    x = rng.uniform(-1, 1, (batch, n)).astype(np.float32)
+    win = rng.uniform(0.1, 1, n).astype(np.float32)
+    d_x, d_win = torch.from_numpy(x).cuda(), torch.from_numpy(win).cuda()
+
+    spec = fft32.rfft_batch(x, win)
+    d_spec = torch.empty((batch, n // 2 + 1), dtype=torch.complex64, device="cuda")
+    fft32.rfft_dev(d_x.data_ptr(), d_spec.data_ptr(), d_win.data_ptr(), n, batch)
+    fft32.synchronize()
+    assert bits_equal(d_spec.cpu().numpy(), spec) and bits_equal(spec, oracle.rfft(x, win)), "rfft"
+
+    back = fft32.irfft_batch(spec, n)
+    d_back = torch.empty_like(d_x)
+    fft32.irfft_dev(d_spec.data_ptr(), d_back.data_ptr(), n, batch)
+    fft32.synchronize()
+    assert bits_equal(d_back.cpu().numpy(), back) and bits_equal(back, oracle.irfft(spec, n)), "irfft"
+
+    dct = fft32.dct2_batch(x)
+    d_dct = torch.empty_like(d_x)
+    fft32.dct2_dev(d_x.data_ptr(), d_dct.data_ptr(), n, batch)
+    fft32.synchronize()
+    assert bits_equal(d_dct.cpu().numpy(), dct) and bits_equal(dct, dct2_ref(x)), "dct2"
 
 
 @pytest.mark.parametrize("kind,dtype,n,batch", [
