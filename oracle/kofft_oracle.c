@@ -162,6 +162,121 @@ int ko_stft_magnitudes_f32(const float *samples, size_t len, size_t win_len, siz
     return rc;
 }
 
+/* ---- direct DCT-I..IV (dct.rs:108-176) / DST-I..IV (dst.rs:89-146), f32 ------------------------------------------------------
+ * The reference's loops: for every k, sum = seed; for i in its range, sum += x[i] * f(angle(i, k)), f = cos (DCT) / sin (DST),
+ * angle in f32 in the reference's order of operations, f32::cos / f32::sin = glibc cosf / sinf on linux-gnu.  Here the angle
+ * table is made once per (family, type, n) and the sum runs over increasing i for a block of outputs k at a time (vectorised over
+ * k only; with -ffp-contract=off every term is one rounded multiply and one rounded add, like the reference's). */
+static int direct_kind_ok(int family, int type) { return (family == 0 || family == 1) && type >= 1 && type <= 4; }
+
+/* the i of the inner loop: dct1 take(n - 1).skip(1); dct3 / dst3 skip(1); the rest every i */
+static void direct_i_range(int family, int type, size_t n, size_t *lo, size_t *hi)
+{
+    *lo = 0;
+    *hi = n;
+    if (family == 0 && type == 1) {
+        *lo = 1;
+        *hi = n > 1 ? n - 1 : 1;
+    } else if (type == 3) {
+        *lo = 1;
+    }
+}
+
+static float direct_angle(int family, int type, float nf, float fi, float fk)
+{
+    const float pi = 3.14159265358979323846f; /* core::f32::consts::PI */
+    if (family == 0) {
+        if (type == 1) return ((pi / (nf - 1.0f)) * fi) * fk;       /* factor * i as f32 * k as f32 */
+        const float f = pi / nf;
+        if (type == 2) return (f * (fi + 0.5f)) * fk;
+        if (type == 3) return (f * fi) * (fk + 0.5f);
+        return (f * (fi + 0.5f)) * (fk + 0.5f);
+    }
+    if (type == 1) return ((fi + 1.0f) * (fk + 1.0f)) * (pi / (nf + 1.0f)); /* (i + 1) * (k + 1) * factor */
+    const float f = pi / nf;
+    if (type == 2) return (f * (fi + 0.5f)) * (fk + 1.0f);
+    if (type == 3) return (f * (fk + 0.5f)) * fi;
+    return (f * (fi + 0.5f)) * (fk + 0.5f);
+}
+
+int ko_direct_table_rows_f32(int family, int type, size_t n, size_t first, size_t count, float *out)
+{
+    if (!direct_kind_ok(family, type)) return KO_ERR_INVALID_VALUE;
+    size_t lo, hi;
+    direct_i_range(family, type, n, &lo, &hi);
+    const float nf = (float)n;
+    for (size_t r = 0; r < count; ++r) {
+        const size_t i = first + r;
+        float *row = out + r * n;
+        if (i < lo || i >= hi) {
+            for (size_t k = 0; k < n; ++k) row[k] = 0.0f;
+            continue;
+        }
+        for (size_t k = 0; k < n; ++k) {
+            const float a = direct_angle(family, type, nf, (float)i, (float)k);
+            row[k] = family == 0 ? cosf(a) : sinf(a);
+        }
+    }
+    return KO_OK;
+}
+
+int ko_direct_table_f32(int family, int type, size_t n, float *out)
+{
+    return ko_direct_table_rows_f32(family, type, n, 0, n, out);
+}
+
+#define DIRECT_ROWS 16  /* rows of x per block: each table row is read once per block */
+#define DIRECT_COLS 512 /* outputs per block: DIRECT_ROWS x DIRECT_COLS running sums stay in L1 / L2 */
+
+int ko_direct_tab_f32(const float *table, int family, int type, const float *x, float *out, size_t n, size_t batch)
+{
+    if (!direct_kind_ok(family, type)) return KO_ERR_INVALID_VALUE;
+    if (n == 0) return KO_OK;
+    size_t lo, hi;
+    direct_i_range(family, type, n, &lo, &hi);
+    const int dct1 = family == 0 && type == 1;
+    for (size_t b0 = 0; b0 < batch; b0 += DIRECT_ROWS) {
+        const size_t nb = batch - b0 < DIRECT_ROWS ? batch - b0 : DIRECT_ROWS;
+        for (size_t k0 = 0; k0 < n; k0 += DIRECT_COLS) {
+            const size_t nk = n - k0 < DIRECT_COLS ? n - k0 : DIRECT_COLS;
+            /* the seed: dct1 input[0] + (+-input[n - 1]) (n == 1: input[0] * 2.0), dct3 / dst3 input[0] / 2.0, else +0 */
+            for (size_t b = 0; b < nb; ++b) {
+                const float *xr = x + (b0 + b) * n;
+                float *acc = out + (b0 + b) * n + k0;
+                for (size_t k = 0; k < nk; ++k) {
+                    float s = 0.0f;
+                    if (dct1)
+                        s = n == 1 ? xr[0] * 2.0f : (((k0 + k) % 2 == 0) ? xr[0] + xr[n - 1] : xr[0] + (-xr[n - 1]));
+                    else if (type == 3)
+                        s = xr[0] / 2.0f;
+                    acc[k] = s;
+                }
+            }
+            for (size_t i = lo; i < hi; ++i) {
+                const float *c = table + i * n + k0;
+                for (size_t b = 0; b < nb; ++b) {
+                    const float xi = dct1 ? 2.0f * x[(b0 + b) * n + i] : x[(b0 + b) * n + i];
+                    float *acc = out + (b0 + b) * n + k0;
+                    for (size_t k = 0; k < nk; ++k) acc[k] = acc[k] + xi * c[k];
+                }
+            }
+        }
+    }
+    return KO_OK;
+}
+
+int ko_direct_f32(int family, int type, const float *x, float *out, size_t n, size_t batch)
+{
+    if (!direct_kind_ok(family, type)) return KO_ERR_INVALID_VALUE;
+    if (n == 0) return KO_OK;
+    float *table = (float *)malloc(n * n * sizeof(float));
+    if (!table) return KO_ERR_ALLOC;
+    int rc = ko_direct_table_f32(family, type, n, table);
+    if (rc == KO_OK) rc = ko_direct_tab_f32(table, family, type, x, out, n, batch);
+    free(table);
+    return rc;
+}
+
 const char *ko_strerror(int code)
 {
     switch (code) {

@@ -263,3 +263,79 @@ def stft_mt(signal: np.ndarray, window: np.ndarray, hop: int, frames: int, threa
                                      C.c_void_p(out.ctypes.data + first * win.size * 8), _SZ(first), _SZ(count)))
     _run_blocks(frames, threads, work)
     return out
+
+
+def fft_mt(x: np.ndarray, inverse: bool = False, threads: int | None = None) -> np.ndarray:
+    """fft(x, inverse) over the last axis with the batch split over threads: a new array, the same bytes as the serial entry."""
+    s = _sfx(x.dtype)
+    a = np.array(x, _cdt(s), order="C", copy=True)
+    if a.ndim == 0 or a.size == 0:
+        return fft(a, inverse)  # (the serial entry decides what an empty or 0-d input is)
+    fft_inplace_mt(a.reshape(-1, a.shape[-1]), inverse, threads)
+    return a
+
+
+def irfft_mt(x: np.ndarray, n: int, threads: int | None = None) -> np.ndarray:
+    """RfftPlanner::irfft_with_scratch on every row of the [batch, m] complex array: [batch, n] real, the batch split over threads."""
+    s = _sfx(x.dtype)
+    a = np.ascontiguousarray(x, _cdt(s))
+    assert a.ndim == 2
+    batch, m = a.shape
+    if m == 0:
+        return irfft(a, n)  # (the serial entry decides: EmptyInput)
+    out = np.empty((batch, n), _rdt(s))
+    fn = getattr(lib(), f"ko_irfft_batch_{s}")
+
+    def work(first, count):
+        _chk(fn(C.c_void_p(a.ctypes.data + first * m * a.itemsize), C.c_void_p(out.ctypes.data + first * n * out.itemsize),
+                _SZ(n), _SZ(count)))
+    _run_blocks(batch, threads, work)
+    return out
+
+
+# ---- dct::dct1..dct4 (dct.rs:108-176) / dst::dst1..dst4 (dst.rs:89-146): the C restatement, tables made once per kind and length ----
+_FAMILY = {"dct": 0, "dst": 1}
+_direct_tables: dict = {}
+
+
+def direct_table(family: str, type: int, n: int, threads: int | None = None) -> np.ndarray:
+    """C[i][k] of the reference's inner loop as an [n, n] float32 array (rows outside its i range +0); rows split over threads."""
+    key = (family, int(type), int(n))
+    if key not in _direct_tables:
+        if len(_direct_tables) >= 4:  # (an n = 4096 table is 64 MiB and takes a fraction of a second to make)
+            _direct_tables.pop(next(iter(_direct_tables)))
+        t = np.empty((n, n), np.float32)
+
+        def work(first, count):
+            _chk(lib().ko_direct_table_rows_f32(_FAMILY[family], int(type), _SZ(n), _SZ(first), _SZ(count),
+                                                C.c_void_p(t.ctypes.data + first * n * 4)))
+        _run_blocks(n, threads, work)
+        _direct_tables[key] = t
+    return _direct_tables[key]
+
+
+def direct(family: str, type: int, x: np.ndarray) -> np.ndarray:
+    """Every output of every row of the [batch, n] float32 array, one thread (ko_direct_f32: its own table)."""
+    a = np.ascontiguousarray(x, np.float32)
+    assert a.ndim == 2
+    out = np.empty(a.shape, np.float32)
+    _chk(lib().ko_direct_f32(_FAMILY[family], int(type), _p(a), _p(out), _SZ(a.shape[1]), _SZ(a.shape[0])))
+    return out
+
+
+def direct_mt(family: str, type: int, x: np.ndarray, threads: int | None = None) -> np.ndarray:
+    """direct() with the table cached and the batch split over threads: the same bytes."""
+    a = np.ascontiguousarray(x, np.float32)
+    assert a.ndim == 2
+    batch, n = a.shape
+    out = np.empty(a.shape, np.float32)
+    if n == 0:
+        return out
+    t = direct_table(family, type, n, threads)
+    fn = lib().ko_direct_tab_f32
+
+    def work(first, count):
+        _chk(fn(_p(t), _FAMILY[family], int(type), C.c_void_p(a.ctypes.data + first * n * 4),
+                C.c_void_p(out.ctypes.data + first * n * 4), _SZ(n), _SZ(count)))
+    _run_blocks(batch, threads, work)
+    return out

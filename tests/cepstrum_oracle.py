@@ -1,4 +1,4 @@
-"""Expected values of cepstrum::real_cepstrum (cepstrum.rs:12-33), composed from the CPU oracle: the oracle's fft of (x, +0), the
+"""Expected values of cepstrum::real_cepstrum (cepstrum.rs:12-33), composed from the CPU oracle (its threaded entries): the oracle's fft of (x, +0), the
 magnitude sqrt(re * re + im * im) on the .real and .imag views in float32 (one rounding per operation: not hypot), the libm crate's
 logf of mag + 1e-12f (restated below, vectorised), then (l, +0) through the oracle's ifft (conj, fft, conj * 1/n; n == 1 returns
 early) and its real parts.  Written apart from the device's restatement (kofft_amd/csrc/libm_logf.hip.h): the two agreeing bit for bit
@@ -70,11 +70,11 @@ def cepstrum_ref(rows: np.ndarray) -> np.ndarray:
     assert x.ndim == 2 and x.shape[1] > 0 and x.shape[1] & (x.shape[1] - 1) == 0
     freq = np.zeros(x.shape, np.complex64)  # Complex32::new(x, 0.0): imaginary parts +0
     freq.real = x
-    spec = pyoracle.fft(freq)
+    spec = pyoracle.fft_mt(freq)
     re, im = spec.real.copy(), spec.imag.copy()
     with np.errstate(all="ignore"):
         mag = np.sqrt(re * re + im * im)  # float32 throughout: two multiplies, one add, a correctly rounded root
         l = libm_logf((mag + EPS).reshape(-1)).reshape(x.shape)
     logspec = np.zeros(x.shape, np.complex64)  # c.im = 0.0
     logspec.real = l
-    return np.ascontiguousarray(pyoracle.ifft(logspec).real)
+    return np.ascontiguousarray(pyoracle.fft_mt(logspec, inverse=True).real)

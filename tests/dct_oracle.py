@@ -1,4 +1,4 @@
-"""Expected values of DctPlanner::plan_dct2 (dct.rs:61-105), composed from the CPU oracle: the oracle's rfft of the mirrored
+"""Expected values of DctPlanner::plan_dct2 (dct.rs:61-105), composed from the CPU oracle: the oracle's rfft (threaded entry) of the mirrored
 2n-sample rows (dct.rs:77-86), then the f32 twist of dct.rs:87-92 in numpy (float32 arrays: one rounding per operation,
 nothing fused).  The angle's cosine and sine come from glibc's cosf / sinf, which Rust's f32::cos / f32::sin call on
 linux-gnu; this module is test infrastructure, not the library's table (tables.cpp), which tests/test_dct_tables.py checks
@@ -42,7 +42,7 @@ def dct2_ref(rows: np.ndarray) -> np.ndarray:
     assert x.ndim == 2 and x.shape[1] > 0
     n = x.shape[1]
     buf = np.concatenate([x, x[:, ::-1]], axis=1)  # buf[i] = buf[2n-1-i] = x[i]
-    spec = pyoracle.rfft(buf)[:, :n]
+    spec = pyoracle.rfft_mt(buf)[:, :n]
     c, s = cos_sin(n)
     return np.float32(0.5) * (spec.real * c + spec.imag * s)
 

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import bits_equal, seeded
 from dct_oracle import dct2_ref
+from rowcheck import assert_rows_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +27,6 @@ def _persist_rows(log2n, cus):
     return None if per_cu is None else per_cu * cus
 
 
-def _rows(batch):
-    return sorted({0, batch // 2, batch - 1})
-
-
 def _dct_twice(f, x):
     """dct2_batch twice on the same input: the two results must be the same bytes (the session fixture does not wrap it)."""
     a = f.dct2_batch(x)
@@ -38,20 +35,9 @@ def _dct_twice(f, x):
     return a
 
 
-def _nan_safe_equal(got, want):
-    """NaNs in the same places, every other value the same bits (signed zeros, subnormals): an Inf - Inf inside the transform is the
-    platform's default NaN, whose sign differs between x86 (the oracle) and gfx950."""
-    ng, nw = np.isnan(got), np.isnan(want)
-    return got.shape == want.shape and np.array_equal(ng, nw) and got[~ng].tobytes() == want[~nw].tobytes()
-
-
-def _check(f, x, all_rows=True, what=""):
-    got = _dct_twice(f, x)
-    if all_rows:
-        assert bits_equal(got, dct2_ref(x)), what
-    else:
-        r = _rows(x.shape[0])
-        assert bits_equal(got[r], dct2_ref(x[r])), what
+def _check(f, x, what=""):
+    """Every row against the oracle."""
+    assert_rows_equal(_dct_twice(f, x), dct2_ref(x), what)
 
 
 @pytest.mark.parametrize("log2n", range(0, 15))
@@ -64,7 +50,7 @@ def test_dct2_pow2_batch_ladder(fft32, oracle, num_cus, log2n):
         batches.append(p + 1)
     for batch in batches:
         x = seeded(6100 + 37 * log2n + batch).uniform(-1, 1, (batch, n)).astype(np.float32)
-        _check(fft32, x, all_rows=batch * n <= (1 << 22), what=f"n={n} batch={batch}")
+        _check(fft32, x, what=f"n={n} batch={batch}")
 
 
 @pytest.fixture(scope="module")
@@ -88,8 +74,7 @@ def test_dct2_fused_equals_composed(fft32, composed32, oracle, num_cus, log2n):
         fused = _dct_twice(fft32, x)
         composed = _dct_twice(composed32, x)
         assert bits_equal(fused, composed), f"n={n} batch={batch}"
-        r = _rows(batch)
-        assert bits_equal(fused[r], dct2_ref(x[r])), f"n={n} batch={batch}"
+        assert_rows_equal(fused, dct2_ref(x), f"n={n} batch={batch}")
 
 
 def test_dct2_unaligned_device_rows(fft32, oracle):
@@ -109,12 +94,12 @@ def test_dct2_unaligned_device_rows(fft32, oracle):
 
 @pytest.mark.parametrize("log2n", range(15, 21))
 def test_dct2_large_pow2(fft32, oracle, num_cus, log2n):
-    """n = 2^15 .. 2^20: the factor path (and the register-file kernel at 2^15 from CUs x 2 transforms); first, middle and last rows."""
+    """n = 2^15 .. 2^20: the factor path (and the register-file kernel at 2^15 from CUs x 2 transforms); every row."""
     n = 1 << log2n
     batches = [3] + ([2 * num_cus + 1] if log2n == 15 else [])
     for batch in batches:
         x = seeded(6300 + log2n + batch).uniform(-1, 1, (batch, n)).astype(np.float32)
-        _check(fft32, x, all_rows=False, what=f"n={n} batch={batch}")
+        _check(fft32, x, what=f"n={n} batch={batch}")
 
 
 @pytest.mark.parametrize("n", [3, 5, 12, 40, 100, 1000, 4095])
@@ -143,8 +128,7 @@ def test_dct2_host_equals_dev(fft32, oracle, monkeypatch):
         f.dct2_dev(d_in.data_ptr(), d_out.data_ptr(), n, batch)
         f.synchronize()
         assert bits_equal(d_out.cpu().numpy(), host), f"n={n} batch={batch}"
-        r = _rows(batch)
-        assert bits_equal(host[r], dct2_ref(x[r])), f"n={n} batch={batch}"
+        assert_rows_equal(host, dct2_ref(x), f"n={n} batch={batch}")
     piped.close()
 
 
@@ -202,4 +186,4 @@ def test_dct2_special_values(fft32, oracle, n):
     got = _dct_twice(fft32, x)
     want = dct2_ref(x)
     assert np.isnan(want).any()
-    assert _nan_safe_equal(got, want), f"n={n}"
+    assert_rows_equal(got, want, f"n={n}", nan_safe=True)

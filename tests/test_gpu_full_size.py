@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal, seeded
+from rowcheck import assert_rows_equal
 
 
 def same_bits(a: np.ndarray, b: np.ndarray) -> bool:
@@ -144,7 +145,7 @@ def test_cfg4_stft_10min_48k(dev_fft, oracle):
 def test_cfg4_istft_of_the_spectra_full_size(dev_fft, oracle, monkeypatch):
     """SURVEY 8(f) row 1 at the bench's size: ISTFT of config #4's 112 500 spectra (fused inverse transform + overlap-add, seams and tail on
     the ordered overlap-add kernel).  The WHOLE output and scratch against the oracle bit for bit (the C restatement takes ~2 s for
-    115 M points), the frames left behind on a sample, the round trip against the signal, and every byte against the two-kernel route."""
+    115 M points), every frame left behind, the round trip against the signal, and every byte against the two-kernel route."""
     import kofft_amd
 
     fft, stream = dev_fft
@@ -169,8 +170,10 @@ def test_cfg4_istft_of_the_spectra_full_size(dev_fft, oracle, monkeypatch):
         fft.istft_dev(work.data_ptr(), frames, win.data_ptr(), win_len, hop, out.data_ptr(), total, scratch.data_ptr())
         stream.synchronize()
         assert bits_equal(out.cpu().numpy(), want)
-        pick = [0, 1, 2, 3, 219, 220, 221, 56_250, frames - 2, frames - 1]  # (220 frames per workgroup run at 512 workgroups: a seam)
-        assert bits_equal(work[pick].cpu().numpy().view(np.complex64).reshape(len(pick), win_len), oracle.ifft(spec_h[pick]))
+        # every frame (220 frames per workgroup run at 512 workgroups: the seams between the runs included)
+        left = work.cpu().numpy().view(np.complex64).reshape(frames, win_len)
+        assert_rows_equal(left, oracle.fft_mt(spec_h, inverse=True), "istft work frames")
+        del left
         ok = scratch > 1e-3
         assert (out[ok] - sig[ok]).abs().max().item() < 1e-3
         # the two-kernel route: same bytes everywhere
@@ -187,8 +190,8 @@ def test_cfg4_istft_of_the_spectra_full_size(dev_fft, oracle, monkeypatch):
 
 
 def test_bluestein_65536x1000_full_size(dev_fft, oracle, monkeypatch):
-    """SURVEY 8(f) row 4 at the bench's size: 65 536 x 1000-pt c32 through the Bluestein arm (persistent kernel).  A sample of rows against
-    the oracle bit for bit, EVERY row against the one-workgroup-per-transform kernel (KOFFT_HIP_BLUESTEIN_PERSIST=0), and the round trip."""
+    """SURVEY 8(f) row 4 at the bench's size: 65 536 x 1000-pt c32 through the Bluestein arm (persistent kernel).  EVERY row against the
+    oracle bit for bit and against the one-workgroup-per-transform kernel (KOFFT_HIP_BLUESTEIN_PERSIST=0), and the round trip."""
     import kofft_amd
 
     fft, stream = dev_fft
@@ -200,9 +203,9 @@ def test_bluestein_65536x1000_full_size(dev_fft, oracle, monkeypatch):
         y = torch.empty_like(x)
         fft.fft_dev_oop(x.data_ptr(), y.data_ptr(), n, batch)
         stream.synchronize()
-        idx = torch.tensor([0, 1, 2, 1023, 1024, 2047, 2048, 32768, 50_000, 65534, 65535], device="cuda")
-        got = y[idx].cpu().numpy().view(np.complex64).reshape(len(idx), n)
-        assert bits_equal(got, oracle.fft(x[idx].cpu().numpy().view(np.complex64).reshape(len(idx), n)))
+        got = y.cpu().numpy().view(np.complex64).reshape(batch, n)
+        assert_rows_equal(got, oracle.fft_mt(x.cpu().numpy().view(np.complex64).reshape(batch, n)), "bluestein 65536 x 1000")
+        del got
         monkeypatch.setenv("KOFFT_HIP_BLUESTEIN_PERSIST", "0")
         old = kofft_amd.HipFftImpl(np.float32, device=0)
         old.set_stream(stream.cuda_stream)

@@ -8,6 +8,7 @@ import pytest
 
 from conftest import bits_equal, seeded
 from hilbert_oracle import hilbert_ref
+from rowcheck import assert_rows_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +26,6 @@ def _persist_rows(log2n, cus):
     return None if per_cu is None else per_cu * cus
 
 
-def _rows(batch):
-    return sorted({0, batch // 2, batch - 1})
-
-
 def _twice(f, x):
     """hilbert_batch twice on the same input: the two results must be the same bytes."""
     a = f.hilbert_batch(x)
@@ -37,23 +34,10 @@ def _twice(f, x):
     return a
 
 
-def _nan_safe_equal(got, want):
-    """NaNs in the same places, every other value the same bits: an Inf - Inf inside the transform is the platform's default NaN,
-    whose sign differs between x86 (the oracle) and gfx950."""
-    g = got.view(np.float32)
-    w = want.view(np.float32)
-    ng, nw = np.isnan(g), np.isnan(w)
-    return got.shape == want.shape and np.array_equal(ng, nw) and g[~ng].tobytes() == w[~nw].tobytes()
-
-
 def _check(f, x, what=""):
     got = _twice(f, x)
     assert got.dtype == np.complex64 and got.shape == x.shape, what
-    if x.size <= (1 << 22):
-        assert bits_equal(got, hilbert_ref(x)), what
-    else:
-        r = _rows(x.shape[0])
-        assert bits_equal(got[r], hilbert_ref(x[r])), what
+    assert_rows_equal(got, hilbert_ref(x), what)
 
 
 @pytest.fixture(scope="module")
@@ -94,8 +78,7 @@ def test_hilbert_fused_equals_composed(fft32, composed32, oracle, num_cus, log2n
         fused = _twice(fft32, x)
         composed = _twice(composed32, x)
         assert bits_equal(fused, composed), f"n={n} batch={batch}"
-        r = _rows(batch)
-        assert bits_equal(fused[r], hilbert_ref(x[r])), f"n={n} batch={batch}"
+        assert_rows_equal(fused, hilbert_ref(x), f"n={n} batch={batch}")
 
 
 def test_hilbert_unaligned_device_rows(fft32, composed32, oracle):
@@ -130,8 +113,7 @@ def test_hilbert_host_equals_dev(fft32, oracle, monkeypatch):
         f.hilbert_dev(d_in.data_ptr(), d_out.data_ptr(), n, batch)
         f.synchronize()
         assert bits_equal(d_out.cpu().numpy(), host), f"n={n} batch={batch}"
-        r = _rows(batch)
-        assert bits_equal(host[r], hilbert_ref(x[r])), f"n={n} batch={batch}"
+        assert_rows_equal(host, hilbert_ref(x), f"n={n} batch={batch}")
 
 
 def test_hilbert_analytic_free_function(oracle):
@@ -192,4 +174,4 @@ def test_hilbert_special_values(fft32, composed32, oracle, n):
     assert np.isnan(want.view(np.float32)).any()
     for f in (fft32, composed32):
         got = _twice(f, x)
-        assert _nan_safe_equal(got, want), f"n={n}"
+        assert_rows_equal(got, want, f"n={n}", nan_safe=True)

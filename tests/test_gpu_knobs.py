@@ -8,13 +8,15 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal, rand_c, seeded
+from rowcheck import assert_rows_equal
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def _complex(oracle, dtype, n, batch, seed, check=None, inverse=True):
+def _complex(oracle, dtype, n, batch, seed, inverse=True):
+    """fft_batch (and ifft_batch of its result) of a seeded batch: every row against the oracle."""
     import kofft_amd
 
     cdt = np.complex64 if dtype == "c32" else np.complex128
@@ -22,27 +24,21 @@ def _complex(oracle, dtype, n, batch, seed, check=None, inverse=True):
     x = rand_c(seeded(seed), (batch, n), cdt)
     y = x.copy()
     f.fft_batch(y)
-    pick = sorted(set(check if check is not None else range(batch)))
-    want = oracle.fft(x[pick])
-    assert bits_equal(y[pick], want), f"{dtype} n={n} batch={batch}: forward differs"
+    want = oracle.fft_mt(x)
+    assert_rows_equal(y, want, f"{dtype} n={n} batch={batch}: forward")
     if inverse:
         f.fft_batch(y, inverse=True)
-        assert bits_equal(y[pick], oracle.ifft(want)), f"{dtype} n={n} batch={batch}: inverse differs"
-
-
-def _edges(batch):
-    return [0, 1, batch // 2, batch - 2, batch - 1]
+        assert_rows_equal(y, oracle.fft_mt(want, inverse=True), f"{dtype} n={n} batch={batch}: inverse")
 
 
 def case_no_persist(oracle):
     import kofft_amd
 
-    _complex(oracle, "c32", 4096, 1300, 11, check=_edges(1300))
+    _complex(oracle, "c32", 4096, 1300, 11)
     f = kofft_amd.HipFftImpl(np.float32)
     rows = seeded(12).uniform(-1, 1, (2100, 2048)).astype(np.float32)
     win = kofft_amd.hann(2048)
-    pick = _edges(2100)
-    assert bits_equal(f.rfft_batch(rows, win)[pick], oracle.rfft(rows[pick], win))
+    assert_rows_equal(f.rfft_batch(rows, win), oracle.rfft_mt(rows, win), "windowed rfft 2048 x 2100")
     sig = seeded(13).uniform(-1, 1, 300_000).astype(np.float32)
     w1k = kofft_amd.hann(1024)
     frames = -(-sig.size // 256)
@@ -50,9 +46,9 @@ def case_no_persist(oracle):
 
 
 def case_grid_pct(oracle):
-    _complex(oracle, "c32", 4096, 1300, 21, check=_edges(1300))
-    _complex(oracle, "c64", 1 << 16, 300, 22, check=_edges(300), inverse=False)
-    _complex(oracle, "c32", 1000, 4300, 23, check=_edges(4300))  # the persistent Bluestein kernel on half its grid
+    _complex(oracle, "c32", 4096, 1300, 21)
+    _complex(oracle, "c64", 1 << 16, 300, 22, inverse=False)
+    _complex(oracle, "c32", 1000, 4300, 23)  # the persistent Bluestein kernel on half its grid
     case_istft_two_kernels(oracle)                               # the fused ISTFT on half its grid (longer runs, other seams)
 
 
@@ -97,8 +93,8 @@ def case_small32(oracle):
 
 
 def case_big_persist(oracle):
-    _complex(oracle, "c64", 1 << 16, 300, 51, check=_edges(300))
-    _complex(oracle, "c32", 1 << 17, 200, 52, check=_edges(200))
+    _complex(oracle, "c64", 1 << 16, 300, 51)
+    _complex(oracle, "c32", 1 << 17, 200, 52)
 
 
 def case_big_persist_three(oracle):
@@ -137,15 +133,14 @@ def case_rfft_wide(oracle):  # rfft / irfft of 32768 and 16384 reals
     f = kofft_amd.HipFftImpl(np.float32)
     for n, batch in ((32768, 1100), (16384, 1100)):
         rows = seeded(61 + n).uniform(-1, 1, (batch, n)).astype(np.float32)
-        pick = _edges(batch)
         got = f.rfft_batch(rows)
-        assert bits_equal(got[pick], oracle.rfft(rows[pick])), f"rfft {n}"
-        assert bits_equal(f.irfft_batch(got, n)[pick], oracle.irfft(got[pick], n)), f"irfft {n}"
+        assert_rows_equal(got, oracle.rfft_mt(rows), f"rfft {n}")
+        assert_rows_equal(f.irfft_batch(got, n), oracle.irfft_mt(got, n), f"irfft {n}")
 
 
 def case_persist64(oracle):
-    _complex(oracle, "c64", 4096, 1100, 71, check=_edges(1100))
-    _complex(oracle, "c64", 8192, 1100, 72, check=_edges(1100))
+    _complex(oracle, "c64", 4096, 1100, 71)
+    _complex(oracle, "c64", 8192, 1100, 72)
 
 
 def case_persist_small(oracle):
@@ -167,28 +162,27 @@ def case_persist_small(oracle):
 def case_split(oracle):
     import kofft_amd
 
-    _complex(oracle, "c32", 8192, 1100, 91, check=_edges(1100))
-    _complex(oracle, "c32", 16384, 1100, 92, check=_edges(1100))
+    _complex(oracle, "c32", 8192, 1100, 91)
+    _complex(oracle, "c32", 16384, 1100, 92)
     # STFT with an 8192-sample window: fft_persist_kernel<float, 13, .., StftIO> (the wave-split kernel otherwise)
     f = kofft_amd.HipFftImpl(np.float32)
     sig = seeded(93).uniform(-1, 1, 1100 * 2048 + 77).astype(np.float32)
     win = kofft_amd.hann(8192)
     frames = -(-sig.size // 2048)
     got = f.stft_into(sig, win, 2048, frames)
-    for first, count in ((0, 2), (frames // 2, 2), (frames - 4, 4)):
-        assert bits_equal(got[first:first + count], oracle.stft_range(sig, win, 2048, first, count)), (first, count)
+    assert_rows_equal(got, oracle.stft_mt(sig, win, 2048, frames), "stft 8192 / 2048")  # every frame
     mags, mx = f.stft_magnitudes(sig, 8192, 2048)  # ... and <.., StftMagIO>
     want, want_max = oracle.stft_magnitudes(sig, 8192, 2048)
     assert bits_equal(mags, want) and mx == want_max
 
 
 def case_regfile(oracle):
-    _complex(oracle, "c32", 32768, 520, 101, check=_edges(520))
-    _complex(oracle, "c64", 16384, 520, 102, check=_edges(520))
+    _complex(oracle, "c32", 32768, 520, 101)
+    _complex(oracle, "c64", 16384, 520, 102)
 
 
 def case_host_pipeline(oracle):
-    _complex(oracle, "c32", 4096, 5000, 111, check=_edges(5000), inverse=False)  # 160 MB: eight chunks through the pipeline
+    _complex(oracle, "c32", 4096, 5000, 111, inverse=False)  # 160 MB: eight chunks through the pipeline
 
 
 def case_zero_copy(oracle):
@@ -241,8 +235,8 @@ def case_bluestein(oracle):
 
 
 def case_bluestein_persist(oracle):  # large batches: the persistent kernel by default, one workgroup per XPB transforms here
-    _complex(oracle, "c32", 1000, 4200, 155, check=_edges(4200))
-    _complex(oracle, "c64", 60, 66000, 156, check=_edges(66000))
+    _complex(oracle, "c32", 1000, 4200, 155)
+    _complex(oracle, "c64", 60, 66000, 156)
 
 
 def case_istft_two_kernels(oracle):  # a frame count the fused kernel takes by default
@@ -264,17 +258,17 @@ def case_big_narrow(oracle):
 
 
 def case_first11(oracle):
-    _complex(oracle, "c32", 1 << 21, 11, 171, check=[0, 5, 10])
-    _complex(oracle, "c64", 1 << 21, 5, 172, check=[0, 4], inverse=False)
+    _complex(oracle, "c32", 1 << 21, 11, 171)
+    _complex(oracle, "c64", 1 << 21, 5, 172, inverse=False)
 
 
 def case_blocked(oracle):
-    _complex(oracle, "c64", 1 << 17, 40, 181, check=_edges(40))
+    _complex(oracle, "c64", 1 << 17, 40, 181)
 
 
 def case_chunk(oracle):  # several chunks, the last one short
-    _complex(oracle, "c64", 1 << 20, 10, 191, check=[0, 3, 4, 9], inverse=False)
-    _complex(oracle, "c32", 1 << 19, 40, 192, check=[0, 15, 16, 39], inverse=False)
+    _complex(oracle, "c64", 1 << 20, 10, 191, inverse=False)
+    _complex(oracle, "c32", 1 << 19, 40, 192, inverse=False)
 
 
 def case_rfft_regfile_two_passes(oracle):  # rfft of 65536 (f32) / 32768 (f64) reals: one pass by default (post-pass = the kernel's epilogue), two here
@@ -284,9 +278,8 @@ def case_rfft_regfile_two_passes(oracle):  # rfft of 65536 (f32) / 32768 (f64) r
         f = kofft_amd.HipFftImpl(dt)
         rows = seeded(64 + n).uniform(-1, 1, (530, n)).astype(dt)
         win = seeded(65 + n).uniform(0.1, 1, n).astype(dt)
-        pick = _edges(530)
-        assert bits_equal(f.rfft_batch(rows)[pick], oracle.rfft(rows[pick])), f"rfft {n}"
-        assert bits_equal(f.rfft_batch(rows, win)[pick], oracle.rfft(rows[pick], win)), f"windowed rfft {n}"
+        assert_rows_equal(f.rfft_batch(rows), oracle.rfft_mt(rows), f"rfft {n}")
+        assert_rows_equal(f.rfft_batch(rows, win), oracle.rfft_mt(rows, win), f"windowed rfft {n}")
 
 
 def case_probe_off(oracle):  # 160 MiB chunks: K candidate placements of the intermediate timed by default, none here
@@ -297,7 +290,7 @@ def case_probe_off(oracle):  # 160 MiB chunks: K candidate placements of the int
     y = x.copy()
     f.fft_batch(y)
     assert f.big_probe_info()["n"] == 0
-    assert bits_equal(y[[0, 9]], oracle.fft(x[[0, 9]]))
+    assert_rows_equal(y, oracle.fft_mt(x), "c64 2^20 x 10, probe off")
 
 
 KNOBS = [
@@ -366,8 +359,7 @@ def test_placement_probe_of_the_intermediate_runs_once_and_touches_nothing(oracl
         assert info["n"] == 5 and 0 <= info["pick"] < 5, info
         assert info["total_us"][info["pick"]] == min(info["total_us"]) and min(info["first_us"]) > 0, info
         got = d.cpu().numpy().view(cdt).reshape(batch, n)
-        pick = [0, batch // 2, batch - 1]
-        assert bits_equal(got[pick], oracle.fft(x[pick])), f"{cdt.__name__}: in-place result after the probe"
+        assert_rows_equal(got, oracle.fft_mt(x), f"{cdt.__name__}: in-place result after the probe")
         assert fn(f._ctx, C.c_void_p(d.data_ptr()), n, batch, 1) == 0  # no second probe: same figures
         f.synchronize()
         assert f.big_probe_info() == info

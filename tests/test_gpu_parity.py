@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, bits_equal, rand_c, seeded
+from rowcheck import assert_rows_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -416,7 +417,7 @@ def test_fft_c64_large_n(fft64, oracle, log2n, batch):
 def test_large_n_persistent_factor_kernels(fft32, fft64, oracle, dtype, log2n, batch):
     """Batches large enough for the persistent factor kernels (fft_tile_persist_kernel / fft_rows_persist_kernel: every
     resident workgroup walks several tiles, prefetching the next; the last factor keeps its table entries resident per row
-    tile): forward and inverse, the first / middle / last transforms bit for bit against the oracle, Parseval on all."""
+    tile): forward and inverse, every transform bit for bit against the oracle, Parseval on all."""
     n = 1 << log2n
     cdt = np.complex128 if dtype == "c64" else np.complex64
     fft = fft64 if dtype == "c64" else fft32
@@ -424,15 +425,13 @@ def test_large_n_persistent_factor_kernels(fft32, fft64, oracle, dtype, log2n, b
     x = rand_c(rng, (batch, n), cdt)
     y = x.copy()
     fft.fft_batch(y)
-    pick = sorted({0, 1, batch // 2, batch - 1})
-    want = oracle.fft(x[pick])
-    tol = REL_TOL_F64 if dtype == "c64" else REL_TOL_F32
-    assert_parity(y[pick], want, f"persistent factors {dtype} 2^{log2n}", tol)
+    want = oracle.fft_mt(x)
+    assert_rows_equal(y, want, f"persistent factors {dtype} 2^{log2n} x {batch}")
     ex = (np.abs(x) ** 2).sum(axis=1, dtype=np.float64)
     ey = (np.abs(y) ** 2).sum(axis=1, dtype=np.float64) / n
     assert np.max(np.abs(ey - ex) / ex) < (1e-8 if dtype == "c64" else 3e-3)  # the recurrence tables drift (2^22 f64: 1.1e-9)
     fft.fft_batch(y, inverse=True)
-    assert_parity(y[pick], oracle.ifft(want), f"persistent factors inverse {dtype} 2^{log2n}", tol)
+    assert_rows_equal(y, oracle.fft_mt(want, inverse=True), f"persistent factors inverse {dtype} 2^{log2n} x {batch}")
 
 
 @pytest.mark.parametrize("dtype,log2n,batch", [("c32", 15, 515), ("c64", 14, 520), ("c32", 15, 1030), ("c64", 14, 777)])
@@ -497,7 +496,7 @@ def test_c32_last_factor_on_row_pairs(oracle, log2n, batch, monkeypatch):
     (f32x2 "scalars": every operation elementwise, each row with its own table entry) through the c64 kernel's structure, 16-row tiles,
     128-byte runs on both sides; the first factor interleaves the rows of a pair in the intermediate (blk_r = 1).
     KOFFT_HIP_BIG_ROW_PAIRS=0 keeps one row per thread slot.  EVERY transform of the batch byte for byte between the two routes, forward
-    and inverse; first / middle / last against the oracle."""
+    and inverse; every transform against the oracle."""
     import kofft_amd
 
     n = 1 << log2n
@@ -513,10 +512,9 @@ def test_c32_last_factor_on_row_pairs(oracle, log2n, batch, monkeypatch):
         f.fft_batch(z, inverse=True)
         outs.append((y, z))
     assert bits_equal(outs[0][0], outs[1][0]) and bits_equal(outs[0][1], outs[1][1])
-    pick = [0, batch // 2, batch - 1]
-    want = oracle.fft(x[pick])
-    assert_parity(outs[0][0][pick], want, f"row pairs c32 2^{log2n}", REL_TOL_F32)
-    assert_parity(outs[0][1][pick], oracle.ifft(want), f"row pairs inverse c32 2^{log2n}", REL_TOL_F32)
+    want = oracle.fft_mt(x)
+    assert_rows_equal(outs[0][0], want, f"row pairs c32 2^{log2n} x {batch}")
+    assert_rows_equal(outs[0][1], oracle.fft_mt(want, inverse=True), f"row pairs inverse c32 2^{log2n} x {batch}")
 
 
 @pytest.mark.parametrize("log2n,batch", [(14, 70), (15, 33), (17, 40), (19, 20), (20, 10)])
@@ -524,7 +522,7 @@ def test_c64_factor_intermediate_layouts_agree(oracle, log2n, batch, monkeypatch
     """Round 4: between the two persistent factor kernels the c64 intermediate is block-interleaved (BigColsIO::out_lane: one
     contiguous 1 KiB run per wavefront store, the last factor's row tile one contiguous stream); KOFFT_HIP_BIG_BLOCKED=0 keeps
     the natural matrix layout.  Same butterflies either way: EVERY transform of the batch byte for byte, forward and inverse,
-    and the first / last against the oracle."""
+    and every transform against the oracle."""
     import kofft_amd
 
     n = 1 << log2n
@@ -539,10 +537,9 @@ def test_c64_factor_intermediate_layouts_agree(oracle, log2n, batch, monkeypatch
         f.fft_batch(z, inverse=True)
         outs.append((y, z))
     assert bits_equal(outs[0][0], outs[1][0]) and bits_equal(outs[0][1], outs[1][1])
-    pick = [0, batch - 1]
-    want = oracle.fft(x[pick])
-    assert_parity(outs[0][0][pick], want, f"blocked intermediate c64 2^{log2n}", REL_TOL_F64)
-    assert_parity(outs[0][1][pick], oracle.ifft(want), f"blocked intermediate inverse c64 2^{log2n}", REL_TOL_F64)
+    want = oracle.fft_mt(x)
+    assert_rows_equal(outs[0][0], want, f"blocked intermediate c64 2^{log2n} x {batch}")
+    assert_rows_equal(outs[0][1], oracle.fft_mt(want, inverse=True), f"blocked intermediate inverse c64 2^{log2n} x {batch}")
 
 
 # ---- real / STFT lengths beyond the fused kernels: composed from fft_dev ------------------------------
@@ -580,28 +577,27 @@ def test_pointwise_factors_folded_into_the_factor_kernels(oracle, fused):
         del os.environ["KOFFT_HIP_BLUESTEIN_FUSED"]
     rng = seeded(6100)
     x = rand_c(rng, (160, 20000))            # m = 65536: two factors, 160 * 256 columns
-    pick = [0, 1, 77, 159]
     y = x.copy()
     f32.fft_batch(y)
-    assert bits_equal(y[pick], oracle.fft(x[pick]))
+    assert_rows_equal(y, oracle.fft_mt(x), f"bluestein c32 n=20000 fused={fused}")
     y = x.copy()
     f32.fft_batch(y, inverse=True)
-    assert bits_equal(y[pick], oracle.ifft(x[pick]))
+    assert_rows_equal(y, oracle.fft_mt(x, inverse=True), f"bluestein inverse c32 n=20000 fused={fused}")
     xd = rand_c(rng, (96, 9001), np.complex128)   # m = 32768 in f64
     yd = xd.copy()
     f64.fft_batch(yd)
-    assert bits_equal(yd[[0, 50, 95]], oracle.fft(xd[[0, 50, 95]]))
+    assert_rows_equal(yd, oracle.fft_mt(xd), f"bluestein c64 n=9001 fused={fused}")
     yd = xd.copy()
     f64.fft_batch(yd, inverse=True)
-    assert bits_equal(yd[[0, 50, 95]], oracle.ifft(xd[[0, 50, 95]]))
+    assert_rows_equal(yd, oracle.fft_mt(xd, inverse=True), f"bluestein inverse c64 n=9001 fused={fused}")
     r = rng.uniform(-1, 1, (80, 65536)).astype(np.float32)   # rfft: m = 32768 complex, window folded into the first factor
     win = rng.uniform(0, 1, 65536).astype(np.float32)
     got = f32.rfft_batch(r, win)
-    assert bits_equal(got[[0, 41, 79]], oracle.rfft(r[[0, 41, 79]], win))
+    assert_rows_equal(got, oracle.rfft_mt(r, win), f"windowed rfft f32 n=65536 fused={fused}")
     rd = rng.uniform(-1, 1, (70, 32768))                        # f64: m = 16384
     wd = rng.uniform(0, 1, 32768)
     gd = f64.rfft_batch(rd, wd)
-    assert bits_equal(gd[[0, 69]], oracle.rfft(rd[[0, 69]], wd))
+    assert_rows_equal(gd, oracle.rfft_mt(rd, wd), f"windowed rfft f64 n=32768 fused={fused}")
 
 
 @pytest.mark.parametrize("n,batch", [(12, 5), (1000, 4), (65536, 2), (34, 3)])
@@ -728,8 +724,7 @@ def test_istft_fused_kernel_large_frame_counts(oracle, monkeypatch, win_len, hop
     scratch = np.full(out_len, 7.0, np.float32)
     K.istft(frames, window, hop, out, scratch, f)
     assert_parity(out, want, f"fused istft win={win_len} hop={hop} frames={nframes}", REL_TOL_F32)
-    pick = sorted({0, 1, 2, 3, 4, nframes // 2, nframes - 3, nframes - 2, nframes - 1})
-    assert_parity(frames[pick], oracle.ifft(spec[pick]), "fused istft leaves the inverse-transformed frames behind", REL_TOL_F32)
+    assert_rows_equal(frames, oracle.fft_mt(spec, inverse=True), f"fused istft leaves the inverse-transformed frames behind win={win_len} hop={hop} frames={nframes}")
     # against the two-kernel route, accumulating into a non-zero output (stft.rs:144: output[..] +=)
     base = rng.uniform(-1, 1, out_len).astype(np.float32)
     out_f, scr_f, fr_f = base.copy(), np.zeros(out_len, np.float32), spec.copy()
@@ -972,7 +967,7 @@ def test_bluestein_one_launch_and_two_launch_routes(oracle, one_kernel, monkeypa
 def test_bluestein_persistent_kernel_large_batches(oracle, dtype, n, batch):
     """Batches that give every workgroup of the chip-sized grid several transforms run bluestein_persist_kernel (twiddles and fft(b) in
     registers, next input prefetched): m = 32 ... 8192 (c32), m = 32 ... 4096 (c64), ragged last round, forward and inverse,
-    first / last / middle rows against the oracle and every row against the one-workgroup-per-transform kernel (small batches)."""
+    every row against the oracle and a sample of rows against the one-workgroup-per-transform kernel (small batches)."""
     import kofft_amd
 
     cdt = np.complex64 if dtype == "c32" else np.complex128
@@ -980,16 +975,15 @@ def test_bluestein_persistent_kernel_large_batches(oracle, dtype, n, batch):
     x = rand_c(seeded(2300 + n), (batch, n), cdt)
     y = x.copy()
     f.fft_batch(y)
-    pick = sorted({0, 1, 2, batch // 3, batch // 2, batch - 3, batch - 2, batch - 1})
-    want = oracle.fft(x[pick])
-    assert_parity(y[pick], want, f"bluestein persistent fft {dtype} n={n}", REL_TOL_F32 if dtype == "c32" else REL_TOL_F64)
-    # every row: the same rows in small batches (the non-persistent kernel, itself checked against the oracle above and elsewhere)
+    want = oracle.fft_mt(x)
+    assert_rows_equal(y, want, f"bluestein persistent fft {dtype} n={n} x {batch}")
+    # every 2000th row: the same rows in small batches (the non-persistent kernel, itself checked against the oracle elsewhere)
     step = 64
     rows = np.arange(0, batch, max(1, batch // 2000))
     ref = np.concatenate([_small_batches(f, x[rows[i:i + step]]) for i in range(0, rows.size, step)])
     assert bits_equal(y[rows], ref), f"bluestein persistent vs per-transform kernel {dtype} n={n}"
     f.fft_batch(y, inverse=True)
-    assert_parity(y[pick], oracle.ifft(want), f"bluestein persistent ifft {dtype} n={n}", REL_TOL_F32 if dtype == "c32" else REL_TOL_F64)
+    assert_rows_equal(y, oracle.fft_mt(want, inverse=True), f"bluestein persistent ifft {dtype} n={n} x {batch}")
 
 
 def _small_batches(f, rows):
@@ -1434,9 +1428,8 @@ def test_irfft_dispatch_boundaries(fft32, oracle, n, batch):
     spec = rand_c(rng, (batch, n // 2 + 1))
     spec[:, 0].imag = 0
     spec[:, -1].imag = 0
-    pick = sorted({0, 1, batch // 3, batch - 2, batch - 1})
     got = fft32.irfft_batch(spec, n)
-    assert_parity(got[pick], oracle.irfft(spec[pick], n), f"irfft n={n} batch={batch}", REL_TOL_F32)
+    assert_rows_equal(got, oracle.irfft_mt(spec, n), f"irfft n={n} batch={batch}")
 
 
 @pytest.mark.parametrize("dtype,log2n,batches", [("c32", 17, (1, 2, 3, 5, 8, 9)), ("c32", 15, (1, 4, 15, 17, 33)), ("c64", 16, (1, 2, 7, 9, 31, 33))])

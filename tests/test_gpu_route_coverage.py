@@ -2,8 +2,7 @@
 `rocprofv3 --kernel-trace --stats` and lists the kernel instantiations of libkofft_hip.so that nothing launched: 345 of 867 when it was
 first run (the host pipeline had been cutting the other tests' batches into eight), among them the f64 kernels whose 16-byte stores
 returned wrong real parts in a few transforms per thousand (fft_device.hip.h: b128_store_guard).  Every case below names the kernels
-it is here for; all of them compare with the oracle bit for bit -- every row where the oracle finishes in seconds, otherwise the first,
-middle and last rows of the batch (one kernel instance computes them all; ends and middle cover the grid's ramp and tail).
+it is here for; all of them compare every row with the oracle bit for bit.
 
 The factor path picks its kernels from (log2 n, batch): ONE transform narrows the tiles twice (quarter-width workgroups), a few narrow
 them once or not at all, and from CUs x 32 columns / rows on the persistent factor kernels run -- so every shape comes in three batch
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal, rand_c, seeded
+from rowcheck import assert_rows_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +32,6 @@ def _persist_batch(log2_len):
     """Transforms that give the persistent factor kernels their CUs x 32 units (complex_impl.hip.h: big_persist_min_units) at the
     smaller of the two factors' unit counts, plus one so that the batch is not a multiple of anything."""
     return max(9, (8192 >> (log2_len // 2 - 1)) + 1)
-
-
-def _rows(batch):
-    return sorted({0, batch // 2, batch - 1})
 
 
 def _ladder(log2_len):
@@ -103,14 +99,12 @@ def test_bluestein_large_m_every_tile_width(fft32, fft64, oracle, dtype, log2m):
         x = rand_c(seeded(9400 + 10 * log2m + batch), (batch, n), _cdt(dtype))
         y = x.copy()
         f.fft_batch(y)
-        rows = _rows(batch)
-        want = oracle.fft(x[rows])
-        assert bits_equal(y[rows], want), f"bluestein {dtype} n={n} (m=2^{log2m}) x {batch} forward"
+        assert_rows_equal(y, oracle.fft_mt(x), f"bluestein {dtype} n={n} (m=2^{log2m}) x {batch} forward")
         z = y.copy()
         f.fft_batch(z, inverse=True)
-        assert bits_equal(z[rows], oracle.ifft(y[rows])), f"bluestein {dtype} n={n} (m=2^{log2m}) x {batch} inverse"
-        # the rows the oracle did not see: a second run of the same calls must give the same bytes (a sporadic fault -- round 6's store
-        # hazard hit a few transforms per thousand, elsewhere on every run -- shows as a difference between two runs)
+        assert_rows_equal(z, oracle.fft_mt(y, inverse=True), f"bluestein {dtype} n={n} (m=2^{log2m}) x {batch} inverse")
+        # a second run of the same calls must give the same bytes (a sporadic fault -- round 6's store hazard hit a few transforms per
+        # thousand, elsewhere on every run -- shows as a difference between two runs)
         y2 = x.copy()
         f.fft_batch(y2)
         z2 = y2.copy()
@@ -145,8 +139,7 @@ def test_windowed_rfft_large_n_every_tile_width(fft32, fft64, oracle, dtype, log
         got = f.rfft_batch(x, win)
         assert bits_equal(got, oracle.rfft_mt(x, win)), f"windowed rfft {dtype} n=2^{log2n} x {batch}"  # every row
         back = f.irfft_batch(got, n)
-        rows = _rows(batch)
-        assert bits_equal(back[rows], oracle.irfft(got[rows], n)), f"irfft {dtype} n=2^{log2n} x {batch}"
+        assert_rows_equal(back, oracle.irfft_mt(got, n), f"irfft {dtype} n=2^{log2n} x {batch}")  # every row
         assert bits_equal(back, f.irfft_batch(got, n)), f"irfft {dtype} n=2^{log2n} x {batch}: two runs differ"
 
 

@@ -1,12 +1,14 @@
 """dct::dct1..dct4 / dst::dst1..dst4 on the device, bit for bit against tests/trig_direct_oracle.py.  The tiled kernel
 (direct_tiled_kernel<M>, n >= 64 and batch >= 64) and the simple kernel (direct_simple_kernel<M>: every other shape, and every
-shape in a context with set_direct_tiled(False)) must agree byte for byte on every output; the oracle checks every output for
-n <= 256 and seeded columns (with both ends and every 128-column tile edge) beyond."""
+shape in a context with set_direct_tiled(False)) must agree byte for byte on every output; the oracle checks every output of every
+row: the numpy restatement for n <= 256, the C restatement (oracle/kofft_oracle.c: ko_direct_f32, checked against the numpy one on CPU
+by tests/test_trig_direct_cpu.py) beyond."""
 import numpy as np
 import pytest
 
 from conftest import bits_equal, seeded
-from trig_direct_oracle import KINDS, direct, sample_cols
+from rowcheck import assert_rows_equal
+from trig_direct_oracle import KINDS, direct
 
 pytestmark = pytest.mark.gpu
 
@@ -37,20 +39,12 @@ def _nan_safe_equal(got, want):
     return got.shape == want.shape and np.array_equal(ng, nw) and got[~ng].tobytes() == want[~nw].tobytes()
 
 
-def _cols(n, seed):
-    return None if n <= 256 else sample_cols(n, 24, seed)
+def _check_oracle(got, family, type, x, what, nan_safe=False):
+    """Every output of every row against the oracle."""
+    from oracle import pyoracle
 
-
-def _check_oracle(got, family, type, x, seed, what, nan_safe=False):
-    n = x.shape[1]
-    cols = _cols(n, n)  # (one column sample per n: the oracle's tables are cached per sample)
-    rows = list(range(x.shape[0])) if x.shape[0] <= 8 or n <= 256 else sorted({0, 1, x.shape[0] // 2, x.shape[0] - 2, x.shape[0] - 1})
-    want = direct(family, type, x[rows], cols)
-    g = got[rows] if cols is None else got[rows][:, cols]
-    ok = _nan_safe_equal(g, want) if nan_safe else bits_equal(g, want)
-    if not ok:
-        bad = np.argwhere(g.view(np.uint32) != want.view(np.uint32))[:5]
-        raise AssertionError(f"{what}: first mismatches {bad.tolist()} got {[g[tuple(b)] for b in bad]} want {[want[tuple(b)] for b in bad]}")
+    want = direct(family, type, x) if x.shape[1] <= 256 else pyoracle.direct_mt(family, type, x)
+    assert_rows_equal(got, want, what, nan_safe=nan_safe)
 
 
 @pytest.mark.parametrize("family,type", KINDS)
@@ -61,7 +55,7 @@ def test_bit_exact_and_tiled_equals_simple(fft32, simple32, family, type, n):
         x = seeded(seed).uniform(-1, 1, (batch, n)).astype(np.float32)
         got = _run(fft32, family, type, x)
         assert bits_equal(got, _run(simple32, family, type, x)), f"{family}{type} n={n} batch={batch}: tiled != simple"
-        _check_oracle(got, family, type, x, seed, f"{family}{type} n={n} batch={batch}")
+        _check_oracle(got, family, type, x, f"{family}{type} n={n} batch={batch}")
 
 
 def _special_rows(n, rng):
@@ -88,7 +82,7 @@ def test_special_values(fft32, simple32, family, type, n):
     x = np.concatenate([x] * (1 + 140 // x.shape[0]))[:max(x.shape[0], 140)]  # >= 64 rows: the tiled kernel runs at n >= 64
     got = _run(fft32, family, type, x)
     assert _nan_safe_equal(got, _run(simple32, family, type, x))
-    _check_oracle(got[:10], family, type, x[:10], 13000 + n, f"{family}{type} n={n} specials", nan_safe=True)
+    _check_oracle(got, family, type, x, f"{family}{type} n={n} specials", nan_safe=True)
     if not (family == "dct" and type == 1) and type != 3:
         assert bits_equal(got[0], np.zeros(n, np.float32)), "an all -0 row gives +0 (the +0.0 seed)"
 

@@ -171,3 +171,33 @@ def _functions(listing):
     if cur:
         out.append((cur, lines))
     return out
+
+
+def _c_oracle_rows(n, rng):
+    """Random rows, rows of one special value, and random rows with specials planted: +-0, subnormals, +-Inf, NaN, 3e38."""
+    specials = np.array([0.0, -0.0, 1e-45, -1e-45, 1e-40, -1.2e-38, np.inf, -np.inf, np.nan, 3e38, -3e38], np.float32)
+    rows = [rng.uniform(-1, 1, n).astype(np.float32) for _ in range(3)]
+    rows += [np.full(n, v, np.float32) for v in (-0.0, 0.0, 3e38, 1e-40)]
+    for j in range(len(specials)):
+        r = rng.uniform(-1, 1, n).astype(np.float32)
+        r[rng.choice(n, size=min(n, 1 + j % 3), replace=False)] = specials[j]
+        rows.append(r)
+    rows.append(specials[rng.integers(0, len(specials), n)])
+    return np.stack(rows)
+
+
+@pytest.mark.parametrize("family,type", KINDS)
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 64, 257, 1000, 4096])
+def test_c_oracle_is_the_numpy_restatement(oracle, family, type, n):
+    """oracle/kofft_oracle.c's ko_direct_f32 (the all-rows, all-columns oracle of the device tests beyond n = 256) is a second
+    transcription of the reference's loops: the bytes of trig_direct_oracle.direct, NaNs included, on every column up to n = 257 and
+    on seeded columns (both ends and every 128-column tile edge) beyond."""
+    from trig_direct_oracle import sample_cols
+
+    x = _c_oracle_rows(n, seeded(9700 + n + 10 * type + (5 if family == "dst" else 0)))
+    got = oracle.direct(family, type, x)
+    cols = None if n <= 257 else sample_cols(n, 24, 9800 + n)
+    want = direct(family, type, x, cols)
+    assert (got if cols is None else got[:, cols]).tobytes() == want.tobytes(), f"{family}{type} n={n}"
+    assert oracle.direct_mt(family, type, x, threads=5).tobytes() == got.tobytes()
+    assert oracle.direct_table(family, type, n)[:, cols or slice(None)].tobytes() == table(family, type, n, None, cols).tobytes()
