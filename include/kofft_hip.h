@@ -270,6 +270,55 @@ int kofft_hip_dst_direct_table_f32(int type, size_t n, float *C);
 int kofft_hip_dst_planner_table_f32(int type, size_t n, float *out);
 int kofft_hip_dst_planner_table_f64(int type, size_t n, double *out);
 
+/* ---- wavelets -------------------------------------------------------------------
+ * wavelet::* (wavelet.rs:12-117, 154-567), f32 only like the reference.  The wavelet ids: */
+#define KOFFT_WAVELET_HAAR 0
+#define KOFFT_WAVELET_DB2 1
+#define KOFFT_WAVELET_DB4 2
+#define KOFFT_WAVELET_SYM4 3
+#define KOFFT_WAVELET_COIF1 4
+/* One level, `batch` contiguous rows.  dwt: rows of len samples in; approx and detail: batch rows of len / 2 each (an odd len
+ * contributes len / 2 outputs, its reflection runs over the whole odd length; len == 1 writes nothing), as <name>_forward.  idwt:
+ * rows of n approximations and n details in; out: batch rows of 2n, as <name>_inverse.
+ * Multi level: multi_level_forward / multi_level_inverse with <name>_forward / <name>_inverse (the <name>_forward_multi /
+ * _inverse_multi of the reference).  dwt_multi: approx holds batch rows of a_L; details holds the levels' details finest first, each
+ * level packed [batch][a_l], one level after another, where a_0 = len and a_l = ceil(a_{l-1} / 2) (an odd row is padded with its last
+ * sample before each level; kofft_hip_dwt_multi_lengths gives them).  levels == 0 copies the input to approx (no details; details
+ * may be null).  idwt_multi: approx holds batch rows of n, details the levels' details packed as above, detail_lens[l] (finest
+ * first) long; out: batch rows of n << levels.  Only the first n << (levels - 1 - l) entries of level l's detail rows are read.
+ * The arithmetic is the reference's, term for term, never fused.
+ * Checks, in this order and before the context or the device is touched: a wavelet id outside 0 .. 4 -> INVALID_VALUE; batch == 0
+ * or len / n == 0 -> KOFFT_OK (an empty result, as the reference); idwt_multi: detail_lens null with levels > 0 -> KOFFT_ERR_NULL,
+ * levels > 64 -> KOFFT_ERR_UNSUPPORTED (both before detail_lens is read), then a detail shorter than the approximation it is folded
+ * into -> MISMATCHED_LENGTHS (the reference indexes past its end and panics; with the forward's own lengths this happens exactly
+ * when one of a_1 .. a_{L-1} is odd); an input or output row (or a detail length) over 2^26 floats, or levels > 64 ->
+ * KOFFT_ERR_UNSUPPORTED; a null context or pointer -> KOFFT_ERR_NULL.  _dev: device
+ * pointers, asynchronous on the context's stream; an input that overlaps an output, or two outputs that overlap -> INVALID_VALUE.
+ * Routes, all giving the same bytes: the fused kernels keep every level of rows of up to 16384 samples (dwt_multi: the input;
+ * idwt_multi: the output) in LDS; the per-level route runs the single-level kernels level by level through context scratch.
+ * kofft_hip_set_wavelet_fused(ctx, on): 1 (the default) takes the fused kernels only where they measured faster (per
+ * wavelet and direction, at least two levels); 0 sends every call level by level; 2 takes the fused kernels wherever the row fits
+ * (A/B measurements, tests); anything else -> INVALID_VALUE. */
+int kofft_hip_dwt_f32(kofft_hip_ctx *ctx, int wavelet, const float *in, float *approx, float *detail, size_t len, size_t batch);
+int kofft_hip_dwt_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_in, float *d_approx, float *d_detail, size_t len, size_t batch);
+int kofft_hip_idwt_f32(kofft_hip_ctx *ctx, int wavelet, const float *approx, const float *detail, float *out, size_t n, size_t batch);
+int kofft_hip_idwt_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_approx, const float *d_detail, float *d_out, size_t n, size_t batch);
+int kofft_hip_dwt_multi_f32(kofft_hip_ctx *ctx, int wavelet, const float *in, float *approx, float *details, size_t len, size_t batch,
+                            size_t levels);
+int kofft_hip_dwt_multi_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_in, float *d_approx, float *d_details, size_t len,
+                                size_t batch, size_t levels);
+int kofft_hip_idwt_multi_f32(kofft_hip_ctx *ctx, int wavelet, const float *approx, const float *details, const size_t *detail_lens,
+                             float *out, size_t n, size_t batch, size_t levels);
+int kofft_hip_idwt_multi_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_approx, const float *d_details, const size_t *detail_lens,
+                                 float *d_out, size_t n, size_t batch, size_t levels);
+int kofft_hip_set_wavelet_fused(kofft_hip_ctx *ctx, int on);
+/* Host only: lens[0 .. levels] = len, a_1 .. a_L (levels > 64 -> UNSUPPORTED, lens null -> NULL). */
+int kofft_hip_dwt_multi_lengths(size_t len, size_t levels, size_t *lens);
+/* Host only (tests): the library's coefficients, 8 floats each, +0 past the filter length.  Forward: lo = h (approximation), hi = g
+ * (detail); inverse: lo multiplies the approximation, hi the detail (db2: gk / hk).  Haar has no arrays: all +0.  A wavelet id
+ * outside 0 .. 4 -> INVALID_VALUE; lo or hi null -> NULL. */
+int kofft_hip_wavelet_taps_f32(int wavelet, int inverse, float *lo, float *hi);
+
 /* ---- STFT ---------------------------------------------------------------------
  * stft::stft (stft.rs:76-105): out = frames * win_len complex, contiguous (the
  * reference's &mut [Vec<Complex32>] flattened).  hop == 0 -> INVALID_HOP_SIZE;

@@ -16,6 +16,8 @@
 //   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
 //   kofft::HipFftImpl<float>::dct_direct         dct::dct1..dct4, dct.rs:108-176 (the direct sums)
 //   kofft::HipFftImpl<float>::dst_direct         dst::dst1..dst4, dst.rs:89-146
+//   kofft::HipFftImpl<float>::dwt / idwt         wavelet::<name>_forward / _inverse, wavelet.rs:12-33, 154-535
+//   kofft::HipFftImpl<float>::dwt_multi / idwt_multi   wavelet::multi_level_forward / _inverse, wavelet.rs:54-84
 //
 // Result<(), FftError> becomes kofft::Result (is_ok / is_err / unwrap / unwrap_err).  A negative C-ABI status
 // (HIP failure, unsupported length) has no FftError variant: it throws kofft::DeviceError, the C++ analogue of
@@ -317,6 +319,98 @@ public:
         const size_t n = input.size() / batch;
         if (n == 0) return type == 3 ? Result::Err(FftError::EmptyInput) : Result::Ok();
         return st(fn(ctx_, type, input.data(), output.data(), n, batch));
+    }
+
+    // wavelet::<name>_forward (wavelet.rs:12-21, 154-493; wavelet = KOFFT_WAVELET_HAAR .. COIF1), f32 only like the reference: `batch`
+    // contiguous rows of len samples in; approx and detail become batch rows of len / 2.  InvalidValue for an unknown wavelet;
+    // MismatchedLengths for rows that do not divide the input; rows over 2^26 throw DeviceError.
+    Result dwt(int wavelet, const std::vector<float> &input, std::vector<float> &approx, std::vector<float> &detail, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the wavelet transforms are f32-only (wavelet.rs)");
+        if (wavelet < 0 || wavelet > 4) return Result::Err(FftError::InvalidValue);
+        if (batch == 0 || input.size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t len = input.size() / batch;
+        approx.assign(batch * (len / 2), 0.0f);
+        detail.assign(batch * (len / 2), 0.0f);
+        if (len / 2 == 0) return Result::Ok();
+        return st(kofft_hip_dwt_f32(ctx_, wavelet, input.data(), approx.data(), detail.data(), len, batch));
+    }
+    // wavelet::<name>_inverse (wavelet.rs:24-33, 190-535): batch rows of n approximations and batch rows of at least n details (the
+    // entries past n are ignored, as in the reference); output becomes batch rows of 2n.  MismatchedLengths for rows that do not
+    // divide the inputs or details shorter than the approximations (the reference panics there).
+    Result idwt(int wavelet, const std::vector<float> &approx, const std::vector<float> &detail, std::vector<float> &output,
+                size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the wavelet transforms are f32-only (wavelet.rs)");
+        if (wavelet < 0 || wavelet > 4) return Result::Err(FftError::InvalidValue);
+        if (batch == 0 || approx.size() % batch != 0 || detail.size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = approx.size() / batch, dn = detail.size() / batch;
+        if (dn < n) return Result::Err(FftError::MismatchedLengths);
+        output.assign(2 * approx.size(), 0.0f);
+        if (n == 0) return Result::Ok();
+        if (dn == n) return st(kofft_hip_idwt_f32(ctx_, wavelet, approx.data(), detail.data(), output.data(), n, batch));
+        return st(kofft_hip_idwt_multi_f32(ctx_, wavelet, approx.data(), detail.data(), &dn, output.data(), n, batch, 1));  // (detail stride dn)
+    }
+    // wavelet::multi_level_forward with <name>_forward (wavelet.rs:54-71, 538-566): approx becomes batch rows of a_L, details[l]
+    // (finest first) batch rows of a_l, a_l = ceil(a_{l-1} / 2) (an odd row is padded with its last sample before each level).
+    Result dwt_multi(int wavelet, const std::vector<float> &input, size_t levels, std::vector<float> &approx,
+                     std::vector<std::vector<float>> &details, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the wavelet transforms are f32-only (wavelet.rs)");
+        if (wavelet < 0 || wavelet > 4) return Result::Err(FftError::InvalidValue);
+        if (batch == 0 || input.size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t len = input.size() / batch;
+        if (levels > 64 || len > (size_t(1) << 26)) return st(KOFFT_ERR_UNSUPPORTED);  // (before anything is allocated)
+        std::vector<size_t> lens(levels + 1);
+        const int lrc = kofft_hip_dwt_multi_lengths(len, levels, lens.data());
+        if (lrc) return st(lrc);
+        size_t total = 0;
+        for (size_t l = 1; l <= levels; ++l) total += lens[l];
+        approx.assign(batch * lens[levels], 0.0f);
+        std::vector<float> packed(batch * total);
+        details.assign(levels, {});
+        if (len != 0) {
+            const Result r = st(kofft_hip_dwt_multi_f32(ctx_, wavelet, input.data(), approx.data(), packed.data(), len, batch, levels));
+            if (r.is_err()) return r;
+        }
+        size_t off = 0;
+        for (size_t l = 1; l <= levels; ++l) {
+            details[l - 1].assign(packed.begin() + off, packed.begin() + off + batch * lens[l]);
+            off += batch * lens[l];
+        }
+        return Result::Ok();
+    }
+    // wavelet::multi_level_inverse with <name>_inverse (wavelet.rs:74-84, 538-566): batch rows of n approximations, details[l] batch
+    // rows each (finest first); output becomes batch rows of n << levels.  MismatchedLengths where the reference would index past a
+    // detail (it panics there) or for rows that do not divide the inputs.
+    Result idwt_multi(int wavelet, const std::vector<float> &approx, const std::vector<std::vector<float>> &details,
+                      std::vector<float> &output, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the wavelet transforms are f32-only (wavelet.rs)");
+        if (wavelet < 0 || wavelet > 4) return Result::Err(FftError::InvalidValue);
+        if (batch == 0 || approx.size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = approx.size() / batch, levels = details.size();
+        std::vector<size_t> lens(levels ? levels : 1);
+        std::vector<float> packed;
+        for (size_t l = 0; l < levels; ++l) {
+            if (details[l].size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+            lens[l] = details[l].size() / batch;
+            packed.insert(packed.end(), details[l].begin(), details[l].end());
+        }
+        if (n == 0) {
+            output.clear();
+            return Result::Ok();
+        }
+        // the output is allocated only for lengths the C ABI takes; otherwise it returns MismatchedLengths or UNSUPPORTED before it
+        // looks at the (null) output
+        const bool fits = levels <= 64 && n <= (size_t(1) << 26) && (n << levels) <= (size_t(1) << 26);
+        float *dst = nullptr;
+        if (fits) {
+            output.assign(batch * (n << levels), 0.0f);
+            dst = output.data();
+        }
+        const float *pd = packed.empty() ? approx.data() : packed.data();
+        return st(kofft_hip_idwt_multi_f32(ctx_, wavelet, approx.data(), pd, lens.data(), dst, n, batch, levels));
     }
 
     // added: contiguous batch (fft::batch over one buffer)

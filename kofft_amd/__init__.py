@@ -8,8 +8,9 @@ from .api import (DctPlanner, DeviceError, fft2d_inplace, fft3d_inplace, flatten
                   batch_inverse, frame, hann, hilbert_analytic, inverse_frame, inverse_parallel, irfft_packed, istft, multi_channel, multi_channel_inverse, new_fft_impl, parallel, real_cepstrum, rfft_packed, stft, stft_magnitudes, stft_multi)
 from ._lib import LibraryMissing, load as load_library
 from . import dct, dst  # noqa: E402  (kofft::dct / kofft::dst: the direct transforms, DstPlanner)
+from . import wavelet  # noqa: E402  (kofft::wavelet: haar, db2, db4, sym4, coif1)
 
 __all__ = ["DctPlanner", "DeviceError", "fft2d_inplace", "fft3d_inplace", "flatten_2d", "flatten_3d", "FftError", "FftPlan", "FftPlanner", "FftStrategy", "HipFftImpl", "HipMulti", "IstftStream", "RfftPlanner", "StftStream",
            "batch", "batch_inverse", "frame", "hann", "hilbert_analytic", "inverse_frame", "inverse_parallel", "irfft_packed", "istft", "multi_channel", "multi_channel_inverse", "new_fft_impl",
-           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_multi", "LibraryMissing", "load_library", "dct", "dst"]
+           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_multi", "LibraryMissing", "load_library", "dct", "dst", "wavelet"]
 __version__ = "0.1.0"

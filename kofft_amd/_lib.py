@@ -86,6 +86,17 @@ SIGNATURES = {
     "kofft_hip_dst_direct_table_f32": (C.c_int, [C.c_int, _sz, C.c_void_p]),
     "kofft_hip_dst_planner_table_f32": (C.c_int, [C.c_int, _sz, C.c_void_p]),
     "kofft_hip_dst_planner_table_f64": (C.c_int, [C.c_int, _sz, C.c_void_p]),
+    "kofft_hip_dwt_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dwt_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_idwt_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_idwt_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dwt_multi_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz, _sz]),
+    "kofft_hip_dwt_multi_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz, _sz]),
+    "kofft_hip_idwt_multi_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz, _sz]),
+    "kofft_hip_idwt_multi_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz, _sz]),
+    "kofft_hip_set_wavelet_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_dwt_multi_lengths": (C.c_int, [_sz, _sz, C.c_void_p]),
+    "kofft_hip_wavelet_taps_f32": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "kofft_hip_stft_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_parallel_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_frame_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p]),

@@ -42,6 +42,7 @@ struct kofft_hip_ctx {
     bool hilbert_fused = true; // kofft_hip_set_hilbert_fused(ctx, 0): analytic signals of every length through the composed route (expand, fft_dev, mask, inverse fft_dev; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
+    int wavelet_fused = 1;    // kofft_hip_set_wavelet_fused: 1 the measured choice (wavelet_use_fused), 0 every multi-level call level by level, 2 the fused kernels wherever they fit (A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
@@ -691,6 +692,20 @@ int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, 
 constexpr size_t kDirectMaxN = 4096;  // the longest row: the n x n table is 64 MiB there
 int direct_check(int family, int type, size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
 int direct_dev(kofft_hip_ctx *ctx, int family, int type, const float *d_in, float *d_out, size_t n, size_t batch);
+// k_wavelet_f32.hip: wavelet::* (haar, db2, db4, sym4, coif1; wavelet_impl.hip.h); *_check: the argument checks alone
+constexpr size_t kWaveletMaxLen = size_t(1) << 26;  // the longest input or output row
+constexpr size_t kWaveletMaxLevels = 64;
+constexpr size_t kWaveletFusedMax = 16384;  // the longest row (forward: input, inverse: output) the fused multi-level kernels keep in LDS
+size_t wavelet_lengths(size_t len, size_t levels, size_t *lens);  // lens[0] = len, lens[l] = ceil(lens[l - 1] / 2); returns sum lens[1..]
+void wavelet_taps(int w, bool inverse, float *lo, float *hi);      // the coefficient table (8 + 8 floats, +0 past the length; haar: none)
+int dwt_check(int w, size_t len, size_t batch, size_t levels, const void *p0, const void *p1, const void *p2, const kofft_hip_ctx *ctx);
+int idwt_check(int w, size_t n, size_t batch, size_t levels, const size_t *dl, const void *p0, const void *p1, const void *p2,
+               const kofft_hip_ctx *ctx);
+int dwt_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_detail, size_t len, size_t batch);
+int idwt_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_detail, float *d_out, size_t n, size_t batch);
+int dwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_details, size_t len, size_t batch, size_t levels);
+int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_details, const size_t *detail_lens, float *d_out,
+                   size_t n, size_t batch, size_t levels);
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

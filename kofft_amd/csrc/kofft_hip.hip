@@ -130,61 +130,115 @@ inline size_t host_chunk_rows(const kofft_hip_ctx *ctx, size_t batch)
     return (batch + parts - 1) / parts;
 }
 
-// One host-pointer call over `batch` independent rows: in_row elements of T per input row, out_row per output row (in_place: one
-// device buffer for both), and an optional side input of side_len elements that every row reads (rfft's window), uploaded once.
-// dev(d_in, d_out, d_side, rows) enqueues the device work for `rows` rows on ctx->stream.  Three ways through:
-//  * zero-copy, when zero_copy_ok and neither direction (input + side input up, output down) is above kZeroCopyMax: the rows go
-//    through the pinned, device-mapped buffer as [input | side | output], 256-byte aligned pieces;
-//  * pipelined (use_host_pipeline, when pipeline_ok): pipeline_chunks over the stages, the side input uploaded ahead of the chunks;
-//  * serial: upload, device work, download through the stages.
+// One host-pointer call over `batch` independent rows of nin input arrays and nout output arrays: in_rows[k] elements of T per row of
+// input k, out_rows[k] per row of output k (in_place: one input, one output, one device buffer for both), and an optional side input
+// of side_len elements that every row reads (rfft's window), uploaded once.  dev(d_ins, d_outs, d_side, rows) enqueues the device work
+// for `rows` rows on ctx->stream; d_ins / d_outs point at each array's first row.  Three ways through:
+//  * zero-copy, when zero_copy_ok and neither direction (inputs + side input up, outputs down) is above kZeroCopyMax: the rows go
+//    through the pinned, device-mapped buffer as [inputs | side | outputs], 256-byte aligned pieces;
+//  * pipelined (use_host_pipeline, when pipeline_ok; every array's rows must be contiguous): pipeline_chunks over the stages, the side
+//    input uploaded ahead of the chunks;
+//  * serial: upload, device work, download through the stages (stage 0: the inputs, stage 1: the outputs, 256-byte aligned pieces).
+constexpr int kMaxRowArrays = 2;
 template <typename T, class Dev>
-int rows_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t batch, size_t in_row, size_t out_row, bool in_place, const T *side,
-              size_t side_len, bool zero_copy_ok, bool pipeline_ok, Dev dev)
+int rows_host_n(kofft_hip_ctx *ctx, size_t batch, int nin, const T *const *ins, const size_t *in_rows, int nout, T *const *outs,
+                const size_t *out_rows, bool in_place, const T *side, size_t side_len, bool zero_copy_ok, bool pipeline_ok, Dev dev)
 {
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_bytes = batch * in_row * sizeof(T), out_bytes = batch * out_row * sizeof(T);
+    auto align = [](size_t b) { return (b + 255) & ~size_t(255); };
+    size_t in_off[kMaxRowArrays], out_off[kMaxRowArrays];  // each array's offset in its piece (zero-copy) or stage
+    size_t in_bytes = 0, out_bytes = 0, in_span = 0, out_span = 0;
+    for (int k = 0; k < nin; ++k) {
+        in_off[k] = align(in_span);
+        in_span = in_off[k] + batch * in_rows[k] * sizeof(T);
+        in_bytes += batch * in_rows[k] * sizeof(T);
+    }
+    for (int k = 0; k < nout; ++k) {
+        out_off[k] = align(out_span);
+        out_span = out_off[k] + batch * out_rows[k] * sizeof(T);
+        out_bytes += batch * out_rows[k] * sizeof(T);
+    }
     const size_t side_bytes = side ? side_len * sizeof(T) : 0;
+    T *d_ins[kMaxRowArrays], *d_outs[kMaxRowArrays];
     if (zero_copy_ok && ctx->zero_copy && std::max(in_bytes + side_bytes, out_bytes) <= kZeroCopyMax) {
-        const size_t o_side = (in_bytes + 255) & ~size_t(255);
-        const size_t o_out = in_place ? 0 : (o_side + side_bytes + 255) & ~size_t(255);
-        if (ensure_pinned(ctx, in_place ? in_bytes : o_out + out_bytes) == KOFFT_OK) {
+        const size_t o_side = align(in_span);
+        const size_t o_out = in_place ? 0 : align(o_side + side_bytes);
+        if (ensure_pinned(ctx, in_place ? in_span : o_out + out_span) == KOFFT_OK) {
             char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-            std::memcpy(h, in, in_bytes);
+            for (int k = 0; k < nin; ++k) {
+                std::memcpy(h + in_off[k], ins[k], batch * in_rows[k] * sizeof(T));
+                d_ins[k] = reinterpret_cast<T *>(dd + in_off[k]);
+            }
             if (side) std::memcpy(h + o_side, side, side_bytes);
             const T *d_side = side ? reinterpret_cast<const T *>(dd + o_side) : nullptr;
-            int zrc = dev(reinterpret_cast<T *>(dd), reinterpret_cast<T *>(dd + o_out), d_side, batch);
+            for (int k = 0; k < nout; ++k) d_outs[k] = reinterpret_cast<T *>(dd + o_out + out_off[k]);
+            int zrc = dev(d_ins, d_outs, d_side, batch);
             if (zrc) return zrc;
             KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            std::memcpy(out, h + o_out, out_bytes);
+            for (int k = 0; k < nout; ++k) std::memcpy(outs[k], h + o_out + out_off[k], batch * out_rows[k] * sizeof(T));
             return KOFFT_OK;
         }
     }
-    int rc = ensure_stage(ctx, 0, in_bytes);
+    int rc = ensure_stage(ctx, 0, in_span);
     if (rc) return rc;
-    if (!in_place && (rc = ensure_stage(ctx, 1, out_bytes))) return rc;
-    T *d_in = static_cast<T *>(ctx->stage[0]), *d_out = in_place ? d_in : static_cast<T *>(ctx->stage[1]);
+    if (!in_place && (rc = ensure_stage(ctx, 1, out_span))) return rc;
+    for (int k = 0; k < nin; ++k) d_ins[k] = reinterpret_cast<T *>(static_cast<char *>(ctx->stage[0]) + in_off[k]);
+    for (int k = 0; k < nout; ++k) d_outs[k] = in_place ? d_ins[0] : reinterpret_cast<T *>(static_cast<char *>(ctx->stage[1]) + out_off[k]);
     const T *d_side = nullptr;
     if (side) {
         if ((rc = ensure_stage(ctx, 2, side_bytes))) return rc;
         d_side = static_cast<const T *>(ctx->stage[2]);
         KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[2], side, side_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (pipeline_ok && use_host_pipeline(ctx, in_bytes + out_bytes, batch, std::min(in_row, out_row) * sizeof(T))) {
+    size_t min_row = SIZE_MAX;
+    for (int k = 0; k < nin; ++k) min_row = std::min(min_row, in_rows[k]);
+    for (int k = 0; k < nout; ++k) min_row = std::min(min_row, out_rows[k]);
+    if (pipeline_ok && use_host_pipeline(ctx, in_bytes + out_bytes, batch, min_row * sizeof(T))) {
         const size_t chunk = host_chunk_rows(ctx, batch);
         auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
         const int prc = pipeline_chunks(
             ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(d_in + c * chunk * in_row, in + c * chunk * in_row, rows(c) * in_row * sizeof(T), hipMemcpyHostToDevice, st); },
-            [&](size_t c) { return dev(d_in + c * chunk * in_row, d_out + c * chunk * out_row, d_side, rows(c)); },
-            [&](size_t c, hipStream_t st) { return hipMemcpyAsync(out + c * chunk * out_row, d_out + c * chunk * out_row, rows(c) * out_row * sizeof(T), hipMemcpyDeviceToHost, st); });
+            [&](size_t c, hipStream_t st) {
+                for (int k = 0; k < nin; ++k) {
+                    const hipError_t e = hipMemcpyAsync(d_ins[k] + c * chunk * in_rows[k], ins[k] + c * chunk * in_rows[k],
+                                                        rows(c) * in_rows[k] * sizeof(T), hipMemcpyHostToDevice, st);
+                    if (e != hipSuccess) return e;
+                }
+                return hipSuccess;
+            },
+            [&](size_t c) {
+                T *ci[kMaxRowArrays], *co[kMaxRowArrays];
+                for (int k = 0; k < nin; ++k) ci[k] = d_ins[k] + c * chunk * in_rows[k];
+                for (int k = 0; k < nout; ++k) co[k] = d_outs[k] + c * chunk * out_rows[k];
+                return dev(ci, co, d_side, rows(c));
+            },
+            [&](size_t c, hipStream_t st) {
+                for (int k = 0; k < nout; ++k) {
+                    const hipError_t e = hipMemcpyAsync(outs[k] + c * chunk * out_rows[k], d_outs[k] + c * chunk * out_rows[k],
+                                                        rows(c) * out_rows[k] * sizeof(T), hipMemcpyDeviceToHost, st);
+                    if (e != hipSuccess) return e;
+                }
+                return hipSuccess;
+            });
         if (prc != KOFFT_ERR_ALLOC) return prc;  // (no helper thread: serial path below)
     }
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = dev(d_in, d_out, d_side, batch);
+    for (int k = 0; k < nin; ++k)
+        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_ins[k], ins[k], batch * in_rows[k] * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    rc = dev(d_ins, d_outs, d_side, batch);
     if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < nout; ++k)
+        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(outs[k], d_outs[k], batch * out_rows[k] * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
     KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KOFFT_OK;
+}
+
+// rows_host_n with one input and one output array: dev(d_in, d_out, d_side, rows)
+template <typename T, class Dev>
+int rows_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t batch, size_t in_row, size_t out_row, bool in_place, const T *side,
+              size_t side_len, bool zero_copy_ok, bool pipeline_ok, Dev dev)
+{
+    return rows_host_n<T>(ctx, batch, 1, &in, &in_row, 1, &out, &out_row, in_place, side, side_len, zero_copy_ok, pipeline_ok,
+                          [&](T *const *d_in, T *const *d_out, const T *d_side, size_t rows) { return dev(d_in[0], d_out[0], d_side, rows); });
 }
 
 template <typename T>
@@ -300,6 +354,62 @@ int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float
     // batch_* are in place).
     return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, false,
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return direct_dev(ctx, family, type, d_in, d_out, n, rows); });
+}
+
+// wavelet::*_forward / *_inverse (one level) and multi_level_forward / _inverse on host rows (k_wavelet_f32.hip)
+int dwt_host(kofft_hip_ctx *ctx, int w, const float *in, float *approx, float *detail, size_t len, size_t batch)
+{
+    int rc = dwt_check(w, len, batch, 0, in, approx, detail, ctx);
+    if (rc || batch == 0 || len / 2 == 0) return rc;
+    const size_t n = len / 2, in_rows[1] = {len}, out_rows[2] = {n, n};
+    float *const outs[2] = {approx, detail};
+    return rows_host_n<float>(ctx, batch, 1, &in, in_rows, 2, outs, out_rows, false, nullptr, 0, true, true,
+                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
+                                  return dwt_dev(ctx, w, d_in[0], d_out[0], d_out[1], len, rows);
+                              });
+}
+
+int idwt_host(kofft_hip_ctx *ctx, int w, const float *approx, const float *detail, float *out, size_t n, size_t batch)
+{
+    const size_t one = n;
+    int rc = idwt_check(w, n, batch, 1, &one, approx, detail, out, ctx);
+    if (rc || batch == 0 || n == 0) return rc;
+    const float *const ins[2] = {approx, detail};
+    const size_t in_rows[2] = {n, n}, out_rows[1] = {2 * n};
+    return rows_host_n<float>(ctx, batch, 2, ins, in_rows, 1, &out, out_rows, false, nullptr, 0, true, true,
+                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
+                                  return idwt_dev(ctx, w, d_in[0], d_in[1], d_out[0], n, rows);
+                              });
+}
+
+// (the details are packed level after level, [batch][a_l] each: not row-contiguous, so no pipeline)
+int dwt_multi_host(kofft_hip_ctx *ctx, int w, const float *in, float *approx, float *details, size_t len, size_t batch, size_t levels)
+{
+    int rc = dwt_check(w, len, batch, levels, in, approx, levels ? details : approx, ctx);
+    if (rc || batch == 0 || len == 0) return rc;
+    size_t lens[kWaveletMaxLevels + 1];
+    const size_t det = wavelet_lengths(len, levels, lens);
+    const size_t in_rows[1] = {len}, out_rows[2] = {lens[levels], det};
+    float *const outs[2] = {approx, details};
+    return rows_host_n<float>(ctx, batch, 1, &in, in_rows, levels ? 2 : 1, outs, out_rows, false, nullptr, 0, true, false,
+                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
+                                  return dwt_multi_dev(ctx, w, d_in[0], d_out[0], levels ? d_out[1] : nullptr, len, rows, levels);
+                              });
+}
+
+int idwt_multi_host(kofft_hip_ctx *ctx, int w, const float *approx, const float *details, const size_t *detail_lens, float *out, size_t n,
+                    size_t batch, size_t levels)
+{
+    int rc = idwt_check(w, n, batch, levels, detail_lens, approx, levels ? details : approx, out, ctx);
+    if (rc || batch == 0 || n == 0) return rc;
+    size_t det = 0;
+    for (size_t l = 0; l < levels; ++l) det += detail_lens[l];
+    const float *const ins[2] = {approx, details};
+    const size_t in_rows[2] = {n, det}, out_rows[1] = {n << levels};
+    return rows_host_n<float>(ctx, batch, levels ? 2 : 1, ins, in_rows, 1, &out, out_rows, false, nullptr, 0, true, false,
+                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
+                                  return idwt_multi_dev(ctx, w, d_in[0], levels ? d_in[1] : nullptr, detail_lens, d_out[0], n, rows, levels);
+                              });
 }
 
 template <typename T>
@@ -681,6 +791,20 @@ int kofft_hip_dst_planner_table_f64(int type, size_t n, double *out)
     kofft_tables::dst_planner_f64(type, n, out);
     return KOFFT_OK;
 }
+int kofft_hip_wavelet_taps_f32(int wavelet, int inverse, float *lo, float *hi)
+{
+    if (wavelet < 0 || wavelet > 4) return KOFFT_ERR_INVALID_VALUE;
+    if (!lo || !hi) return KOFFT_ERR_NULL;
+    wavelet_taps(wavelet, inverse != 0, lo, hi);
+    return KOFFT_OK;
+}
+int kofft_hip_dwt_multi_lengths(size_t len, size_t levels, size_t *lens)
+{
+    if (levels > kWaveletMaxLevels) return KOFFT_ERR_UNSUPPORTED;
+    if (!lens) return KOFFT_ERR_NULL;
+    wavelet_lengths(len, levels, lens);
+    return KOFFT_OK;
+}
 int kofft_hip_hann_f32(size_t len, float *out)
 {
     if (!out && len) return KOFFT_ERR_NULL;
@@ -810,6 +934,49 @@ int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on)
     if (!ctx) return KOFFT_ERR_NULL;
     ctx->direct_tiled = on != 0;
     return KOFFT_OK;
+}
+int kofft_hip_set_wavelet_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (on < 0 || on > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->wavelet_fused = on;
+    return KOFFT_OK;
+}
+int kofft_hip_dwt_f32(kofft_hip_ctx *ctx, int wavelet, const float *in, float *approx, float *detail, size_t len, size_t batch)
+{
+    return dwt_host(ctx, wavelet, in, approx, detail, len, batch);
+}
+int kofft_hip_dwt_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_in, float *d_approx, float *d_detail, size_t len, size_t batch)
+{
+    return dwt_dev(ctx, wavelet, d_in, d_approx, d_detail, len, batch);
+}
+int kofft_hip_idwt_f32(kofft_hip_ctx *ctx, int wavelet, const float *approx, const float *detail, float *out, size_t n, size_t batch)
+{
+    return idwt_host(ctx, wavelet, approx, detail, out, n, batch);
+}
+int kofft_hip_idwt_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_approx, const float *d_detail, float *d_out, size_t n, size_t batch)
+{
+    return idwt_dev(ctx, wavelet, d_approx, d_detail, d_out, n, batch);
+}
+int kofft_hip_dwt_multi_f32(kofft_hip_ctx *ctx, int wavelet, const float *in, float *approx, float *details, size_t len, size_t batch,
+                            size_t levels)
+{
+    return dwt_multi_host(ctx, wavelet, in, approx, details, len, batch, levels);
+}
+int kofft_hip_dwt_multi_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_in, float *d_approx, float *d_details, size_t len,
+                                size_t batch, size_t levels)
+{
+    return dwt_multi_dev(ctx, wavelet, d_in, d_approx, d_details, len, batch, levels);
+}
+int kofft_hip_idwt_multi_f32(kofft_hip_ctx *ctx, int wavelet, const float *approx, const float *details, const size_t *detail_lens,
+                             float *out, size_t n, size_t batch, size_t levels)
+{
+    return idwt_multi_host(ctx, wavelet, approx, details, detail_lens, out, n, batch, levels);
+}
+int kofft_hip_idwt_multi_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d_approx, const float *d_details, const size_t *detail_lens,
+                                 float *d_out, size_t n, size_t batch, size_t levels)
+{
+    return idwt_multi_dev(ctx, wavelet, d_approx, d_details, detail_lens, d_out, n, batch, levels);
 }
 int kofft_hip_dct_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch)
 {
