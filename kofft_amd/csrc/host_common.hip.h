@@ -220,7 +220,8 @@ template <> constexpr int max_log2<float>() { return 14; }
 template <> constexpr int max_log2<double>() { return 13; }
 
 // hipFuncSetAttribute once per (kernel instance, device): `done` is a function-local static of the caller's template
-// instance, one bit per device ordinal.
+// instance, one bit per device ordinal.  Later calls skip it, so `lds` must be the largest the kernel ever takes (a
+// constant of the instance, or its maximum where the LDS depends on the call: launch_fwd_fused).
 inline int set_dyn_lds_once(kofft_hip_ctx *ctx, std::atomic<unsigned long long> &done, const void *kern, size_t lds)
 {
     const unsigned long long bit = 1ull << (ctx->device & 63);

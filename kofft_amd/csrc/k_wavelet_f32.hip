@@ -81,8 +81,14 @@ int launch_fwd_fused(kofft_hip_ctx *ctx, const float *x, float *approx, float *d
     if (rpb > rows) rpb = rows;
     const size_t bufa = (rpb * len + 3) & ~size_t(3);
     const size_t lds = (bufa + rpb * ((len + 1) / 2)) * sizeof(float);
+    // The LDS grows with the row past kWaveletPackFloats (one row per workgroup: 72000 bytes at 12000 samples, 98304 at 16384), but the
+    // attribute is set once per process: it is set to the largest this kernel takes, the kWaveletFusedMax-sample row, whatever row
+    // length comes first.  (Shorter rows pack rpb rows into at most kWaveletPackFloats + kWaveletPackFloats floats: 64 KiB.)
+    constexpr size_t kMaxLds = (((kWaveletFusedMax + 3) & ~size_t(3)) + (kWaveletFusedMax + 1) / 2) * sizeof(float);
+    static_assert(kMaxLds >= 2 * kWaveletPackFloats * sizeof(float) && kMaxLds <= 160 * 1024, "fused forward LDS");
+    if (lds > kMaxLds) return KOFFT_ERR_UNSUPPORTED;  // (never: len <= kWaveletFusedMax, use_fused)
     if (lds > (size_t(64) << 10)) {
-        const int rc = set_dyn_lds_once(ctx, lds_set, reinterpret_cast<const void *>(wavelet_fwd_fused_kernel<W>), lds);
+        const int rc = set_dyn_lds_once(ctx, lds_set, reinterpret_cast<const void *>(wavelet_fwd_fused_kernel<W>), kMaxLds);
         if (rc) return rc;
     }
     const size_t blocks = (rows + rpb - 1) / rpb;
