@@ -47,6 +47,9 @@ def _twice(fn, *args):
 
 # ---- device-form operations: inputs uploaded up front, outputs read after one synchronisation -----------------------------------
 
+PAD = 4
+
+
 class Op:
     """One _dev call on fresh device buffers: enqueue(f) on the context's current stream, check() against the oracle afterwards."""
 
@@ -55,14 +58,15 @@ class Op:
 
         self.what = what
         self.ins = [torch.from_numpy(np.ascontiguousarray(a, F).reshape(-1)).cuda() for a in inputs]
-        self.out = torch.full((max(1, out_floats),), 7.0, dtype=torch.float32, device="cuda")
-        self.out_floats = out_floats
+        self.out = torch.full((out_floats + PAD,), 7.0, dtype=torch.float32, device="cuda")  # PAD floats behind the output: checked by result()
+        self.out_floats, self.fill = out_floats, 7.0
         self.call, self.want, self.out_view = call, want, out_view
 
     def enqueue(self, f):
         self.call(f, *[t.data_ptr() for t in self.ins], self.out.data_ptr())
 
     def result(self):
+        assert bool((self.out[self.out_floats:] == self.fill).all()), f"{self.what}: the padding behind the output was written"
         got = self.out[:self.out_floats].cpu().numpy()
         return self.out_view(got) if self.out_view else got
 
@@ -305,6 +309,7 @@ def test_rowwise_device_calls_can_be_captured_into_a_hip_graph(oracle):
     direct_bytes = [op.result().tobytes() for _, op in plan]
     for _, op in plan:
         op.out.fill_(0.0)
+        op.fill = 0.0
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):

@@ -98,18 +98,24 @@ def _data(rng, shape, specials):
     return x
 
 
+def _padding_holds(torch, t, off, floats, fill):
+    pad = torch.cat([t[:off], t[off + floats:]])
+    assert bool((pad == fill).all()), f"the padding around a {floats}-float device buffer was written (fill {fill})"
+
+
 class Dev:
     """Device copies of host arrays at a chosen float offset from a 16-byte aligned allocation."""
 
     def __init__(self, off):
         import torch
 
-        self.torch, self.off, self.keep = torch, off, []
+        self.torch, self.off, self.keep, self.fill = torch, off, [], {}
 
     def put(self, a):
         t = self.torch.zeros(a.size + self.off + 4, dtype=self.torch.float32, device="cuda")
         t[self.off:self.off + a.size] = self.torch.from_numpy(np.ascontiguousarray(a, F).reshape(-1).view(F)).cuda()
         self.keep.append(t)
+        self.fill[id(t)] = 0.0
         # torch fills and copies on its own stream, the library runs on the context's: both must be done before the call
         self.torch.cuda.synchronize()
         return t.data_ptr() + 4 * self.off
@@ -117,11 +123,17 @@ class Dev:
     def empty(self, floats, fill=7.0):
         t = self.torch.full((floats + self.off + 4,), fill, dtype=self.torch.float32, device="cuda")
         self.keep.append(t)
+        self.fill[id(t)] = fill
         self.torch.cuda.synchronize()
         return t.data_ptr() + 4 * self.off, t
 
+    def check_padding(self, t, floats):
+        """The floats in front of and behind the `floats` the call may write still hold the allocation's fill value."""
+        _padding_holds(self.torch, t, self.off, floats, self.fill[id(t)])
+
     def get(self, t, floats):
         self.torch.cuda.synchronize()
+        self.check_padding(t, floats)
         return t[self.off:self.off + floats].cpu().numpy()
 
 
@@ -177,6 +189,7 @@ def _rowwise_call(f, fam, kind, x, form):
     import torch
 
     torch.cuda.synchronize()
+    _padding_holds(torch, t_out, off, out_floats, 7.0)
     return t_out[off:off + out_floats].cpu().numpy().view(out_dt).reshape(b, n)
 
 
