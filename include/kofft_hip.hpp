@@ -413,6 +413,54 @@ public:
         return st(kofft_hip_idwt_multi_f32(ctx_, wavelet, approx.data(), pd, lens.data(), dst, n, batch, levels));
     }
 
+    // czt::czt_f32 (czt.rs:16-54): batch rows of input.size() / batch reals; output becomes batch rows of m complex bins.  m == 0 gives
+    // an empty output, an empty row m bins of (+0, +0), as in the reference.  MismatchedLengths for rows that do not divide the input.
+    Result czt(const std::vector<float> &input, size_t m, Complex32 w, Complex32 a, std::vector<Complex32> &output, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the chirp-Z transform is f32-only (czt.rs)");
+        if (batch == 0 || input.size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = input.size() / batch;
+        const bool fits = n <= 4096 && m <= 4096;  // beyond: the C ABI returns UNSUPPORTED before it looks at the output
+        output.assign(fits ? batch * m : 0, Complex32::zero());
+        if (m == 0) return Result::Ok();
+        return st(kofft_hip_czt_f32(ctx_, input.data(), reinterpret_cast<float *>(output.data()), n, m, w.re, w.im, a.re, a.im, batch));
+    }
+    // ... on device memory, asynchronous on the context's stream: batch rows of n floats in, batch rows of m complex out; the two must
+    // not overlap (InvalidValue)
+    Result czt_dev(const float *d_in, float *d_out, size_t n, size_t m, Complex32 w, Complex32 a, size_t batch) const
+    {
+        static_assert(std::is_same<T, float>::value, "the chirp-Z transform is f32-only (czt.rs)");
+        return st(kofft_hip_dev_czt_f32(ctx_, d_in, d_out, n, m, w.re, w.im, a.re, a.im, batch));
+    }
+    // 0: by batch and by whether the table is already there; 1 / 2: always sums on the fly / always a device-built table (the same bytes)
+    Result set_czt_route(int mode) const { return st(kofft_hip_set_czt_route(ctx_, mode)); }
+    // goertzel::goertzel_f32 (goertzel.rs:16-36) of batch rows against every one of target_freqs: output becomes batch rows of
+    // target_freqs.size() magnitudes.  EmptyInput for empty rows, then InvalidValue for sample_rate <= 0, as in the reference.
+    Result goertzel(const std::vector<float> &input, float sample_rate, const std::vector<float> &target_freqs, std::vector<float> &output,
+                    size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the Goertzel detector is f32-only (goertzel.rs)");
+        if (batch == 0 || input.size() % batch != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = input.size() / batch;
+        const bool fits = n <= (size_t(1) << 26) && target_freqs.size() <= 1024;
+        output.assign(fits ? batch * target_freqs.size() : 0, 0.0f);
+        return st(kofft_hip_goertzel_f32(ctx_, input.data(), output.data(), n, batch, sample_rate, target_freqs.data(), target_freqs.size()));
+    }
+    // the reference's call: one row, one frequency
+    Result goertzel(const std::vector<float> &input, float sample_rate, float target_freq, float &magnitude) const
+    {
+        std::vector<float> out;
+        Result r = goertzel(input, sample_rate, std::vector<float>{target_freq}, out);
+        if (r.is_ok()) magnitude = out[0];
+        return r;
+    }
+    // ... on device memory (target_freqs stays a host array), asynchronous on the context's stream
+    Result goertzel_dev(const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate, const std::vector<float> &target_freqs) const
+    {
+        static_assert(std::is_same<T, float>::value, "the Goertzel detector is f32-only (goertzel.rs)");
+        return st(kofft_hip_dev_goertzel_f32(ctx_, d_in, d_out, n, batch, sample_rate, target_freqs.data(), target_freqs.size()));
+    }
+
     // added: contiguous batch (fft::batch over one buffer)
     Result fft_batch(std::vector<C> &data, size_t n, bool inverse = false) const
     {

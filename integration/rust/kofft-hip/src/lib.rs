@@ -38,6 +38,11 @@ extern "C" {
                                     win_len: usize, hop: usize, output: *mut f32, out_len: usize) -> c_int;
     fn kofft_hip_stft_magnitudes_f32(ctx: *mut KofftHipCtx, samples: *const f32, len: usize, win_len: usize, hop: usize,
                                      mags: *mut f32, frames: usize, max_mag: *mut f32) -> c_int;
+    fn kofft_hip_czt_f32(ctx: *mut KofftHipCtx, input: *const f32, out: *mut f32, n: usize, m: usize, wr: f32, wi: f32, ar: f32, ai: f32,
+                         batch: usize) -> c_int;
+    fn kofft_hip_goertzel_f32(ctx: *mut KofftHipCtx, input: *const f32, out: *mut f32, n: usize, batch: usize, sample_rate: f32,
+                              target_freqs: *const f32, nfreq: usize) -> c_int;
+    fn kofft_hip_set_czt_route(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
     fn kofft_hip_fftnd_c32(ctx: *mut KofftHipCtx, data: *mut f32, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     fn kofft_hip_fftnd_c64(ctx: *mut KofftHipCtx, data: *mut f64, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     // multi-GPU: one process, one context per device, optional RCCL all-gather (include/kofft_hip.h, "multi-GPU")
@@ -310,6 +315,46 @@ impl HipFftImpl<f32> {
             kofft_hip_stft_magnitudes_f32(self.ctx, samples.as_ptr(), samples.len(), win_len, hop, flat.as_mut_ptr(), frames, &mut max_mag)
         })?;
         Ok((flat.chunks(half.max(1)).take(frames).map(|c| c.to_vec()).collect(), max_mag))
+    }
+}
+
+impl HipFftImpl<f32> {
+    /// `czt::czt_f32` (kofft czt.rs:16-54) with the reference's signature: `m` bins of the chirp-Z transform of one real signal.
+    pub fn czt_f32(&self, input: &[f32], m: usize, w: (f32, f32), a: (f32, f32)) -> Vec<(f32, f32)> {
+        let mut out = vec![(0.0f32, 0.0f32); m];
+        self.czt_batch(input, input.len(), m, w, a, &mut out).expect("one row within the library's bounds (n, m <= 4096)");
+        out
+    }
+
+    /// Batched form: `input` holds rows of `n` reals, `out` as many rows of `m` bins.
+    pub fn czt_batch(&self, input: &[f32], n: usize, m: usize, w: (f32, f32), a: (f32, f32), out: &mut [(f32, f32)]) -> Result<(), FftError> {
+        let batch = if n == 0 { if m == 0 { 0 } else { out.len() / m } } else { input.len() / n };
+        if (n != 0 && input.len() % n != 0) || out.len() != batch * m { return Err(FftError::MismatchedLengths); }
+        status(self.ctx, unsafe {
+            kofft_hip_czt_f32(self.ctx, input.as_ptr(), out.as_mut_ptr() as *mut f32, n, m, w.0, w.1, a.0, a.1, batch)
+        })
+    }
+
+    /// 0: the route chosen by batch and by whether the table is already there; 1: sums on the fly; 2: a device-built table (the same bytes).
+    pub fn set_czt_route(&self, mode: i32) -> Result<(), FftError> {
+        status(self.ctx, unsafe { kofft_hip_set_czt_route(self.ctx, mode as c_int) })
+    }
+
+    /// `goertzel::goertzel_f32` (kofft goertzel.rs:16-36) with the reference's signature and errors.
+    pub fn goertzel_f32(&self, input: &[f32], sample_rate: f32, target_freq: f32) -> Result<f32, FftError> {
+        let mut out = [0.0f32];
+        self.goertzel_batch(input, input.len(), sample_rate, &[target_freq], &mut out)?;
+        Ok(out[0])
+    }
+
+    /// Batched form: rows of `n` samples against every one of `target_freqs`; `out` holds `batch * target_freqs.len()` magnitudes.
+    pub fn goertzel_batch(&self, input: &[f32], n: usize, sample_rate: f32, target_freqs: &[f32], out: &mut [f32]) -> Result<(), FftError> {
+        if n == 0 { return Err(FftError::EmptyInput); }
+        let batch = input.len() / n;
+        if input.len() % n != 0 || out.len() != batch * target_freqs.len() { return Err(FftError::MismatchedLengths); }
+        status(self.ctx, unsafe {
+            kofft_hip_goertzel_f32(self.ctx, input.as_ptr(), out.as_mut_ptr(), n, batch, sample_rate, target_freqs.as_ptr(), target_freqs.len())
+        })
     }
 }
 

@@ -9,8 +9,9 @@ from .api import (DctPlanner, DeviceError, fft2d_inplace, fft3d_inplace, flatten
 from ._lib import LibraryMissing, load as load_library
 from . import dct, dst  # noqa: E402  (kofft::dct / kofft::dst: the direct transforms, DstPlanner)
 from . import wavelet  # noqa: E402  (kofft::wavelet: haar, db2, db4, sym4, coif1)
+from . import czt, goertzel  # noqa: E402  (kofft::czt::czt_f32, kofft::goertzel::goertzel_f32)
 
 __all__ = ["DctPlanner", "DeviceError", "fft2d_inplace", "fft3d_inplace", "flatten_2d", "flatten_3d", "FftError", "FftPlan", "FftPlanner", "FftStrategy", "HipFftImpl", "HipMulti", "IstftStream", "RfftPlanner", "StftStream",
            "batch", "batch_inverse", "frame", "hann", "hilbert_analytic", "inverse_frame", "inverse_parallel", "irfft_packed", "istft", "multi_channel", "multi_channel_inverse", "new_fft_impl",
-           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_multi", "LibraryMissing", "load_library", "dct", "dst", "wavelet"]
+           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_multi", "LibraryMissing", "load_library", "dct", "dst", "wavelet", "czt", "goertzel"]
 __version__ = "0.1.0"

@@ -46,27 +46,29 @@ __device__ __forceinline__ float direct_term_x(float v)
 }
 
 // ---- simple kernel: one lane per (row, k) ---------------------------------------------------------------------------------------
-// A workgroup covers rpb = 256 / n rows (n < 256: lane = row * n + k, one 32-bit division) or 256 outputs k of one row (blockIdx.x
-// walks the k chunks); blockIdx.y strides over the row groups.  (No 64-bit division: its expansion holds v_fmac_f32.)
+// A row holds n inputs and nk outputs (the eight DCT / DST kinds: nk = n; the chirp-Z sums of spectral_impl.hip.h: nk = 2 m, the
+// interleaved complex bins).  A workgroup covers rpb = 256 / nk rows (nk < 256: lane = row * nk + k, one 32-bit division) or 256
+// outputs k of one row (blockIdx.x walks the k chunks); blockIdx.y strides over the row groups.  (No 64-bit division: its expansion
+// holds v_fmac_f32.)
 template <int M>
 __global__ __launch_bounds__(256) void direct_simple_kernel(const float *__restrict__ x, const float *__restrict__ c, float *__restrict__ out,
-                                                            const int n, const int ldc, const int ib, const int ie, const size_t batch,
-                                                            const int rpb)
+                                                            const int n, const int nk, const int ldc, const int ib, const int ie,
+                                                            const size_t batch, const int rpb)
 {
     const unsigned tid = threadIdx.x;
     unsigned r = 0, k = blockIdx.x * 256u + tid;
     if (rpb > 1) {
-        r = tid / (unsigned)n;
-        k = tid - r * (unsigned)n;
+        r = tid / (unsigned)nk;
+        k = tid - r * (unsigned)nk;
         if (r >= (unsigned)rpb) return;
     }
-    if (k >= (unsigned)n) return;
+    if (k >= (unsigned)nk) return;
     const float *ck = c + k;
     for (size_t b = (size_t)blockIdx.y * rpb + r; b < batch; b += (size_t)gridDim.y * rpb) {
         const float *xr = x + b * n;
         float acc = direct_init<M>(xr, n, (int)k);
         for (int i = ib; i < ie; ++i) acc = acc + direct_term_x<M>(xr[i]) * ck[(size_t)i * ldc];
-        out[b * n + k] = acc;
+        out[b * nk + k] = acc;
     }
 }
 
@@ -82,8 +84,8 @@ typedef float dt_f4 __attribute__((ext_vector_type(4)));
 
 template <int M>
 __global__ __launch_bounds__(256) void direct_tiled_kernel(const float *__restrict__ x, const float *__restrict__ c, float *__restrict__ out,
-                                                           const int n, const int ldc, const int ib, const int ie, const size_t batch,
-                                                           const unsigned ktiles, const bool vec_out)
+                                                           const int n, const int nk, const int ldc, const int ib, const int ie,
+                                                           const size_t batch, const unsigned ktiles, const bool vec_out)
 {
     __shared__ __attribute__((aligned(16))) float xs[DT_KC][DT_XS];
     __shared__ __attribute__((aligned(16))) float cs[DT_KC][DT_BN];
@@ -169,26 +171,26 @@ __global__ __launch_bounds__(256) void direct_tiled_kernel(const float *__restri
         __syncthreads();
     }
 
-    // 16-byte stores (vec_out: n % 4 == 0 and a 16-byte aligned output) through b128_store_guard, else 4-byte ones
+    // 16-byte stores (vec_out: nk % 4 == 0 and a 16-byte aligned output) through b128_store_guard, else 4-byte ones
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const size_t row = row0 + rr(r);
         if (row >= batch) continue;
-        float *orow = out + row * n;
+        float *orow = out + row * nk;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int k = k0 + kc(2 * h);
             const dt_f4 v = dt_f4{acc[r][2 * h].x, acc[r][2 * h].y, acc[r][2 * h + 1].x, acc[r][2 * h + 1].y};
-            if (vec_out && k + 4 <= n) {
+            if (vec_out && k + 4 <= nk) {
                 typedef unsigned v4u __attribute__((ext_vector_type(4)));
                 const v4u bits = __builtin_bit_cast(v4u, v);
                 *reinterpret_cast<v4u *>(orow + k) = bits;
                 b128_store_guard(bits);
             } else {
-                if (k < n) orow[k] = v.x;
-                if (k + 1 < n) orow[k + 1] = v.y;
-                if (k + 2 < n) orow[k + 2] = v.z;
-                if (k + 3 < n) orow[k + 3] = v.w;
+                if (k < nk) orow[k] = v.x;
+                if (k + 1 < nk) orow[k + 1] = v.y;
+                if (k + 2 < nk) orow[k + 2] = v.z;
+                if (k + 3 < nk) orow[k + 3] = v.w;
             }
         }
     }
@@ -231,34 +233,37 @@ inline int get_direct_table(kofft_hip_ctx *ctx, int family, int type, size_t n, 
     return KOFFT_OK;
 }
 
-// Where a tile would be mostly padding the simple kernel runs (the crossover measured with tools/bench_trig_direct.py)
-inline bool direct_use_tiled(const kofft_hip_ctx *ctx, size_t n, size_t batch)
+// Where a tile would be mostly padding the simple kernel runs (the crossover measured with tools/bench_trig_direct.py);
+// nk: the outputs per row
+inline bool direct_use_tiled(const kofft_hip_ctx *ctx, size_t nk, size_t batch)
 {
-    return ctx->direct_tiled && n >= 64 && batch >= 64;
+    return ctx->direct_tiled && nk >= 64 && batch >= 64;
 }
 
 template <int M>
-int launch_direct(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *table, size_t n, size_t batch, size_t ib, size_t ie)
+int launch_direct(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *table, size_t n, size_t nk, size_t batch, size_t ib,
+                  size_t ie)
 {
-    const int ldc = (int)direct_ldc(n);
-    if (direct_use_tiled(ctx, n, batch)) {
+    const int ldc = (int)direct_ldc(nk);
+    if (direct_use_tiled(ctx, nk, batch)) {
         const unsigned ktiles = (unsigned)(ldc / DT_BN);
-        const bool vec_out = (n % 4) == 0 && (reinterpret_cast<size_t>(d_out) & 15) == 0;
+        const bool vec_out = (nk % 4) == 0 && (reinterpret_cast<size_t>(d_out) & 15) == 0;
         // row tiles per launch: a grid of at most 2^30 workgroups
         const size_t max_rows = (size_t(1) << 30) / ktiles * DT_BM;
         for (size_t b0 = 0; b0 < batch; b0 += max_rows) {
             const size_t nb = batch - b0 < max_rows ? batch - b0 : max_rows;
             const size_t blocks = (nb + DT_BM - 1) / DT_BM * ktiles;
-            hipLaunchKernelGGL(direct_tiled_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_in + b0 * n, table, d_out + b0 * n,
-                               (int)n, ldc, (int)ib, (int)ie, nb, ktiles, vec_out);
+            hipLaunchKernelGGL(direct_tiled_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_in + b0 * n, table, d_out + b0 * nk,
+                               (int)n, (int)nk, ldc, (int)ib, (int)ie, nb, ktiles, vec_out);
             KOFFT_HIP_TRY(ctx, hipGetLastError());
         }
         return KOFFT_OK;
     }
-    const int rpb = n < 256 ? (int)(256 / n) : 1;
+    const int rpb = nk < 256 ? (int)(256 / nk) : 1;
     const size_t groups = (batch + rpb - 1) / rpb;
-    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(groups < 65535 ? groups : 65535));
-    hipLaunchKernelGGL(direct_simple_kernel<M>, grid, dim3(256), 0, ctx->stream, d_in, table, d_out, (int)n, ldc, (int)ib, (int)ie, batch, rpb);
+    const dim3 grid((unsigned)((nk + 255) / 256), (unsigned)(groups < 65535 ? groups : 65535));
+    hipLaunchKernelGGL(direct_simple_kernel<M>, grid, dim3(256), 0, ctx->stream, d_in, table, d_out, (int)n, (int)nk, ldc, (int)ib, (int)ie, batch,
+                       rpb);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
 }

@@ -30,6 +30,14 @@
 // context
 // ---------------------------------------------------------------------------------
 #define KOFFT_BIG_PROBE_MAX 8  /* candidates of the intermediate's placement probe (big_probe_pick) */
+// One cached chirp-Z parameter set (k_spectral_f32.hip): key = (n, m, bits of wr, wi, ar, ai), compared whole; d_small = [wpow: 2 m |
+// apow: 2 n] floats, d_table = the n x ldc table once a call has taken the table route.
+struct kofft_spectral_slot {
+    std::vector<unsigned> key;
+    void *d_small = nullptr;
+    void *d_table = nullptr;
+};
+constexpr size_t kSpectralSlots = 4;  // a 4096 x 4096 chirp-Z table is 128 MiB
 struct kofft_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -43,6 +51,7 @@ struct kofft_hip_ctx {
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     int wavelet_fused = 1;    // kofft_hip_set_wavelet_fused: 1 the measured choice (wavelet_use_fused), 0 every multi-level call level by level, 2 the fused kernels wherever they fit (A/B, tests)
+    int czt_route = 0;        // kofft_hip_set_czt_route: 0 by batch and by whether the table is there (czt_use_table), 1 every call on czt_recur_kernel<CZT_SUM>, 2 every call through a table and the direct kernels (A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
@@ -79,6 +88,12 @@ struct kofft_hip_ctx {
     // 2/3 = RfftPlanner post-pass table f32/f64, 13 = DctPlanner (cos, sin) table f32, 20 .. 27 = the direct DCT / DST tables
     // (direct_impl.hip.h).
     std::map<std::pair<int, size_t>, void *> tables;
+    // chirp-Z tables: most recently used first, at most kSpectralSlots; an evicted slot is freed after the stream is synchronised.
+    // goertzel_coeff: the device-pointer Goertzel's coefficients (kGoertzelMaxFreqs floats), goertzel_last what it holds.
+    // kofft_hip_destroy and kofft_hip_release_scratch drop all of it (spectral_drop)
+    std::vector<kofft_spectral_slot> czt_slots;
+    void *goertzel_coeff = nullptr;
+    std::vector<float> goertzel_last;
     // staging for the host-pointer entry points
     void *stage[3] = {nullptr, nullptr, nullptr};
     size_t stage_bytes[3] = {0, 0, 0};
@@ -707,6 +722,21 @@ int idwt_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_de
 int dwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_details, size_t len, size_t batch, size_t levels);
 int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_details, const size_t *detail_lens, float *d_out,
                    size_t n, size_t batch, size_t levels);
+// k_direct_f32.hip: the +0-seeded sums out[b][k] = sum_i x[b][i] * table[i][k], i < n, k < nk, on direct_tiled_kernel<DIR_ZERO> /
+// direct_simple_kernel<DIR_ZERO> (direct_use_tiled(ctx, nk, batch)); table: n rows of direct_ldc(nk) floats
+int direct_zero_sums(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *table, size_t n, size_t nk, size_t batch);
+// k_spectral_f32.hip: czt::czt_f32 and goertzel::goertzel_f32 (spectral_impl.hip.h); *_check: the argument checks alone
+constexpr size_t kCztMax = 4096;                       // the longest row and the most bins: the table is 128 MiB there
+constexpr size_t kGoertzelMaxLen = size_t(1) << 26;
+constexpr size_t kGoertzelMaxFreqs = 1024;
+int czt_check(size_t n, size_t m, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
+int czt_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch);
+int goertzel_check(size_t n, size_t batch, float sample_rate, const void *freqs, size_t nfreq, const void *in, const void *out,
+                   const kofft_hip_ctx *ctx);
+int goertzel_launch(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *d_coeff, size_t n, size_t batch, size_t nfreq);
+int goertzel_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate, const float *target_freqs,
+                 size_t nfreq);
+void spectral_drop(kofft_hip_ctx *ctx);  // frees every slot and the coefficient buffer; the caller has synchronised the stream
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

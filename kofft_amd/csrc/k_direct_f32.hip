@@ -30,9 +30,14 @@ int direct_dev(kofft_hip_ctx *ctx, int family, int type, const float *d_in, floa
     if (rc) return rc;
     size_t ib, ie;
     kofft_tables::direct_range(family, type, n, &ib, &ie);
-    if (family == 0 && type == 1) return launch_direct<DIR_DCT1>(ctx, d_in, d_out, table, n, batch, ib, ie);
-    if (type == 3) return launch_direct<DIR_HALF>(ctx, d_in, d_out, table, n, batch, ib, ie);
-    return launch_direct<DIR_ZERO>(ctx, d_in, d_out, table, n, batch, ib, ie);
+    if (family == 0 && type == 1) return launch_direct<DIR_DCT1>(ctx, d_in, d_out, table, n, n, batch, ib, ie);
+    if (type == 3) return launch_direct<DIR_HALF>(ctx, d_in, d_out, table, n, n, batch, ib, ie);
+    return launch_direct<DIR_ZERO>(ctx, d_in, d_out, table, n, n, batch, ib, ie);
+}
+
+int direct_zero_sums(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *table, size_t n, size_t nk, size_t batch)
+{
+    return launch_direct<DIR_ZERO>(ctx, d_in, d_out, table, n, nk, batch, 0, n);
 }
 
 }  // namespace host

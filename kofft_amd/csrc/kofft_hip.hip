@@ -356,6 +356,31 @@ int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return direct_dev(ctx, family, type, d_in, d_out, n, rows); });
 }
 
+// czt::czt_f32 on host rows: n reals in, m complex out (k_spectral_f32.hip)
+int czt_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch)
+{
+    int rc = czt_check(n, m, batch, in, out, ctx);
+    if (rc || batch == 0 || m == 0) return rc;
+    if (n == 0) {  // the loop body never runs: (+0, +0) in every bin
+        std::memset(out, 0, batch * 2 * m * sizeof(float));
+        return KOFFT_OK;
+    }
+    return rows_host<float>(ctx, in, out, batch, n, 2 * m, false, nullptr, 0, true, false,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return czt_dev(ctx, d_in, d_out, n, m, wr, wi, ar, ai, rows); });
+}
+
+// goertzel::goertzel_f32 on host rows against nfreq frequencies: the coefficients go up as the side input
+int goertzel_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch, float sample_rate, const float *target_freqs,
+                  size_t nfreq)
+{
+    int rc = goertzel_check(n, batch, sample_rate, target_freqs, nfreq, in, out, ctx);
+    if (rc || batch == 0 || nfreq == 0) return rc;
+    std::vector<float> coeff(nfreq);
+    kofft_tables::goertzel_coeff_f32(n, sample_rate, target_freqs, nfreq, coeff.data());
+    return rows_host<float>(ctx, in, out, batch, n, nfreq, false, coeff.data(), nfreq, true, true,
+                            [&](float *d_in, float *d_out, const float *d_coeff, size_t rows) { return goertzel_launch(ctx, d_in, d_out, d_coeff, n, rows, nfreq); });
+}
+
 // wavelet::*_forward / *_inverse (one level) and multi_level_forward / _inverse on host rows (k_wavelet_f32.hip)
 int dwt_host(kofft_hip_ctx *ctx, int w, const float *in, float *approx, float *detail, size_t len, size_t batch)
 {
@@ -645,6 +670,7 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->tables) (void)hipFree(kv.second);
+    spectral_drop(ctx);
     for (int i = 0; i < 3; ++i)
         if (ctx->stage[i]) (void)hipFree(ctx->stage[i]);
     if (ctx->big_tmp && !ctx->big_tmp_external) (void)hipFree(ctx->big_tmp);
@@ -725,6 +751,7 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
         *bufs[i] = nullptr;
         *sizes[i] = 0;
     }
+    spectral_drop(ctx);  // the chirp-Z tables (up to 4 x 128 MiB) and the Goertzel coefficient arrays: rebuilt by the next call that needs them
     ctx->big_tmp_external = false;  // (KOFFT_EXP_API builds: the script's intermediate is forgotten, the next call allocates its own)
     ctx->big_probe_n = 0;
     ctx->big_probe_pick = -1;
@@ -977,6 +1004,50 @@ int kofft_hip_idwt_multi_f32_dev(kofft_hip_ctx *ctx, int wavelet, const float *d
                                  float *d_out, size_t n, size_t batch, size_t levels)
 {
     return idwt_multi_dev(ctx, wavelet, d_approx, d_details, detail_lens, d_out, n, batch, levels);
+}
+int kofft_hip_czt_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch)
+{
+    return czt_host(ctx, in, out, n, m, wr, wi, ar, ai, batch);
+}
+int kofft_hip_dev_czt_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t m, float wr, float wi, float ar, float ai,
+                          size_t batch)
+{
+    return czt_dev(ctx, d_in, d_out, n, m, wr, wi, ar, ai, batch);
+}
+int kofft_hip_goertzel_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch, float sample_rate,
+                           const float *target_freqs, size_t nfreq)
+{
+    return goertzel_host(ctx, in, out, n, batch, sample_rate, target_freqs, nfreq);
+}
+int kofft_hip_dev_goertzel_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate,
+                               const float *target_freqs, size_t nfreq)
+{
+    return goertzel_dev(ctx, d_in, d_out, n, batch, sample_rate, target_freqs, nfreq);
+}
+int kofft_hip_set_czt_route(kofft_hip_ctx *ctx, int mode)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (mode < 0 || mode > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->czt_route = mode;
+    return KOFFT_OK;
+}
+int kofft_hip_czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, float ai, float *C)
+{
+    if (n == 0 || m == 0) return KOFFT_OK;
+    if (n > kCztMax || m > kCztMax) return KOFFT_ERR_UNSUPPORTED;
+    if (!C) return KOFFT_ERR_NULL;
+    kofft_tables::czt_table_f32(n, m, wr, wi, ar, ai, 2 * m, C);
+    return KOFFT_OK;
+}
+int kofft_hip_goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff)
+{
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (sample_rate <= 0.0f) return KOFFT_ERR_INVALID_VALUE;
+    if (nfreq == 0) return KOFFT_OK;
+    if (n > kGoertzelMaxLen || nfreq > kGoertzelMaxFreqs) return KOFFT_ERR_UNSUPPORTED;
+    if (!target_freqs || !coeff) return KOFFT_ERR_NULL;
+    kofft_tables::goertzel_coeff_f32(n, sample_rate, target_freqs, nfreq, coeff);
+    return KOFFT_OK;
 }
 int kofft_hip_dct_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch)
 {

@@ -256,4 +256,65 @@ void direct_table_f32(int family, int type, size_t n, size_t ldc, float *c)
 }
 void dst_planner_f32(int type, size_t n, float *out) { dst_planner<float>(type, n, out); }
 void dst_planner_f64(int type, size_t n, double *out) { dst_planner<double>(type, n, out); }
+// ---- czt::czt_f32 and goertzel::goertzel_f32 (spectral_impl.hip.h) -----------------------------------------------------------------
+// The un-fused complex product the reference spells out three times (czt.rs:28-29, 43-44, 47-48)
+static inline void czt_mul(float pr, float pi, float qr, float qi, float *tr, float *ti)
+{
+    *tr = pr * qr - pi * qi;
+    *ti = pr * qi + pi * qr;
+}
+
+void czt_wpow_f32(size_t m, float wr, float wi, float *wpow)
+{
+    float pr = 1.0f, pi = 0.0f;
+    for (size_t k = 0; k < m; ++k) {
+        wpow[2 * k] = pr;
+        wpow[2 * k + 1] = pi;
+        czt_mul(pr, pi, wr, wi, &pr, &pi);
+    }
+}
+
+void czt_apow_f32(size_t n, float ar, float ai, float *apow)
+{
+    const float denom = ar * ar + ai * ai;
+    const float ir = denom == 0.0f ? 0.0f : ar / denom;
+    const float ii = denom == 0.0f ? 0.0f : -ai / denom;
+    float pr = 1.0f, pi = 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        apow[2 * i] = pr;
+        apow[2 * i + 1] = pi;
+        czt_mul(pr, pi, ir, ii, &pr, &pi);
+    }
+}
+
+void czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, float ai, size_t ldc, float *c)
+{
+    if (n == 0 || m == 0) return;
+    std::vector<float> wpow(2 * m), apow(2 * n), wnk(2 * m);
+    czt_wpow_f32(m, wr, wi, wpow.data());
+    czt_apow_f32(n, ar, ai, apow.data());
+    for (size_t k = 0; k < m; ++k) {
+        wnk[2 * k] = 1.0f;
+        wnk[2 * k + 1] = 0.0f;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        float *row = c + i * ldc;
+        for (size_t k = 0; k < m; ++k) {
+            czt_mul(apow[2 * i], apow[2 * i + 1], wnk[2 * k], wnk[2 * k + 1], &row[2 * k], &row[2 * k + 1]);
+            czt_mul(wnk[2 * k], wnk[2 * k + 1], wpow[2 * k], wpow[2 * k + 1], &wnk[2 * k], &wnk[2 * k + 1]);
+        }
+        for (size_t k = 2 * m; k < ldc; ++k) row[k] = 0.0f;
+    }
+}
+
+void goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff)
+{
+    const float nf = (float)n;
+    for (size_t j = 0; j < nfreq; ++j) {
+        const float k = floorf((target_freqs[j] * nf) / sample_rate);
+        const float omega = ((2.0f * Num<float>::pi()) * k) / nf;
+        coeff[j] = 2.0f * cosf(omega);
+    }
+}
+
 }  // namespace kofft_tables

@@ -24,4 +24,14 @@ void bluestein_f64(size_t n, size_t m, double *chirp, double *b);
 size_t radix4_triples(size_t n);
 void radix4_f32(size_t n, unsigned *perm, float *w);
 void radix4_f64(size_t n, unsigned *perm, double *w);
+// czt::czt_f32 (czt.rs:16-54), all f32 and unfused.  wpow: m complex, wpow[k] = w multiplied k times into (1, 0) (czt.rs:25-32; the
+// reference restarts at every k, a running prefix gives the same bits).  apow: n complex, apow[i] = a_inv multiplied i times into
+// (1, 0), a_inv = (ar / denom, -ai / denom), denom = ar * ar + ai * ai, (0, 0) at denom == 0 (czt.rs:19-21, 47-50).
+void czt_wpow_f32(size_t m, float wr, float wi, float *wpow);
+void czt_apow_f32(size_t n, float ar, float ai, float *apow);
+// The table of the chirp-Z sums: C[i][2k], C[i][2k + 1] = apow[i] * wpow[k]^i (czt.rs:38-46), n rows of 2 m floats, row stride
+// ldc >= 2 m; columns 2 m .. ldc - 1 are +0.  The host restatement of what czt_recur_kernel<TABLE> builds on the device.
+void czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, float ai, size_t ldc, float *c);
+// goertzel::goertzel_f32 (goertzel.rs:23-26): coeff[j] = 2 * cosf(((2 * PI) * floorf((f_j * n) / rate)) / n), n as f32, glibc cosf
+void goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff);
 }  // namespace kofft_tables
