@@ -117,6 +117,34 @@ int kofft_hip_fft_c32_dev_oop(kofft_hip_ctx *ctx, const float *d_in, float *d_ou
 int kofft_hip_fft_c64_dev_oop(kofft_hip_ctx *ctx, const double *d_in, double *d_out, size_t n,
                               size_t batch, int inverse);
 
+/* ---- planar (split re / im) complex FFT ------------------------------------------
+ * FftImpl::fft_split / ifft_split (fft.rs:1365-1439; FftPlan::fft_split, fft_split_complex,
+ * fft_complex_vec: fft.rs:2081-2153) on `batch` contiguous transforms of length n whose real
+ * and imaginary parts lie in two separate planes of batch * n reals each -- the reference's
+ * SoA layout (SplitComplex, ComplexVec: num.rs:236-308).  The result re + i im is
+ * kofft_hip_fft_c32 / _c64 of the interleaved data bit for bit, both directions (inverse != 0:
+ * im = -im, the transform, im = -im, re *= 1/n, im *= 1/n); n == 1 leaves both planes as they
+ * are.  Checks, in the order of kofft_hip_fft_c32 and before the context is touched:
+ * batch == 0 -> KOFFT_OK; n == 0 -> EMPTY_INPUT; n beyond the complex transform's range
+ * (2^26 for powers of two, 2^25 otherwise) -> KOFFT_ERR_UNSUPPORTED; a null pointer or
+ * context -> KOFFT_ERR_NULL.  Host form: in place.  kofft_hip_dev_*: device pointers (named
+ * like kofft_hip_dev_czt_f32), asynchronous on the context's stream; d_re_in == d_re_out and d_im_in == d_im_out (in place) are allowed,
+ * any other overlap between the four planes is undefined.  Planes need only the alignment of
+ * their element (4 / 8 bytes).  Powers of two 2 .. 2^14 (f32) / 2 .. 2^13 (f64) run in one
+ * launch on the planes themselves; every other length -- and, after
+ * kofft_hip_set_split_fused(ctx, 0), every length of that context -- is packed into
+ * interleaved rows, transformed and unpacked (the same bytes; A/B measurements and tests).
+ * (One corner: the f64 ifft_split scales by 1 / (n as f64) where ifft scales by
+ * 1 / (n as f32 as f64); the two differ only for lengths above 2^24 that f32 cannot hold,
+ * and this entry follows ifft there.) */
+int kofft_hip_fft_split_c32(kofft_hip_ctx *ctx, float *re, float *im, size_t n, size_t batch, int inverse);
+int kofft_hip_fft_split_c64(kofft_hip_ctx *ctx, double *re, double *im, size_t n, size_t batch, int inverse);
+int kofft_hip_dev_fft_split_c32(kofft_hip_ctx *ctx, const float *d_re_in, const float *d_im_in, float *d_re_out, float *d_im_out,
+                                size_t n, size_t batch, int inverse);
+int kofft_hip_dev_fft_split_c64(kofft_hip_ctx *ctx, const double *d_re_in, const double *d_im_in, double *d_re_out, double *d_im_out,
+                                size_t n, size_t batch, int inverse);
+int kofft_hip_set_split_fused(kofft_hip_ctx *ctx, int on);
+
 /* ScalarFftImpl::fft_radix4 (fft.rs:1455-1548) byte for byte.  kofft's fft_with_strategy(.., FftStrategy::Radix4)
  * (fft.rs:1356) runs it for powers of four, and from n = 16 its output is NOT the DFT (its "bit-reversal for radix-4" loop,
  * fft.rs:1462-1474, flips one bit per base-4 digit instead of reversing the digits).  A drop-in returns the reference's

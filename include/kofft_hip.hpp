@@ -11,6 +11,8 @@
 //   kofft::batch / batch_inverse / multi_channel fft.rs:2156-2191
 //   kofft::stft / istft / parallel / frame / StftStream  stft.rs:76-156, 232-263, 355-372, 160-206
 //   kofft::hann                                  window.rs:24-28
+//   kofft::HipFftImpl<T>::fft_split / ifft_split, SplitComplex<T>, ComplexVec, fft_split_complex, fft_complex_vec
+//                                                fft.rs:1365-1439, 2081-2153, num.rs:236-308 (the planes go to the device as they are)
 //   kofft::HipFftImpl<float>::dct2               DctPlanner::plan_dct2, dct.rs:61-105
 //   kofft::HipFftImpl<float>::hilbert_analytic   hilbert::hilbert_analytic, hilbert.rs:13-47
 //   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
@@ -107,6 +109,11 @@ template <> struct Abi<float> {
     static int fftnd(kofft_hip_ctx *c, float *d, size_t dp, size_t r, size_t cl, int inv) { return kofft_hip_fftnd_c32(c, d, dp, r, cl, inv); }
     static int radix4(kofft_hip_ctx *c, float *d, size_t n, size_t b) { return kofft_hip_fft_radix4_c32(c, d, n, b); }
     static int iradix4(kofft_hip_ctx *c, float *d, size_t n, size_t b) { return kofft_hip_ifft_radix4_c32(c, d, n, b); }
+    static int split(kofft_hip_ctx *c, float *re, float *im, size_t n, size_t b, int inv) { return kofft_hip_fft_split_c32(c, re, im, n, b, inv); }
+    static int split_dev(kofft_hip_ctx *c, const float *ri, const float *ii, float *ro, float *io, size_t n, size_t b, int inv)
+    {
+        return kofft_hip_dev_fft_split_c32(c, ri, ii, ro, io, n, b, inv);
+    }
 };
 template <> struct Abi<double> {
     static int fft(kofft_hip_ctx *c, double *d, size_t n, size_t b, int inv) { return kofft_hip_fft_c64(c, d, n, b, inv); }
@@ -118,6 +125,11 @@ template <> struct Abi<double> {
     static int fftnd(kofft_hip_ctx *c, double *d, size_t dp, size_t r, size_t cl, int inv) { return kofft_hip_fftnd_c64(c, d, dp, r, cl, inv); }
     static int radix4(kofft_hip_ctx *c, double *d, size_t n, size_t b) { return kofft_hip_fft_radix4_c64(c, d, n, b); }
     static int iradix4(kofft_hip_ctx *c, double *d, size_t n, size_t b) { return kofft_hip_ifft_radix4_c64(c, d, n, b); }
+    static int split(kofft_hip_ctx *c, double *re, double *im, size_t n, size_t b, int inv) { return kofft_hip_fft_split_c64(c, re, im, n, b, inv); }
+    static int split_dev(kofft_hip_ctx *c, const double *ri, const double *ii, double *ro, double *io, size_t n, size_t b, int inv)
+    {
+        return kofft_hip_dev_fft_split_c64(c, ri, ii, ro, io, n, b, inv);
+    }
 };
 }  // namespace detail
 
@@ -150,7 +162,7 @@ public:
         output = input;
         return ifft(output);
     }
-    Result fft_split(std::vector<T> &re, std::vector<T> &im) const  // fft.rs:556-570
+    virtual Result fft_split(std::vector<T> &re, std::vector<T> &im) const  // fft.rs:556-570
     {
         if (re.size() != im.size()) return Result::Err(FftError::MismatchedLengths);
         std::vector<C> buf(re.size());
@@ -160,7 +172,7 @@ public:
         for (size_t i = 0; i < re.size(); ++i) { re[i] = buf[i].re; im[i] = buf[i].im; }
         return Result::Ok();
     }
-    Result ifft_split(std::vector<T> &re, std::vector<T> &im) const  // fft.rs:572-586
+    virtual Result ifft_split(std::vector<T> &re, std::vector<T> &im) const  // fft.rs:572-586
     {
         if (re.size() != im.size()) return Result::Err(FftError::MismatchedLengths);
         std::vector<C> buf(re.size());
@@ -198,6 +210,31 @@ public:
     Result fft(std::vector<C> &input) const override { return st(detail::Abi<T>::fft(ctx_, fp(input), input.size(), 1, 0)); }
     Result ifft(std::vector<C> &input) const override { return st(detail::Abi<T>::fft(ctx_, fp(input), input.size(), 1, 1)); }
     Result stockham_fft(std::vector<C> &input) const { return fft(input); }  // fft.rs:634-640
+    // fft.rs:1365-1439: the SoA entries, in place on the two planes through the C entry (no packing on the host); the bytes are
+    // those of fft / ifft on re + i im
+    Result fft_split(std::vector<T> &re, std::vector<T> &im) const override
+    {
+        if (re.size() != im.size()) return Result::Err(FftError::MismatchedLengths);
+        return st(detail::Abi<T>::split(ctx_, re.data(), im.data(), re.size(), 1, 0));
+    }
+    Result ifft_split(std::vector<T> &re, std::vector<T> &im) const override
+    {
+        if (re.size() != im.size()) return Result::Err(FftError::MismatchedLengths);
+        return st(detail::Abi<T>::split(ctx_, re.data(), im.data(), re.size(), 1, 1));
+    }
+    // added: every row of two contiguous planes of batch * n reals, in place
+    Result fft_split_batch(std::vector<T> &re, std::vector<T> &im, size_t n, bool inverse = false) const
+    {
+        if (re.size() != im.size() || (n != 0 && re.size() % n != 0)) return Result::Err(FftError::MismatchedLengths);
+        return st(detail::Abi<T>::split(ctx_, re.data(), im.data(), n, n == 0 ? 1 : re.size() / n, inverse ? 1 : 0));
+    }
+    // added: device pointers, asynchronous on the context's stream; an output plane may be its own input
+    Result fft_split_dev(const T *d_re_in, const T *d_im_in, T *d_re_out, T *d_im_out, size_t n, size_t batch, bool inverse = false) const
+    {
+        return st(detail::Abi<T>::split_dev(ctx_, d_re_in, d_im_in, d_re_out, d_im_out, n, batch, inverse ? 1 : 0));
+    }
+    // false: every planar transform of this context through pack, n-point transform, unpack (the same bytes; A/B, tests)
+    Result set_split_fused(bool on) const { return st(kofft_hip_set_split_fused(ctx_, on ? 1 : 0)); }
     Result fft_strided(std::vector<C> &input, size_t stride, std::vector<C> &scratch) const override
     {
         return st(detail::Abi<T>::strided(ctx_, fp(input), input.size(), stride, scratch.size(), 0));
@@ -527,6 +564,74 @@ public:
     }
 };
 
+// num.rs:236-261: a view of two caller-owned planes.  The constructor does not compare the lengths (the reference's struct literal does
+// not either, tests/split.rs:65-74: fft_split_complex then returns MismatchedLengths); new_() asserts like SplitComplex::new.
+template <typename T>
+struct SplitComplex {
+    std::vector<T> &re, &im;
+    SplitComplex(std::vector<T> &r, std::vector<T> &i) : re(r), im(i) {}
+    static SplitComplex new_(std::vector<T> &r, std::vector<T> &i)
+    {
+        if (r.size() != i.size()) throw std::logic_error("SplitComplex::new: re.len() != im.len()");
+        return SplitComplex(r, i);
+    }
+    size_t len() const { return re.size(); }
+    bool is_empty() const { return re.empty(); }
+    static SplitComplex copy_from_complex(const std::vector<Complex<T>> &input, std::vector<T> &r, std::vector<T> &i)  // num.rs:332-339
+    {
+        if (input.size() != r.size() || input.size() != i.size()) throw std::logic_error("copy_from_complex: lengths differ");
+        for (size_t k = 0; k < input.size(); ++k) { r[k] = input[k].re; i[k] = input[k].im; }
+        return SplitComplex(r, i);
+    }
+    void copy_to_complex(std::vector<Complex<T>> &out) const  // num.rs:341-348
+    {
+        if (re.size() != im.size() || re.size() != out.size()) throw std::logic_error("copy_to_complex: lengths differ");
+        for (size_t k = 0; k < re.size(); ++k) out[k] = Complex<T>(re[k], im[k]);
+    }
+};
+using SplitComplex32 = SplitComplex<float>;
+using SplitComplex64 = SplitComplex<double>;
+
+// num.rs:264-308: two owned f32 planes
+struct ComplexVec {
+    std::vector<float> re, im;
+    ComplexVec() = default;
+    ComplexVec(std::vector<float> r, std::vector<float> i) : re(std::move(r)), im(std::move(i))
+    {
+        if (re.size() != im.size()) throw std::logic_error("ComplexVec::new: re.len() != im.len()");
+    }
+    size_t len() const { return re.size(); }
+    bool is_empty() const { return re.empty(); }
+    static ComplexVec from_complex_vec(const std::vector<Complex32> &v)
+    {
+        ComplexVec c;
+        c.re.reserve(v.size());
+        c.im.reserve(v.size());
+        for (const Complex32 &x : v) { c.re.push_back(x.re); c.im.push_back(x.im); }
+        return c;
+    }
+    std::vector<Complex32> to_complex_vec() const
+    {
+        std::vector<Complex32> out(re.size());
+        for (size_t k = 0; k < re.size(); ++k) out[k] = Complex32(re[k], im[k]);
+        return out;
+    }
+    bool operator==(const ComplexVec &o) const { return re == o.re && im == o.im; }
+};
+
+// fft::fft_split / ifft_split / fft_split_complex / ifft_split_complex / fft_complex_vec / ifft_complex_vec (fft.rs:2129-2153).  The
+// reference builds ScalarFftImpl::default() per call; here the caller passes the implementation, as for batch() below.
+template <typename T>
+Result fft_split(const FftImpl<T> &fft, std::vector<T> &re, std::vector<T> &im) { return fft.fft_split(re, im); }
+template <typename T>
+Result ifft_split(const FftImpl<T> &fft, std::vector<T> &re, std::vector<T> &im) { return fft.ifft_split(re, im); }
+template <typename T>
+Result fft_split_complex(const FftImpl<T> &fft, SplitComplex<T> data) { return fft.fft_split(data.re, data.im); }
+template <typename T>
+Result ifft_split_complex(const FftImpl<T> &fft, SplitComplex<T> data) { return fft.ifft_split(data.re, data.im); }
+inline Result fft_complex_vec(const FftImpl<float> &fft, ComplexVec &data) { return fft.fft_split(data.re, data.im); }
+inline Result ifft_complex_vec(const FftImpl<float> &fft, ComplexVec &data) { return fft.ifft_split(data.re, data.im); }
+
 // fft::FftPlan (fft.rs:1989-2094): a length and a strategy bound to an implementation.  FftPlan::fft (fft.rs:2012-2038):
 // an f32 plan with strategy Radix2 / Radix4 takes the *_with_twiddles shortcut, and every *_with_twiddles is stockham_fft
 // (fft.rs:1645-1660) -- the Stockham transform, NOT fft_radix4; every other plan goes through fft_with_strategy, where
@@ -562,6 +667,29 @@ public:
         if (input.size() != n || output.size() != n) return Result::Err(FftError::MismatchedLengths);
         output = input;
         return ifft(output);
+    }
+    Result fft_split(std::vector<T> &re, std::vector<T> &im) const  // fft.rs:2081-2086
+    {
+        if (re.size() != n || im.size() != n) return Result::Err(FftError::MismatchedLengths);
+        return fft_.fft_split(re, im);
+    }
+    Result ifft_split(std::vector<T> &re, std::vector<T> &im) const  // fft.rs:2088-2093
+    {
+        if (re.size() != n || im.size() != n) return Result::Err(FftError::MismatchedLengths);
+        return fft_.ifft_split(re, im);
+    }
+    // fft.rs:2096-2112 (FftPlan<f32> in the reference)
+    template <typename U = T, typename = std::enable_if_t<std::is_same<U, float>::value>>
+    Result fft_complex_vec(ComplexVec &data) const
+    {
+        if (data.len() != n) return Result::Err(FftError::MismatchedLengths);
+        return fft_.fft_split(data.re, data.im);
+    }
+    template <typename U = T, typename = std::enable_if_t<std::is_same<U, float>::value>>
+    Result ifft_complex_vec(ComplexVec &data) const
+    {
+        if (data.len() != n) return Result::Err(FftError::MismatchedLengths);
+        return fft_.ifft_split(data.re, data.im);
     }
 
 private:

@@ -22,6 +22,9 @@ extern "C" {
     fn kofft_hip_last_error(ctx: *const KofftHipCtx) -> *const c_char;
     fn kofft_hip_fft_c32(ctx: *mut KofftHipCtx, data: *mut f32, n: usize, batch: usize, inverse: c_int) -> c_int;
     fn kofft_hip_fft_c64(ctx: *mut KofftHipCtx, data: *mut f64, n: usize, batch: usize, inverse: c_int) -> c_int;
+    fn kofft_hip_fft_split_c32(ctx: *mut KofftHipCtx, re: *mut f32, im: *mut f32, n: usize, batch: usize, inverse: c_int) -> c_int;
+    fn kofft_hip_fft_split_c64(ctx: *mut KofftHipCtx, re: *mut f64, im: *mut f64, n: usize, batch: usize, inverse: c_int) -> c_int;
+    fn kofft_hip_set_split_fused(ctx: *mut KofftHipCtx, on: c_int) -> c_int;
     fn kofft_hip_fft_radix4_c32(ctx: *mut KofftHipCtx, data: *mut f32, n: usize, batch: usize) -> c_int;
     fn kofft_hip_fft_radix4_c64(ctx: *mut KofftHipCtx, data: *mut f64, n: usize, batch: usize) -> c_int;
     fn kofft_hip_fft_c32_strided(ctx: *mut KofftHipCtx, data: *mut f32, len: usize, stride: usize, n: usize, inverse: c_int) -> c_int;
@@ -142,7 +145,7 @@ impl<T: Float> Drop for HipFftImpl<T> {
 }
 
 macro_rules! impl_fft {
-    ($t:ty, $cplx:ty, $fft:ident, $strided:ident, $radix4:ident) => {
+    ($t:ty, $cplx:ty, $fft:ident, $strided:ident, $radix4:ident, $split:ident) => {
         impl FftImpl<$t> for HipFftImpl<$t> {
             // Complex<T> is #[repr(C)] {re, im} (kofft num.rs:105-110, tests/complex_repr.rs): a slice of n
             // complex values is 2n scalars.
@@ -185,6 +188,16 @@ macro_rules! impl_fft {
                 for i in 0..n { output[i * out_stride] = scratch[i]; }
                 Ok(())
             }
+            // kofft fft.rs:1365-1439: the SoA entries override the trait's pack / fft / unpack defaults (fft.rs:556-586) -- the
+            // planes go to the device as they are (kofft_hip_fft_split_*), the bytes are those of fft / ifft on re + i im.
+            fn fft_split(&self, re: &mut [$t], im: &mut [$t]) -> Result<(), FftError> {
+                if re.len() != im.len() { return Err(FftError::MismatchedLengths); }
+                status(self.ctx, unsafe { $split(self.ctx, re.as_mut_ptr(), im.as_mut_ptr(), re.len(), 1, 0) })
+            }
+            fn ifft_split(&self, re: &mut [$t], im: &mut [$t]) -> Result<(), FftError> {
+                if re.len() != im.len() { return Err(FftError::MismatchedLengths); }
+                status(self.ctx, unsafe { $split(self.ctx, re.as_mut_ptr(), im.as_mut_ptr(), re.len(), 1, 1) })
+            }
             fn fft_with_strategy(&self, input: &mut [$cplx], strategy: FftStrategy) -> Result<(), FftError> {
                 // kofft fft.rs:1337-1363: Radix2 / SplitRadix / Auto run the Stockham path (fft and stockham_fft agree for
                 // n >= 2); Radix4 runs the crate's fft_radix4 arm (fft.rs:1356) byte for byte -- not a DFT from n = 16 (its
@@ -205,6 +218,17 @@ macro_rules! impl_fft {
         }
 
         impl HipFftImpl<$t> {
+            /// `fft_split` / `ifft_split` on every row of two contiguous `[batch * n]` planes, in place (one kernel launch for the
+            /// powers of two up to 2^14 / 2^13).
+            pub fn fft_split_batch(&self, re: &mut [$t], im: &mut [$t], n: usize, inverse: bool) -> Result<(), FftError> {
+                if re.len() != im.len() || (n != 0 && re.len() % n != 0) { return Err(FftError::MismatchedLengths); }
+                let batch = if n == 0 { 1 } else { re.len() / n };
+                status(self.ctx, unsafe { $split(self.ctx, re.as_mut_ptr(), im.as_mut_ptr(), n, batch, inverse as c_int) })
+            }
+            /// `false`: every planar transform of this context through pack, n-point transform, unpack (the same bytes; A/B, tests).
+            pub fn set_split_fused(&self, on: bool) -> Result<(), FftError> {
+                status(self.ctx, unsafe { kofft_hip_set_split_fused(self.ctx, on as c_int) })
+            }
             /// `fft::batch` over one contiguous `[batch * n]` buffer (one kernel launch).
             pub fn fft_batch(&self, data: &mut [$cplx], n: usize, inverse: bool) -> Result<(), FftError> {
                 if n != 0 && data.len() % n != 0 { return Err(FftError::MismatchedLengths); }
@@ -215,8 +239,8 @@ macro_rules! impl_fft {
     };
 }
 
-impl_fft!(f32, Complex32, kofft_hip_fft_c32, kofft_hip_fft_c32_strided, kofft_hip_fft_radix4_c32);
-impl_fft!(f64, Complex64, kofft_hip_fft_c64, kofft_hip_fft_c64_strided, kofft_hip_fft_radix4_c64);
+impl_fft!(f32, Complex32, kofft_hip_fft_c32, kofft_hip_fft_c32_strided, kofft_hip_fft_radix4_c32, kofft_hip_fft_split_c32);
+impl_fft!(f64, Complex64, kofft_hip_fft_c64, kofft_hip_fft_c64_strided, kofft_hip_fft_radix4_c64, kofft_hip_fft_split_c64);
 
 macro_rules! impl_ndfft {
     ($t:ty, $cplx:ty, $nd:ident) => {

@@ -50,6 +50,11 @@ SIGNATURES = {
     "kofft_hip_fft_c64_dev": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_int]),
     "kofft_hip_fft_c32_dev_oop": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_int]),
     "kofft_hip_fft_c64_dev_oop": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_int]),
+    "kofft_hip_fft_split_c32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_int]),
+    "kofft_hip_fft_split_c64": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_int]),
+    "kofft_hip_dev_fft_split_c32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz, C.c_int]),
+    "kofft_hip_dev_fft_split_c64": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz, C.c_int]),
+    "kofft_hip_set_split_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_fft_radix4_c32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz]),
     "kofft_hip_fft_radix4_c64": (C.c_int, [_ctx, C.c_void_p, _sz, _sz]),
     "kofft_hip_fft_radix4_c32_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),

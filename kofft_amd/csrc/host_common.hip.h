@@ -48,6 +48,7 @@ struct kofft_hip_ctx {
     bool istft_fused = true;  // KOFFT_HIP_ISTFT_FUSED=0: ISTFT always as inverse transforms + the overlap-add kernel
     bool dct_fused = true;    // kofft_hip_set_dct_fused(ctx, 0): DCT-II of every length through the composed route (mirror, fft_dev, post-pass; A/B, tests)
     bool hilbert_fused = true; // kofft_hip_set_hilbert_fused(ctx, 0): analytic signals of every length through the composed route (expand, fft_dev, mask, inverse fft_dev; A/B, tests)
+    bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     int wavelet_fused = 1;    // kofft_hip_set_wavelet_fused: 1 the measured choice (wavelet_use_fused), 0 every multi-level call level by level, 2 the fused kernels wherever they fit (A/B, tests)
@@ -704,6 +705,18 @@ int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batc
 int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
 int hilbert_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: hilbert::hilbert_analytic
 int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: cepstrum::real_cepstrum
+// k_planar_f32/f64.hip: FftImpl::fft_split / ifft_split on planes of batch * n reals (planar_impl.hip.h); planar_check: the argument
+// checks alone, in the order of fft_dev and before the context or a device is touched
+inline int planar_check(size_t n, size_t batch, const void *p0, const void *p1, const void *p2, const void *p3, const kofft_hip_ctx *ctx)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;  // fft.rs:794
+    if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !p0 || !p1 || !p2 || !p3) return KOFFT_ERR_NULL;
+    return KOFFT_OK;
+}
+template <typename T>
+int planar_dev(kofft_hip_ctx *ctx, const T *d_re_in, const T *d_im_in, T *d_re_out, T *d_im_out, size_t n, size_t batch, int inverse);
 // k_direct_f32.hip: dct::dct1..4 (family 0) / dst::dst1..4 (family 1), the direct sums; direct_check: the argument checks alone
 constexpr size_t kDirectMaxN = 4096;  // the longest row: the n x n table is 64 MiB there
 int direct_check(int family, int type, size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);

@@ -131,7 +131,7 @@ inline size_t host_chunk_rows(const kofft_hip_ctx *ctx, size_t batch)
 }
 
 // One host-pointer call over `batch` independent rows of nin input arrays and nout output arrays: in_rows[k] elements of T per row of
-// input k, out_rows[k] per row of output k (in_place: one input, one output, one device buffer for both), and an optional side input
+// input k, out_rows[k] per row of output k (in_place: output k is input k transformed, one device buffer for both), and an optional side input
 // of side_len elements that every row reads (rfft's window), uploaded once.  dev(d_ins, d_outs, d_side, rows) enqueues the device work
 // for `rows` rows on ctx->stream; d_ins / d_outs point at each array's first row.  Three ways through:
 //  * zero-copy, when zero_copy_ok and neither direction (inputs + side input up, outputs down) is above kZeroCopyMax: the rows go
@@ -183,7 +183,7 @@ int rows_host_n(kofft_hip_ctx *ctx, size_t batch, int nin, const T *const *ins, 
     if (rc) return rc;
     if (!in_place && (rc = ensure_stage(ctx, 1, out_span))) return rc;
     for (int k = 0; k < nin; ++k) d_ins[k] = reinterpret_cast<T *>(static_cast<char *>(ctx->stage[0]) + in_off[k]);
-    for (int k = 0; k < nout; ++k) d_outs[k] = in_place ? d_ins[0] : reinterpret_cast<T *>(static_cast<char *>(ctx->stage[1]) + out_off[k]);
+    for (int k = 0; k < nout; ++k) d_outs[k] = in_place ? d_ins[k] : reinterpret_cast<T *>(static_cast<char *>(ctx->stage[1]) + out_off[k]);
     const T *d_side = nullptr;
     if (side) {
         if ((rc = ensure_stage(ctx, 2, side_bytes))) return rc;
@@ -251,6 +251,21 @@ int fft_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inverse)
     if (!ctx || !data) return KOFFT_ERR_NULL;
     return rows_host<T>(ctx, data, data, batch, 2 * n, 2 * n, true, nullptr, 0, is_pow2(n), true,
                         [&](T *d_in, T *d_out, const T *, size_t rows) { return fft_dev<T>(ctx, d_in, d_out, n, rows, inverse); });
+}
+
+// FftImpl::fft_split / ifft_split on host planes of batch * n reals each, in place (planar_impl.hip.h)
+template <typename T>
+int planar_host(kofft_hip_ctx *ctx, T *re, T *im, size_t n, size_t batch, int inverse)
+{
+    const int rc = planar_check(n, batch, re, im, re, im, ctx);
+    if (rc || batch == 0) return rc;
+    if (n == 1) return KOFFT_OK;  // the planes themselves
+    T *const planes[2] = {re, im};
+    const size_t rows[2] = {n, n};
+    return rows_host_n<T>(ctx, batch, 2, planes, rows, 2, planes, rows, true, nullptr, 0, is_pow2(n), true,
+                          [&](T *const *d_in, T *const *d_out, const T *, size_t nb) {
+                              return planar_dev<T>(ctx, d_in[0], d_in[1], d_out[0], d_out[1], n, nb, inverse);
+                          });
 }
 
 // ScalarFftImpl::fft_radix4 on a host buffer (fft_radix4.hip.h); inverse: FftPlan::ifft's loop around it (fft.rs:2040-2055)
@@ -864,6 +879,30 @@ int kofft_hip_fft_c64_dev_oop(kofft_hip_ctx *ctx, const double *d_in, double *d_
                               int inverse)
 {
     return fft_dev<double>(ctx, d_in, d_out, n, batch, inverse);
+}
+int kofft_hip_fft_split_c32(kofft_hip_ctx *ctx, float *re, float *im, size_t n, size_t batch, int inverse)
+{
+    return planar_host<float>(ctx, re, im, n, batch, inverse);
+}
+int kofft_hip_fft_split_c64(kofft_hip_ctx *ctx, double *re, double *im, size_t n, size_t batch, int inverse)
+{
+    return planar_host<double>(ctx, re, im, n, batch, inverse);
+}
+int kofft_hip_dev_fft_split_c32(kofft_hip_ctx *ctx, const float *d_re_in, const float *d_im_in, float *d_re_out, float *d_im_out, size_t n,
+                                size_t batch, int inverse)
+{
+    return planar_dev<float>(ctx, d_re_in, d_im_in, d_re_out, d_im_out, n, batch, inverse);
+}
+int kofft_hip_dev_fft_split_c64(kofft_hip_ctx *ctx, const double *d_re_in, const double *d_im_in, double *d_re_out, double *d_im_out, size_t n,
+                                size_t batch, int inverse)
+{
+    return planar_dev<double>(ctx, d_re_in, d_im_in, d_re_out, d_im_out, n, batch, inverse);
+}
+int kofft_hip_set_split_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->planar_fused = on != 0;
+    return KOFFT_OK;
 }
 int kofft_hip_fft_radix4_c32(kofft_hip_ctx *ctx, float *data, size_t n, size_t batch) { return fft_radix4_host<float>(ctx, data, n, batch, 0); }
 int kofft_hip_fft_radix4_c64(kofft_hip_ctx *ctx, double *data, size_t n, size_t batch) { return fft_radix4_host<double>(ctx, data, n, batch, 0); }
