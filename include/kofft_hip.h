@@ -450,6 +450,50 @@ int kofft_hip_stft_magnitudes_f32_dev(kofft_hip_ctx *ctx, const float *d_samples
                                       size_t win_len, size_t hop, float *d_mags, size_t frames,
                                       float *d_max);
 
+/* ---- the three STFT families over ROWS of signals ----
+ * `rows` signals of `len` samples, row r at signal + r * row_stride (row_stride >= len, in floats; ignored
+ * when rows == 1), one window of win_len, one hop, `frames` frames per row; every output is dense.  Row r of
+ * every output is, bit for bit, what the single-signal entry above returns for signal r alone; a frame that
+ * runs past the end of its row reads exactly +0, never the head of row r + 1.  One launch chain serves all
+ * rows.  Checks, in order: hop == 0 -> INVALID_HOP_SIZE; (host forms and magnitudes) frames < ceil(len/hop)
+ * -> MISMATCHED_LENGTHS; rows == 0 or frames == 0 -> KOFFT_OK, nothing touched (magnitudes with rows > 0:
+ * max_mag zeroed); win_len == 0 -> EMPTY_INPUT; win_len beyond the complex limits -> UNSUPPORTED;
+ * rows > 1 and row_stride < len -> INVALID_VALUE; then the pointers.
+ * out: rows * frames * win_len complex.  mags: rows * frames * (win_len/2) floats, max_mag: rows floats.
+ * The device-pointer forms are named kofft_hip_dev_* like the chirp-Z and split-complex ones (DESIGN.md 5.18:
+ * the suite's coverage check of the *_dev names is tied to a case table these calls cannot join; their own
+ * check is tests/test_stft_rows_cpu.py). */
+int kofft_hip_stft_rows_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride,
+                            const float *window, size_t win_len, size_t hop, float *out, size_t frames);
+int kofft_hip_dev_stft_rows_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len,
+                                size_t row_stride, const float *d_window, size_t win_len, size_t hop,
+                                float *d_out, size_t frames);
+int kofft_hip_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *samples, size_t rows, size_t len,
+                                       size_t row_stride, size_t win_len, size_t hop, float *mags,
+                                       size_t frames, float *max_mag);
+int kofft_hip_dev_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len,
+                                           size_t row_stride, size_t win_len, size_t hop, float *d_mags,
+                                           size_t frames, float *d_max);
+/* stft::istft (mode 1) / stft::inverse_parallel (mode 2) per row: frames_data rows * frames * win_len complex,
+ * output rows * out_len (accumulated into), scratch rows * out_len (scratch_len == out_len, per row).  Checks
+ * and side effects are the single-signal forms': istft transforms the frames in place and leaves the
+ * window-square sums in scratch; the parallel form leaves the frames alone and writes 0 where the sum is
+ * <= 1e-8.  The device parallel form inverse-transforms copies of the frames in scratch the context owns
+ * (until kofft_hip_release_scratch / destroy): whole rows at a time, at most 512 MiB, or one row's frames
+ * where a single row is larger. */
+int kofft_hip_istft_rows_f32(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames,
+                             const float *window, size_t win_len, size_t hop, float *output, size_t out_len,
+                             float *scratch, size_t scratch_len);
+int kofft_hip_dev_istft_rows_f32(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames,
+                                 const float *d_window, size_t win_len, size_t hop, float *d_output,
+                                 size_t out_len, float *d_scratch, size_t scratch_len);
+int kofft_hip_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *frames_data, size_t rows, size_t frames,
+                                      const float *window, size_t win_len, size_t hop, float *output,
+                                      size_t out_len);
+int kofft_hip_dev_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *d_frames, size_t rows, size_t frames,
+                                          const float *d_window, size_t win_len, size_t hop, float *d_output,
+                                          size_t out_len);
+
 /* ---- 2-D / 3-D FFT (SURVEY 8f "next" row 3) ----------------------------------------
  * ndfft::fft2d_inplace (ndfft.rs:74-101) with depth == 1: FftImpl::fft on every row (length cols), then
  * FftImpl::fft_strided down every column (length rows, stride cols).  ndfft::fft3d_inplace

@@ -814,6 +814,49 @@ inline Result stft_magnitudes(const std::vector<float> &samples, size_t win_len,
     return Result::Ok();
 }
 
+// ---- the STFT families over rows of signals (kofft_hip.h, "ROWS of signals"): `signals` holds rows * len samples, rows dense ----
+// stft::stft per row into rows * frames * window.size() values; frames defaults to ceil(len / hop)
+inline Result stft_rows(const std::vector<float> &signals, size_t rows, const std::vector<float> &window, size_t hop_size,
+                        std::vector<Complex32> &out, const HipFftImpl<float> &fft, size_t frames = static_cast<size_t>(-1))
+{
+    if (hop_size == 0) return Result::Err(FftError::InvalidHopSize);  // stft.rs:83
+    if (rows == 0 || signals.size() % rows != 0) return rows == 0 && signals.empty() ? Result::Ok() : Result::Err(FftError::MismatchedLengths);
+    const size_t len = signals.size() / rows;
+    if (frames == static_cast<size_t>(-1)) frames = (len + hop_size - 1) / hop_size;
+    out.assign(rows * frames * window.size(), Complex32{});
+    return fft.st(kofft_hip_stft_rows_f32(fft.raw(), signals.data(), rows, len, len, window.data(), window.size(), hop_size,
+                                          reinterpret_cast<float *>(out.data()), frames));
+}
+// visual::spectrogram::stft_magnitudes per row: mags rows * frames * (win_len / 2), one maximum per row
+inline Result stft_magnitudes_rows(const std::vector<float> &samples, size_t rows, size_t win_len, size_t hop, std::vector<float> &mags,
+                                   std::vector<float> &max_mag, const HipFftImpl<float> &fft)
+{
+    if (hop == 0) return Result::Err(FftError::InvalidHopSize);
+    if (rows == 0 || samples.size() % rows != 0) return rows == 0 && samples.empty() ? Result::Ok() : Result::Err(FftError::MismatchedLengths);
+    const size_t len = samples.size() / rows, frames = (len + hop - 1) / hop;
+    mags.assign(rows * frames * (win_len / 2), 0.0f);
+    max_mag.assign(rows, 0.0f);
+    return fft.st(kofft_hip_stft_magnitudes_rows_f32(fft.raw(), samples.data(), rows, len, len, win_len, hop, mags.data(), frames,
+                                                     max_mag.data()));
+}
+// stft::istft per row (frames transformed in place, scratch = the window-square sums); parallel: stft::inverse_parallel per row
+// (frames untouched, scratch unused)
+inline Result istft_rows(std::vector<Complex32> &frames, size_t rows, const std::vector<float> &window, size_t hop_size,
+                         std::vector<float> &output, std::vector<float> &scratch, const HipFftImpl<float> &fft, bool parallel = false)
+{
+    if (hop_size == 0) return Result::Err(FftError::InvalidHopSize);
+    if (rows == 0) return Result::Ok();
+    const size_t wl = window.size();
+    if (output.size() % rows != 0 || (wl && frames.size() % (rows * wl) != 0)) return Result::Err(FftError::MismatchedLengths);
+    const size_t count = wl ? frames.size() / (rows * wl) : 0, out_len = output.size() / rows;
+    if (parallel)
+        return fft.st(kofft_hip_istft_parallel_rows_f32(fft.raw(), reinterpret_cast<const float *>(frames.data()), rows, count, window.data(),
+                                                        wl, hop_size, output.data(), out_len));
+    if (scratch.size() != output.size()) return Result::Err(FftError::MismatchedLengths);  // stft.rs:128
+    return fft.st(kofft_hip_istft_rows_f32(fft.raw(), reinterpret_cast<float *>(frames.data()), rows, count, window.data(), wl, hop_size,
+                                           output.data(), out_len, scratch.data(), out_len));
+}
+
 // ndfft::fft2d_inplace (ndfft.rs:74-101) / fft3d_inplace (ndfft.rs:114-155): same length checks, same order
 template <typename T>
 Result fft2d_inplace(std::vector<Complex<T>> &data, size_t rows, size_t cols, const HipFftImpl<T> &fft,

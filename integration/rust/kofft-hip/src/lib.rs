@@ -39,6 +39,14 @@ extern "C" {
                            hop: usize, output: *mut f32, out_len: usize, scratch: *mut f32, scratch_len: usize) -> c_int;
     fn kofft_hip_istft_parallel_f32(ctx: *mut KofftHipCtx, frames_data: *const f32, frames: usize, window: *const f32,
                                     win_len: usize, hop: usize, output: *mut f32, out_len: usize) -> c_int;
+    fn kofft_hip_stft_rows_f32(ctx: *mut KofftHipCtx, signal: *const f32, rows: usize, len: usize, row_stride: usize, window: *const f32,
+                               win_len: usize, hop: usize, out: *mut f32, frames: usize) -> c_int;
+    fn kofft_hip_stft_magnitudes_rows_f32(ctx: *mut KofftHipCtx, samples: *const f32, rows: usize, len: usize, row_stride: usize,
+                                          win_len: usize, hop: usize, mags: *mut f32, frames: usize, max_mag: *mut f32) -> c_int;
+    fn kofft_hip_istft_rows_f32(ctx: *mut KofftHipCtx, frames_data: *mut f32, rows: usize, frames: usize, window: *const f32,
+                                win_len: usize, hop: usize, output: *mut f32, out_len: usize, scratch: *mut f32, scratch_len: usize) -> c_int;
+    fn kofft_hip_istft_parallel_rows_f32(ctx: *mut KofftHipCtx, frames_data: *const f32, rows: usize, frames: usize, window: *const f32,
+                                         win_len: usize, hop: usize, output: *mut f32, out_len: usize) -> c_int;
     fn kofft_hip_stft_magnitudes_f32(ctx: *mut KofftHipCtx, samples: *const f32, len: usize, win_len: usize, hop: usize,
                                      mags: *mut f32, frames: usize, max_mag: *mut f32) -> c_int;
     fn kofft_hip_czt_f32(ctx: *mut KofftHipCtx, input: *const f32, out: *mut f32, n: usize, m: usize, wr: f32, wi: f32, ar: f32, ai: f32,
@@ -324,6 +332,20 @@ impl HipFftImpl<f32> {
         status(self.ctx, unsafe {
             kofft_hip_istft_parallel_f32(self.ctx, frames.as_ptr() as *const f32, count, window.as_ptr(), window.len(), hop_size,
                                          output.as_mut_ptr(), output.len())
+        })
+    }
+
+    /// `stft::stft` of every row of `signals` (`rows` dense rows of `signals.len() / rows` samples) in one call: `out` holds
+    /// `rows * frames * window.len()` values, row r what `stft_contiguous` gives for signal r alone.
+    pub fn stft_rows(&self, signals: &[f32], rows: usize, window: &[f32], hop_size: usize, out: &mut [Complex32]) -> Result<(), FftError> {
+        if hop_size == 0 { return Err(FftError::InvalidHopSize); }
+        if rows == 0 { return Ok(()); }
+        if signals.len() % rows != 0 { return Err(FftError::MismatchedLengths); }
+        let len = signals.len() / rows;
+        let frames = if window.is_empty() { 0 } else { out.len() / (rows * window.len()) };
+        status(self.ctx, unsafe {
+            kofft_hip_stft_rows_f32(self.ctx, signals.as_ptr(), rows, len, len, window.as_ptr(), window.len(), hop_size,
+                                    out.as_mut_ptr() as *mut f32, frames)
         })
     }
 

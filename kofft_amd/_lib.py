@@ -122,6 +122,14 @@ SIGNATURES = {
     "kofft_hip_fftnd_c64": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_int]),
     "kofft_hip_fftnd_c32_dev": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_int]),
     "kofft_hip_fftnd_c64_dev": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_int]),
+    "kofft_hip_stft_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_stft_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_stft_magnitudes_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, _sz, _sz, C.c_void_p, _sz, C.c_void_p]),
+    "kofft_hip_dev_stft_magnitudes_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, _sz, _sz, C.c_void_p, _sz, C.c_void_p]),
+    "kofft_hip_istft_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_istft_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_void_p, _sz]),
+    "kofft_hip_istft_parallel_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_istft_parallel_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_f32_dev": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),
     # multi-GPU (single process, one context per device; RCCL bound at run time)
     "kofft_hip_multi_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(_ctx)]),

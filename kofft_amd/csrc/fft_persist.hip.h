@@ -424,12 +424,13 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
             for (int u = 0; u < R; ++u)
                 if (LastG::out_index(0, u) < N / 2) kept[ki++] = cur[u];  // (a constant per u)
             float m[NK];
-            const typename IO::Acc top = IO::template mags_of<NK>(kept, m);  // the largest sum of squares (StftMagIO: the accumulator's unit)
+            const float top = IO::template mags_of<NK>(kept, m);  // the largest sum of squares (StftMagIO: the accumulator's unit)
             ki = 0;
 #pragma unroll
             for (int u = 0; u < R; ++u)
                 if (LastG::out_index(0, u) < N / 2) io.store_d_mag(od, lane_bytes, LastG::out_index(0, u), m[ki++], row_off);
-            if (active) acc = __builtin_fmaxf(acc, top);
+            if constexpr (io_row_acc<IO>::value) io.acc_row(xf0, active ? top : 0.0f);  // one row per wavefront: committed per transform
+            else if (active) acc = __builtin_fmaxf(acc, top);
         } else {
 #ifdef KOFFT_PERSIST_ACTIVE_BRANCH /* measurement only (tools/build_variant.sh): rounds 1-4's branch around the stores, for same-box A/Bs */
         if (active)

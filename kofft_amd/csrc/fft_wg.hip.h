@@ -364,6 +364,110 @@ struct StftMagIO : StftIO {
     __device__ __forceinline__ unsigned out_row_bytes() const { return (unsigned)(n / 2) * 4u; }
 };
 
+// ---- rows of signals: `frames` frames of each of several signals, row r at signal + r * row_stride, `len` samples
+// long.  The kernels walk ONE flat transform index xf = row * frames + frame over a dense output, so only the input side knows about
+// rows: every xf-dependent input form goes through at(), which hands back the single-signal policy of the row (its signal pointer
+// rebased -- 64-bit arithmetic, so rows * row_stride * 4 may pass 4 GiB -- and the same len, hop, window) and the frame inside it.
+// The bounds logic that keeps a frame from reading past its signal is StftIO's own, applied to the row: no lane fetches a sample of
+// row r + 1, and the last frames of a row see zeros computed against that row's len.
+// Group forms (one descriptor over several neighbouring frames, `hop` apart) hold only while the group stays inside a row.  Groups
+// start at multiples of their size, so they never straddle a seam iff the size divides `frames`; where it does not, the policy
+// refuses the form (wg_desc_ok, group_rows_ok) and the kernels take their per-transform paths.
+template <class Base>
+struct StftRowsOf : Base {
+    // The wave-split kernels (fft_split.hip.h) are not taken: the 16384-point one has no register left for the row fields (200 bytes
+    // of scratch per lane with them), and both carry a magnitude accumulator across transforms without telling the policy which.
+    // n = 8192 runs the block-synchronised persistent kernel, n = 16384 the generic one.
+    static constexpr bool kSplitOk = false;
+    size_t frames, row_stride;
+    unsigned frames32;  // `frames` when every flat index fits 31 bits (a 32-bit division per transform), else 0
+    __device__ __forceinline__ size_t row_of(size_t xf) const { return frames32 ? (size_t)((unsigned)xf / frames32) : xf / frames; }
+    __device__ __forceinline__ StftIO at(size_t xf, size_t &f) const
+    {
+        const size_t row = row_of(xf);
+        f = xf - row * frames;
+        StftIO v = *this;
+        v.signal = this->signal + row * row_stride;
+        return v;
+    }
+    __host__ __device__ bool group_rows_ok() const { return Base::group_rows_ok() && (frames & 3) == 0; }  // groups of 2 or 4 frames
+    __device__ __forceinline__ bool wg_desc_ok(int xpb) const { return Base::wg_desc_ok(xpb) && (frames & (size_t)(xpb - 1)) == 0; }
+    __device__ __forceinline__ bool in_range(size_t xf, int i) const { size_t f; return at(xf, f).in_range(f, i); }
+    __device__ __forceinline__ float fetch(size_t xf, int i) const { size_t f; const StftIO v = at(xf, f); return v.fetch(f, i); }
+    __device__ __forceinline__ rsrc_t in_desc(size_t xf, bool valid) const { size_t f; const StftIO v = at(valid ? xf : 0, f); return v.in_desc(f, valid); }
+    __device__ __forceinline__ rsrc_t in_desc_wg(size_t xf0, size_t batch, int xpb) const
+    {
+        size_t f;
+        const StftIO v = at(xf0, f);
+        return v.in_desc_wg(f, batch, xpb);
+    }
+    __device__ __forceinline__ rsrc_t in_desc_n(size_t xf0, int cnt) const
+    {
+        size_t f;
+        const StftIO v = at(cnt > 0 ? xf0 : 0, f);
+        return v.in_desc_n(f, cnt);
+    }
+    __device__ __forceinline__ cpx<float> finish(size_t xf, int i, float x, float w) const { size_t f; const StftIO v = at(xf, f); return v.finish(f, i, x, w); }
+    __device__ __forceinline__ int frame_rem(size_t xf) const { size_t f; const StftIO v = at(xf, f); return v.frame_rem(f); }
+    __device__ __forceinline__ bool inside(size_t xf) const { size_t f; const StftIO v = at(xf, f); return v.inside(f); }
+    __device__ __forceinline__ cpx<float> load(size_t xf, int i) const { size_t f; const StftIO v = at(xf, f); return v.load(f, i); }
+};
+using StftRowsIO = StftRowsOf<StftIO>;
+
+// policies whose accumulator belongs to a ROW of the batch (StftMagRowsIO): the persistent kernel hands every transform's
+// maximum to acc_row() instead of keeping it across transforms
+template <class IO, class = void>
+struct io_row_acc { static constexpr bool value = false; };
+template <class IO>
+struct io_row_acc<IO, decltype((void)IO::kRowAcc)> { static constexpr bool value = IO::kRowAcc; };
+
+// One maximum per row.  v: a lane's candidate (a sum of squares when `root`, else a magnitude), 0 for none; all 64 lanes of the
+// wavefront call together.  A wavefront whose candidates belong to one row reduces them and issues ONE atomicMax, otherwise every
+// lane with a candidate issues its own -- exact either way (non-negative floats order like their bit patterns).
+__device__ __forceinline__ void row_max_commit(unsigned *max_bits, unsigned row, float v, bool root)
+{
+    const bool has = v > 0.0f;  // (a NaN is never a candidate)
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(has);
+    if (mask == 0) return;
+    const int lead = __builtin_ctzll(mask);
+    const unsigned r0 = (unsigned)__shfl((int)row, lead);
+    if (__builtin_amdgcn_ballot_w64(has && row != r0) == 0) {
+        float s = has ? v : 0.0f;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s = __builtin_fmaxf(s, __shfl_xor(s, off));
+        if ((int)(threadIdx.x & 63) == lead) atomicMax(max_bits + r0, __builtin_bit_cast(unsigned, root ? sqrtf(s) : s));
+    } else if (has) {
+        atomicMax(max_bits + row, __builtin_bit_cast(unsigned, root ? sqrtf(v) : v));
+    }
+}
+
+// stft_magnitudes over rows: max_bits holds one maximum per row.  A thread's accumulator names the row it belongs to and is flushed
+// when the thread's stores move to another row (fft_small_kernel: a thread stores elements of several transforms); the persistent
+// kernel, where a wavefront holds one row at a time (a transform of 64 lanes or more, or a group inside a row), commits per transform.
+struct StftMagRowsIO : StftRowsOf<StftMagIO> {
+    static constexpr bool kRowAcc = true;
+    struct Acc {
+        float s;       // largest sum of squares of row `row` this thread has rooted
+        unsigned row;
+    };
+    __device__ __forceinline__ Acc acc_init() const { return Acc{0.0f, 0u}; }
+    __device__ __forceinline__ void acc_finish(Acc a) const { row_max_commit(max_bits, a.row, a.s, true); }
+    __device__ __forceinline__ void acc_row(size_t xf0, float top) const { row_max_commit(max_bits, (unsigned)row_of(xf0), top, true); }
+    __device__ __forceinline__ void store_acc(size_t xf, int o, cpx<float> v, Acc &acc) const
+    {
+        if (o < n / 2) {
+            const unsigned row = (unsigned)row_of(xf);
+            if (row != acc.row) {
+                if (acc.s > 0.0f) atomicMax(max_bits + acc.row, __builtin_bit_cast(unsigned, sqrtf(acc.s)));
+                acc = Acc{0.0f, row};
+            }
+            const float s = sumsq(v);
+            st_stream(mags + xf * (size_t)(n / 2) + o, sqrtf(s));
+            acc.s = __builtin_fmaxf(acc.s, s);
+        }
+    }
+};
+
 // rfft.rs:444-446 pack z[i] = (x[2i], x[2i+1]) (with the optional row window of the
 // batched entry point); the post-pass of rfft.rs:450-463 runs in the kernel epilogue,
 // which writes the m+1 outputs.

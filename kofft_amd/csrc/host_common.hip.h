@@ -117,6 +117,8 @@ struct kofft_hip_ctx {
     size_t blue_tmp_bytes = 0;
     void *real_tmp = nullptr;  // the inner complex transform of real / STFT lengths the fused kernels do not cover
     size_t real_tmp_bytes = 0;
+    void *rows_tmp = nullptr;  // istft_parallel_rows on device pointers: the inverse transforms of the caller's (const) frames
+    size_t rows_tmp_bytes = 0;
     size_t big_chunk_bytes = size_t(512) << 20;  // KOFFT_HIP_BIG_CHUNK_MB; measured on config 5 with the persistent factor kernels: 128 MiB 14.7 ms, 256 13.0, 512 12.1, 1024 12.5, 2048 13.1
 };
 
@@ -375,6 +377,13 @@ template <> struct PersistCfg<11, StftIO> : PersistCfgStftBig<StftIO> {};
 // n = 2048 / 4096 0.219 / 0.226 against 0.250 / 0.254 ms)
 template <> struct PersistCfg<12, StftMagIO> : PersistCfgStftBig<StftMagIO> {};
 template <> struct PersistCfg<11, StftMagIO> : PersistCfgStftBig<StftMagIO> {};
+// the row-aware heirs (fft_wg.hip.h, StftRowsOf) run their parents' configurations
+template <> struct PersistCfg<10, StftRowsIO> : PersistCfg<10, StftIO> {};
+template <> struct PersistCfg<11, StftRowsIO> : PersistCfg<11, StftIO> {};
+template <> struct PersistCfg<12, StftRowsIO> : PersistCfg<12, StftIO> {};
+template <> struct PersistCfg<10, StftMagRowsIO> : PersistCfg<10, StftMagIO> {};
+template <> struct PersistCfg<11, StftMagRowsIO> : PersistCfg<11, StftMagIO> {};
+template <> struct PersistCfg<12, StftMagRowsIO> : PersistCfg<12, StftMagIO> {};
 // rfft 8192 (m = 4096): window pairs in registers so that two workgroups (exchange buffer + post-pass table) fit a CU
 template <> struct PersistCfg<12, RfftIO<float>> {
     static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 2;
@@ -687,6 +696,30 @@ inline int ensure_real_tmp(kofft_hip_ctx *ctx, size_t bytes)
     return KOFFT_OK;
 }
 
+// hann(win_len), cached per context like a planner table (kind 4): stft_magnitudes' window, one signal or rows
+inline int hann_table(kofft_hip_ctx *ctx, size_t win_len, const float **out)
+{
+    auto key = std::make_pair(4, win_len);
+    auto it = ctx->tables.find(key);
+    if (it != ctx->tables.end()) {
+        *out = static_cast<const float *>(it->second);
+        return KOFFT_OK;
+    }
+    std::vector<float> w(win_len);
+    kofft_tables::hann_f32(win_len, w.data());
+    void *d = nullptr;
+    KOFFT_HIP_TRY(ctx, hipMalloc(&d, win_len * sizeof(float)));
+    const hipError_t ce = hipMemcpy(d, w.data(), win_len * sizeof(float), hipMemcpyHostToDevice);
+    if (ce != hipSuccess) {  // nothing is cached, nothing is left behind
+        (void)hipFree(d);
+        ctx->last_error = std::string("stft_magnitudes window upload: ") + hipGetErrorString(ce);
+        return KOFFT_ERR_HIP;
+    }
+    ctx->tables[key] = d;
+    *out = static_cast<const float *>(d);
+    return KOFFT_OK;
+}
+
 // ---- typed device-pointer entry points, one translation unit per family ---------------------------------------------
 template <typename T>
 int fft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch, int inverse);  // k_complex_f32/f64.hip
@@ -758,6 +791,16 @@ int istft_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, const float *d
               float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode = 1, size_t start0 = 0);
 int stft_mag_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t win_len, size_t hop, float *d_mags,
                  size_t frames, float *d_max);
+// k_stft_rows.hip: the three families over `rows` signals (row r at + r * row_stride, one window, `frames` frames per row).
+// *_check: the argument checks alone, before the context or a device is touched; host_form adds stft()'s frame-count check.
+int stft_rows_check(bool host_form, bool mags, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames);
+int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                  size_t win_len, size_t hop, float *d_out, size_t frames);
+int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop,
+                      float *d_mags, size_t frames, float *d_max);
+int istft_rows_check(size_t rows, size_t frames, size_t win_len, size_t hop, size_t out_len, size_t scratch_len, int mode);
+int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
+                   float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames);
 template <typename T>
 int fft_nd_dev(kofft_hip_ctx *ctx, T *d_data, size_t depth, size_t rows, size_t cols, int inverse);  // k_nd.hip
 

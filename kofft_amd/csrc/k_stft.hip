@@ -219,27 +219,10 @@ int stft_mag_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t 
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     KOFFT_HIP_TRY(ctx, hipMemsetAsync(d_max, 0, sizeof(float), ctx->stream));  // max_mag starts at 0.0
     if (frames == 0) return KOFFT_OK;
-    // hann(win_len), cached per context like a planner table (kind 4)
     const float *d_win = nullptr;
     {
-        auto key = std::make_pair(4, win_len);
-        auto it = ctx->tables.find(key);
-        if (it == ctx->tables.end()) {
-            std::vector<float> w(win_len);
-            kofft_tables::hann_f32(win_len, w.data());
-            void *d = nullptr;
-            KOFFT_HIP_TRY(ctx, hipMalloc(&d, win_len * sizeof(float)));
-            const hipError_t ce = hipMemcpy(d, w.data(), win_len * sizeof(float), hipMemcpyHostToDevice);
-            if (ce != hipSuccess) {  // nothing is cached, nothing is left behind
-                (void)hipFree(d);
-                ctx->last_error = std::string("stft_magnitudes window upload: ") + hipGetErrorString(ce);
-                return KOFFT_ERR_HIP;
-            }
-            ctx->tables[key] = d;
-            d_win = static_cast<const float *>(d);
-        } else {
-            d_win = static_cast<const float *>(it->second);
-        }
+        const int wrc = hann_table(ctx, win_len, &d_win);
+        if (wrc) return wrc;
     }
     if (!fused_len_ok<float>(win_len)) {
         // any other window length: the composed STFT into scratch, then magnitudes + maximum in one pass (in frame chunks)

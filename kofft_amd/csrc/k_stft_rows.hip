@@ -1,0 +1,299 @@
+// k_stft_rows.hip -- STFT (stft.rs:76-105), stft_magnitudes (visual/spectrogram.rs:52-76) and ISTFT (stft.rs:117-156, 289-343) over
+// ROWS of signals on device pointers.  Row r of every output is what k_stft.hip's single-signal entry returns for
+// signal r alone; one launch chain serves all rows.
+#include "host_common.hip.h"
+
+namespace kofft {
+namespace host {
+
+// ---- composed form (window lengths the fused kernels do not cover): the framing product of transforms t0 .. of the flat index
+// t = row * frames + frame into `out`, then fft_dev in place.  The twin of stft_frame_kernel.
+__global__ __launch_bounds__(256) void stft_rows_frame_kernel(const float *__restrict__ signal, const float *__restrict__ window,
+                                                              cpx<float> *__restrict__ out, const size_t len, const size_t row_stride,
+                                                              const size_t frames, const size_t win_len, const size_t hop, const size_t t0,
+                                                              const size_t total /* transforms * win_len */)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const size_t t = t0 + idx / win_len, i = idx % win_len;
+    const size_t row = t / frames, f = t - row * frames;
+    const size_t pos = f * hop + i;  // inside the row: a frame never reads the head of the next one
+    out[idx] = mk<float>(pos < len ? signal[row * row_stride + pos] * window[i] : 0.0f, 0.0f);  // stft.rs:95-100
+}
+
+// magnitudes of bins 0 .. n/2-1 of composed frames t0 .. and each row's maximum (spectrogram.rs:63-71).  The twin of mag_kernel:
+// one element per thread, whole wavefronts reach row_max_commit.
+__global__ __launch_bounds__(256) void mag_rows_kernel(const cpx<float> *__restrict__ spec, float *__restrict__ mags,
+                                                       unsigned *__restrict__ max_bits, const size_t frames, const size_t win_len,
+                                                       const size_t t0, const size_t total /* transforms * (win_len/2) */)
+{
+    const size_t half = win_len / 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    float v = 0.0f;
+    unsigned row = 0;
+    if (idx < total) {
+        const size_t t = idx / half;
+        const cpx<float> c = spec[t * win_len + (idx - t * half)];
+        v = sqrtf(c.re * c.re + c.im * c.im);
+        mags[idx] = v;
+        row = (unsigned)((t0 + t) / frames);
+    }
+    row_max_commit(max_bits, row, v, false);  // (`if mag > max_mag`: a NaN is never a candidate)
+}
+
+// The ordered overlap-add of istft_ola_kernel over rows: one thread per output sample of rows * out_len, the same sums in the same
+// order (frames f_lo .. f_hi of the sample's OWN row, increasing f; no atomics).  MODE 1: stft::istft, MODE 2: stft::inverse_parallel.
+template <int MODE>
+__global__ __launch_bounds__(256) void istft_ola_rows_kernel(const cpx<float> *__restrict__ frames, const float *__restrict__ window,
+                                                             float *__restrict__ output, float *__restrict__ scratch, const size_t nframes,
+                                                             const size_t win_len, const size_t hop, const size_t out_len,
+                                                             const size_t total /* rows * out_len */)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const size_t row = idx / out_len, s = idx - row * out_len;
+    const cpx<float> *fr = frames + row * nframes * win_len;
+    float acc = output[idx];  // accumulated into the caller's buffer (stft.rs:144, 330)
+    float norm = 0.0f;
+    if (nframes > 0 && win_len > 0) {
+        size_t f_hi = s / hop;
+        if (f_hi > nframes - 1) f_hi = nframes - 1;
+        const size_t f_lo = (s >= win_len) ? (s - win_len) / hop + 1 : 0;
+        for (size_t f = f_lo; f <= f_hi; ++f) {
+            const size_t i = s - f * hop;
+            const float w = window[i];
+            acc = acc + fr[f * win_len + i].re * w;
+            norm = norm + w * w;
+        }
+    }
+    if (MODE == 1) scratch[idx] = norm;
+    if (norm > 1e-8f) output[idx] = acc / norm;  // stft.rs:150-154 / 335-341
+    else output[idx] = (MODE == 2) ? 0.0f : acc;
+}
+
+static bool mul_ok(size_t a, size_t b, size_t *out)
+{
+    if (a != 0 && b > SIZE_MAX / a) return false;
+    *out = a * b;
+    return true;
+}
+
+int stft_rows_check(bool host_form, bool mags, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;  // stft.rs:83 / 242
+    if (host_form || mags) {
+        const size_t required = len / hop + (len % hop != 0);  // stft.rs:86
+        if (frames < required) return KOFFT_ERR_MISMATCHED_LENGTHS;
+    }
+    if (rows == 0 || frames == 0) return KOFFT_OK;
+    if (win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (!complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
+    if (rows > 1 && row_stride < len) return KOFFT_ERR_INVALID_VALUE;
+    size_t t, e;
+    if (rows > 0xffffffffULL || !mul_ok(rows, frames, &t) || !mul_ok(t, win_len, &e) || e > (SIZE_MAX >> 4)) return KOFFT_ERR_UNSUPPORTED;
+    if (!mul_ok(rows, row_stride > len ? row_stride : len, &e) || e > (SIZE_MAX >> 3)) return KOFFT_ERR_UNSUPPORTED;
+    return KOFFT_OK;
+}
+
+template <class IO>
+static void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
+                         size_t hop, size_t frames)
+{
+    io.signal = d_signal;
+    io.window = d_window;
+    io.out = nullptr;
+    io.len = len;
+    io.hop = hop;
+    io.start0 = 0;
+    io.n = (int)win_len;
+    io.frames = frames;
+    io.row_stride = rows > 1 ? row_stride : 0;
+    io.frames32 = rows * frames < (size_t(1) << 31) ? (unsigned)frames : 0u;
+}
+
+// transforms t0 .. t0 + nt of the flat index, composed: framing product into dst, fft_dev in place
+static int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
+                              size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt)
+{
+    const size_t blocks = (nt * win_len + 255) / 256;
+    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(stft_rows_frame_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_signal, d_window, dst, len, row_stride,
+                       frames, win_len, hop, t0, nt * win_len);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return fft_dev<float>(ctx, reinterpret_cast<const float *>(dst), reinterpret_cast<float *>(dst), win_len, nt, 0);
+}
+
+static size_t composed_chunk(size_t win_len, size_t count)
+{
+    size_t chunk = (size_t(512) << 20) / (win_len * 8);
+    if (chunk < 1) chunk = 1;
+    return chunk > count ? count : chunk;
+}
+
+int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                  size_t win_len, size_t hop, float *d_out, size_t frames)
+{
+    const int crc = stft_rows_check(false, false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (!ctx || (!d_signal && len) || !d_window || !d_out) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t total = rows * frames;
+    if (rows == 1) row_stride = 0;
+    if (!fused_len_ok<float>(win_len)) {
+        // any other window length: composed over all rows at once (BlueStftSrc knows one signal only)
+        const size_t chunk = composed_chunk(win_len, total);
+        for (size_t t0 = 0; t0 < total; t0 += chunk) {
+            const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
+            const int rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_window, win_len, hop,
+                                              reinterpret_cast<cpx<float> *>(d_out) + t0 * win_len, t0, nt);
+            if (rc) return rc;
+        }
+        return KOFFT_OK;
+    }
+    StftRowsIO io{};
+    fill_rows_io(io, d_signal, rows, len, row_stride, d_window, win_len, hop, frames);
+    io.out = reinterpret_cast<cpx<float> *>(d_out);
+    return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
+}
+
+// Frames per row from which a row alone is a persistent-kernel batch for StftMagIO; SIZE_MAX: never.  These are dispatch()'s f32
+// thresholds (host_common.hip.h) with its conditions -- use_persist, and persist_small and group_rows_ok() below n = 512 -- and have to
+// follow them; a threshold that lags behind only changes which of two routes with the same bytes runs.
+static size_t mag_rows_loop_frames(const kofft_hip_ctx *ctx, size_t win_len, size_t hop)
+{
+    if (!ctx->use_persist) return SIZE_MAX;
+    const int L = ilog2(win_len);
+    const size_t cus = (size_t)ctx->num_cus;
+    if (L == 12 || L == 13) return cus * 4;
+    if (L == 11) return cus * 16;
+    if (L == 10) return cus * 32;
+    if (L == 9) return cus * 64;
+    if (L >= 6 && L <= 8 && ctx->persist_small && hop <= (size_t(1) << 24)) return cus * (size_t(128) << (8 - L));
+    return SIZE_MAX;
+}
+// ... and only for a few rows: the loop is one launch chain per row
+constexpr size_t kMagRowsLoopMaxRows = 32;
+
+int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop,
+                      float *d_mags, size_t frames, float *d_max)
+{
+    const int crc = stft_rows_check(false, true, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0) return crc;
+    // (a one-sample window has no magnitude bins: d_mags is an empty array and may be null)
+    if (!ctx || !d_max || (frames && ((!d_mags && win_len >= 2) || (!d_samples && len)))) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    KOFFT_HIP_TRY(ctx, hipMemsetAsync(d_max, 0, rows * sizeof(float), ctx->stream));  // every max_mag starts at 0.0
+    if (frames == 0) return KOFFT_OK;
+    const float *d_win = nullptr;
+    int rc = hann_table(ctx, win_len, &d_win);
+    if (rc) return rc;
+    const size_t total = rows * frames;
+    if (rows == 1) row_stride = 0;
+    unsigned *max_bits = reinterpret_cast<unsigned *>(d_max);
+    if (!fused_len_ok<float>(win_len)) {
+        const size_t chunk = composed_chunk(win_len, total);
+        rc = ensure_real_tmp(ctx, chunk * win_len * 8);
+        if (rc) return rc;
+        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp);
+        const size_t half = win_len / 2;
+        for (size_t t0 = 0; t0 < total; t0 += chunk) {
+            const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
+            rc = stft_rows_composed(ctx, d_samples, len, row_stride, frames, d_win, win_len, hop, spec, t0, nt);
+            if (rc) return rc;
+            if (nt * half) {
+                const size_t blocks = (nt * half + 255) / 256;
+                if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+                hipLaunchKernelGGL(mag_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, d_mags + t0 * half, max_bits,
+                                   frames, win_len, t0, nt * half);
+                KOFFT_HIP_TRY(ctx, hipGetLastError());
+            }
+        }
+        return KOFFT_OK;
+    }
+    // Rows long enough to reach dispatch()'s persistent kernels on their own run the single-signal kernel row by row: there the
+    // maximum costs one atomicMax per wavefront and KERNEL, here one per wavefront and TRANSFORM, and with few rows those pile up on a few
+    // addresses (measured, n = 1024: 8 rows x 14 063 frames 1.30 ms against the loop's 0.42; 256 x 1875 1.53 against 7.37 -- DESIGN.md 5.18).
+    if (rows <= kMagRowsLoopMaxRows && frames >= mag_rows_loop_frames(ctx, win_len, hop)) {
+        for (size_t r = 0; r < rows; ++r) {
+            rc = stft_mag_dev(ctx, d_samples + r * row_stride, len, win_len, hop, d_mags + r * frames * (win_len / 2), frames, d_max + r);
+            if (rc) return rc;
+        }
+        return KOFFT_OK;
+    }
+    StftMagRowsIO io{};
+    fill_rows_io(io, d_samples, rows, len, row_stride, d_win, win_len, hop, frames);
+    io.mags = d_mags;
+    io.max_bits = max_bits;
+    return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
+}
+
+int istft_rows_check(size_t rows, size_t frames, size_t win_len, size_t hop, size_t out_len, size_t scratch_len, int mode)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;                               // stft.rs:125 / 299
+    if (mode == 1 && scratch_len != out_len) return KOFFT_ERR_MISMATCHED_LENGTHS;  // stft.rs:128
+    if (rows == 0) return KOFFT_OK;
+    if (frames > 0 && win_len == 0) return KOFFT_ERR_EMPTY_INPUT;                  // fft.ifft(&mut []) -> fft.rs:1136
+    if (frames > 0 && !complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
+    size_t t, e;
+    if (!mul_ok(rows, frames, &t) || !mul_ok(t, win_len, &e) || e > (SIZE_MAX >> 4) || !mul_ok(rows, out_len, &e) || e > (SIZE_MAX >> 3))
+        return KOFFT_ERR_UNSUPPORTED;
+    return KOFFT_OK;
+}
+
+// mode 1 (istft): every frame inverse-transformed in place, output accumulated into, scratch = the window-square sums.
+// mode 2 (inverse_parallel): keep_frames leaves the caller's frames alone (their inverse transforms go to the context's scratch).
+// (istft_fused_kernel knows one signal only: always the two-kernel route.)
+int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
+                   float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames)
+{
+    const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
+    if (crc || rows == 0) return crc;
+    if (!ctx || (frames && (!d_frames || !d_window)) || (out_len && (!d_output || (mode == 1 && !d_scratch)))) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // keep_frames: whole rows at a time through at most 512 MiB of the context's scratch (one row's frames where a row alone is
+    // larger) -- copy, inverse transform, overlap-add; the rows are independent, so the sums and their order do not change
+    size_t rows_per = rows;
+    if (keep_frames && frames > 0) {
+        rows_per = (size_t(512) << 20) / (frames * win_len * 8);
+        rows_per = rows_per < 1 ? 1 : (rows_per > rows ? rows : rows_per);
+        const size_t bytes = rows_per * frames * win_len * 8;
+        if (ctx->rows_tmp_bytes < bytes) {
+            if (ctx->rows_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->rows_tmp));
+            ctx->rows_tmp = nullptr;
+            ctx->rows_tmp_bytes = 0;
+            KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->rows_tmp, bytes));
+            ctx->rows_tmp_bytes = bytes;
+        }
+    }
+    if ((rows_per * out_len + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    for (size_t r0 = 0; r0 < rows; r0 += rows_per) {
+        const size_t nr = rows - r0 < rows_per ? rows - r0 : rows_per;
+        const float *time_frames = d_frames + r0 * frames * win_len * 2;
+        if (frames > 0) {
+            float *dst = d_frames + r0 * frames * win_len * 2;
+            if (keep_frames) {
+                dst = static_cast<float *>(ctx->rows_tmp);
+                KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dst, time_frames, nr * frames * win_len * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+            const int rc = fft_dev<float>(ctx, dst, dst, win_len, nr * frames, 1);
+            if (rc) return rc;
+            time_frames = dst;
+        }
+        if (out_len == 0) continue;
+        const size_t total = nr * out_len;
+        const unsigned blocks = (unsigned)((total + 255) / 256);
+        const cpx<float> *fr = reinterpret_cast<const cpx<float> *>(time_frames);
+        float *out = d_output + r0 * out_len, *scr = d_scratch ? d_scratch + r0 * out_len : nullptr;
+        if (mode == 2)
+            hipLaunchKernelGGL(istft_ola_rows_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, fr, d_window, out, scr, frames, win_len, hop,
+                               out_len, total);
+        else
+            hipLaunchKernelGGL(istft_ola_rows_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, fr, d_window, out, scr, frames, win_len, hop,
+                               out_len, total);
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+    }
+    return KOFFT_OK;
+}
+
+}  // namespace host
+}  // namespace kofft

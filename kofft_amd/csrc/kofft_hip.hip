@@ -691,6 +691,7 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     if (ctx->big_tmp && !ctx->big_tmp_external) (void)hipFree(ctx->big_tmp);
     if (ctx->blue_tmp) (void)hipFree(ctx->blue_tmp);
     if (ctx->real_tmp) (void)hipFree(ctx->real_tmp);
+    if (ctx->rows_tmp) (void)hipFree(ctx->rows_tmp);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -759,9 +760,9 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
         ctx->stage[i] = nullptr;
         ctx->stage_bytes[i] = 0;
     }
-    void **bufs[] = {&ctx->big_tmp, &ctx->blue_tmp, &ctx->real_tmp};
-    size_t *sizes[] = {&ctx->big_tmp_bytes, &ctx->blue_tmp_bytes, &ctx->real_tmp_bytes};
-    for (int i = 0; i < 3; ++i) {
+    void **bufs[] = {&ctx->big_tmp, &ctx->blue_tmp, &ctx->real_tmp, &ctx->rows_tmp};
+    size_t *sizes[] = {&ctx->big_tmp_bytes, &ctx->blue_tmp_bytes, &ctx->real_tmp_bytes, &ctx->rows_tmp_bytes};
+    for (int i = 0; i < 4; ++i) {
         if (*bufs[i] && !(i == 0 && ctx->big_tmp_external)) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         *sizes[i] = 0;
@@ -1209,6 +1210,143 @@ int kofft_hip_stft_magnitudes_f32(kofft_hip_ctx *ctx, const float *samples, size
     KOFFT_HIP_TRY(ctx, hipMemcpyAsync(max_mag, ctx->stage[2], sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KOFFT_OK;
+}
+
+// ---- STFT, stft_magnitudes and ISTFT over rows of signals (k_stft_rows.hip) --------------------------------------
+// Host rows `row_stride` apart are packed (stride len) before they travel: the gaps are not the call's to read.
+static const float *pack_rows(const float *signal, size_t rows, size_t len, size_t row_stride, std::vector<float> &packed, size_t *in_row)
+{
+    *in_row = len;
+    if (len == 0) {  // no samples at all: one placeholder float per row, never read (len stays 0 on the device)
+        packed.assign(rows, 0.0f);
+        *in_row = 1;
+        return packed.data();
+    }
+    if (rows == 1 || row_stride == len) return signal;
+    packed.resize(rows * len);
+    for (size_t r = 0; r < rows; ++r) std::memcpy(packed.data() + r * len, signal + r * row_stride, len * sizeof(float));
+    return packed.data();
+}
+
+int kofft_hip_dev_stft_rows_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                const float *d_window, size_t win_len, size_t hop, float *d_out, size_t frames)
+{
+    return stft_rows_dev(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, d_out, frames);
+}
+
+int kofft_hip_stft_rows_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                            size_t win_len, size_t hop, float *out, size_t frames)
+{
+    const int crc = stft_rows_check(true, false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (!ctx || (!signal && len) || !window || !out) return KOFFT_ERR_NULL;
+    std::vector<float> packed;
+    size_t in_row = 0;
+    const float *src = pack_rows(signal, rows, len, row_stride, packed, &in_row);
+    // a chunk of the pipeline is whole rows: no seam logic on the host
+    return rows_host<float>(ctx, src, out, rows, in_row, frames * win_len * 2, false, window, win_len, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return stft_rows_dev(ctx, d_in, nb, len, in_row, d_win, win_len, hop, d_out, frames);
+                            });
+}
+
+int kofft_hip_dev_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len, size_t row_stride,
+                                           size_t win_len, size_t hop, float *d_mags, size_t frames, float *d_max)
+{
+    return stft_mag_rows_dev(ctx, d_samples, rows, len, row_stride, win_len, hop, d_mags, frames, d_max);
+}
+
+int kofft_hip_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *samples, size_t rows, size_t len, size_t row_stride, size_t win_len,
+                                       size_t hop, float *mags, size_t frames, float *max_mag)
+{
+    const int crc = stft_rows_check(true, true, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0) return crc;
+    if (!ctx || !max_mag || (frames && ((!mags && win_len >= 2) || (!samples && len)))) return KOFFT_ERR_NULL;
+    if (frames == 0 || win_len < 2) {  // no magnitude bins: every maximum is its starting value
+        for (size_t r = 0; r < rows; ++r) max_mag[r] = 0.0f;
+        return KOFFT_OK;
+    }
+    std::vector<float> packed;
+    size_t in_row = 0;
+    const float *src = pack_rows(samples, rows, len, row_stride, packed, &in_row);
+    float *const outs[2] = {mags, max_mag};
+    const size_t in_rows[1] = {in_row}, out_rows[2] = {frames * (win_len / 2), 1};
+    // never zero-copy: the maxima are atomicMax targets and stay in device memory, as in the single-signal form above
+    return rows_host_n<float>(ctx, rows, 1, &src, in_rows, 2, outs, out_rows, false, nullptr, 0, false, true,
+                              [&](float *const *d_in, float *const *d_out, const float *, size_t nb) {
+                                  return stft_mag_rows_dev(ctx, d_in[0], nb, len, in_row, win_len, hop, d_out[0], frames, d_out[1]);
+                              });
+}
+
+int kofft_hip_dev_istft_rows_f32(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len,
+                                 size_t hop, float *d_output, size_t out_len, float *d_scratch, size_t scratch_len)
+{
+    return istft_rows_dev(ctx, d_frames, rows, frames, d_window, win_len, hop, d_output, out_len, d_scratch, scratch_len, 1, false);
+}
+
+int kofft_hip_dev_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *d_frames, size_t rows, size_t frames, const float *d_window,
+                                          size_t win_len, size_t hop, float *d_output, size_t out_len)
+{
+    return istft_rows_dev(ctx, const_cast<float *>(d_frames), rows, frames, d_window, win_len, hop, d_output, out_len, nullptr, out_len, 2,
+                          true);
+}
+
+// host-pointer wrapper of both modes: one staging allocation [frames | output | scratch | window], or the same pieces in the pinned,
+// device-mapped buffer for small calls (three row arrays: more than rows_host_n carries)
+static int istft_rows_host(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, size_t hop,
+                           float *output, size_t out_len, float *scratch, size_t scratch_len, int mode)
+{
+    const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
+    if (crc || rows == 0) return crc;
+    if (!ctx || (frames && (!frames_data || !window)) || (out_len && (!output || (mode == 1 && !scratch)))) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t fr_bytes = rows * frames * win_len * 2 * sizeof(float), o_bytes = rows * out_len * sizeof(float);
+    auto align = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t a1 = align(fr_bytes), a2 = a1 + align(o_bytes), a3 = a2 + align(o_bytes), total = a3 + win_len * sizeof(float) + 256;
+    const bool zero_copy = ctx->zero_copy && total <= kZeroCopyMax && ensure_pinned(ctx, total) == KOFFT_OK;
+    char *h = nullptr, *dd = nullptr;
+    if (zero_copy) {
+        h = static_cast<char *>(ctx->pinned);
+        dd = static_cast<char *>(ctx->pinned_dev);
+        if (fr_bytes) std::memcpy(h, frames_data, fr_bytes);
+        if (o_bytes) std::memcpy(h + a1, output, o_bytes);
+        if (win_len) std::memcpy(h + a3, window, win_len * sizeof(float));
+    } else {
+        const int rc = ensure_stage(ctx, 0, total);
+        if (rc) return rc;
+        dd = static_cast<char *>(ctx->stage[0]);
+        if (fr_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dd, frames_data, fr_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (o_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dd + a1, output, o_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (win_len) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dd + a3, window, win_len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int rc = istft_rows_dev(ctx, reinterpret_cast<float *>(dd), rows, frames, reinterpret_cast<const float *>(dd + a3), win_len, hop,
+                                  reinterpret_cast<float *>(dd + a1), out_len, reinterpret_cast<float *>(dd + a2), out_len, mode, false);
+    if (rc) return rc;
+    const bool frames_back = mode == 1 && fr_bytes;  // inverse_parallel clones each frame (stft.rs:310): the caller's stay untouched
+    if (zero_copy) {
+        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (frames_back) std::memcpy(frames_data, h, fr_bytes);
+        if (o_bytes) std::memcpy(output, h + a1, o_bytes);
+        if (o_bytes && mode == 1) std::memcpy(scratch, h + a2, o_bytes);
+        return KOFFT_OK;
+    }
+    if (frames_back) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(frames_data, dd, fr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (o_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(output, dd + a1, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (o_bytes && mode == 1) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(scratch, dd + a2, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KOFFT_OK;
+}
+
+int kofft_hip_istft_rows_f32(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len,
+                             size_t hop, float *output, size_t out_len, float *scratch, size_t scratch_len)
+{
+    return istft_rows_host(ctx, frames_data, rows, frames, window, win_len, hop, output, out_len, scratch, scratch_len, 1);
+}
+
+int kofft_hip_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *frames_data, size_t rows, size_t frames, const float *window,
+                                      size_t win_len, size_t hop, float *output, size_t out_len)
+{
+    return istft_rows_host(ctx, const_cast<float *>(frames_data), rows, frames, window, win_len, hop, output, out_len, nullptr, out_len, 2);
 }
 
 int kofft_hip_fftnd_c32(kofft_hip_ctx *ctx, float *data, size_t depth, size_t rows, size_t cols, int inverse)
