@@ -95,9 +95,9 @@ struct kofft_hip_ctx {
     std::vector<kofft_spectral_slot> czt_slots;
     void *goertzel_coeff = nullptr;
     std::vector<float> goertzel_last;
-    // staging for the host-pointer entry points
-    void *stage[3] = {nullptr, nullptr, nullptr};
-    size_t stage_bytes[3] = {0, 0, 0};
+    // staging for the host-pointer entry points: one device buffer, laid out by host_layout() (host_layout.h)
+    void *stage = nullptr;
+    size_t stage_bytes = 0;
     // intermediate of the two-factor large-n path (fft_big.hip.h): `big_chunk` transforms at a time
     void *big_tmp = nullptr;
     size_t big_tmp_bytes = 0;
@@ -208,15 +208,26 @@ inline int ensure_pinned(kofft_hip_ctx *ctx, size_t bytes)
     return KOFFT_OK;
 }
 
-inline int ensure_stage(kofft_hip_ctx *ctx, int which, size_t bytes)
+inline int ensure_stage(kofft_hip_ctx *ctx, size_t bytes)
 {
-    if (ctx->stage_bytes[which] >= bytes) return KOFFT_OK;
-    if (ctx->stage[which]) KOFFT_HIP_TRY(ctx, hipFree(ctx->stage[which]));
-    ctx->stage[which] = nullptr;
-    ctx->stage_bytes[which] = 0;
-    KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->stage[which], bytes));
-    ctx->stage_bytes[which] = bytes;
+    if (ctx->stage_bytes >= bytes) return KOFFT_OK;
+    if (ctx->stage) KOFFT_HIP_TRY(ctx, hipFree(ctx->stage));
+    ctx->stage = nullptr;
+    ctx->stage_bytes = 0;
+    KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->stage, bytes));
+    ctx->stage_bytes = bytes;
     return KOFFT_OK;
+}
+
+// both buffers of the host staging path go (kofft_hip_destroy, kofft_hip_release_scratch)
+inline void drop_host_buffers(kofft_hip_ctx *ctx)
+{
+    if (ctx->stage) (void)hipFree(ctx->stage);
+    ctx->stage = nullptr;
+    ctx->stage_bytes = 0;
+    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    ctx->pinned = ctx->pinned_dev = nullptr;
+    ctx->pinned_bytes = 0;
 }
 
 // ---------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // kofft_hip.hip -- host-pointer wrappers (staging, pipelining, zero-copy) and the extern "C" ABI of
 // include/kofft_hip.h.  The kernels live in the k_*.hip translation units (host_common.hip.h).
 #include "host_common.hip.h"
+#include "host_layout.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -118,127 +119,125 @@ int pipeline_chunks(kofft_hip_ctx *ctx, size_t nchunks, Up up, Run run, Down dow
     return rc;
 }
 
-// does a host batch of `bytes` (both directions together) in `batch` independent rows, `row_bytes` in the smaller of the input and
-// output row, go through the pipeline?
+// does a host batch of `bytes` (both directions together) in `batch` independent rows, `row_bytes` in the smallest row of an array that
+// travels, go through the pipeline?
 inline bool use_host_pipeline(const kofft_hip_ctx *ctx, size_t bytes, size_t batch, size_t row_bytes)
 {
     return ctx->host_pipeline && bytes >= (size_t(128) << 20) && batch >= 16 && row_bytes <= (size_t(8) << 20);
 }
-inline size_t host_chunk_rows(const kofft_hip_ctx *ctx, size_t batch)
-{
-    const size_t parts = (size_t)(ctx->host_chunks > 0 ? ctx->host_chunks : 8);
-    return (batch + parts - 1) / parts;
-}
 
-// One host-pointer call over `batch` independent rows of nin input arrays and nout output arrays: in_rows[k] elements of T per row of
-// input k, out_rows[k] per row of output k (in_place: output k is input k transformed, one device buffer for both), and an optional side input
-// of side_len elements that every row reads (rfft's window), uploaded once.  dev(d_ins, d_outs, d_side, rows) enqueues the device work
-// for `rows` rows on ctx->stream; d_ins / d_outs point at each array's first row.  Three ways through:
-//  * zero-copy, when zero_copy_ok and neither direction (inputs + side input up, outputs down) is above kZeroCopyMax: the rows go
-//    through the pinned, device-mapped buffer as [inputs | side | outputs], 256-byte aligned pieces;
-//  * pipelined (use_host_pipeline, when pipeline_ok; every array's rows must be contiguous): pipeline_chunks over the stages, the side
-//    input uploaded ahead of the chunks;
-//  * serial: upload, device work, download through the stages (stage 0: the inputs, stage 1: the outputs, 256-byte aligned pieces).
-constexpr int kMaxRowArrays = 2;
+// One array of a host-pointer call: `row` elements of T per row (0: an empty array).  `up` is copied to the device before the work,
+// `down` receives the device's copy after it -- the same pointer for an array transformed in place, both null for device-only space.
+template <typename T>
+struct HostArray {
+    const T *up;
+    T *down;
+    size_t row;
+};
+
+// The one way a host-pointer call reaches the device: `batch` independent rows of n <= kMaxHostArrays arrays, and an optional side
+// input of side_len elements that every row reads (rfft's window, the Goertzel coefficients), uploaded once.  The arrays and the side
+// input lie in one buffer as host_layout() places them; dev(d, d_side, rows) enqueues the device work for `rows` rows on ctx->stream,
+// d[k] pointing at array k's first row (never null, also for an empty array).  Three ways through:
+//  * zero-copy, when the caller's own rule allows it (`zero_copy`) and the context does: the buffer is the pinned, device-mapped one,
+//    which the kernels read and write over PCIe;
+//  * pipelined (use_host_pipeline, when pipeline_ok; every array's rows must be contiguous): pipeline_chunks over the staged device
+//    buffer, chunk c of array k being its rows [c * chunk, ...), the side input uploaded ahead of the chunks;
+//  * serial: upload (the arrays, then the side input: a small copy queued ahead of the large ones costs a staged call of a few MiB
+//    about 12 us), device work, download through the staged device buffer.
 template <typename T, class Dev>
-int rows_host_n(kofft_hip_ctx *ctx, size_t batch, int nin, const T *const *ins, const size_t *in_rows, int nout, T *const *outs,
-                const size_t *out_rows, bool in_place, const T *side, size_t side_len, bool zero_copy_ok, bool pipeline_ok, Dev dev)
+int stage_host(kofft_hip_ctx *ctx, size_t batch, int n, const HostArray<T> *a, const T *side, size_t side_len, bool zero_copy,
+               bool pipeline_ok, Dev dev)
 {
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto align = [](size_t b) { return (b + 255) & ~size_t(255); };
-    size_t in_off[kMaxRowArrays], out_off[kMaxRowArrays];  // each array's offset in its piece (zero-copy) or stage
-    size_t in_bytes = 0, out_bytes = 0, in_span = 0, out_span = 0;
-    for (int k = 0; k < nin; ++k) {
-        in_off[k] = align(in_span);
-        in_span = in_off[k] + batch * in_rows[k] * sizeof(T);
-        in_bytes += batch * in_rows[k] * sizeof(T);
-    }
-    for (int k = 0; k < nout; ++k) {
-        out_off[k] = align(out_span);
-        out_span = out_off[k] + batch * out_rows[k] * sizeof(T);
-        out_bytes += batch * out_rows[k] * sizeof(T);
-    }
+    size_t row[kMaxHostArrays];
+    for (int k = 0; k < n; ++k) row[k] = a[k].row;
     const size_t side_bytes = side ? side_len * sizeof(T) : 0;
-    T *d_ins[kMaxRowArrays], *d_outs[kMaxRowArrays];
-    if (zero_copy_ok && ctx->zero_copy && std::max(in_bytes + side_bytes, out_bytes) <= kZeroCopyMax) {
-        const size_t o_side = align(in_span);
-        const size_t o_out = in_place ? 0 : align(o_side + side_bytes);
-        if (ensure_pinned(ctx, in_place ? in_span : o_out + out_span) == KOFFT_OK) {
-            char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-            for (int k = 0; k < nin; ++k) {
-                std::memcpy(h + in_off[k], ins[k], batch * in_rows[k] * sizeof(T));
-                d_ins[k] = reinterpret_cast<T *>(dd + in_off[k]);
-            }
-            if (side) std::memcpy(h + o_side, side, side_bytes);
-            const T *d_side = side ? reinterpret_cast<const T *>(dd + o_side) : nullptr;
-            for (int k = 0; k < nout; ++k) d_outs[k] = reinterpret_cast<T *>(dd + o_out + out_off[k]);
-            int zrc = dev(d_ins, d_outs, d_side, batch);
-            if (zrc) return zrc;
-            KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            for (int k = 0; k < nout; ++k) std::memcpy(outs[k], h + o_out + out_off[k], batch * out_rows[k] * sizeof(T));
-            return KOFFT_OK;
-        }
+    const HostLayout lay = host_layout(n, row, batch, sizeof(T), side_bytes);
+    auto bytes = [&](int k) { return batch * row[k] * sizeof(T); };
+    T *d[kMaxHostArrays];
+    auto point_at = [&](void *base) {  // -> the side input there
+        for (int k = 0; k < n; ++k) d[k] = reinterpret_cast<T *>(static_cast<char *>(base) + lay.off[k]);
+        return side ? reinterpret_cast<const T *>(static_cast<char *>(base) + lay.side) : nullptr;
+    };
+    if (zero_copy && ctx->zero_copy && ensure_pinned(ctx, lay.total) == KOFFT_OK) {
+        char *h = static_cast<char *>(ctx->pinned);
+        for (int k = 0; k < n; ++k)
+            if (a[k].up && bytes(k)) std::memcpy(h + lay.off[k], a[k].up, bytes(k));
+        if (side_bytes) std::memcpy(h + lay.side, side, side_bytes);
+        const T *d_side = point_at(ctx->pinned_dev);
+        const int zrc = dev(d, d_side, batch);
+        if (zrc) return zrc;
+        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int k = 0; k < n; ++k)
+            if (a[k].down && bytes(k)) std::memcpy(a[k].down, h + lay.off[k], bytes(k));
+        return KOFFT_OK;
     }
-    int rc = ensure_stage(ctx, 0, in_span);
+    int rc = ensure_stage(ctx, lay.total);
     if (rc) return rc;
-    if (!in_place && (rc = ensure_stage(ctx, 1, out_span))) return rc;
-    for (int k = 0; k < nin; ++k) d_ins[k] = reinterpret_cast<T *>(static_cast<char *>(ctx->stage[0]) + in_off[k]);
-    for (int k = 0; k < nout; ++k) d_outs[k] = in_place ? d_ins[k] : reinterpret_cast<T *>(static_cast<char *>(ctx->stage[1]) + out_off[k]);
-    const T *d_side = nullptr;
-    if (side) {
-        if ((rc = ensure_stage(ctx, 2, side_bytes))) return rc;
-        d_side = static_cast<const T *>(ctx->stage[2]);
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[2], side, side_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const T *d_side = point_at(ctx->stage);
+    auto side_up = [&] { return side_bytes ? hipMemcpyAsync(const_cast<T *>(d_side), side, side_bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
+    // rows [r0, r0 + nr) of every array that travels in this direction
+    auto copy_rows = [&](bool up, size_t r0, size_t nr, hipStream_t st) {
+        for (int k = 0; k < n; ++k) {
+            const size_t at = r0 * row[k], nb = nr * row[k] * sizeof(T);
+            hipError_t e = hipSuccess;
+            if (up && a[k].up && nb) e = hipMemcpyAsync(d[k] + at, a[k].up + at, nb, hipMemcpyHostToDevice, st);
+            if (!up && a[k].down && nb) e = hipMemcpyAsync(a[k].down + at, d[k] + at, nb, hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    size_t moved = 0, min_row = SIZE_MAX;
+    for (int k = 0; k < n; ++k) {
+        if (!a[k].up && !a[k].down) continue;
+        moved += ((a[k].up ? 1 : 0) + (a[k].down ? 1 : 0)) * bytes(k);
+        min_row = std::min(min_row, row[k]);
     }
-    size_t min_row = SIZE_MAX;
-    for (int k = 0; k < nin; ++k) min_row = std::min(min_row, in_rows[k]);
-    for (int k = 0; k < nout; ++k) min_row = std::min(min_row, out_rows[k]);
-    if (pipeline_ok && use_host_pipeline(ctx, in_bytes + out_bytes, batch, min_row * sizeof(T))) {
-        const size_t chunk = host_chunk_rows(ctx, batch);
+    if (pipeline_ok && use_host_pipeline(ctx, moved, batch, min_row * sizeof(T))) {
+        KOFFT_HIP_TRY(ctx, side_up());
+        const size_t chunk = host_chunk_rows(batch, ctx->host_chunks);
         auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
         const int prc = pipeline_chunks(
-            ctx, (batch + chunk - 1) / chunk,
-            [&](size_t c, hipStream_t st) {
-                for (int k = 0; k < nin; ++k) {
-                    const hipError_t e = hipMemcpyAsync(d_ins[k] + c * chunk * in_rows[k], ins[k] + c * chunk * in_rows[k],
-                                                        rows(c) * in_rows[k] * sizeof(T), hipMemcpyHostToDevice, st);
-                    if (e != hipSuccess) return e;
-                }
-                return hipSuccess;
-            },
+            ctx, (batch + chunk - 1) / chunk, [&](size_t c, hipStream_t st) { return copy_rows(true, c * chunk, rows(c), st); },
             [&](size_t c) {
-                T *ci[kMaxRowArrays], *co[kMaxRowArrays];
-                for (int k = 0; k < nin; ++k) ci[k] = d_ins[k] + c * chunk * in_rows[k];
-                for (int k = 0; k < nout; ++k) co[k] = d_outs[k] + c * chunk * out_rows[k];
-                return dev(ci, co, d_side, rows(c));
+                T *dc[kMaxHostArrays];
+                for (int k = 0; k < n; ++k) dc[k] = d[k] + c * chunk * row[k];
+                return dev(dc, d_side, rows(c));
             },
-            [&](size_t c, hipStream_t st) {
-                for (int k = 0; k < nout; ++k) {
-                    const hipError_t e = hipMemcpyAsync(outs[k] + c * chunk * out_rows[k], d_outs[k] + c * chunk * out_rows[k],
-                                                        rows(c) * out_rows[k] * sizeof(T), hipMemcpyDeviceToHost, st);
-                    if (e != hipSuccess) return e;
-                }
-                return hipSuccess;
-            });
+            [&](size_t c, hipStream_t st) { return copy_rows(false, c * chunk, rows(c), st); });
         if (prc != KOFFT_ERR_ALLOC) return prc;  // (no helper thread: serial path below)
     }
-    for (int k = 0; k < nin; ++k)
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_ins[k], ins[k], batch * in_rows[k] * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    rc = dev(d_ins, d_outs, d_side, batch);
+    KOFFT_HIP_TRY(ctx, copy_rows(true, 0, batch, ctx->stream));
+    KOFFT_HIP_TRY(ctx, side_up());
+    rc = dev(d, d_side, batch);
     if (rc) return rc;
-    for (int k = 0; k < nout; ++k)
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(outs[k], d_outs[k], batch * out_rows[k] * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    KOFFT_HIP_TRY(ctx, copy_rows(false, 0, batch, ctx->stream));
     KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KOFFT_OK;
 }
 
+// stage_host under the row-wise entry points' zero-copy rule: neither direction (up-arrays + side input, down-arrays) above kZeroCopyMax
+template <typename T, class Dev>
+int rows_host_n(kofft_hip_ctx *ctx, size_t batch, int n, const HostArray<T> *a, const T *side, size_t side_len, bool zero_copy_ok,
+                bool pipeline_ok, Dev dev)
+{
+    size_t up = side ? side_len * sizeof(T) : 0, down = 0;
+    for (int k = 0; k < n; ++k) {
+        if (a[k].up) up += batch * a[k].row * sizeof(T);
+        if (a[k].down) down += batch * a[k].row * sizeof(T);
+    }
+    return stage_host<T>(ctx, batch, n, a, side, side_len, zero_copy_ok && std::max(up, down) <= kZeroCopyMax, pipeline_ok, dev);
+}
+
 // rows_host_n with one input and one output array: dev(d_in, d_out, d_side, rows)
 template <typename T, class Dev>
-int rows_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t batch, size_t in_row, size_t out_row, bool in_place, const T *side,
-              size_t side_len, bool zero_copy_ok, bool pipeline_ok, Dev dev)
+int rows_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t batch, size_t in_row, size_t out_row, const T *side, size_t side_len,
+              bool zero_copy_ok, bool pipeline_ok, Dev dev)
 {
-    return rows_host_n<T>(ctx, batch, 1, &in, &in_row, 1, &out, &out_row, in_place, side, side_len, zero_copy_ok, pipeline_ok,
-                          [&](T *const *d_in, T *const *d_out, const T *d_side, size_t rows) { return dev(d_in[0], d_out[0], d_side, rows); });
+    const HostArray<T> a[2] = {{in, nullptr, in_row}, {nullptr, out, out_row}};
+    return rows_host_n<T>(ctx, batch, 2, a, side, side_len, zero_copy_ok, pipeline_ok,
+                          [&](T *const *d, const T *d_side, size_t rows) { return dev(d[0], d[1], d_side, rows); });
 }
 
 template <typename T>
@@ -249,8 +248,9 @@ int fft_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inverse)
     if (n > (size_t(1) << (is_pow2(n) ? max_log2_big<T>() : max_log2_big<T>() - 1))) return KOFFT_ERR_UNSUPPORTED;
     if (n == 1) return KOFFT_OK;
     if (!ctx || !data) return KOFFT_ERR_NULL;
-    return rows_host<T>(ctx, data, data, batch, 2 * n, 2 * n, true, nullptr, 0, is_pow2(n), true,
-                        [&](T *d_in, T *d_out, const T *, size_t rows) { return fft_dev<T>(ctx, d_in, d_out, n, rows, inverse); });
+    const HostArray<T> a{data, data, 2 * n};
+    return rows_host_n<T>(ctx, batch, 1, &a, nullptr, 0, is_pow2(n), true,
+                          [&](T *const *d, const T *, size_t rows) { return fft_dev<T>(ctx, d[0], d[0], n, rows, inverse); });
 }
 
 // FftImpl::fft_split / ifft_split on host planes of batch * n reals each, in place (planar_impl.hip.h)
@@ -260,12 +260,9 @@ int planar_host(kofft_hip_ctx *ctx, T *re, T *im, size_t n, size_t batch, int in
     const int rc = planar_check(n, batch, re, im, re, im, ctx);
     if (rc || batch == 0) return rc;
     if (n == 1) return KOFFT_OK;  // the planes themselves
-    T *const planes[2] = {re, im};
-    const size_t rows[2] = {n, n};
-    return rows_host_n<T>(ctx, batch, 2, planes, rows, 2, planes, rows, true, nullptr, 0, is_pow2(n), true,
-                          [&](T *const *d_in, T *const *d_out, const T *, size_t nb) {
-                              return planar_dev<T>(ctx, d_in[0], d_in[1], d_out[0], d_out[1], n, nb, inverse);
-                          });
+    const HostArray<T> a[2] = {{re, re, n}, {im, im, n}};
+    return rows_host_n<T>(ctx, batch, 2, a, nullptr, 0, is_pow2(n), true,
+                          [&](T *const *d, const T *, size_t nb) { return planar_dev<T>(ctx, d[0], d[1], d[0], d[1], n, nb, inverse); });
 }
 
 // ScalarFftImpl::fft_radix4 on a host buffer (fft_radix4.hip.h); inverse: FftPlan::ifft's loop around it (fft.rs:2040-2055)
@@ -277,17 +274,9 @@ int fft_radix4_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inv
     if (n > (size_t(1) << max_log2_big<T>())) return KOFFT_ERR_UNSUPPORTED;
     if (n == 1) return KOFFT_OK;
     if (!ctx || !data) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = batch * n * 2 * sizeof(T);
-    int rc = ensure_stage(ctx, 0, bytes);
-    if (rc) return rc;
-    T *d = static_cast<T *>(ctx->stage[0]);
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = fft_radix4_dev<T>(ctx, d, d, n, batch, inverse);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    const HostArray<T> a{data, data, 2 * n};
+    return stage_host<T>(ctx, batch, 1, &a, nullptr, 0, false, false,
+                         [&](T *const *d, const T *, size_t rows) { return fft_radix4_dev<T>(ctx, d[0], d[0], n, rows, inverse); });
 }
 
 // fft_strided / ifft_strided (fft.rs:1175-1199, 1236-1260): gather, transform, scatter.
@@ -321,7 +310,7 @@ int rfft_host(kofft_hip_ctx *ctx, const T *in, T *out, const T *window, size_t n
     const size_t m = n / 2;
     if (!complex_len_ok(m)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    return rows_host<T>(ctx, in, out, batch, n, (m + 1) * 2, false, window, n, true, true,
+    return rows_host<T>(ctx, in, out, batch, n, (m + 1) * 2, window, n, true, true,
                         [&](T *d_in, T *d_out, const T *d_win, size_t rows) { return rfft_dev<T>(ctx, d_in, d_out, d_win, n, rows); });
 }
 
@@ -332,7 +321,7 @@ int dct2_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t 
     if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, true,
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, true,
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return dct2_dev(ctx, d_in, d_out, n, rows); });
 }
 
@@ -344,7 +333,7 @@ int hilbert_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size
     if (!is_pow2(n)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
     if (n > (size_t(1) << max_log2_big<float>())) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    return rows_host<float>(ctx, in, out, batch, n, 2 * n, false, nullptr, 0, true, true,
+    return rows_host<float>(ctx, in, out, batch, n, 2 * n, nullptr, 0, true, true,
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return hilbert_dev(ctx, d_in, d_out, n, rows); });
 }
 
@@ -356,7 +345,7 @@ int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, siz
     if (!is_pow2(n)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
     if (n > (size_t(1) << max_log2_big<float>())) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, true,
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, true,
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return cepstrum_dev(ctx, d_in, d_out, n, rows); });
 }
 
@@ -367,7 +356,7 @@ int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float
     if (rc || batch == 0 || n == 0) return rc;
     // No pipeline: the whole input is on the device before any output is written back, so in == out works (the reference's
     // batch_* are in place).
-    return rows_host<float>(ctx, in, out, batch, n, n, false, nullptr, 0, true, false,
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, false,
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return direct_dev(ctx, family, type, d_in, d_out, n, rows); });
 }
 
@@ -380,7 +369,7 @@ int czt_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t m
         std::memset(out, 0, batch * 2 * m * sizeof(float));
         return KOFFT_OK;
     }
-    return rows_host<float>(ctx, in, out, batch, n, 2 * m, false, nullptr, 0, true, false,
+    return rows_host<float>(ctx, in, out, batch, n, 2 * m, nullptr, 0, true, false,
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return czt_dev(ctx, d_in, d_out, n, m, wr, wi, ar, ai, rows); });
 }
 
@@ -392,7 +381,7 @@ int goertzel_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, siz
     if (rc || batch == 0 || nfreq == 0) return rc;
     std::vector<float> coeff(nfreq);
     kofft_tables::goertzel_coeff_f32(n, sample_rate, target_freqs, nfreq, coeff.data());
-    return rows_host<float>(ctx, in, out, batch, n, nfreq, false, coeff.data(), nfreq, true, true,
+    return rows_host<float>(ctx, in, out, batch, n, nfreq, coeff.data(), nfreq, true, true,
                             [&](float *d_in, float *d_out, const float *d_coeff, size_t rows) { return goertzel_launch(ctx, d_in, d_out, d_coeff, n, rows, nfreq); });
 }
 
@@ -401,12 +390,9 @@ int dwt_host(kofft_hip_ctx *ctx, int w, const float *in, float *approx, float *d
 {
     int rc = dwt_check(w, len, batch, 0, in, approx, detail, ctx);
     if (rc || batch == 0 || len / 2 == 0) return rc;
-    const size_t n = len / 2, in_rows[1] = {len}, out_rows[2] = {n, n};
-    float *const outs[2] = {approx, detail};
-    return rows_host_n<float>(ctx, batch, 1, &in, in_rows, 2, outs, out_rows, false, nullptr, 0, true, true,
-                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
-                                  return dwt_dev(ctx, w, d_in[0], d_out[0], d_out[1], len, rows);
-                              });
+    const HostArray<float> a[3] = {{in, nullptr, len}, {nullptr, approx, len / 2}, {nullptr, detail, len / 2}};
+    return rows_host_n<float>(ctx, batch, 3, a, nullptr, 0, true, true,
+                              [&](float *const *d, const float *, size_t rows) { return dwt_dev(ctx, w, d[0], d[1], d[2], len, rows); });
 }
 
 int idwt_host(kofft_hip_ctx *ctx, int w, const float *approx, const float *detail, float *out, size_t n, size_t batch)
@@ -414,12 +400,9 @@ int idwt_host(kofft_hip_ctx *ctx, int w, const float *approx, const float *detai
     const size_t one = n;
     int rc = idwt_check(w, n, batch, 1, &one, approx, detail, out, ctx);
     if (rc || batch == 0 || n == 0) return rc;
-    const float *const ins[2] = {approx, detail};
-    const size_t in_rows[2] = {n, n}, out_rows[1] = {2 * n};
-    return rows_host_n<float>(ctx, batch, 2, ins, in_rows, 1, &out, out_rows, false, nullptr, 0, true, true,
-                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
-                                  return idwt_dev(ctx, w, d_in[0], d_in[1], d_out[0], n, rows);
-                              });
+    const HostArray<float> a[3] = {{approx, nullptr, n}, {detail, nullptr, n}, {nullptr, out, 2 * n}};
+    return rows_host_n<float>(ctx, batch, 3, a, nullptr, 0, true, true,
+                              [&](float *const *d, const float *, size_t rows) { return idwt_dev(ctx, w, d[0], d[1], d[2], n, rows); });
 }
 
 // (the details are packed level after level, [batch][a_l] each: not row-contiguous, so no pipeline)
@@ -429,12 +412,10 @@ int dwt_multi_host(kofft_hip_ctx *ctx, int w, const float *in, float *approx, fl
     if (rc || batch == 0 || len == 0) return rc;
     size_t lens[kWaveletMaxLevels + 1];
     const size_t det = wavelet_lengths(len, levels, lens);
-    const size_t in_rows[1] = {len}, out_rows[2] = {lens[levels], det};
-    float *const outs[2] = {approx, details};
-    return rows_host_n<float>(ctx, batch, 1, &in, in_rows, levels ? 2 : 1, outs, out_rows, false, nullptr, 0, true, false,
-                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
-                                  return dwt_multi_dev(ctx, w, d_in[0], d_out[0], levels ? d_out[1] : nullptr, len, rows, levels);
-                              });
+    const HostArray<float> a[3] = {{in, nullptr, len}, {nullptr, approx, lens[levels]}, {nullptr, details, det}};
+    return rows_host_n<float>(ctx, batch, levels ? 3 : 2, a, nullptr, 0, true, false, [&](float *const *d, const float *, size_t rows) {
+        return dwt_multi_dev(ctx, w, d[0], d[1], levels ? d[2] : nullptr, len, rows, levels);
+    });
 }
 
 int idwt_multi_host(kofft_hip_ctx *ctx, int w, const float *approx, const float *details, const size_t *detail_lens, float *out, size_t n,
@@ -444,12 +425,10 @@ int idwt_multi_host(kofft_hip_ctx *ctx, int w, const float *approx, const float 
     if (rc || batch == 0 || n == 0) return rc;
     size_t det = 0;
     for (size_t l = 0; l < levels; ++l) det += detail_lens[l];
-    const float *const ins[2] = {approx, details};
-    const size_t in_rows[2] = {n, det}, out_rows[1] = {n << levels};
-    return rows_host_n<float>(ctx, batch, levels ? 2 : 1, ins, in_rows, 1, &out, out_rows, false, nullptr, 0, true, false,
-                              [&](float *const *d_in, float *const *d_out, const float *, size_t rows) {
-                                  return idwt_multi_dev(ctx, w, d_in[0], levels ? d_in[1] : nullptr, detail_lens, d_out[0], n, rows, levels);
-                              });
+    const HostArray<float> a[3] = {{approx, nullptr, n}, {nullptr, out, n << levels}, {details, nullptr, det}};
+    return rows_host_n<float>(ctx, batch, levels ? 3 : 2, a, nullptr, 0, true, false, [&](float *const *d, const float *, size_t rows) {
+        return idwt_multi_dev(ctx, w, d[0], levels ? d[2] : nullptr, detail_lens, d[1], n, rows, levels);
+    });
 }
 
 template <typename T>
@@ -461,7 +440,7 @@ int irfft_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t n, size_t batch)
     const size_t m = n / 2;
     if (!complex_len_ok(m)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !in || !out) return KOFFT_ERR_NULL;
-    return rows_host<T>(ctx, in, out, batch, (m + 1) * 2, n, false, nullptr, 0, true, true,
+    return rows_host<T>(ctx, in, out, batch, (m + 1) * 2, n, nullptr, 0, true, true,
                         [&](T *d_in, T *d_out, const T *, size_t rows) { return irfft_dev<T>(ctx, d_in, d_out, n, rows); });
 }
 
@@ -474,96 +453,62 @@ int stft_host(kofft_hip_ctx *ctx, const float *signal, size_t len, const float *
     if (win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (!complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || (!signal && len) || !window || !out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t lo = start0 < len ? start0 : len;
     size_t hi = start0 + (count - 1) * hop + win_len;
     if (hi > len) hi = len;
     if (hi < lo) hi = lo;
     const size_t span = hi - lo;
     const size_t out_bytes = count * win_len * 2 * sizeof(float);
-    if (ctx->zero_copy && (span + win_len) * sizeof(float) + out_bytes <= kZeroCopyMax &&
-        ensure_pinned(ctx, (span + win_len) * sizeof(float) + out_bytes + 768) == KOFFT_OK) {
-        // frame() / StftStream / short signals: [samples | window | spectra] in the pinned, device-mapped buffer
-        const size_t o_win = (span * sizeof(float) + 255) & ~size_t(255), o_out = (o_win + win_len * sizeof(float) + 255) & ~size_t(255);
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        if (span) std::memcpy(h, signal + lo, span * sizeof(float));
-        std::memcpy(h + o_win, window, win_len * sizeof(float));
-        int zrc = stft_dev(ctx, reinterpret_cast<const float *>(dd), span, reinterpret_cast<const float *>(dd + o_win), win_len,
-                           start0 - lo, hop, reinterpret_cast<float *>(dd + o_out), count);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(out, h + o_out, out_bytes);
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, (span ? span : 1) * sizeof(float));
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, out_bytes);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 2, win_len * sizeof(float));
-    if (rc) return rc;
-    if (span)
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[0], signal + lo, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[2], window, win_len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    // positions are relative to `lo`; a start past the end of the signal leaves every sample zero
-    rc = stft_dev(ctx, static_cast<const float *>(ctx->stage[0]), span, static_cast<const float *>(ctx->stage[2]),
-                  win_len, start0 - lo, hop, static_cast<float *>(ctx->stage[1]), count);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->stage[1], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    const HostArray<float> a[2] = {{signal + lo, nullptr, span}, {nullptr, out, count * win_len * 2}};
+    // frame() / StftStream / short signals go zero-copy.  Positions are relative to `lo`; a start past the end of the signal leaves
+    // every sample zero.
+    return stage_host<float>(ctx, 1, 2, a, window, win_len, (span + win_len) * sizeof(float) + out_bytes <= kZeroCopyMax, false,
+                             [&](float *const *d, const float *d_win, size_t) {
+                                 return stft_dev(ctx, d[0], span, d_win, win_len, start0 - lo, hop, d[1], count);
+                             });
 }
 
-// host-pointer wrapper shared by istft / inverse_parallel / inverse_frame
-int istft_host(kofft_hip_ctx *ctx, float *frames_data, size_t frames, const float *window, size_t win_len, size_t hop,
-               float *output, size_t out_len, float *scratch, size_t scratch_len, int mode, size_t start0, bool copy_frames_back)
+// The three arrays of a host-pointer ISTFT over `rows` signals (1: istft / inverse_parallel / inverse_frame): the frames go up and, unless
+// mode 2 (inverse_parallel clones each frame, stft.rs:310: the caller's stay untouched), come back inverse-transformed; the output goes
+// up and comes back; the window-square sums only come back (mode 1) or stay on the device.  dev(d_frames, d_window, d_output, d_scratch).
+template <class Dev>
+int istft_stage(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, float *output,
+                size_t out_len, float *scratch, int mode, Dev dev)
+{
+    if (!ctx || (frames && (!frames_data || !window)) || (out_len && (!output || (mode == 1 && !scratch)))) return KOFFT_ERR_NULL;
+    const size_t fr_bytes = rows * frames * win_len * 2 * sizeof(float), o_bytes = rows * out_len * sizeof(float);
+    auto align = [](size_t b) { return (b + 255) & ~size_t(255); };
+    // one frame (IstftStream, inverse_frame) or a short batch goes zero-copy
+    const size_t total = align(fr_bytes) + 2 * align(o_bytes) + win_len * sizeof(float) + 256;
+    const HostArray<float> a[3] = {{frames_data, mode == 2 ? nullptr : frames_data, frames * win_len * 2},
+                                   {output, output, out_len},
+                                   {nullptr, mode == 1 ? scratch : nullptr, out_len}};
+    return stage_host<float>(ctx, rows, 3, a, window, win_len, total <= kZeroCopyMax, false,
+                             [&](float *const *d, const float *d_win, size_t) { return dev(d[0], d_win, d[1], d[2]); });
+}
+
+int istft_host(kofft_hip_ctx *ctx, float *frames_data, size_t frames, const float *window, size_t win_len, size_t hop, float *output,
+               size_t out_len, float *scratch, size_t scratch_len, int mode, size_t start0)
 {
     if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;
     if (mode == 1 && scratch_len != out_len) return KOFFT_ERR_MISMATCHED_LENGTHS;
     if (frames > 0 && win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (frames > 0 && !complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
-    if (!ctx || (frames && (!frames_data || !window)) || (out_len && (!output || (mode == 1 && !scratch)))) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t fr_bytes = frames * win_len * 2 * sizeof(float);
-    const size_t o_bytes = out_len * sizeof(float);
-    // one staging allocation: [frames | output | scratch | window]
-    const size_t a0 = 0, a1 = (fr_bytes + 255) & ~size_t(255), a2 = a1 + ((o_bytes + 255) & ~size_t(255)),
-                 a3 = a2 + ((o_bytes + 255) & ~size_t(255)), total = a3 + win_len * sizeof(float) + 256;
-    if (ctx->zero_copy && total <= kZeroCopyMax && ensure_pinned(ctx, total) == KOFFT_OK) {
-        // one frame (IstftStream, inverse_frame) or a short batch: the kernels work on the pinned, device-mapped buffer
-        char *h = static_cast<char *>(ctx->pinned), *dd = static_cast<char *>(ctx->pinned_dev);
-        if (fr_bytes) std::memcpy(h + a0, frames_data, fr_bytes);
-        if (o_bytes) std::memcpy(h + a1, output, o_bytes);
-        if (win_len) std::memcpy(h + a3, window, win_len * sizeof(float));
-        int zrc = istft_dev(ctx, reinterpret_cast<float *>(dd + a0), frames, reinterpret_cast<const float *>(dd + a3), win_len, hop,
-                            reinterpret_cast<float *>(dd + a1), out_len, reinterpret_cast<float *>(dd + a2),
-                            mode == 1 ? scratch_len : out_len, mode, start0);
-        if (zrc) return zrc;
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (fr_bytes && copy_frames_back) std::memcpy(frames_data, h + a0, fr_bytes);
-        if (o_bytes) {
-            std::memcpy(output, h + a1, o_bytes);
-            if (mode == 1 && scratch) std::memcpy(scratch, h + a2, o_bytes);
-        }
-        return KOFFT_OK;
-    }
-    int rc = ensure_stage(ctx, 0, total);
-    if (rc) return rc;
-    char *base = static_cast<char *>(ctx->stage[0]);
-    if (fr_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(base + a0, frames_data, fr_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (o_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(base + a1, output, o_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (win_len) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(base + a3, window, win_len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    rc = istft_dev(ctx, reinterpret_cast<float *>(base + a0), frames, reinterpret_cast<const float *>(base + a3), win_len, hop,
-                   reinterpret_cast<float *>(base + a1), out_len, reinterpret_cast<float *>(base + a2), mode == 1 ? scratch_len : out_len,
-                   mode, start0);
-    if (rc) return rc;
-    if (fr_bytes && copy_frames_back)
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(frames_data, base + a0, fr_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (o_bytes) {
-        KOFFT_HIP_TRY(ctx, hipMemcpyAsync(output, base + a1, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (mode == 1 && scratch) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(scratch, base + a2, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    return istft_stage(ctx, frames_data, 1, frames, window, win_len, output, out_len, scratch, mode,
+                       [&](float *d_frames, const float *d_win, float *d_out, float *d_scr) {
+                           return istft_dev(ctx, d_frames, frames, d_win, win_len, hop, d_out, out_len, d_scr, out_len, mode, start0);
+                       });
+}
+
+int istft_rows_host(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, size_t hop,
+                    float *output, size_t out_len, float *scratch, size_t scratch_len, int mode)
+{
+    const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
+    if (crc || rows == 0) return crc;
+    return istft_stage(ctx, frames_data, rows, frames, window, win_len, output, out_len, scratch, mode,
+                       [&](float *d_frames, const float *d_win, float *d_out, float *d_scr) {
+                           return istft_rows_dev(ctx, d_frames, rows, frames, d_win, win_len, hop, d_out, out_len, d_scr, out_len, mode, false);
+                       });
 }
 
 template <typename T>
@@ -573,17 +518,9 @@ int fft_nd_host(kofft_hip_ctx *ctx, T *data, size_t depth, size_t rows, size_t c
     for (size_t n : {depth, rows, cols})
         if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !data) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = depth * rows * cols * 2 * sizeof(T);
-    int rc = ensure_stage(ctx, 0, bytes);
-    if (rc) return rc;
-    T *d = static_cast<T *>(ctx->stage[0]);
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = fft_nd_dev<T>(ctx, d, depth, rows, cols, inverse);
-    if (rc) return rc;
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    const HostArray<T> a{data, data, 2 * depth * rows * cols};
+    return stage_host<T>(ctx, 1, 1, &a, nullptr, 0, false, false,
+                         [&](T *const *d, const T *, size_t) { return fft_nd_dev<T>(ctx, d[0], depth, rows, cols, inverse); });
 }
 
 }  // namespace
@@ -686,13 +623,11 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->tables) (void)hipFree(kv.second);
     spectral_drop(ctx);
-    for (int i = 0; i < 3; ++i)
-        if (ctx->stage[i]) (void)hipFree(ctx->stage[i]);
+    drop_host_buffers(ctx);
     if (ctx->big_tmp && !ctx->big_tmp_external) (void)hipFree(ctx->big_tmp);
     if (ctx->blue_tmp) (void)hipFree(ctx->blue_tmp);
     if (ctx->real_tmp) (void)hipFree(ctx->real_tmp);
     if (ctx->rows_tmp) (void)hipFree(ctx->rows_tmp);
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -755,11 +690,7 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
     if (!ctx) return KOFFT_ERR_NULL;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 3; ++i) {
-        if (ctx->stage[i]) (void)hipFree(ctx->stage[i]);
-        ctx->stage[i] = nullptr;
-        ctx->stage_bytes[i] = 0;
-    }
+    drop_host_buffers(ctx);
     void **bufs[] = {&ctx->big_tmp, &ctx->blue_tmp, &ctx->real_tmp, &ctx->rows_tmp};
     size_t *sizes[] = {&ctx->big_tmp_bytes, &ctx->blue_tmp_bytes, &ctx->real_tmp_bytes, &ctx->rows_tmp_bytes};
     for (int i = 0; i < 4; ++i) {
@@ -771,9 +702,6 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
     ctx->big_tmp_external = false;  // (KOFFT_EXP_API builds: the script's intermediate is forgotten, the next call allocates its own)
     ctx->big_probe_n = 0;
     ctx->big_probe_pick = -1;
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    ctx->pinned = ctx->pinned_dev = nullptr;
-    ctx->pinned_bytes = 0;
     return KOFFT_OK;
 }
 
@@ -1162,22 +1090,21 @@ int kofft_hip_istft_f32_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, 
 int kofft_hip_istft_f32(kofft_hip_ctx *ctx, float *frames_data, size_t frames, const float *window, size_t win_len,
                         size_t hop, float *output, size_t out_len, float *scratch, size_t scratch_len)
 {
-    return istft_host(ctx, frames_data, frames, window, win_len, hop, output, out_len, scratch, scratch_len, 1, 0, true);
+    return istft_host(ctx, frames_data, frames, window, win_len, hop, output, out_len, scratch, scratch_len, 1, 0);
 }
 
 int kofft_hip_istft_parallel_f32(kofft_hip_ctx *ctx, const float *frames_data, size_t frames, const float *window,
                                  size_t win_len, size_t hop, float *output, size_t out_len)
 {
     // inverse_parallel clones each frame (stft.rs:310): the caller's frames are left untouched
-    return istft_host(ctx, const_cast<float *>(frames_data), frames, window, win_len, hop, output, out_len, nullptr, out_len, 2, 0,
-                      false);
+    return istft_host(ctx, const_cast<float *>(frames_data), frames, window, win_len, hop, output, out_len, nullptr, out_len, 2, 0);
 }
 
 int kofft_hip_istft_frame_f32(kofft_hip_ctx *ctx, float *frame, const float *window, size_t win_len, size_t start,
                               float *output, size_t out_len)
 {
     // inverse_frame (stft.rs:384-399): ifft(frame) in place, output[start + i] += frame[i].re * window[i], no normalisation
-    return istft_host(ctx, frame, 1, window, win_len, win_len ? win_len : 1, output, out_len, nullptr, out_len, 0, start, true);
+    return istft_host(ctx, frame, 1, window, win_len, win_len ? win_len : 1, output, out_len, nullptr, out_len, 0, start);
 }
 
 int kofft_hip_stft_magnitudes_f32_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t win_len, size_t hop,
@@ -1194,37 +1121,20 @@ int kofft_hip_stft_magnitudes_f32(kofft_hip_ctx *ctx, const float *samples, size
     if (frames > 0 && win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (frames > 0 && !complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !max_mag || (frames && (!mags || (!samples && len)))) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t m_bytes = frames * (win_len / 2) * sizeof(float);
-    int rc = ensure_stage(ctx, 0, (len ? len : 1) * sizeof(float));
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 1, m_bytes + 256);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, 2, 256);
-    if (rc) return rc;
-    if (len) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[0], samples, len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    rc = stft_mag_dev(ctx, static_cast<const float *>(ctx->stage[0]), len, win_len, hop, static_cast<float *>(ctx->stage[1]), frames,
-                      static_cast<float *>(ctx->stage[2]));
-    if (rc) return rc;
-    if (m_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(mags, ctx->stage[1], m_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(max_mag, ctx->stage[2], sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
+    // never zero-copy: the maximum is an atomicMax target and stays in device memory
+    const HostArray<float> a[3] = {{samples, nullptr, len}, {nullptr, mags, frames * (win_len / 2)}, {nullptr, max_mag, 1}};
+    return stage_host<float>(ctx, 1, 3, a, nullptr, 0, false, false, [&](float *const *d, const float *, size_t) {
+        return stft_mag_dev(ctx, d[0], len, win_len, hop, d[1], frames, d[2]);
+    });
 }
 
 // ---- STFT, stft_magnitudes and ISTFT over rows of signals (k_stft_rows.hip) --------------------------------------
 // Host rows `row_stride` apart are packed (stride len) before they travel: the gaps are not the call's to read.
-static const float *pack_rows(const float *signal, size_t rows, size_t len, size_t row_stride, std::vector<float> &packed, size_t *in_row)
+static const float *pack_rows(const float *signal, size_t rows, size_t len, size_t row_stride, std::vector<float> &packed)
 {
-    *in_row = len;
-    if (len == 0) {  // no samples at all: one placeholder float per row, never read (len stays 0 on the device)
-        packed.assign(rows, 0.0f);
-        *in_row = 1;
-        return packed.data();
-    }
-    if (rows == 1 || row_stride == len) return signal;
+    if (len == 0 || rows == 1 || row_stride == len) return signal;
     packed.resize(rows * len);
-    for (size_t r = 0; r < rows; ++r) std::memcpy(packed.data() + r * len, signal + r * row_stride, len * sizeof(float));
+    for (size_t r = 0; r < rows; ++r) std::copy_n(signal + r * row_stride, len, packed.data() + r * len);
     return packed.data();
 }
 
@@ -1241,12 +1151,11 @@ int kofft_hip_stft_rows_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows
     if (crc || rows == 0 || frames == 0) return crc;
     if (!ctx || (!signal && len) || !window || !out) return KOFFT_ERR_NULL;
     std::vector<float> packed;
-    size_t in_row = 0;
-    const float *src = pack_rows(signal, rows, len, row_stride, packed, &in_row);
+    const float *src = pack_rows(signal, rows, len, row_stride, packed);
     // a chunk of the pipeline is whole rows: no seam logic on the host
-    return rows_host<float>(ctx, src, out, rows, in_row, frames * win_len * 2, false, window, win_len, true, true,
+    return rows_host<float>(ctx, src, out, rows, len, frames * win_len * 2, window, win_len, true, true,
                             [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
-                                return stft_rows_dev(ctx, d_in, nb, len, in_row, d_win, win_len, hop, d_out, frames);
+                                return stft_rows_dev(ctx, d_in, nb, len, len, d_win, win_len, hop, d_out, frames);
                             });
 }
 
@@ -1267,15 +1176,12 @@ int kofft_hip_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *samples,
         return KOFFT_OK;
     }
     std::vector<float> packed;
-    size_t in_row = 0;
-    const float *src = pack_rows(samples, rows, len, row_stride, packed, &in_row);
-    float *const outs[2] = {mags, max_mag};
-    const size_t in_rows[1] = {in_row}, out_rows[2] = {frames * (win_len / 2), 1};
+    const float *src = pack_rows(samples, rows, len, row_stride, packed);
     // never zero-copy: the maxima are atomicMax targets and stay in device memory, as in the single-signal form above
-    return rows_host_n<float>(ctx, rows, 1, &src, in_rows, 2, outs, out_rows, false, nullptr, 0, false, true,
-                              [&](float *const *d_in, float *const *d_out, const float *, size_t nb) {
-                                  return stft_mag_rows_dev(ctx, d_in[0], nb, len, in_row, win_len, hop, d_out[0], frames, d_out[1]);
-                              });
+    const HostArray<float> a[3] = {{src, nullptr, len}, {nullptr, mags, frames * (win_len / 2)}, {nullptr, max_mag, 1}};
+    return rows_host_n<float>(ctx, rows, 3, a, nullptr, 0, false, true, [&](float *const *d, const float *, size_t nb) {
+        return stft_mag_rows_dev(ctx, d[0], nb, len, len, win_len, hop, d[1], frames, d[2]);
+    });
 }
 
 int kofft_hip_dev_istft_rows_f32(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len,
@@ -1289,52 +1195,6 @@ int kofft_hip_dev_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *d_fra
 {
     return istft_rows_dev(ctx, const_cast<float *>(d_frames), rows, frames, d_window, win_len, hop, d_output, out_len, nullptr, out_len, 2,
                           true);
-}
-
-// host-pointer wrapper of both modes: one staging allocation [frames | output | scratch | window], or the same pieces in the pinned,
-// device-mapped buffer for small calls (three row arrays: more than rows_host_n carries)
-static int istft_rows_host(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, size_t hop,
-                           float *output, size_t out_len, float *scratch, size_t scratch_len, int mode)
-{
-    const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
-    if (crc || rows == 0) return crc;
-    if (!ctx || (frames && (!frames_data || !window)) || (out_len && (!output || (mode == 1 && !scratch)))) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t fr_bytes = rows * frames * win_len * 2 * sizeof(float), o_bytes = rows * out_len * sizeof(float);
-    auto align = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t a1 = align(fr_bytes), a2 = a1 + align(o_bytes), a3 = a2 + align(o_bytes), total = a3 + win_len * sizeof(float) + 256;
-    const bool zero_copy = ctx->zero_copy && total <= kZeroCopyMax && ensure_pinned(ctx, total) == KOFFT_OK;
-    char *h = nullptr, *dd = nullptr;
-    if (zero_copy) {
-        h = static_cast<char *>(ctx->pinned);
-        dd = static_cast<char *>(ctx->pinned_dev);
-        if (fr_bytes) std::memcpy(h, frames_data, fr_bytes);
-        if (o_bytes) std::memcpy(h + a1, output, o_bytes);
-        if (win_len) std::memcpy(h + a3, window, win_len * sizeof(float));
-    } else {
-        const int rc = ensure_stage(ctx, 0, total);
-        if (rc) return rc;
-        dd = static_cast<char *>(ctx->stage[0]);
-        if (fr_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dd, frames_data, fr_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (o_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dd + a1, output, o_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (win_len) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dd + a3, window, win_len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    const int rc = istft_rows_dev(ctx, reinterpret_cast<float *>(dd), rows, frames, reinterpret_cast<const float *>(dd + a3), win_len, hop,
-                                  reinterpret_cast<float *>(dd + a1), out_len, reinterpret_cast<float *>(dd + a2), out_len, mode, false);
-    if (rc) return rc;
-    const bool frames_back = mode == 1 && fr_bytes;  // inverse_parallel clones each frame (stft.rs:310): the caller's stay untouched
-    if (zero_copy) {
-        KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (frames_back) std::memcpy(frames_data, h, fr_bytes);
-        if (o_bytes) std::memcpy(output, h + a1, o_bytes);
-        if (o_bytes && mode == 1) std::memcpy(scratch, h + a2, o_bytes);
-        return KOFFT_OK;
-    }
-    if (frames_back) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(frames_data, dd, fr_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (o_bytes) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(output, dd + a1, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (o_bytes && mode == 1) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(scratch, dd + a2, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KOFFT_OK;
 }
 
 int kofft_hip_istft_rows_f32(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len,
