@@ -286,6 +286,12 @@ int kofft_hip_dct_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in
 int kofft_hip_dst_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, float *out, size_t n, size_t batch);
 int kofft_hip_dst_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in, float *d_out, size_t n, size_t batch);
 int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on);
+/* The 4096-point c32 streaming kernel walks the first rows of a batch with the stride of its grid and
+ * hands out the last ones by claim (one fetch-add per row), so that a workgroup that falls behind
+ * leaves rows to the others.  pct = 0 .. 100: the share of the batch that is claimed (100: all of
+ * it; 0: only what the grid's stride leaves over); pct < 0: the library's measured default;
+ * pct > 100 -> INVALID_VALUE.  The same bytes at every setting (A/B measurements and tests). */
+int kofft_hip_set_persist_claim_pct(kofft_hip_ctx *ctx, int pct);
 /* The tables of the direct transforms, host only (tests): C = n * n floats, C[i * n + k] as
  * above; rows outside the kind's i range are +0.  type not 1 .. 4 -> INVALID_VALUE; n == 0 ->
  * KOFFT_OK; n > 4096 -> KOFFT_ERR_UNSUPPORTED; C null -> KOFFT_ERR_NULL. */

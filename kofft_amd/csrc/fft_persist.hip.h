@@ -10,7 +10,7 @@
 //   * everything that depends on the thread but not on the transform is read ONCE per workgroup into
 //     registers: the twiddles of passes 1.. (pass 0's indices are compile-time constants -> scalar
 //     loads), the window samples of STFT/rfft framing, the rfft post-pass table entries;
-//   * n = 4096 (256 threads per transform): two LDS exchange buffers, 2 barriers per transform;
+//   * n = 4096 (256 threads per transform): one LDS exchange buffer (NBUF = 1), four barriers per transform;
 //     n = 1024 (64 threads = one wavefront per transform): the exchange is wave-synchronous, no
 //     s_barrier at all -- the four waves of a workgroup free-run.
 // Results are bit-identical to fft_wg_kernel: the same butterflies consume the same table entries.
@@ -164,6 +164,51 @@ struct persist_tw_global { static constexpr bool value = false; };
 template <class CFG>
 struct persist_tw_global<CFG, decltype((void)CFG::kTwGlobal)> { static constexpr bool value = CFG::kTwGlobal; };
 
+// CFG::kClaim (c32 n = 4096): the end of the batch is handed out by claim instead of by the grid's stride (fft_persist_kernel below).
+template <class CFG, class = void>
+struct persist_claim { static constexpr bool value = false; };
+template <class CFG>
+struct persist_claim<CFG, decltype((void)CFG::kClaim)> { static constexpr bool value = CFG::kClaim; };
+
+// The claim hand-out's kernel argument: rows [0, split) are walked with the grid's stride (split is a multiple of the stride), rows
+// [split, batch) are claimed XPB at a time with one fetch-add on counters[0].  counters[1] counts the workgroups that have made their
+// one failing claim; the last of them stores zeros to both, so that the next launch on the context's stream starts from zero without
+// any host-side reset (launch_persist; the context zeroes them once when it allocates them).
+struct PersistClaim {
+    unsigned *counters;
+    size_t split;
+};
+// the IO policy of a kClaim configuration's kernel: the configuration's own policy plus the hand-out's argument
+template <class IO>
+struct PersistClaimIO : IO {
+    PersistClaim claim;
+};
+// persist_transform's hook around the barrier behind its second scatter (the last one of a three-pass transform): put() in front of
+// it, get() behind it (the claimed row travels from the claiming
+// lane to the workgroup through one LDS word)
+struct NoXchg {
+    __device__ __forceinline__ void put() const {}
+    __device__ __forceinline__ void get() const {}
+};
+
+#ifdef KOFFT_PERSIST_STAMPS /* diagnostic builds only (tools/persist_progress.py): one record per workgroup, written by lane 0 of its first wavefront */
+constexpr int kPersistStampWgs = 4096, kPersistStampWords = 16;
+static __device__ unsigned long long g_persist_stamps[kPersistStampWgs * kPersistStampWords];
+__device__ __forceinline__ unsigned long long persist_stamp()
+{
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    return t;
+}
+// the constant 100 MHz clock: the one to compare workgroups on different XCDs by
+__device__ __forceinline__ unsigned long long persist_stamp_real()
+{
+    unsigned long long t;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    return t;
+}
+#endif
+
 // Everything a thread keeps across transforms.
 // CFG (kofft_hip.hip: PersistCfg<L, IO>) carries the per-size, per-policy choices: BLOCK, NBUF, MINW and where the
 // thread-invariant operands live -- kInvInLds (window samples in one LDS copy per workgroup instead of R registers)
@@ -223,12 +268,12 @@ __host__ __device__ constexpr bool persist_twg_top_part(int L) { return KOFFT_TW
 struct NoPrefetchParts {
     __device__ __forceinline__ void operator()(int) const {}
 };
-template <typename T, int L, int RL, int EPI, class CFG, class IO, class Parts = NoPrefetchParts>
+template <typename T, int L, int RL, int EPI, class CFG, class IO, class Parts = NoPrefetchParts, class Xchg = NoXchg>
 __device__ __forceinline__ void persist_transform(const typename persist_raw<IO, ((1 << L) >> RL)>::type *raw,
                                                   const PersistState<T, L, RL, EPI, IO, CFG> &st,
                                                   const IO &io, const cpx<T> *__restrict__ tw, cpx<T> *buf0, cpx<T> *buf1,
                                                   const size_t xf0, const int cnt, const int sub, const int tau,
-                                                  typename persist_acc<IO>::type &acc, const Parts &part = Parts{})
+                                                  typename persist_acc<IO>::type &acc, const Parts &part = Parts{}, const Xchg &xchg = Xchg{})
 {
     // The wavefront's group: cnt (0 .. G) valid transforms starting at xf0; this lane belongs to number `sub`.
     constexpr int NBUF = CFG::NBUF;
@@ -307,7 +352,9 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
     if constexpr (NP >= 3) {
         if (NBUF == 1) exchange_sync<WAVE>();
         persist_lds_scatter<T, L, RL, 1>(cur, buf1, st.sc);
+        xchg.put();
         exchange_sync<WAVE>();
+        xchg.get();
         persist_lds_gather<T, L, RL, 2>(cur, buf1, st.g2);
         if constexpr (St::TWG) pass_tw_global(std::integral_constant<int, 2>{});
         else if constexpr (NP == 3 && CFG::kTwLastInLds) wg_compute<T, L, RL, 2>(cur, io, st.tw_lds, xf, tau);
@@ -447,6 +494,14 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
 // BLOCK threads carry XPB = BLOCK/TPT transforms at a time (TPT = N/16 threads each).
 // NBUF = 1: one LDS exchange buffer per transform slot; NBUF = 2 (block-synchronised sizes): exchanges
 // alternate between two buffers, which halves the number of barriers.
+//
+// CFG::kClaim (PersistClaim above): the rows from `split` on are not walked but claimed.  No workgroup ever waits for another one: a
+// claim is one fetch-add, and a claim at or beyond the end of the batch means "no more work" -- its prefetch goes through the empty
+// descriptor like a missing next row's.  The claim runs one step ahead of the loads: the row whose loads are issued at the top of step t
+// was claimed at the top of step t - 1, IN FRONT of that step's prefetch loads (vmcnt counts in issue order: waiting for the claim
+// leaves the 16 loads behind it in flight), by one lane; the others read it from one LDS word behind a barrier the transform has anyway.
+// A kClaim configuration's kernel takes the hand-out's argument as a member of its IO policy (PersistClaimIO<IO>): the kernel's signature,
+// and with it every other instantiation, stays what it was.
 template <typename T, int L, int RL, int EPI, class IO, class CFG>
 __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(const IO io, const cpx<T> *__restrict__ tw,
                                                                             const size_t batch)
@@ -517,7 +572,62 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
 
     const size_t step = (size_t)gridDim.x * XPB;
     size_t base = (size_t)blockIdx.x * XPB;
-    if (base >= batch) return;  // the whole workgroup leaves together
+    constexpr bool CLAIMS = persist_claim<CFG>::value;
+#ifdef KOFFT_PERSIST_STAMPS
+    const unsigned long long stamp_entry = persist_stamp(), stamp_entry_real = persist_stamp_real();
+    unsigned long long stamp_landed = 0, stamp_landed_real = 0, stamp_rows = 0;
+#define KOFFT_PERSIST_STAMP_LANDED()                                                                                  \
+    {                                                                                                                 \
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RS) : "memory"); /* everything in front of the next row's loads */    \
+        stamp_landed = persist_stamp();                                                                               \
+        stamp_landed_real = persist_stamp_real();                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                            \
+    }
+#define KOFFT_PERSIST_STAMP_ROW() ++stamp_rows;
+#else
+#define KOFFT_PERSIST_STAMP_LANDED()
+#define KOFFT_PERSIST_STAMP_ROW()
+#endif
+    // (claim hand-out) the row after `base`, and the LDS words the claims travel through
+    [[maybe_unused]] size_t nbase = 0;
+    [[maybe_unused]] unsigned long long *claim_word = nullptr;
+    if constexpr (CLAIMS) {
+        static_assert(NP == 3 && NBUF == 1 && !WAVE && G == 1 && persist_depth<CFG>::value == 1 && !persist_tw_global<CFG>::value &&
+                          !(RawSel::pair || RawSel::pair_lds) && !CFG::kInvInLds && !CFG::kTwLastInLds && EPI != EPI_RFFT,
+                      "claim hand-out: block-synchronised three-pass transforms, one row ahead, nothing else in LDS");
+        claim_word = reinterpret_cast<unsigned long long *>(smem_raw + (size_t)XPB * NBUF * persist_slot_elems(L) * sizeof(cpx<T>));
+        // The first two rows.  Walked rows need no claim (split is a multiple of the stride: with split > 0 every workgroup's first
+        // row is a walked one); otherwise lane 0 claims them here, once per kernel, and the workgroup waits for its own lane only.
+        const bool first_walked = io.claim.split > 0;
+        const bool second_walked = first_walked && base + step < io.claim.split;
+        nbase = base + step;
+        if (!second_walked) {  // workgroup-uniform
+            if (tid == 0) {
+                size_t r0 = base, r1 = batch;
+                if (!first_walked) r0 = io.claim.split + (size_t)XPB * atomicAdd(io.claim.counters, 1u);
+                if (r0 < batch) r1 = io.claim.split + (size_t)XPB * atomicAdd(io.claim.counters, 1u);  // (never a second claim after a failed one)
+                claim_word[0] = r0;
+                claim_word[1] = r1;
+            }
+            __syncthreads();
+            base = claim_word[0];
+            nbase = claim_word[1];  // (claim_word[0] is next written behind three barriers of the first transform)
+        }
+    }
+    // (claim hand-out) a workgroup makes exactly ONE failing claim and counts itself here afterwards; the last one to arrive has seen
+    // every claim of the launch completed and resets both counters for the next launch
+    [[maybe_unused]] auto claim_leave = [&]() {
+        if constexpr (CLAIMS) {
+            if (tid == 0 && atomicAdd(io.claim.counters + 1, 1u) == gridDim.x - 1) {
+                __hip_atomic_store(io.claim.counters, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(io.claim.counters + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    };
+    if (base >= batch) {  // the whole workgroup leaves together
+        if constexpr (CLAIMS) claim_leave();
+        return;
+    }
 
     // Raw register sets swap roles every transform (no register copies): while the transform held in one set is
     // computed, the others receive the loads of the transforms that follow.
@@ -550,9 +660,80 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     if constexpr (io_has_acc<IO>::value) acc = io.acc_init();
     auto finish = [&]() {
         if constexpr (io_has_acc<IO>::value) io.acc_finish(acc);
+        if constexpr (CLAIMS) claim_leave();
+#ifdef KOFFT_PERSIST_STAMPS
+        if (tid == 0 && blockIdx.x < kPersistStampWgs) {
+            unsigned long long *rec = g_persist_stamps + (size_t)blockIdx.x * kPersistStampWords;
+            rec[0] = stamp_entry;
+            rec[1] = stamp_landed;
+            rec[2] = persist_stamp();  // the last row's stores have been issued
+            rec[3] = stamp_entry_real;
+            rec[4] = stamp_landed_real;
+            rec[5] = persist_stamp_real();
+            rec[6] = stamp_rows;
+            rec[7] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID, all 32 bits
+            rec[8] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
+            rec[9] = gridDim.x;
+            rec[10] = 1;  // record written
+        }
+#endif
     };
 
-    if constexpr (DEPTH == 1 && St::TWG && !(RawSel::pair || RawSel::pair_lds)) {
+    if constexpr (CLAIMS) {
+        // One step: claim the row AFTER the next one (where it is a claimed row and the next one exists), issue the next row's loads, run
+        // the transform held in CUR -- which hands the claimed row from lane 0 to the workgroup.  `more` stays workgroup-uniform.
+        // (the counter's address depends on an opaque VGPR: with a uniform address the compiler folds the wavefront's fetch-adds into one
+        // and hands the result round with v_readfirstlane -- behind an s_waitcnt vmcnt(0) right at the claim)
+        // (an opaque INDEX, not an opaque pointer: that one would lose its address space, and behind a flat_atomic every counted vmcnt wait
+        // of the loop becomes vmcnt(0))
+        unsigned claim_index = 0;
+        asm volatile("" : "+v"(claim_index));
+        unsigned *const claim_next = io.claim.counters + claim_index;
+        // (the ticket stays a bare register until put(): anything computed from it next to the fetch-add would wait for it there, in front
+        // of the prefetch, with vmcnt(0) -- the previous transform's stores included)
+        struct ClaimXchg {
+            unsigned long long *word;
+            size_t split;
+            const unsigned *ticket;
+            size_t *claimed;
+            bool writer;  // the claiming lane, in a step that claims
+            __device__ __forceinline__ void put() const
+            {
+                if (writer) *word = split + (size_t)XPB * *ticket;
+            }
+            __device__ __forceinline__ void get() const { *claimed = *word; }
+        };
+#define KOFFT_PERSIST_STEP_CLAIM(CUR, NXT, LEAVE)                                                                    \
+    {                                                                                                                \
+        const bool more = nbase < batch;                   /* workgroup-uniform */                                   \
+        const bool walked = nbase + step < io.claim.split; /* workgroup-uniform */                                   \
+        const bool claims = more && !walked && tid == 0;                                                             \
+        unsigned ticket; /* (no initial value: merging one with the fetch-add's result would be a copy, and a wait, at the claim) */ \
+        size_t claimed = batch;                                                                                      \
+        if (claims) ticket = atomicAdd(claim_next, 1u);                                                              \
+        __builtin_amdgcn_sched_barrier(0); /* the claim in front of the prefetch */                                  \
+        issue(NXT, nbase);                                                                                           \
+        __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of CUR's first use */                          \
+        KOFFT_PERSIST_STEP_STAMP                                                                                     \
+        const ClaimXchg xchg{claim_word, io.claim.split, &ticket, &claimed, claims};                                 \
+        persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, base + wslot, group_cnt(base), sub, tau, acc, NoPrefetchParts{}, xchg); \
+        KOFFT_PERSIST_STAMP_ROW()                                                                                    \
+        if (!more) LEAVE;                                                                                            \
+        base = nbase;                                                                                                \
+        nbase = walked ? nbase + step : (size_t)claimed; /* (a failed claim: at or beyond the end) */                \
+    }
+#define KOFFT_PERSIST_STEP_STAMP KOFFT_PERSIST_STAMP_LANDED()
+        KOFFT_PERSIST_STEP_CLAIM(ra, rb, { finish(); return; })
+#undef KOFFT_PERSIST_STEP_STAMP
+#define KOFFT_PERSIST_STEP_STAMP
+        for (;;) {
+            KOFFT_PERSIST_STEP_CLAIM(rb, ra, break)
+            KOFFT_PERSIST_STEP_CLAIM(ra, rb, break)
+        }
+#undef KOFFT_PERSIST_STEP_STAMP
+        finish();
+#undef KOFFT_PERSIST_STEP_CLAIM
+    } else if constexpr (DEPTH == 1 && St::TWG && !(RawSel::pair || RawSel::pair_lds)) {
         // kTwGlobal: the next transform's loads in NP - 1 parts behind the passes' table loads (persist_transform)
         constexpr bool TOP = persist_twg_top_part(L);
         constexpr int PARTS = TOP ? NP : NP - 1;  // (part 0 at the top of the step,) part p behind pass p's entries
@@ -588,7 +769,9 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         const bool more = nbase < batch; /* workgroup-uniform */                                                     \
         issue(NXT, nbase);                                                                                           \
         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of CUR's first use */                          \
+        KOFFT_PERSIST_STEP_STAMP                                                                                                     \
         persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, base + wslot, group_cnt(base), sub, tau, acc); \
+        KOFFT_PERSIST_STAMP_ROW()                                                                                    \
         if (!more) LEAVE;                                                                                            \
         base = nbase;                                                                                                \
     }
@@ -597,11 +780,15 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         // With the first step inside the loop the compiler must merge the entry state (no stores yet) with the back-edge
         // state and emits vmcnt(15 - i) for both -- which, on the back edge, waits for the previous transform's STORES to
         // complete, once per two transforms.  After the peel both predecessors of the loop header look the same.
+#define KOFFT_PERSIST_STEP_STAMP KOFFT_PERSIST_STAMP_LANDED()
         KOFFT_PERSIST_STEP(ra, rb, { finish(); return; })
+#undef KOFFT_PERSIST_STEP_STAMP
+#define KOFFT_PERSIST_STEP_STAMP
         for (;;) {
             KOFFT_PERSIST_STEP(rb, ra, break)
             KOFFT_PERSIST_STEP(ra, rb, break)
         }
+#undef KOFFT_PERSIST_STEP_STAMP
         finish();
 #undef KOFFT_PERSIST_STEP
     } else {
@@ -632,5 +819,7 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     }
 }
 
+#undef KOFFT_PERSIST_STAMP_LANDED
+#undef KOFFT_PERSIST_STAMP_ROW
 
 }  // namespace kofft

@@ -55,6 +55,8 @@ struct kofft_hip_ctx {
     int czt_route = 0;        // kofft_hip_set_czt_route: 0 by batch and by whether the table is there (czt_use_table), 1 every call on czt_recur_kernel<CZT_SUM>, 2 every call through a table and the direct kernels (A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
+    int persist_claim_pct = -1; // kofft_hip_set_persist_claim_pct: percent of the batch the kClaim persistent kernels hand out by claim, 0 .. 100 (-1: the configuration's; A/B, tests)
+    unsigned *persist_claim_counters = nullptr;  // device: [next claim, workgroups done]; zeroed at creation, every kClaim launch leaves them at zero
     bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
     int big_three_min = 22;    // KOFFT_HIP_BIG_THREE_MIN: smallest log2 n split into three factors
     bool small32 = true;       // KOFFT_HIP_SMALL32=0: f32 n = 32 on the thread-group kernel instead of one thread per transform (A/B)
@@ -311,6 +313,7 @@ int launch_wg(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch)
 //   MINW            waves per SIMD the kernel must fit (register budget); WG_PER_CU = workgroups launched per CU
 //   kInvInLds       window samples / irfft table in one LDS copy per workgroup instead of registers
 //   kTwLastInLds    the last pass reads its twiddles from an LDS copy of the table (frees 24..30 VGPRs)
+//   kClaim          (default off) the end of the batch is handed out by claim; kClaimPct: how much of it, in percent
 template <int L, class IO> struct PersistCfg;
 template <class IO> struct PersistCfgBase {
     static constexpr int NBUF = 1, RL = 4;
@@ -332,6 +335,18 @@ template <bool INV> struct PersistCfg<12, ComplexIO<double, INV>> {
 #define KOFFT_C12_DEPTH 1  // (round 5 A/B: two transforms ahead for the n = 4096 kernels -- three register sets, 166 VGPRs)
 #endif
 template <class IO> struct PersistCfg<12, IO> : PersistCfgBase<IO> { static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_C12_DEPTH; };
+// c32 n = 4096 (round 7): the last kClaimPct percent of the batch are claimed row by row instead of walked (fft_persist.hip.h,
+// PersistClaim), so that a workgroup that falls behind leaves rows to the others; the table of fractions is in DESIGN.md 5.2.
+#ifndef KOFFT_C12_CLAIM
+#define KOFFT_C12_CLAIM true
+#endif
+#ifndef KOFFT_C12_CLAIM_PCT
+#define KOFFT_C12_CLAIM_PCT 25
+#endif
+template <bool INV> struct PersistCfg<12, ComplexIO<float, INV>> : PersistCfgBase<ComplexIO<float, INV>> {
+    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_C12_DEPTH, kClaimPct = KOFFT_C12_CLAIM_PCT;
+    static constexpr bool kClaim = KOFFT_C12_CLAIM;
+};
 template <class IO> struct PersistCfg<11, IO> : PersistCfgBase<IO> { static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2; };
 template <class IO> struct PersistCfg<10, IO> : PersistCfgBase<IO> {
     static constexpr int BLOCK = 256, MINW = IO::kLeanRegisters ? 3 : 2, WG_PER_CU = MINW;
@@ -453,9 +468,13 @@ template <> struct PersistGrid<10, RfftIO<float>> {
 };
 
 template <typename T, int L, int EPI, class IO>
+int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch);
+template <typename T, int L, int EPI, class IO>
 int launch_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch)
 {
     using Cfg = PersistCfg<L, IO>;
+    if constexpr (persist_claim<Cfg>::value) return launch_persist_claim<T, L, EPI>(ctx, io, tw, batch);
+    else {
     constexpr int RL = Cfg::RL;
     constexpr int XPB = Cfg::BLOCK / ((1 << L) >> RL);
     constexpr size_t lds = (size_t)XPB * Cfg::NBUF * persist_slot_elems(L) * sizeof(cpx<T>) +
@@ -475,6 +494,43 @@ int launch_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t ba
     const size_t need = (batch + XPB - 1) / XPB;
     if (blocks > need) blocks = need;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Cfg::BLOCK), lds, ctx->stream, io, tw, batch);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+    }
+}
+
+// The same for a kClaim configuration.  Rows [0, split) are walked as above, split a multiple of the grid's stride; rows [split, batch)
+// are claimed through the context's two counters, which every launch leaves at zero (no reset here, nothing a captured graph's replay
+// would miss: pointer and split are plain kernel arguments that depend on the batch alone).  They ride in the kernel's IO policy.
+template <typename T, int L, int EPI, class IO>
+int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch)
+{
+    using Cfg = PersistCfg<L, IO>;
+    constexpr int RL = Cfg::RL;
+    constexpr int XPB = Cfg::BLOCK / ((1 << L) >> RL);
+    constexpr size_t lds = (size_t)XPB * Cfg::NBUF * persist_slot_elems(L) * sizeof(cpx<T>) + 16;  // + the words the claims travel through
+    static_assert(lds * Cfg::WG_PER_CU <= 160 * 1024, "LDS budget");
+    if (!ctx->persist_claim_counters) {
+        ctx->last_error = "the context has no claim counters";
+        return KOFFT_ERR_ALLOC;
+    }
+    using KIO = PersistClaimIO<IO>;  // the kernel's policy: `io` plus the hand-out's argument
+    auto kern = fft_persist_kernel<T, L, RL, EPI, KIO, Cfg>;
+    {
+        static std::atomic<unsigned long long> attr_done{0};
+        const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
+        if (arc) return arc;
+    }
+    size_t blocks = (size_t)ctx->num_cus * PersistGrid<L, IO>::wg_per_cu(Cfg::WG_PER_CU, batch * sizeof(cpx<T>) << L);
+    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;  // measurement knob
+    if (blocks < 1) blocks = 1;
+    const size_t need = (batch + XPB - 1) / XPB;
+    if (blocks > need) blocks = need;  // (every workgroup's first walked row exists)
+    const size_t stride = blocks * XPB;
+    const size_t pct = ctx->persist_claim_pct < 0 ? (size_t)Cfg::kClaimPct : (ctx->persist_claim_pct > 100 ? 100 : (size_t)ctx->persist_claim_pct);
+    const size_t claimed = batch / 100 * pct + batch % 100 * pct / 100;
+    const KIO kio{io, PersistClaim{ctx->persist_claim_counters, (batch - claimed) / stride * stride}};
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Cfg::BLOCK), lds, ctx->stream, kio, tw, batch);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
 }

@@ -612,6 +612,14 @@ int kofft_hip_create(int device, kofft_hip_ctx **out)
         return KOFFT_ERR_HIP;
     }
     ctx->stream = ctx->own_stream;
+    // the claim counters of the kClaim persistent kernels (fft_persist.hip.h): zero once, here; every launch leaves them at zero
+    if (hipMalloc(reinterpret_cast<void **>(&ctx->persist_claim_counters), 64) != hipSuccess ||
+        hipMemsetAsync(ctx->persist_claim_counters, 0, 64, ctx->own_stream) != hipSuccess) {
+        if (ctx->persist_claim_counters) (void)hipFree(ctx->persist_claim_counters);
+        (void)hipStreamDestroy(ctx->own_stream);
+        delete ctx;
+        return KOFFT_ERR_ALLOC;
+    }
     *out = ctx;
     return KOFFT_OK;
 }
@@ -628,6 +636,7 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     if (ctx->blue_tmp) (void)hipFree(ctx->blue_tmp);
     if (ctx->real_tmp) (void)hipFree(ctx->real_tmp);
     if (ctx->rows_tmp) (void)hipFree(ctx->rows_tmp);
+    if (ctx->persist_claim_counters) (void)hipFree(ctx->persist_claim_counters);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -928,6 +937,13 @@ int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on)
 {
     if (!ctx) return KOFFT_ERR_NULL;
     ctx->direct_tiled = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_set_persist_claim_pct(kofft_hip_ctx *ctx, int pct)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (pct > 100) return KOFFT_ERR_INVALID_VALUE;
+    ctx->persist_claim_pct = pct < 0 ? -1 : pct;
     return KOFFT_OK;
 }
 int kofft_hip_set_wavelet_fused(kofft_hip_ctx *ctx, int on)

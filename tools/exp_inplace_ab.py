@@ -7,6 +7,7 @@ given with --libs (name=path) over --rounds rounds, so box drift lands on every 
 with --parse (the cells file records how many library dispatches each cell made).
 
 usage (GPU box): python3 tools/exp_inplace_ab.py [--libs head=kofft_amd/lib/libkofft_hip.so ld0=kofft_amd/lib_ld0/libkofft_hip.so]
+                 (name=path@PCT: that build with PCT percent of the batch handed out by claim, kofft_hip_set_persist_claim_pct)
                  python3 tools/exp_inplace_ab.py --parse <kernel_trace.csv> [--counters <counter_collection.csv>] --cells <cells.json>"""
 import argparse
 import csv
@@ -21,7 +22,7 @@ N, BATCH = 4096, 65536
 
 
 class Lib:
-    def __init__(self, path):
+    def __init__(self, path, claim_pct=None):
         self.lib = C.CDLL(str(path))
         self.lib.kofft_hip_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         self.lib.kofft_hip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -29,6 +30,9 @@ class Lib:
         self.lib.kofft_hip_fft_c32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
         self.ctx = C.c_void_p()
         assert self.lib.kofft_hip_create(0, C.byref(self.ctx)) == 0
+        if claim_pct is not None:  # name=path@PCT: the share of the batch handed out by claim (kofft_hip_set_persist_claim_pct)
+            self.lib.kofft_hip_set_persist_claim_pct.argtypes = [C.c_void_p, C.c_int]
+            assert self.lib.kofft_hip_set_persist_claim_pct(self.ctx, int(claim_pct)) == 0
 
     def set_stream(self, s):
         assert self.lib.kofft_hip_set_stream(self.ctx, C.c_void_p(s)) == 0
@@ -100,7 +104,8 @@ def main():
     libs = []
     for spec in args.libs:
         name, path = spec.split("=", 1)
-        lib = Lib(path)
+        path, _, pct = path.partition("@")
+        lib = Lib(path, int(pct) if pct else None)
         lib.set_stream(stream.cuda_stream)
         libs.append((name, lib))
     cells, summary = [], defaultdict(list)
