@@ -500,6 +500,28 @@ int kofft_hip_dev_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *d_fra
                                           const float *d_window, size_t win_len, size_t hop, float *d_output,
                                           size_t out_len);
 
+/* ---- one-sided STFT over rows of signals, and its inverse ----
+ * K = win_len / 2 + 1 (integer division).  Forward: the arguments, checks and check order of kofft_hip_stft_rows_f32 /
+ * kofft_hip_dev_stft_rows_f32 (plus rows * frames * K too large -> UNSUPPORTED); out is dense rows * frames * K complex, 8-byte
+ * aligned, and out[r][f][k], k < K, has exactly the bits the rows call writes to [r][f][k] -- the prefix of the full frame, for
+ * every window length that call takes; nothing of bins K .. win_len - 1 is written anywhere.  Window lengths that are not a power
+ * of two go through scratch the context owns (at most 512 MiB, until kofft_hip_release_scratch / destroy).
+ * Inverse: half is rows * frames * K complex and is only read.  Every frame is completed to F[k] = half[k] for k < K,
+ * F[k] = (half[win_len - k].re, -half[win_len - k].im) for K <= k < win_len (the imaginary parts of bins 0 and win_len / 2 are
+ * used as given), and the result is exactly kofft_hip_istft_parallel_rows_f32 of F: output (rows * out_len) is accumulated into
+ * and normalised, a sample whose window-square sum is <= 1e-8 becomes 0.  Checks: those of the parallel rows form, in its order.
+ * Both device forms work through scratch the context owns, like kofft_hip_dev_istft_parallel_rows_f32. */
+int kofft_hip_stft_onesided_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride,
+                                const float *window, size_t win_len, size_t hop, float *out, size_t frames);
+int kofft_hip_dev_stft_onesided_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len,
+                                    size_t row_stride, const float *d_window, size_t win_len, size_t hop,
+                                    float *d_out, size_t frames);
+int kofft_hip_istft_onesided_f32(kofft_hip_ctx *ctx, const float *half, size_t rows, size_t frames,
+                                 const float *window, size_t win_len, size_t hop, float *output, size_t out_len);
+int kofft_hip_dev_istft_onesided_f32(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames,
+                                     const float *d_window, size_t win_len, size_t hop, float *d_output,
+                                     size_t out_len);
+
 /* ---- 2-D / 3-D FFT (SURVEY 8f "next" row 3) ----------------------------------------
  * ndfft::fft2d_inplace (ndfft.rs:74-101) with depth == 1: FftImpl::fft on every row (length cols), then
  * FftImpl::fft_strided down every column (length rows, stride cols).  ndfft::fft3d_inplace

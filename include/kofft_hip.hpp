@@ -857,6 +857,32 @@ inline Result istft_rows(std::vector<Complex32> &frames, size_t rows, const std:
                                            output.data(), out_len, scratch.data(), out_len));
 }
 
+// the one-sided STFT per row (kofft_hip.h, "one-sided STFT"): rows * frames * (window.size() / 2 + 1) values, bit for bit the first
+// window.size() / 2 + 1 bins of every frame of stft_rows; frames defaults to ceil(len / hop)
+inline Result stft_onesided(const std::vector<float> &signals, size_t rows, const std::vector<float> &window, size_t hop_size,
+                            std::vector<Complex32> &out, const HipFftImpl<float> &fft, size_t frames = static_cast<size_t>(-1))
+{
+    if (hop_size == 0) return Result::Err(FftError::InvalidHopSize);  // stft.rs:83
+    if (rows == 0 || signals.size() % rows != 0) return rows == 0 && signals.empty() ? Result::Ok() : Result::Err(FftError::MismatchedLengths);
+    const size_t len = signals.size() / rows;
+    if (frames == static_cast<size_t>(-1)) frames = (len + hop_size - 1) / hop_size;
+    out.assign(rows * frames * (window.size() / 2 + 1), Complex32{});
+    return fft.st(kofft_hip_stft_onesided_f32(fft.raw(), signals.data(), rows, len, len, window.data(), window.size(), hop_size,
+                                              reinterpret_cast<float *>(out.data()), frames));
+}
+// stft::inverse_parallel per row of the Hermitian completion of one-sided frames (`half`: rows * frames * (window.size() / 2 + 1)
+// values, only read); output: rows * out_len, accumulated into
+inline Result istft_onesided(const std::vector<Complex32> &half, size_t rows, const std::vector<float> &window, size_t hop_size,
+                             std::vector<float> &output, const HipFftImpl<float> &fft)
+{
+    if (hop_size == 0) return Result::Err(FftError::InvalidHopSize);
+    if (rows == 0) return Result::Ok();
+    const size_t wl = window.size(), bins = wl / 2 + 1;
+    if (output.size() % rows != 0 || half.size() % (rows * bins) != 0) return Result::Err(FftError::MismatchedLengths);
+    return fft.st(kofft_hip_istft_onesided_f32(fft.raw(), reinterpret_cast<const float *>(half.data()), rows, half.size() / (rows * bins),
+                                               window.data(), wl, hop_size, output.data(), output.size() / rows));
+}
+
 // ndfft::fft2d_inplace (ndfft.rs:74-101) / fft3d_inplace (ndfft.rs:114-155): same length checks, same order
 template <typename T>
 Result fft2d_inplace(std::vector<Complex<T>> &data, size_t rows, size_t cols, const HipFftImpl<T> &fft,

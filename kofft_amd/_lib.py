@@ -131,6 +131,10 @@ SIGNATURES = {
     "kofft_hip_dev_istft_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_void_p, _sz]),
     "kofft_hip_istft_parallel_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_dev_istft_parallel_rows_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_stft_onesided_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_stft_onesided_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_istft_onesided_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_istft_onesided_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_stft_f32_dev": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),
     # multi-GPU (single process, one context per device; RCCL bound at run time)
     "kofft_hip_multi_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(_ctx)]),

@@ -478,6 +478,17 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
                 if (LastG::out_index(0, u) < N / 2) io.store_d_mag(od, lane_bytes, LastG::out_index(0, u), m[ki++], row_off);
             if constexpr (io_row_acc<IO>::value) io.acc_row(xf0, active ? top : 0.0f);  // one row per wavefront: committed per transform
             else if (active) acc = __builtin_fmaxf(acc, top);
+        } else if constexpr (io_half_keep<IO>::value) {
+            // bins 0 .. N/2 in rows of N/2 + 1 (StftHalfIO).  The group's descriptor spans several rows, so a bin above N/2 would land in the
+            // next frame's row, inside the bounds: which stores exist is decided here.  Register part and thread part of the output index
+            // are disjoint bit fields (as above): registers below N/2 are stored by every lane, the one register AT N/2 by lane tau == 0
+            // alone -- the other lanes aim outside the descriptor, still no branch -- and the rest, with their share of the last stage, are dead.
+            static_assert((LastG::out_index(0, 1) % TPT) == 0 && TPT <= N / 2, "register part and thread part of the index: disjoint bit fields");
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                if (LastG::out_index(0, u) < N / 2) io.store_d_kept(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
+                else if (LastG::out_index(0, u) == N / 2) io.store_d_nyquist(od, tau, LastG::out_index(0, u), cur[u], row_off);
+            }
         } else {
 #ifdef KOFFT_PERSIST_ACTIVE_BRANCH /* measurement only (tools/build_variant.sh): rounds 1-4's branch around the stores, for same-box A/Bs */
         if (active)

@@ -441,6 +441,51 @@ __device__ __forceinline__ void row_max_commit(unsigned *max_bits, unsigned row,
     }
 }
 
+// policies that keep bins 0 .. n/2 of every transform in dense rows of n/2 + 1 (StftHalfIO): the persistent kernel decides per
+// REGISTER which stores exist (fft_persist.hip.h)
+template <class IO, class = void>
+struct io_half_keep { static constexpr bool value = false; };
+template <class IO>
+struct io_half_keep<IO, decltype((void)IO::kHalfKeep)> { static constexpr bool value = IO::kHalfKeep; };
+
+// One-sided STFT: StftIO's frames and arithmetic, bins 0 .. n/2 stored as dense rows of K = n/2 + 1 complex values.  Bin o
+// of transform xf is kept iff o <= n/2, at out[xf * K + o]; the input side is StftIO's, untouched.  Rows are 8-byte aligned only (K may be
+// odd), so no store here is wider than one bin.  A descriptor over several rows (out_desc_n) does not drop a bin above n/2 -- its offset
+// lies inside the NEXT row -- so every descriptor store decides explicitly, and a store that must not happen aims kDropOff bytes past
+// anything a descriptor of this policy covers (cnt rows of at most 2^14 bins) instead of being branched around (fft_persist.hip.h, round 5).
+struct StftHalfIO : StftIO {
+    static constexpr bool kSplitOk = false;  // the wave-split kernels are not taken (as for rows: StftRowsOf)
+    static constexpr bool kHalfKeep = true;
+    static constexpr int kDropOff = 0x40000000;
+    __device__ __forceinline__ size_t bins() const { return (size_t)(n / 2) + 1; }
+    __device__ __forceinline__ rsrc_t out_desc(size_t xf) const { return make_rsrc(out + xf * bins(), (unsigned)bins() * 8u); }
+    __device__ __forceinline__ rsrc_t out_desc_n(size_t xf0, int cnt) const
+    {
+        return make_rsrc(out + (cnt > 0 ? xf0 : 0) * bins(), (unsigned)(cnt > 0 ? cnt : 0) * (unsigned)bins() * 8u);
+    }
+    __device__ __forceinline__ unsigned out_row_bytes() const { return (unsigned)bins() * 8u; }
+    // lane_bytes = 8 * tau: bin ou + tau
+    __device__ __forceinline__ void store_d(rsrc_t d, int lane_bytes, int ou, cpx<float> v, int row_off = 0) const
+    {
+        const bool keep = ou + (lane_bytes >> 3) <= n / 2;
+        buf_store_cpx<float>(v, d, keep ? row_off + lane_bytes : kDropOff, ou * 8);
+    }
+    // the persistent kernel's forms: a register whose bins are all kept, and the one register that holds bin n/2 in lane tau == 0
+    __device__ __forceinline__ void store_d_kept(rsrc_t d, int lane_bytes, int ou, cpx<float> v, int row_off) const
+    {
+        buf_store_cpx<float>(v, d, row_off + lane_bytes, ou * 8);
+    }
+    __device__ __forceinline__ void store_d_nyquist(rsrc_t d, int tau, int ou, cpx<float> v, int row_off) const
+    {
+        buf_store_cpx<float>(v, d, tau == 0 ? row_off : kDropOff, ou * 8);
+    }
+    __device__ __forceinline__ void store(size_t xf, int o, cpx<float> v) const
+    {
+        if (o <= n / 2) st_stream(out + xf * bins() + o, v);
+    }
+};
+using StftHalfRowsIO = StftRowsOf<StftHalfIO>;
+
 // stft_magnitudes over rows: max_bits holds one maximum per row.  A thread's accumulator names the row it belongs to and is flushed
 // when the thread's stores move to another row (fft_small_kernel: a thread stores elements of several transforms); the persistent
 // kernel, where a wavefront holds one row at a time (a transform of 64 lanes or more, or a group inside a row), commits per transform.

@@ -410,6 +410,10 @@ template <> struct PersistCfg<12, StftRowsIO> : PersistCfg<12, StftIO> {};
 template <> struct PersistCfg<10, StftMagRowsIO> : PersistCfg<10, StftMagIO> {};
 template <> struct PersistCfg<11, StftMagRowsIO> : PersistCfg<11, StftMagIO> {};
 template <> struct PersistCfg<12, StftMagRowsIO> : PersistCfg<12, StftMagIO> {};
+// (the one-sided STFT, k_stft_onesided.hip: StftIO's arithmetic and registers, fewer stores)
+template <> struct PersistCfg<10, StftHalfRowsIO> : PersistCfg<10, StftIO> {};
+template <> struct PersistCfg<11, StftHalfRowsIO> : PersistCfg<11, StftIO> {};
+template <> struct PersistCfg<12, StftHalfRowsIO> : PersistCfg<12, StftIO> {};
 // rfft 8192 (m = 4096): window pairs in registers so that two workgroups (exchange buffer + post-pass table) fit a CU
 template <> struct PersistCfg<12, RfftIO<float>> {
     static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 2;
@@ -866,8 +870,39 @@ int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t
 int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop,
                       float *d_mags, size_t frames, float *d_max);
 int istft_rows_check(size_t rows, size_t frames, size_t win_len, size_t hop, size_t out_len, size_t scratch_len, int mode);
+// (mode 2 with keep_frames only) half: d_frames holds bins 0 .. win_len/2 of every frame, rows * frames * (win_len/2 + 1) complex; the
+// walk's copy into the context's scratch is then the Hermitian completion (expand_half, k_stft_onesided.hip)
 int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
-                   float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames);
+                   float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames, bool half = false);
+// transforms t0 .. t0 + nt of the flat index row * frames + frame, composed (any window length): framing product into dst, fft_dev in place
+int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
+                       size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt);
+size_t composed_chunk(size_t win_len, size_t count);  // transforms per pass through at most 512 MiB of scratch
+// the input side of a StftRowsOf policy (row_stride: 0 when rows == 1)
+template <class IO>
+inline void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
+                         size_t hop, size_t frames)
+{
+    io.signal = d_signal;
+    io.window = d_window;
+    io.out = nullptr;
+    io.len = len;
+    io.hop = hop;
+    io.start0 = 0;
+    io.n = (int)win_len;
+    io.frames = frames;
+    io.row_stride = rows > 1 ? row_stride : 0;
+    io.frames32 = rows * frames < (size_t(1) << 31) ? (unsigned)frames : 0u;
+}
+// k_stft_onesided.hip: the STFT with bins 0 .. win_len/2 of every frame kept, rows * frames * (win_len/2 + 1) complex, bit for bit the
+// prefix of stft_rows_dev's frames, and inverse_parallel of the Hermitian completion of such frames
+int stft_onesided_check(bool host_form, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames);
+int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                      size_t win_len, size_t hop, float *d_out, size_t frames);
+int istft_onesided_dev(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
+                       float *d_output, size_t out_len);
+// dst[t][k] = src[t][k] for k <= win_len/2, conj(src[t][win_len - k]) above: nt frames of win_len/2 + 1 bins -> nt frames of win_len
+int expand_half(kofft_hip_ctx *ctx, const float *d_half, float *d_full, size_t nt, size_t win_len);
 template <typename T>
 int fft_nd_dev(kofft_hip_ctx *ctx, T *d_data, size_t depth, size_t rows, size_t cols, int inverse);  // k_nd.hip
 

@@ -1,0 +1,100 @@
+// k_stft_onesided.hip -- the one-sided STFT over rows of signals and its inverse on device pointers.  Forward: the
+// frames of k_stft_rows.hip's stft_rows_dev with bins 0 .. n/2 of every frame kept, dense rows of K = n/2 + 1 complex values, bit for bit
+// the prefix of the full frames (StftRowsOf<StftHalfIO>: the same kernels, the same arithmetic, fewer stores).  Inverse:
+// stft::inverse_parallel (stft.rs:289-343) of the Hermitian completion of such frames.
+#include "host_common.hip.h"
+
+namespace kofft {
+namespace host {
+
+// composed frames (any window length) -> their kept bins: dst[t][k] = src[t][k], k < bins.  One bin per thread.
+__global__ __launch_bounds__(256) void pack_half_kernel(const cpx<float> *__restrict__ src, cpx<float> *__restrict__ dst, const size_t win_len,
+                                                        const size_t bins, const size_t total /* transforms * bins */)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const size_t t = idx / bins, k = idx - t * bins;
+    dst[idx] = src[t * win_len + k];
+}
+
+// the completed frame F[k] = H[k] for k < bins, (H[n - k].re, -H[n - k].im) above; the imaginary parts of H[0] and H[n/2] as given.
+// One bin of F per thread; `half` is only read.
+__global__ __launch_bounds__(256) void expand_half_kernel(const cpx<float> *__restrict__ half, cpx<float> *__restrict__ full,
+                                                          const size_t win_len, const size_t bins, const size_t total /* transforms * win_len */)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const size_t t = idx / win_len, k = idx - t * win_len;
+    const cpx<float> *h = half + t * bins;
+    if (k < bins) {
+        full[idx] = h[k];
+    } else {
+        const cpx<float> c = h[win_len - k];
+        full[idx] = mk<float>(c.re, -c.im);
+    }
+}
+
+int expand_half(kofft_hip_ctx *ctx, const float *d_half, float *d_full, size_t nt, size_t win_len)
+{
+    const size_t total = nt * win_len;
+    if (total == 0) return KOFFT_OK;
+    const size_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(expand_half_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const cpx<float> *>(d_half),
+                       reinterpret_cast<cpx<float> *>(d_full), win_len, win_len / 2 + 1, total);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
+// stft_rows_check's checks in its order, then the size of the one-sided output
+int stft_onesided_check(bool host_form, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames)
+{
+    const int crc = stft_rows_check(host_form, false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    const size_t total = rows * frames, bins = win_len / 2 + 1;  // (rows * frames * win_len passed the check above)
+    if (bins > (SIZE_MAX >> 4) / total) return KOFFT_ERR_UNSUPPORTED;
+    return KOFFT_OK;
+}
+
+int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                      size_t win_len, size_t hop, float *d_out, size_t frames)
+{
+    const int crc = stft_onesided_check(false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (!ctx || (!d_signal && len) || !d_window || !d_out) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t total = rows * frames, bins = win_len / 2 + 1;
+    if (rows == 1) row_stride = 0;
+    if (!fused_len_ok<float>(win_len)) {
+        // any other window length: the composed frames in the context's scratch, at most 512 MiB at a time, then their kept bins
+        const size_t chunk = composed_chunk(win_len, total);
+        if ((chunk * bins + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+        int rc = ensure_real_tmp(ctx, chunk * win_len * 8);
+        if (rc) return rc;
+        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp);
+        for (size_t t0 = 0; t0 < total; t0 += chunk) {
+            const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
+            rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_window, win_len, hop, spec, t0, nt);
+            if (rc) return rc;
+            hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)((nt * bins + 255) / 256)), dim3(256), 0, ctx->stream, spec,
+                               reinterpret_cast<cpx<float> *>(d_out) + t0 * bins, win_len, bins, nt * bins);
+            KOFFT_HIP_TRY(ctx, hipGetLastError());
+        }
+        return KOFFT_OK;
+    }
+    StftHalfRowsIO io{};
+    fill_rows_io(io, d_signal, rows, len, row_stride, d_window, win_len, hop, frames);
+    io.out = reinterpret_cast<cpx<float> *>(d_out);
+    return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
+}
+
+// istft_rows_dev's mode 2 walk with the Hermitian completion in the place of its copy: d_half is never written
+int istft_onesided_dev(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
+                       float *d_output, size_t out_len)
+{
+    return istft_rows_dev(ctx, const_cast<float *>(d_half), rows, frames, d_window, win_len, hop, d_output, out_len, nullptr, out_len, 2, true,
+                          true);
+}
+
+}  // namespace host
+}  // namespace kofft

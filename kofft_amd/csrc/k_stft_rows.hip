@@ -95,25 +95,9 @@ int stft_rows_check(bool host_form, bool mags, size_t rows, size_t len, size_t r
     return KOFFT_OK;
 }
 
-template <class IO>
-static void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
-                         size_t hop, size_t frames)
-{
-    io.signal = d_signal;
-    io.window = d_window;
-    io.out = nullptr;
-    io.len = len;
-    io.hop = hop;
-    io.start0 = 0;
-    io.n = (int)win_len;
-    io.frames = frames;
-    io.row_stride = rows > 1 ? row_stride : 0;
-    io.frames32 = rows * frames < (size_t(1) << 31) ? (unsigned)frames : 0u;
-}
-
 // transforms t0 .. t0 + nt of the flat index, composed: framing product into dst, fft_dev in place
-static int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
-                              size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt)
+int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
+                       size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt)
 {
     const size_t blocks = (nt * win_len + 255) / 256;
     if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
@@ -123,7 +107,7 @@ static int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t 
     return fft_dev<float>(ctx, reinterpret_cast<const float *>(dst), reinterpret_cast<float *>(dst), win_len, nt, 0);
 }
 
-static size_t composed_chunk(size_t win_len, size_t count)
+size_t composed_chunk(size_t win_len, size_t count)
 {
     size_t chunk = (size_t(512) << 20) / (win_len * 8);
     if (chunk < 1) chunk = 1;
@@ -244,12 +228,14 @@ int istft_rows_check(size_t rows, size_t frames, size_t win_len, size_t hop, siz
 // mode 2 (inverse_parallel): keep_frames leaves the caller's frames alone (their inverse transforms go to the context's scratch).
 // (istft_fused_kernel knows one signal only: always the two-kernel route.)
 int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
-                   float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames)
+                   float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames, bool half)
 {
     const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
     if (crc || rows == 0) return crc;
     if (!ctx || (frames && (!d_frames || !d_window)) || (out_len && (!d_output || (mode == 1 && !d_scratch)))) return KOFFT_ERR_NULL;
+    if (half && !(keep_frames && mode == 2)) return KOFFT_ERR_INVALID_VALUE;  // (never: istft_onesided_dev is the one caller)
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t in_frame = half ? (win_len / 2 + 1) * 2 : win_len * 2;  // floats of one frame as the caller holds it
     // keep_frames: whole rows at a time through at most 512 MiB of the context's scratch (one row's frames where a row alone is
     // larger) -- copy, inverse transform, overlap-add; the rows are independent, so the sums and their order do not change
     size_t rows_per = rows;
@@ -268,12 +254,17 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
     if ((rows_per * out_len + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     for (size_t r0 = 0; r0 < rows; r0 += rows_per) {
         const size_t nr = rows - r0 < rows_per ? rows - r0 : rows_per;
-        const float *time_frames = d_frames + r0 * frames * win_len * 2;
+        const float *time_frames = d_frames + r0 * frames * in_frame;
         if (frames > 0) {
-            float *dst = d_frames + r0 * frames * win_len * 2;
+            float *dst = d_frames + r0 * frames * in_frame;
             if (keep_frames) {
                 dst = static_cast<float *>(ctx->rows_tmp);
-                KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dst, time_frames, nr * frames * win_len * 8, hipMemcpyDeviceToDevice, ctx->stream));
+                if (half) {  // the completed frames F[k] = H[k], k <= n/2; conj(H[n - k]) above
+                    const int erc = expand_half(ctx, time_frames, dst, nr * frames, win_len);
+                    if (erc) return erc;
+                } else {
+                    KOFFT_HIP_TRY(ctx, hipMemcpyAsync(dst, time_frames, nr * frames * win_len * 8, hipMemcpyDeviceToDevice, ctx->stream));
+                }
             }
             const int rc = fft_dev<float>(ctx, dst, dst, win_len, nr * frames, 1);
             if (rc) return rc;

@@ -471,16 +471,17 @@ int stft_host(kofft_hip_ctx *ctx, const float *signal, size_t len, const float *
 // The three arrays of a host-pointer ISTFT over `rows` signals (1: istft / inverse_parallel / inverse_frame): the frames go up and, unless
 // mode 2 (inverse_parallel clones each frame, stft.rs:310: the caller's stay untouched), come back inverse-transformed; the output goes
 // up and comes back; the window-square sums only come back (mode 1) or stay on the device.  dev(d_frames, d_window, d_output, d_scratch).
+// bins: complex values per frame as the caller holds them -- win_len, or win_len / 2 + 1 for one-sided frames (mode 2).
 template <class Dev>
 int istft_stage(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, float *output,
-                size_t out_len, float *scratch, int mode, Dev dev)
+                size_t out_len, float *scratch, int mode, Dev dev, size_t bins)
 {
     if (!ctx || (frames && (!frames_data || !window)) || (out_len && (!output || (mode == 1 && !scratch)))) return KOFFT_ERR_NULL;
-    const size_t fr_bytes = rows * frames * win_len * 2 * sizeof(float), o_bytes = rows * out_len * sizeof(float);
+    const size_t fr_bytes = rows * frames * bins * 2 * sizeof(float), o_bytes = rows * out_len * sizeof(float);
     auto align = [](size_t b) { return (b + 255) & ~size_t(255); };
     // one frame (IstftStream, inverse_frame) or a short batch goes zero-copy
     const size_t total = align(fr_bytes) + 2 * align(o_bytes) + win_len * sizeof(float) + 256;
-    const HostArray<float> a[3] = {{frames_data, mode == 2 ? nullptr : frames_data, frames * win_len * 2},
+    const HostArray<float> a[3] = {{frames_data, mode == 2 ? nullptr : frames_data, frames * bins * 2},
                                    {output, output, out_len},
                                    {nullptr, mode == 1 ? scratch : nullptr, out_len}};
     return stage_host<float>(ctx, rows, 3, a, window, win_len, total <= kZeroCopyMax, false,
@@ -497,7 +498,7 @@ int istft_host(kofft_hip_ctx *ctx, float *frames_data, size_t frames, const floa
     return istft_stage(ctx, frames_data, 1, frames, window, win_len, output, out_len, scratch, mode,
                        [&](float *d_frames, const float *d_win, float *d_out, float *d_scr) {
                            return istft_dev(ctx, d_frames, frames, d_win, win_len, hop, d_out, out_len, d_scr, out_len, mode, start0);
-                       });
+                       }, win_len);
 }
 
 int istft_rows_host(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, size_t hop,
@@ -508,7 +509,7 @@ int istft_rows_host(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t 
     return istft_stage(ctx, frames_data, rows, frames, window, win_len, output, out_len, scratch, mode,
                        [&](float *d_frames, const float *d_win, float *d_out, float *d_scr) {
                            return istft_rows_dev(ctx, d_frames, rows, frames, d_win, win_len, hop, d_out, out_len, d_scr, out_len, mode, false);
-                       });
+                       }, win_len);
 }
 
 template <typename T>
@@ -1223,6 +1224,45 @@ int kofft_hip_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *frames_da
                                       size_t win_len, size_t hop, float *output, size_t out_len)
 {
     return istft_rows_host(ctx, const_cast<float *>(frames_data), rows, frames, window, win_len, hop, output, out_len, nullptr, out_len, 2);
+}
+
+// ---- one-sided STFT over rows of signals and its inverse (k_stft_onesided.hip) ----------------------------------------
+int kofft_hip_dev_stft_onesided_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                    const float *d_window, size_t win_len, size_t hop, float *d_out, size_t frames)
+{
+    return stft_onesided_dev(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, d_out, frames);
+}
+
+int kofft_hip_stft_onesided_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                                size_t win_len, size_t hop, float *out, size_t frames)
+{
+    const int crc = stft_onesided_check(true, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (!ctx || (!signal && len) || !window || !out) return KOFFT_ERR_NULL;
+    std::vector<float> packed;
+    const float *src = pack_rows(signal, rows, len, row_stride, packed);
+    return rows_host<float>(ctx, src, out, rows, len, frames * (win_len / 2 + 1) * 2, window, win_len, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return stft_onesided_dev(ctx, d_in, nb, len, len, d_win, win_len, hop, d_out, frames);
+                            });
+}
+
+int kofft_hip_dev_istft_onesided_f32(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window,
+                                     size_t win_len, size_t hop, float *d_output, size_t out_len)
+{
+    return istft_onesided_dev(ctx, d_half, rows, frames, d_window, win_len, hop, d_output, out_len);
+}
+
+int kofft_hip_istft_onesided_f32(kofft_hip_ctx *ctx, const float *half, size_t rows, size_t frames, const float *window, size_t win_len,
+                                 size_t hop, float *output, size_t out_len)
+{
+    const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, out_len, 2);
+    if (crc || rows == 0) return crc;
+    // mode 2: the staged frames go up and do not come back
+    return istft_stage(ctx, const_cast<float *>(half), rows, frames, window, win_len, output, out_len, nullptr, 2,
+                       [&](float *d_half, const float *d_win, float *d_out, float *) {
+                           return istft_onesided_dev(ctx, d_half, rows, frames, d_win, win_len, hop, d_out, out_len);
+                       }, win_len / 2 + 1);
 }
 
 int kofft_hip_fftnd_c32(kofft_hip_ctx *ctx, float *data, size_t depth, size_t rows, size_t cols, int inverse)
