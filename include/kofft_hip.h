@@ -347,6 +347,50 @@ int kofft_hip_czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, fl
  * nfreq > 1024 -> KOFFT_ERR_UNSUPPORTED; a null pointer -> KOFFT_ERR_NULL. */
 int kofft_hip_goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff);
 
+/* ---- Hartley transform ------------------------------------------------------------------
+ * hartley::dht / batch / multi_channel (hartley.rs:12-57), f32 only like the reference, on `batch` contiguous rows of n reals in and
+ * out:  out[b][k] = sum_i x[b][i] * H[i][k], the sum seeded with +0, i ascending, one f32 multiply and one f32 add per term, never
+ * fused.  H[i][k] = cosf(a) + sinf(a) (one f32 add), a = factor * ((i * k) as f32), factor = (2.0 * PI) / (n as f32), where cosf and
+ * sinf are the libm crate's (hartley.rs:8), not glibc's: kofft_amd/csrc/libm_trigf.hip.h restates them.  H is symmetric and depends
+ * on n only; a context keeps the n x n table of every length it has seen (64 MiB at n = 4096) until kofft_hip_destroy.
+ * Checks, in this order and before the context or the device is touched: batch == 0 -> KOFFT_OK; n == 0 -> KOFFT_OK (an empty
+ * result, as the reference); n > 4096 -> KOFFT_ERR_UNSUPPORTED (the bound of the table); a null pointer or context -> KOFFT_ERR_NULL;
+ * (device pointers) in and out overlap -> INVALID_VALUE.  The host form allows in == out (hartley::batch works in place).
+ * kofft_hip_dev_dht_f32: device pointers, asynchronous on the context's stream -- the first call of a length included: the table is
+ * built by a kernel on that stream.  (Named kofft_hip_dev_* for the reason given at the chirp-Z entries; its guard-band cases live
+ * in tests/test_gpu_hartley.py.)  The sums run on the kernels of the direct DCT / DST by the same rule (kofft_hip_set_direct_tiled
+ * applies).  kofft_hip_set_dht_table_device(ctx, 0): tables of lengths not seen yet are built on the host (up to 16 threads) and
+ * uploaded instead -- the same bytes (A/B measurements and tests); on: the default. */
+int kofft_hip_dht_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_dev_dht_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_set_dht_table_device(kofft_hip_ctx *ctx, int on);
+/* Host only (tests): H = n * n floats, H[i * n + k] as above.  n == 0 -> KOFFT_OK; n > 4096 -> KOFFT_ERR_UNSUPPORTED; H null ->
+ * KOFFT_ERR_NULL. */
+int kofft_hip_dht_table_f32(size_t n, float *H);
+/* Host only (tests): the restated cosf / sinf of `count` arguments.  count == 0 -> KOFFT_OK; a null pointer -> KOFFT_ERR_NULL; any
+ * finite |x| >= 0x4dc90fdb (about 4.2e8; the crate's rem_pio2_large is not restated) -> KOFFT_ERR_UNSUPPORTED, nothing written. */
+int kofft_hip_libm_trigf(const float *x, size_t count, float *cos_out, float *sin_out);
+
+/* ---- windows beyond Hann, host only like kofft_hip_hann_f32 -----------------------------------
+ * window::hamming / blackman / kaiser (window.rs:31-61) and window_more::tukey / bartlett / bohman / nuttall (window_more.rs:13-64):
+ * out = len floats, every expression in f32 in Rust's parse order (`2.0 * PI * i as f32 / len as f32` is ((2 PI) * i) / len).
+ * `.cos()` is glibc's cosf (hamming, blackman, tukey); cosf / sinf imported from the libm crate are the restated ones (bohman,
+ * nuttall).  param: kaiser's beta, tukey's alpha, ignored by the rest.  Checks, in this order: kind not one of the constants ->
+ * INVALID_VALUE; len == 0 -> KOFFT_OK, but EMPTY_INPUT for kaiser (the reference computes `len - 1` in usize: it underflows); out
+ * null -> KOFFT_ERR_NULL.  Edge cases, as the reference:
+ *   len == 1  hamming 0.08 (0.54 - 0.46), blackman 0.42 - 0.5 + 0.08, tukey 1.0; bartlett, bohman, nuttall and kaiser divide zero by zero: NaN.
+ *   kaiser    bessel0 is the 19-term series as written; sqrtf the correctly rounded root.
+ *   tukey     alpha is clamped to [0, 1] by f32::clamp, which keeps a NaN; edge = floorf(alpha * (len - 1) / 2) `as usize`, a
+ *             saturating cast (NaN and negatives give 0): alpha <= 0 and a NaN alpha give len ones. */
+#define KOFFT_WINDOW_HAMMING 0
+#define KOFFT_WINDOW_BLACKMAN 1
+#define KOFFT_WINDOW_KAISER 2
+#define KOFFT_WINDOW_TUKEY 3
+#define KOFFT_WINDOW_BARTLETT 4
+#define KOFFT_WINDOW_BOHMAN 5
+#define KOFFT_WINDOW_NUTTALL 6
+int kofft_hip_window_f32(int kind, size_t len, float param, float *out);
+
 /* ---- wavelets -------------------------------------------------------------------
  * wavelet::* (wavelet.rs:12-117, 154-567), f32 only like the reference.  The wavelet ids: */
 #define KOFFT_WAVELET_HAAR 0

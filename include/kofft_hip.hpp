@@ -20,6 +20,8 @@
 //   kofft::HipFftImpl<float>::dst_direct         dst::dst1..dst4, dst.rs:89-146
 //   kofft::HipFftImpl<float>::dwt / idwt         wavelet::<name>_forward / _inverse, wavelet.rs:12-33, 154-535
 //   kofft::HipFftImpl<float>::dwt_multi / idwt_multi   wavelet::multi_level_forward / _inverse, wavelet.rs:54-84
+//   kofft::HipFftImpl<float>::dht                hartley::dht / batch, hartley.rs:12-57
+//   kofft::hamming / blackman / kaiser / tukey / bartlett / bohman / nuttall   window.rs:31-61, window_more.rs:13-64
 //
 // Result<(), FftError> becomes kofft::Result (is_ok / is_err / unwrap / unwrap_err).  A negative C-ABI status
 // (HIP failure, unsupported length) has no FftError variant: it throws kofft::DeviceError, the C++ analogue of
@@ -357,6 +359,26 @@ public:
         if (n == 0) return type == 3 ? Result::Err(FftError::EmptyInput) : Result::Ok();
         return st(fn(ctx_, type, input.data(), output.data(), n, batch));
     }
+
+    // hartley::dht (hartley.rs:12-27) on batch rows of input.size() / batch reals, bit for bit the reference's sums with the libm
+    // crate's cosf / sinf.  MismatchedLengths for rows that do not divide the input or an output of another size; n == 0 is an empty
+    // result; n > 4096 throws DeviceError (the table bound).  input and output may be the same vector (hartley::batch is in place).
+    Result dht(const std::vector<float> &input, std::vector<float> &output, size_t batch = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the Hartley transform is f32-only (hartley.rs)");
+        if (batch == 0 || input.size() % batch != 0 || output.size() != input.size()) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = input.size() / batch;
+        if (n == 0) return Result::Ok();
+        return st(kofft_hip_dht_f32(ctx_, input.data(), output.data(), n, batch));
+    }
+    // ... on device memory, asynchronous on the context's stream; the two must not overlap (InvalidValue)
+    Result dht_dev(const float *d_in, float *d_out, size_t n, size_t batch) const
+    {
+        static_assert(std::is_same<T, float>::value, "the Hartley transform is f32-only (hartley.rs)");
+        return st(kofft_hip_dev_dht_f32(ctx_, d_in, d_out, n, batch));
+    }
+    // true (the default): the table of a new length is built by a kernel; false: on the host and uploaded (the same bytes)
+    Result set_dht_table_device(bool on) const { return st(kofft_hip_set_dht_table_device(ctx_, on ? 1 : 0)); }
 
     // wavelet::<name>_forward (wavelet.rs:12-21, 154-493; wavelet = KOFFT_WAVELET_HAAR .. COIF1), f32 only like the reference: `batch`
     // contiguous rows of len samples in; approx and detail become batch rows of len / 2.  InvalidValue for an unknown wavelet;
@@ -742,6 +764,22 @@ inline std::vector<float> hann(size_t len)  // window.rs:24-28
     kofft_hip_hann_f32(len, w.data());
     return w;
 }
+// window::hamming / blackman / kaiser (window.rs:31-61), window_more::tukey / bartlett / bohman / nuttall (window_more.rs:13-64):
+// kind = KOFFT_WINDOW_*, param = kaiser's beta or tukey's alpha.  An unknown kind and kaiser of length 0 (the reference underflows
+// `len - 1` there) throw std::invalid_argument.
+inline std::vector<float> window(int kind, size_t len, float param = 0.0f)
+{
+    std::vector<float> w(len);
+    if (kofft_hip_window_f32(kind, len, param, w.data()) != 0) throw std::invalid_argument("kofft::window: unknown kind, or kaiser of length 0");
+    return w;
+}
+inline std::vector<float> hamming(size_t len) { return window(KOFFT_WINDOW_HAMMING, len); }
+inline std::vector<float> blackman(size_t len) { return window(KOFFT_WINDOW_BLACKMAN, len); }
+inline std::vector<float> kaiser(size_t len, float beta) { return window(KOFFT_WINDOW_KAISER, len, beta); }
+inline std::vector<float> tukey(size_t len, float alpha) { return window(KOFFT_WINDOW_TUKEY, len, alpha); }
+inline std::vector<float> bartlett(size_t len) { return window(KOFFT_WINDOW_BARTLETT, len); }
+inline std::vector<float> bohman(size_t len) { return window(KOFFT_WINDOW_BOHMAN, len); }
+inline std::vector<float> nuttall(size_t len) { return window(KOFFT_WINDOW_NUTTALL, len); }
 
 // stft::stft (stft.rs:76-105): output frames are resized to the window length and overwritten
 inline Result stft(const std::vector<float> &signal, const std::vector<float> &window, size_t hop_size,

@@ -54,6 +54,9 @@ extern "C" {
     fn kofft_hip_goertzel_f32(ctx: *mut KofftHipCtx, input: *const f32, out: *mut f32, n: usize, batch: usize, sample_rate: f32,
                               target_freqs: *const f32, nfreq: usize) -> c_int;
     fn kofft_hip_set_czt_route(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
+    fn kofft_hip_dht_f32(ctx: *mut KofftHipCtx, input: *const f32, out: *mut f32, n: usize, batch: usize) -> c_int;
+    fn kofft_hip_set_dht_table_device(ctx: *mut KofftHipCtx, on: c_int) -> c_int;
+    fn kofft_hip_window_f32(kind: c_int, len: usize, param: f32, out: *mut f32) -> c_int;
     fn kofft_hip_fftnd_c32(ctx: *mut KofftHipCtx, data: *mut f32, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     fn kofft_hip_fftnd_c64(ctx: *mut KofftHipCtx, data: *mut f64, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     // multi-GPU: one process, one context per device, optional RCCL all-gather (include/kofft_hip.h, "multi-GPU")
@@ -402,6 +405,75 @@ impl HipFftImpl<f32> {
             kofft_hip_goertzel_f32(self.ctx, input.as_ptr(), out.as_mut_ptr(), n, batch, sample_rate, target_freqs.as_ptr(), target_freqs.len())
         })
     }
+}
+
+impl HipFftImpl<f32> {
+    /// `hartley::dht` (kofft hartley.rs:12-27) of every row of `n` reals in `input`, into `out` (the same length): the reference's
+    /// sums bit for bit, the libm crate's cosf / sinf in the table.  `n == 0` is an empty result; `n > 4096` panics (the table bound).
+    pub fn dht_batch(&self, input: &[f32], n: usize, out: &mut [f32]) -> Result<(), FftError> {
+        if out.len() != input.len() || (n != 0 && input.len() % n != 0) || (n == 0 && !input.is_empty()) { return Err(FftError::MismatchedLengths); }
+        if n == 0 { return Ok(()); }
+        status(self.ctx, unsafe { kofft_hip_dht_f32(self.ctx, input.as_ptr(), out.as_mut_ptr(), n, input.len() / n) })
+    }
+
+    /// `true` (the default): the Hartley table of a new length is built by a kernel; `false`: on the host and uploaded (the same bytes).
+    pub fn set_dht_table_device(&self, on: bool) -> Result<(), FftError> {
+        status(self.ctx, unsafe { kofft_hip_set_dht_table_device(self.ctx, on as c_int) })
+    }
+}
+
+/// `kofft::hartley` (hartley.rs:12-57) on the device: the reference's three functions with a context in front.
+pub mod hartley {
+    use super::HipFftImpl;
+
+    /// `hartley::dht`.
+    pub fn dht(fft: &HipFftImpl<f32>, input: &[f32]) -> Vec<f32> {
+        let mut out = vec![0.0f32; input.len()];
+        fft.dht_batch(input, input.len(), &mut out).expect("one row: the lengths agree");
+        out
+    }
+
+    /// `hartley::batch`: every row replaced by its transform; rows of one length go to the device in one call.
+    pub fn batch(fft: &HipFftImpl<f32>, batches: &mut [Vec<f32>]) {
+        let mut lens: Vec<usize> = batches.iter().map(|b| b.len()).filter(|&n| n != 0).collect();
+        lens.sort_unstable();
+        lens.dedup();
+        for n in lens {
+            let idx: Vec<usize> = (0..batches.len()).filter(|&j| batches[j].len() == n).collect();
+            let flat: Vec<f32> = idx.iter().flat_map(|&j| batches[j].iter().copied()).collect();
+            let mut out = vec![0.0f32; flat.len()];
+            fft.dht_batch(&flat, n, &mut out).expect("rows of one length");
+            for (t, &j) in idx.iter().enumerate() {
+                batches[j].copy_from_slice(&out[t * n..(t + 1) * n]);
+            }
+        }
+    }
+
+    /// `hartley::multi_channel`: `batch`.
+    pub fn multi_channel(fft: &HipFftImpl<f32>, channels: &mut [Vec<f32>]) {
+        batch(fft, channels)
+    }
+}
+
+/// `kofft::window` / `kofft::window_more` beyond `hann` (window.rs:31-61, window_more.rs:13-64), generated by the library's host
+/// recipes bit for bit; no device is involved.
+pub mod window {
+    use core::ffi::c_int;
+
+    fn make(kind: c_int, len: usize, param: f32) -> Vec<f32> {
+        let mut w = vec![0.0f32; len];
+        let rc = unsafe { super::kofft_hip_window_f32(kind, len, param, w.as_mut_ptr()) };
+        assert_eq!(rc, 0, "kofft_hip_window_f32 status {rc}");
+        w
+    }
+    pub fn hamming(len: usize) -> Vec<f32> { make(0, len, 0.0) }
+    pub fn blackman(len: usize) -> Vec<f32> { make(1, len, 0.0) }
+    /// Panics at `len == 0`, where the reference underflows `len - 1`.
+    pub fn kaiser(len: usize, beta: f32) -> Vec<f32> { make(2, len, beta) }
+    pub fn tukey(len: usize, alpha: f32) -> Vec<f32> { make(3, len, alpha) }
+    pub fn bartlett(len: usize) -> Vec<f32> { make(4, len, 0.0) }
+    pub fn bohman(len: usize) -> Vec<f32> { make(5, len, 0.0) }
+    pub fn nuttall(len: usize) -> Vec<f32> { make(6, len, 0.0) }
 }
 
 /// `stft::parallel` (kofft stft.rs:232-263) across `ngpu` devices of this process: frames are the parallel unit, device

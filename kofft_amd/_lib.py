@@ -98,6 +98,12 @@ SIGNATURES = {
     "kofft_hip_dev_goertzel_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_float, C.c_void_p, _sz]),
     "kofft_hip_set_czt_route": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_czt_table_f32": (C.c_int, [_sz, _sz, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "kofft_hip_dht_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_dht_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_dht_table_device": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_dht_table_f32": (C.c_int, [_sz, C.c_void_p]),
+    "kofft_hip_libm_trigf": (C.c_int, [C.c_void_p, _sz, C.c_void_p, C.c_void_p]),
+    "kofft_hip_window_f32": (C.c_int, [C.c_int, _sz, C.c_float, C.c_void_p]),
     "kofft_hip_goertzel_coeff_f32": (C.c_int, [_sz, C.c_float, C.c_void_p, _sz, C.c_void_p]),
     "kofft_hip_dwt_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_dwt_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _sz]),

@@ -51,6 +51,7 @@ struct kofft_hip_ctx {
     bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
+    bool dht_table_device = true; // kofft_hip_set_dht_table_device(ctx, 0): the Hartley table of a new length built on the host and uploaded instead of by dht_table_kernel (the same bytes; A/B, tests)
     int wavelet_fused = 1;    // kofft_hip_set_wavelet_fused: 1 the measured choice (wavelet_use_fused), 0 every multi-level call level by level, 2 the fused kernels wherever they fit (A/B, tests)
     int czt_route = 0;        // kofft_hip_set_czt_route: 0 by batch and by whether the table is there (czt_use_table), 1 every call on czt_recur_kernel<CZT_SUM>, 2 every call through a table and the direct kernels (A/B, tests)
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
@@ -89,7 +90,7 @@ struct kofft_hip_ctx {
     std::string last_error;
     // planner caches: (kind, n) -> device table.  kind 0/1 = FftPlanner twiddles f32/f64,
     // 2/3 = RfftPlanner post-pass table f32/f64, 13 = DctPlanner (cos, sin) table f32, 20 .. 27 = the direct DCT / DST tables
-    // (direct_impl.hip.h).
+    // (direct_impl.hip.h), 28 = the Hartley table (hartley_impl.hip.h).
     std::map<std::pair<int, size_t>, void *> tables;
     // chirp-Z tables: most recently used first, at most kSpectralSlots; an evicted slot is freed after the stream is synchronised.
     // goertzel_coeff: the device-pointer Goertzel's coefficients (kGoertzelMaxFreqs floats), goertzel_last what it holds.
@@ -842,6 +843,9 @@ int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float
 // k_direct_f32.hip: the +0-seeded sums out[b][k] = sum_i x[b][i] * table[i][k], i < n, k < nk, on direct_tiled_kernel<DIR_ZERO> /
 // direct_simple_kernel<DIR_ZERO> (direct_use_tiled(ctx, nk, batch)); table: n rows of direct_ldc(nk) floats
 int direct_zero_sums(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *table, size_t n, size_t nk, size_t batch);
+// k_hartley_f32.hip: hartley::dht (hartley_impl.hip.h), n <= kDirectMaxN; dht_check: the argument checks alone
+int dht_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
+int dht_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
 // k_spectral_f32.hip: czt::czt_f32 and goertzel::goertzel_f32 (spectral_impl.hip.h); *_check: the argument checks alone
 constexpr size_t kCztMax = 4096;                       // the longest row and the most bins: the table is 128 MiB there
 constexpr size_t kGoertzelMaxLen = size_t(1) << 26;

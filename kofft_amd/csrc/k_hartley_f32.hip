@@ -1,0 +1,78 @@
+// k_hartley_f32.hip -- hartley::dht (hartley.rs:12-57) on float rows: the table kernel (hartley_impl.hip.h), the table cache and the
+// hand-over to the kernels of the direct DCT / DST.
+#include "hartley_impl.hip.h"
+
+namespace kofft {
+namespace host {
+
+// Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
+int dht_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return KOFFT_OK;  // hartley.rs:13-14: an empty result
+    if (n > kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !in || !out) return KOFFT_ERR_NULL;
+    return KOFFT_OK;
+}
+
+// The n x direct_ldc(n) table, built at the first call of a (context, n) and kept until the context is destroyed: on the device by
+// dht_table_kernel (stream-ordered before the sums that read it; a later kofft_hip_set_stream orders the new stream after it), or
+// on the host and uploaded (kofft_hip_set_dht_table_device(ctx, 0)).
+static int get_dht_table(kofft_hip_ctx *ctx, size_t n, const float **out)
+{
+    const auto key = std::make_pair(kDhtTableKind, n);
+    auto it = ctx->tables.find(key);
+    if (it != ctx->tables.end()) {
+        *out = static_cast<const float *>(it->second);
+        return KOFFT_OK;
+    }
+    const size_t ldc = direct_ldc(n);
+    void *d = nullptr;
+    if (ctx->dht_table_device) {
+        KOFFT_HIP_TRY(ctx, hipMalloc(&d, n * ldc * sizeof(float)));
+        const float factor = (2.0f * 3.14159265358979323846f) / (float)n;  // hartley.rs:15
+        const dim3 grid((unsigned)((ldc + 4 * DHT_BLOCK - 1) / (4 * DHT_BLOCK)), (unsigned)n);
+        hipLaunchKernelGGL(dht_table_kernel, grid, dim3(DHT_BLOCK), 0, ctx->stream, static_cast<float *>(d), (int)n, (int)ldc, factor);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            ctx->last_error = std::string("dht table launch: ") + hipGetErrorString(e);
+            return KOFFT_ERR_HIP;
+        }
+    } else {
+        std::vector<float> host;
+        try {
+            host.resize(n * ldc);
+        } catch (const std::bad_alloc &) {
+            return KOFFT_ERR_ALLOC;
+        }
+        kofft_tables::dht_table_f32(n, ldc, host.data());
+        KOFFT_HIP_TRY(ctx, hipMalloc(&d, host.size() * sizeof(float)));
+        // synchronous copy: a table is built once per (context, n)
+        const hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            ctx->last_error = std::string("dht table upload: ") + hipGetErrorString(e);
+            return KOFFT_ERR_HIP;
+        }
+    }
+    ctx->tables[key] = d;
+    *out = static_cast<const float *>(d);
+    return KOFFT_OK;
+}
+
+int dht_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    int rc = dht_check(n, batch, d_in, d_out, ctx);
+    if (rc || batch == 0 || n == 0) return rc;
+    // tiles of one row run in different workgroups: an output that overlaps the input would be read after it is written
+    if (d_in < d_out + batch * n && d_out < d_in + batch * n) return KOFFT_ERR_INVALID_VALUE;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const float *table = nullptr;
+    rc = get_dht_table(ctx, n, &table);
+    if (rc) return rc;
+    return direct_zero_sums(ctx, d_in, d_out, table, n, n, batch);
+}
+
+}  // namespace host
+}  // namespace kofft

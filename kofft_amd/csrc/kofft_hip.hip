@@ -360,6 +360,16 @@ int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return direct_dev(ctx, family, type, d_in, d_out, n, rows); });
 }
 
+// hartley::dht on host rows of n reals in and out (k_hartley_f32.hip)
+int dht_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
+{
+    int rc = dht_check(n, batch, in, out, ctx);
+    if (rc || batch == 0 || n == 0) return rc;
+    // No pipeline, like direct_host: in == out works (hartley::batch is in place).
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, false,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return dht_dev(ctx, d_in, d_out, n, rows); });
+}
+
 // czt::czt_f32 on host rows: n reals in, m complex out (k_spectral_f32.hip)
 int czt_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch)
 {
@@ -1049,6 +1059,39 @@ int kofft_hip_dst_direct_f32(kofft_hip_ctx *ctx, int type, const float *in, floa
 int kofft_hip_dst_direct_f32_dev(kofft_hip_ctx *ctx, int type, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     return direct_dev(ctx, 1, type, d_in, d_out, n, batch);
+}
+int kofft_hip_dht_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch) { return dht_host(ctx, in, out, n, batch); }
+int kofft_hip_dev_dht_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    return dht_dev(ctx, d_in, d_out, n, batch);
+}
+int kofft_hip_set_dht_table_device(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->dht_table_device = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_dht_table_f32(size_t n, float *H)
+{
+    if (n == 0) return KOFFT_OK;
+    if (n > kofft::host::kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!H) return KOFFT_ERR_NULL;
+    kofft_tables::dht_table_f32(n, n, H);
+    return KOFFT_OK;
+}
+int kofft_hip_libm_trigf(const float *x, size_t count, float *cos_out, float *sin_out)
+{
+    if (count == 0) return KOFFT_OK;
+    if (!x || !cos_out || !sin_out) return KOFFT_ERR_NULL;
+    return kofft_tables::libm_trigf(x, count, cos_out, sin_out) ? KOFFT_OK : KOFFT_ERR_UNSUPPORTED;
+}
+int kofft_hip_window_f32(int kind, size_t len, float param, float *out)
+{
+    if (kind < 0 || kind >= kofft_tables::kWindowKinds) return KOFFT_ERR_INVALID_VALUE;
+    if (len == 0) return kind == KOFFT_WINDOW_KAISER ? KOFFT_ERR_EMPTY_INPUT : KOFFT_OK;
+    if (!out) return KOFFT_ERR_NULL;
+    kofft_tables::window_f32(kind, len, param, out);
+    return KOFFT_OK;
 }
 int kofft_hip_rfft_f64(kofft_hip_ctx *ctx, const double *in, double *out, const double *window, size_t n,
                        size_t batch)

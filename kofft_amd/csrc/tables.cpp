@@ -318,3 +318,137 @@ void goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, 
 }
 
 }  // namespace kofft_tables
+
+// ---- hartley::dht and the windows beyond Hann ---------------------------------------------------------------------------------------
+#include "libm_trigf.hip.h"
+
+namespace {
+void dht_rows(size_t n, size_t ldc, float *h, size_t r0, size_t r1)
+{
+    const float factor = (2.0f * Num<float>::pi()) / (float)n;  // hartley.rs:15
+    for (size_t i = r0; i < r1; ++i) {
+        float *row = h + i * ldc;
+        for (size_t k = 0; k < n; ++k) {
+            const float angle = factor * (float)(i * k);  // hartley.rs:19
+            row[k] = kofft::libm_cosf(angle) + kofft::libm_sinf(angle);
+        }
+        std::fill(row + n, row + ldc, 0.0f);
+    }
+}
+
+// window.rs:9-21
+float bessel0(float x)
+{
+    float sum = 1.0f;
+    const float y = x * x / 4.0f;
+    float t = y;
+    float k = 1.0f;
+    for (int n = 1; n < 20; ++n) {
+        k *= (float)n;
+        sum += t / (k * k);
+        t *= y;
+    }
+    return sum;
+}
+
+// Rust's `as usize` of an f32: NaN and negatives 0, beyond the range usize::MAX
+size_t saturating_usize(float v)
+{
+    if (!(v > 0.0f)) return 0;
+    if (v >= 18446744073709551616.0f) return ~size_t(0);
+    return (size_t)v;
+}
+}  // namespace
+
+namespace kofft_tables {
+bool libm_trigf(const float *x, size_t count, float *cos_out, float *sin_out)
+{
+    for (size_t j = 0; j < count; ++j)
+        if (!kofft::libm_trigf_in_range(x[j])) return false;
+    for (size_t j = 0; j < count; ++j) {
+        if (cos_out) cos_out[j] = kofft::libm_cosf(x[j]);
+        if (sin_out) sin_out[j] = kofft::libm_sinf(x[j]);
+    }
+    return true;
+}
+
+void dht_table_f32(size_t n, size_t ldc, float *h)
+{
+    // the thread rule of direct_table_f32
+    size_t threads = std::min<size_t>({size_t(16), std::max<size_t>(1, std::thread::hardware_concurrency()), std::max<size_t>(1, n * n >> 16)});
+    if (threads <= 1) {
+        dht_rows(n, ldc, h, 0, n);
+        return;
+    }
+    std::vector<std::thread> pool;
+    const size_t per = (n + threads - 1) / threads;
+    for (size_t t = 0; t < threads; ++t) {
+        const size_t r0 = t * per, r1 = std::min(n, r0 + per);
+        if (r0 >= r1) break;
+        pool.emplace_back(dht_rows, n, ldc, h, r0, r1);
+    }
+    for (auto &th : pool) th.join();
+}
+
+void window_f32(int kind, size_t len, float param, float *out)
+{
+    const float pi = Num<float>::pi();  // core::f32::consts::PI
+    const float lenf = (float)len;
+    switch (kind) {
+    case 0:  // hamming, window.rs:31-35: glibc cosf
+        for (size_t i = 0; i < len; ++i) out[i] = 0.54f - 0.46f * cosf(2.0f * pi * (float)i / lenf);
+        break;
+    case 1:  // blackman, window.rs:38-48
+        for (size_t i = 0; i < len; ++i) {
+            const float x = (float)i / lenf;
+            out[i] = 0.42f - 0.5f * cosf(2.0f * pi * x) + 0.08f * cosf(4.0f * pi * x);
+        }
+        break;
+    case 2: {  // kaiser, window.rs:52-61; the crate's sqrtf is the correctly rounded root (NaN below zero)
+        const float denom = bessel0(param);
+        const float m = (float)(len - 1) / 2.0f;
+        for (size_t i = 0; i < len; ++i) {
+            const float r = ((float)i - m) / m;
+            out[i] = bessel0(param * sqrtf(1.0f - r * r)) / denom;
+        }
+        break;
+    }
+    case 3: {  // tukey, window_more.rs:13-28: f32::clamp keeps a NaN, `as usize` saturates, .cos() is glibc's
+        float alpha = param;
+        if (alpha < 0.0f) alpha = 0.0f;
+        if (alpha > 1.0f) alpha = 1.0f;
+        const size_t edge = saturating_usize(floorf(alpha * (lenf - 1.0f) / 2.0f));
+        for (size_t n = 0; n < len; ++n) {
+            if (n < edge) {
+                out[n] = 0.5f * (1.0f + cosf(pi * (2.0f * (float)n / (alpha * (lenf - 1.0f)) - 1.0f)));
+            } else if (n < len - edge) {
+                out[n] = 1.0f;
+            } else {
+                out[n] = 0.5f * (1.0f + cosf(pi * (2.0f * (float)n / (alpha * (lenf - 1.0f)) - 2.0f / alpha + 1.0f)));
+            }
+        }
+        break;
+    }
+    case 4:  // bartlett, window_more.rs:31-39
+        for (size_t i = 0; i < len; ++i) {
+            const float x = ((float)i - (lenf - 1.0f) / 2.0f) / ((lenf - 1.0f) / 2.0f);
+            out[i] = 1.0f - fabsf(x);
+        }
+        break;
+    case 5:  // bohman, window_more.rs:42-50: the crate's cosf / sinf
+        for (size_t i = 0; i < len; ++i) {
+            const float x = ((float)i / (lenf - 1.0f)) - 0.5f;
+            out[i] = (1.0f - fabsf(x)) * kofft::libm_cosf(pi * x) + 1.0f / pi * kofft::libm_sinf(pi * x);
+        }
+        break;
+    default:  // nuttall, window_more.rs:53-64: the crate's cosf
+        for (size_t n = 0; n < len; ++n) {
+            const float x = 2.0f * pi * (float)n / (lenf - 1.0f);
+            out[n] = 0.355768f - 0.487396f * kofft::libm_cosf(x) + 0.144232f * kofft::libm_cosf(2.0f * x) -
+                     0.012604f * kofft::libm_cosf(3.0f * x);
+        }
+        break;
+    }
+}
+
+}  // namespace kofft_tables

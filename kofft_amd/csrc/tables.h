@@ -34,4 +34,16 @@ void czt_apow_f32(size_t n, float ar, float ai, float *apow);
 void czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, float ai, size_t ldc, float *c);
 // goertzel::goertzel_f32 (goertzel.rs:23-26): coeff[j] = 2 * cosf(((2 * PI) * floorf((f_j * n) / rate)) / n), n as f32, glibc cosf
 void goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff);
+// The libm crate's cosf / sinf (libm_trigf.hip.h compiled for the host) of count arguments; either output may be null.  False, and
+// nothing written, if an argument needs rem_pio2_large (a finite |x| >= 0x4dc90fdb), which the header does not restate.
+bool libm_trigf(const float *x, size_t count, float *cos_out, float *sin_out);
+// hartley::dht (hartley.rs:12-27): H[i][k] = cosf(a) + sinf(a), a = factor * ((i * k) as f32), factor = (2.0 * PI) / n as f32, the
+// crate's cosf / sinf and one f32 add; n rows of ldc >= n floats, columns n .. ldc - 1 are +0.  Built on up to 16 host threads; the
+// host restatement of what dht_table_kernel (hartley_impl.hip.h) builds on the device.
+void dht_table_f32(size_t n, size_t ldc, float *h);
+// window::hamming / blackman / kaiser (window.rs:31-61) and window_more::tukey / bartlett / bohman / nuttall (window_more.rs:13-64),
+// kind = KOFFT_WINDOW_* of include/kofft_hip.h (0 .. 6), all arithmetic in f32 in Rust's parse order; param: kaiser's beta, tukey's
+// alpha, ignored otherwise.  The caller has checked the kind and, for kaiser, len != 0.
+void window_f32(int kind, size_t len, float param, float *out);
+constexpr int kWindowKinds = 7;
 }  // namespace kofft_tables
