@@ -46,10 +46,8 @@ __global__ __launch_bounds__(256) void cepstrum_real_kernel(const cpx<float> *__
 
 inline int cepstrum_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
-    // rows per chunk as dct2_composed_dev: 512 MiB of scratch at most
-    size_t chunk = (size_t(512) << 20) / (n * sizeof(cpx<float>));
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    // rows per chunk as dct2_composed_dev: scratch_chunk_bytes of scratch at most
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(cpx<float>), batch);
     int rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<float>));
     if (rc) return rc;
     float *zf = static_cast<float *>(ctx->real_tmp);

@@ -226,9 +226,7 @@ int fft_axis2_core(kofft_hip_ctx *ctx, cpx<T> *data, int LT, int I, size_t block
     const cpx<T> *tw = nullptr;
     int rc = get_table<T>(ctx, Kind<T>::tw, len, &tw);
     if (rc) return rc;
-    size_t chunk = (size_t(512) << 20) / block_bytes;
-    if (chunk < 1) chunk = 1;
-    if (chunk > blocks) chunk = blocks;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, block_bytes, blocks);
     rc = ensure_real_tmp(ctx, chunk * block_bytes);
     if (rc) return rc;
     cpx<T> *mid = static_cast<cpx<T> *>(ctx->real_tmp);
@@ -871,9 +869,7 @@ int fft_bluestein_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, siz
         }
     }
     const size_t xf_bytes = m * sizeof(cpx<T>);
-    size_t chunk = (size_t(512) << 20) / xf_bytes;
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, xf_bytes, batch);
     if (ctx->blue_tmp_bytes < chunk * xf_bytes) {
         if (ctx->blue_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->blue_tmp));
         ctx->blue_tmp = nullptr;
@@ -1043,9 +1039,7 @@ int fft_radix4_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t
         return KOFFT_OK;
     }
     const size_t xf_bytes = n * sizeof(cpx<T>);
-    size_t chunk = (size_t(512) << 20) / xf_bytes;
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, xf_bytes, batch);
     const int prc = ensure_real_tmp(ctx, chunk * xf_bytes);
     if (prc) return prc;
     cpx<T> *tmp = static_cast<cpx<T> *>(ctx->real_tmp);

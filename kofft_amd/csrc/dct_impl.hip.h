@@ -213,10 +213,8 @@ inline int dct2_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out
     if (rc) return rc;
     rc = get_table<float>(ctx, Kind<float>::dct2, n, &cs);
     if (rc) return rc;
-    // rows per chunk as rfft_composed_dev, counted on the mirrored 2n-real rows: 512 MiB of scratch at most
-    size_t chunk = (size_t(512) << 20) / (2 * n * sizeof(float));
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    // rows per chunk as rfft_composed_dev, counted on the mirrored 2n-real rows: scratch_chunk_bytes of scratch at most
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, 2 * n * sizeof(float), batch);
     rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<float>));
     if (rc) return rc;
     float *z = static_cast<float *>(ctx->real_tmp);

@@ -24,6 +24,7 @@
 #include "fft_regfile.hip.h"
 #include "fft_split_wide.hip.h"
 #include "fft_wg.hip.h"
+#include "host_layout.h"
 #include "tables.h"
 
 // ---------------------------------------------------------------------------------
@@ -122,6 +123,7 @@ struct kofft_hip_ctx {
     size_t real_tmp_bytes = 0;
     void *rows_tmp = nullptr;  // istft_parallel_rows on device pointers: the inverse transforms of the caller's (const) frames
     size_t rows_tmp_bytes = 0;
+    size_t scratch_chunk_bytes = kofft::host::kScratchChunkDefaultBytes;  // KOFFT_HIP_SCRATCH_CHUNK_MB (1 .. 512): the scratch of one pass of every chunk loop but the factor path's (scratch_chunk_rows, host_layout.h); the N-D transpose panels take twice this
     size_t big_chunk_bytes = size_t(512) << 20;  // KOFFT_HIP_BIG_CHUNK_MB; measured on config 5 with the persistent factor kernels: 128 MiB 14.7 ms, 256 13.0, 512 12.1, 1024 12.5, 2048 13.1
 };
 
@@ -881,7 +883,7 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
 // transforms t0 .. t0 + nt of the flat index row * frames + frame, composed (any window length): framing product into dst, fft_dev in place
 int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
                        size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt);
-size_t composed_chunk(size_t win_len, size_t count);  // transforms per pass through at most 512 MiB of scratch
+size_t composed_chunk(const kofft_hip_ctx *ctx, size_t win_len, size_t count);  // transforms per pass through at most ctx->scratch_chunk_bytes of scratch
 // the input side of a StftRowsOf policy (row_stride: 0 when rows == 1)
 template <class IO>
 inline void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,

@@ -36,5 +36,37 @@ inline size_t host_chunk_rows(size_t batch, int parts)
     return (batch + p - 1) / p;
 }
 
+// ---- scratch chunks: the host routes that work through a scratch buffer take a large batch in pieces of at most `cap_bytes` of it ----
+// The default cap (kofft_hip_ctx::scratch_chunk_bytes) and the largest one KOFFT_HIP_SCRATCH_CHUNK_MB may set: the flat kernels' 32-bit
+// index math (a chunk holds at most 2^27 floats) and the 0x7fffffff block checks of the chunk loops rest on this ceiling.
+constexpr size_t kScratchChunkDefaultBytes = size_t(512) << 20;
+constexpr long kScratchChunkMaxMb = 512;
+
+// rows (transforms, blocks) per piece: cap_bytes / row_bytes, at least 1 (a row larger than the cap goes alone), at most `count`;
+// count == 0: 0, no piece at all.  Piece k covers rows [k * chunk, min((k + 1) * chunk, count)).
+inline size_t scratch_chunk_rows(size_t cap_bytes, size_t row_bytes, size_t count)
+{
+    if (count == 0) return 0;
+    size_t chunk = row_bytes ? cap_bytes / row_bytes : count;
+    if (chunk < 1) chunk = 1;
+    return chunk > count ? count : chunk;
+}
+
+// KOFFT_HIP_SCRATCH_CHUNK_MB: a whole number of MiB from 1 to kScratchChunkMaxMb, nothing before or after it.  true: *bytes is set;
+// false (empty, not a number, trailing text, out of range): *bytes is left alone.
+inline bool parse_scratch_chunk_mb(const char *text, size_t *bytes)
+{
+    if (!text || !*text) return false;
+    long mb = 0;
+    for (const char *p = text; *p; ++p) {
+        if (*p < '0' || *p > '9') return false;
+        mb = mb * 10 + (*p - '0');
+        if (mb > kScratchChunkMaxMb) return false;
+    }
+    if (mb < 1) return false;
+    *bytes = (size_t)mb << 20;
+    return true;
+}
+
 }  // namespace host
 }  // namespace kofft

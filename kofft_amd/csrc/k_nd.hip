@@ -27,7 +27,7 @@ int fft_axis_dev(kofft_hip_ctx *ctx, T *d_data, size_t len, size_t lines, size_t
     }
     if (stride == inner && (!fused_len_ok<T>(len) || (ctx->nd_transpose && len >= (size_t)ctx->nd_transpose_min && lines * len * sizeof(cpx<T>) >= (size_t(16) << 20)))) {
         const size_t outer = lines / inner;  // dense [len][inner] blocks, outer_stride apart
-        const size_t cap = size_t(1) << 30, col_bytes = len * sizeof(cpx<T>);
+        const size_t cap = 2 * ctx->scratch_chunk_bytes, col_bytes = len * sizeof(cpx<T>);
         size_t P = cap / col_bytes;
         if (P > inner) P = inner;
         if (P >= 32) P &= ~size_t(31);

@@ -41,9 +41,7 @@ __global__ __launch_bounds__(256) void mag_kernel(const cpx<float> *__restrict__
 static int stft_composed_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len,
                              size_t start0, size_t hop, float *d_out, size_t count)
 {
-    size_t chunk = (size_t(512) << 20) / (win_len * 8);
-    if (chunk < 1) chunk = 1;
-    if (chunk > count) chunk = count;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, win_len * 8, count);
     if ((chunk * win_len + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     for (size_t f0 = 0; f0 < count; f0 += chunk) {
         const size_t nf = (count - f0 < chunk) ? count - f0 : chunk;
@@ -226,9 +224,7 @@ int stft_mag_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t 
     }
     if (!fused_len_ok<float>(win_len)) {
         // any other window length: the composed STFT into scratch, then magnitudes + maximum in one pass (in frame chunks)
-        size_t chunk = (size_t(512) << 20) / (win_len * 8);
-        if (chunk < 1) chunk = 1;
-        if (chunk > frames) chunk = frames;
+        const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, win_len * 8, frames);
         int rc = ensure_real_tmp(ctx, chunk * win_len * 8);
         if (rc) return rc;
         float *spec = static_cast<float *>(ctx->real_tmp);

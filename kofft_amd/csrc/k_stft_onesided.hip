@@ -66,8 +66,8 @@ int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, si
     const size_t total = rows * frames, bins = win_len / 2 + 1;
     if (rows == 1) row_stride = 0;
     if (!fused_len_ok<float>(win_len)) {
-        // any other window length: the composed frames in the context's scratch, at most 512 MiB at a time, then their kept bins
-        const size_t chunk = composed_chunk(win_len, total);
+        // any other window length: the composed frames in the context's scratch, at most scratch_chunk_bytes at a time, then their kept bins
+        const size_t chunk = composed_chunk(ctx, win_len, total);
         if ((chunk * bins + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
         int rc = ensure_real_tmp(ctx, chunk * win_len * 8);
         if (rc) return rc;

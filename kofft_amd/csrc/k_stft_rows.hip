@@ -107,11 +107,9 @@ int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, si
     return fft_dev<float>(ctx, reinterpret_cast<const float *>(dst), reinterpret_cast<float *>(dst), win_len, nt, 0);
 }
 
-size_t composed_chunk(size_t win_len, size_t count)
+size_t composed_chunk(const kofft_hip_ctx *ctx, size_t win_len, size_t count)
 {
-    size_t chunk = (size_t(512) << 20) / (win_len * 8);
-    if (chunk < 1) chunk = 1;
-    return chunk > count ? count : chunk;
+    return scratch_chunk_rows(ctx->scratch_chunk_bytes, win_len * 8, count);
 }
 
 int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
@@ -125,7 +123,7 @@ int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t
     if (rows == 1) row_stride = 0;
     if (!fused_len_ok<float>(win_len)) {
         // any other window length: composed over all rows at once (BlueStftSrc knows one signal only)
-        const size_t chunk = composed_chunk(win_len, total);
+        const size_t chunk = composed_chunk(ctx, win_len, total);
         for (size_t t0 = 0; t0 < total; t0 += chunk) {
             const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
             const int rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_window, win_len, hop,
@@ -175,7 +173,7 @@ int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, s
     if (rows == 1) row_stride = 0;
     unsigned *max_bits = reinterpret_cast<unsigned *>(d_max);
     if (!fused_len_ok<float>(win_len)) {
-        const size_t chunk = composed_chunk(win_len, total);
+        const size_t chunk = composed_chunk(ctx, win_len, total);
         rc = ensure_real_tmp(ctx, chunk * win_len * 8);
         if (rc) return rc;
         cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp);
@@ -236,12 +234,11 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
     if (half && !(keep_frames && mode == 2)) return KOFFT_ERR_INVALID_VALUE;  // (never: istft_onesided_dev is the one caller)
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t in_frame = half ? (win_len / 2 + 1) * 2 : win_len * 2;  // floats of one frame as the caller holds it
-    // keep_frames: whole rows at a time through at most 512 MiB of the context's scratch (one row's frames where a row alone is
+    // keep_frames: whole rows at a time through at most scratch_chunk_bytes of the context's scratch (one row's frames where a row alone is
     // larger) -- copy, inverse transform, overlap-add; the rows are independent, so the sums and their order do not change
     size_t rows_per = rows;
     if (keep_frames && frames > 0) {
-        rows_per = (size_t(512) << 20) / (frames * win_len * 8);
-        rows_per = rows_per < 1 ? 1 : (rows_per > rows ? rows : rows_per);
+        rows_per = scratch_chunk_rows(ctx->scratch_chunk_bytes, frames * win_len * 8, rows);
         const size_t bytes = rows_per * frames * win_len * 8;
         if (ctx->rows_tmp_bytes < bytes) {
             if (ctx->rows_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->rows_tmp));

@@ -613,6 +613,7 @@ int kofft_hip_create(int device, kofft_hip_ctx **out)
         const long mb = atol(e);
         if (mb > 0) ctx->big_chunk_bytes = (size_t)mb << 20;
     }
+    if (const char *e = getenv("KOFFT_HIP_SCRATCH_CHUNK_MB")) (void)parse_scratch_chunk_mb(e, &ctx->scratch_chunk_bytes);
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)

@@ -106,10 +106,8 @@ inline unsigned planar_flat_blocks(const kofft_hip_ctx *ctx, size_t total)
 template <typename T>
 int planar_composed_dev(kofft_hip_ctx *ctx, const T *re_in, const T *im_in, T *re_out, T *im_out, size_t n, size_t batch, int inverse)
 {
-    // rows per chunk as dct2_composed_dev: 512 MiB of interleaved scratch at most (one row where a row is longer)
-    size_t chunk = (size_t(512) << 20) / (n * sizeof(cpx<T>));
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    // rows per chunk as dct2_composed_dev: scratch_chunk_bytes of interleaved scratch at most (one row where a row is longer)
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(cpx<T>), batch);
     int rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<T>));
     if (rc) return rc;
     cpx<T> *z = static_cast<cpx<T> *>(ctx->real_tmp);

@@ -123,9 +123,7 @@ int rfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_wi
     const cpx<T> *rtab = nullptr;
     int rc = get_table<T>(ctx, Kind<T>::rt, m, &rtab);
     if (rc) return rc;
-    size_t chunk = (size_t(512) << 20) / (n * sizeof(T));
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(T), batch);
     if ((chunk * (m + 1) + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     // Powers of two beyond the single-workgroup sizes (round 3): the window product rides on the factor path's first load
     // (BigColsIO PRE_WINDOW) -- one pass over the input less.  Other lengths (Bluestein's inner transform) keep the kernel.
@@ -200,9 +198,7 @@ int irfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, si
     const cpx<T> *rtab = nullptr;
     int rc = get_table<T>(ctx, Kind<T>::rt, m, &rtab);
     if (rc) return rc;
-    size_t chunk = (size_t(512) << 20) / (n * sizeof(T));
-    if (chunk < 1) chunk = 1;
-    if (chunk > batch) chunk = batch;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(T), batch);
     if ((chunk * m + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     rc = ensure_real_tmp(ctx, chunk * m * sizeof(cpx<T>));
     if (rc) return rc;

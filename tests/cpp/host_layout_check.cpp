@@ -1,6 +1,7 @@
 // host_layout_check.cpp -- properties of the host staging layout (kofft_amd/csrc/host_layout.h) over seeded random array sets,
 // built with -fsanitize=address,undefined by tests/test_host_layout.py.  The pieces are laid into a real buffer of `total` bytes and
 // every chunk of every array is written through, so an offset or a chunk that leaves its piece is also a sanitizer report.
+// Then the scratch-chunk helper of the device routes' chunk loops (scratch_chunk_rows) and the parser of its size knob.
 #include "../../kofft_amd/csrc/host_layout.h"
 
 #include <cstdio>
@@ -67,6 +68,63 @@ int main()
         for (int k = 0; k <= n; ++k)
             for (size_t b = 0; b < len[k]; b += 97)
                 CHECK(buf[off[k] + b] == (k < n ? k + 1 : 0), "set %d piece %d: byte %zu holds %d", it, k, b, (int)buf[off[k] + b]);
+    }
+    // ---- scratch_chunk_rows: rows per piece of a chunk loop under a scratch cap.  The pieces are written into a scratch of exactly
+    // `cap` bytes (one row where a row alone is larger) and counted off against the rows: a piece past the cap is a sanitizer report.
+    const size_t caps[] = {1, 255, 4096, size_t(1) << 20, (size_t(1) << 20) + 1, size_t(8) << 20, kScratchChunkDefaultBytes, 2 * kScratchChunkDefaultBytes};
+    for (int it = 0; it < 6000; ++it) {
+        const size_t cap = (it % 3 == 0) ? draw(1, 70000) : caps[rng() % (sizeof(caps) / sizeof(caps[0]))];
+        const size_t row_bytes = (it % 11 == 0) ? 0 : (it % 5 == 0) ? draw(cap / 2 + 1, 2 * cap + 8) : draw(1, cap < 64 ? 64 : cap < 40000 ? cap : 40000);
+        const size_t count = (it % 13 == 0) ? 0 : (it % 4 == 0) ? draw(1, 4) : draw(1, 3000);
+        const size_t chunk = scratch_chunk_rows(cap, row_bytes, count);
+        if (count == 0) {
+            CHECK(chunk == 0, "chunk case %d: %zu rows per piece of an empty batch", it, chunk);
+            continue;
+        }
+        CHECK(chunk >= 1 && chunk <= count, "chunk case %d: %zu rows per piece of %zu rows", it, chunk, count);
+        if (row_bytes == 0) {  // nothing to hold: one piece
+            CHECK(chunk == count, "chunk case %d: rows of no bytes in pieces of %zu, not %zu", it, chunk, count);
+            continue;
+        }
+        if (row_bytes > cap) CHECK(chunk == 1, "chunk case %d: a row of %zu bytes over the cap %zu in pieces of %zu", it, row_bytes, cap, chunk);
+        else CHECK(chunk * row_bytes <= cap, "chunk case %d: %zu rows of %zu bytes exceed the cap %zu", it, chunk, row_bytes, cap);
+        // (the largest that fits: one more row would pass the cap or the batch)
+        CHECK(chunk == count || (chunk + 1) * row_bytes > cap, "chunk case %d: %zu rows per piece where %zu fit", it, chunk, chunk + 1);
+        if (problems || chunk == 0) continue;
+        // the loop of every route: for (b0 = 0; b0 < count; b0 += chunk) nb = min(chunk, count - b0)
+        const bool small = cap <= 70000 && row_bytes <= cap;
+        std::vector<unsigned char> scratch(small ? cap : 1, 0);
+        size_t next = 0, pieces = 0;
+        for (size_t b0 = 0; b0 < count; b0 += chunk, ++pieces) {
+            const size_t nb = count - b0 < chunk ? count - b0 : chunk;
+            CHECK(b0 == next && nb >= 1, "chunk case %d: piece %zu starts at row %zu after %zu", it, pieces, b0, next);
+            next = b0 + nb;
+            if (small) std::memset(scratch.data(), (int)(pieces + 1), nb * row_bytes);  // rows b0 .. at the head of the scratch
+        }
+        CHECK(next == count, "chunk case %d: the pieces end at row %zu of %zu", it, next, count);
+        CHECK(pieces == (count + chunk - 1) / chunk, "chunk case %d: %zu pieces", it, pieces);
+    }
+    // the values the dispatch comments and the GPU seam tests count on
+    CHECK(scratch_chunk_rows(kScratchChunkDefaultBytes, 8, 7) == 7 && scratch_chunk_rows(size_t(1) << 20, 4000, 1000) == 262 &&
+              scratch_chunk_rows(size_t(1) << 20, 8000, 1000) == 131 && scratch_chunk_rows(size_t(1) << 20, size_t(1) << 21, 3) == 1,
+          "scratch_chunk_rows: known values");
+
+    // ---- KOFFT_HIP_SCRATCH_CHUNK_MB: 1 .. 512 MiB set the size, anything else leaves it alone
+    {
+        const size_t untouched = 12345;
+        struct { const char *text; bool ok; size_t mb; } cases[] = {
+            {"1", true, 1}, {"512", true, 512}, {"8", true, 8}, {"160", true, 160}, {"007", true, 7},
+            {"0", false, 0}, {"-3", false, 0}, {"513", false, 0}, {"junk", false, 0}, {"", false, 0}, {"12x", false, 0}, {" 4", false, 0},
+            {"4 ", false, 0}, {"+4", false, 0}, {"1.5", false, 0}, {"99999999999999999999999999", false, 0}, {"0x10", false, 0}};
+        for (const auto &c : cases) {
+            size_t bytes = untouched;
+            const bool ok = parse_scratch_chunk_mb(c.text, &bytes);
+            CHECK(ok == c.ok, "knob \"%s\": %s", c.text, ok ? "accepted" : "refused");
+            CHECK(bytes == (c.ok ? c.mb << 20 : untouched), "knob \"%s\": %zu bytes", c.text, bytes);
+        }
+        size_t bytes = untouched;
+        CHECK(!parse_scratch_chunk_mb(nullptr, &bytes) && bytes == untouched, "knob: a null string");
+        CHECK(kScratchChunkDefaultBytes == (size_t)kScratchChunkMaxMb << 20, "the default is the ceiling");
     }
     std::printf("%d problems\n", problems);
     return problems ? 1 : 0;

@@ -293,6 +293,12 @@ def case_probe_off(oracle):  # 160 MiB chunks: K candidate placements of the int
     assert_rows_equal(y, oracle.fft_mt(x), "c64 2^20 x 10, probe off")
 
 
+def case_scratch_chunk(oracle):  # 1 MiB of scratch per pass: several pieces, the last one short (every loop: tests/test_gpu_scratch_seams.py)
+    from test_gpu_scratch_seams import knob_case
+
+    knob_case(oracle)
+
+
 KNOBS = [
     ("KOFFT_HIP_NO_PERSIST", "1", case_no_persist),
     ("KOFFT_HIP_PERSIST_GRID_PCT", "50", case_grid_pct),
@@ -322,6 +328,7 @@ KNOBS = [
     ("KOFFT_HIP_BIG_ROW_PAIRS", "0", case_big_persist),
     ("KOFFT_HIP_BIG_CHUNK_MB", "64", case_chunk),
     ("KOFFT_HIP_BIG_PROBE", "0", case_probe_off),
+    ("KOFFT_HIP_SCRATCH_CHUNK_MB", "1", case_scratch_chunk),
 ]
 
 

@@ -77,11 +77,13 @@ def _dev(f, re, im, inverse, in_place=False, offset=0):
         return d[offset:].view(a.shape)
 
     d_re, d_im = up(re), up(im)
+    torch.cuda.synchronize()  # the slice assignments above are copies on torch's stream; the context's own stream does not wait for it
     if in_place:
         o_re, o_im = f.fft_split_dev(d_re, d_im, inverse=inverse)
         assert o_re is d_re and o_im is d_im
     else:
         o_re, o_im = up(np.zeros_like(re)), up(np.zeros_like(im))
+        torch.cuda.synchronize()
         f.fft_split_dev(d_re, d_im, o_re, o_im, inverse=inverse)
     f.synchronize()
     if not in_place:

@@ -1,5 +1,7 @@
 """AddressSanitizer + UBSan over the host staging layout (kofft_amd/csrc/host_layout.h): where the arrays of a host-pointer call lie
-in the staging buffer, and which rows a chunk of the pipelined route covers.  A plain executable: the header needs no GPU and no HIP."""
+in the staging buffer, which rows a chunk of the pipelined route covers, how many rows the device routes' chunk loops take per pass
+under their scratch cap (scratch_chunk_rows) and which values KOFFT_HIP_SCRATCH_CHUNK_MB accepts.  A plain executable: the header needs
+no GPU and no HIP."""
 import subprocess
 from pathlib import Path
 
