@@ -48,10 +48,10 @@ inline int cepstrum_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d
 {
     // rows per chunk as dct2_composed_dev: scratch_chunk_bytes of scratch at most
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(cpx<float>), batch);
-    int rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<float>));
+    int rc = ensure(ctx, ctx->real_tmp, chunk * n * sizeof(cpx<float>));
     if (rc) return rc;
-    float *zf = static_cast<float *>(ctx->real_tmp);
-    cpx<float> *z = static_cast<cpx<float> *>(ctx->real_tmp);
+    float *zf = static_cast<float *>(ctx->real_tmp.p);
+    cpx<float> *z = static_cast<cpx<float> *>(ctx->real_tmp.p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk, total = n * nb;
         const dim3 grid(hilbert_flat_blocks(ctx, total));

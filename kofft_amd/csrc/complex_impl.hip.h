@@ -15,6 +15,8 @@ namespace host {
 #ifndef KOFFT_ROWS_C32_CAP_KB
 #define KOFFT_ROWS_C32_CAP_KB 80
 #endif
+// units (columns / rows) per CU from which the persistent factor kernels run: every resident workgroup gets several tiles
+constexpr size_t kBigPersistMinUnits = 32;
 
 // The persistent, prefetching form of a factor (fft_tile_persist_kernel): 512 threads per CU (one or several workgroups),
 // so that every thread may use 256 registers -- two register sets and a pass's twiddles, no scratch.
@@ -38,17 +40,14 @@ int launch_tile_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size
         if (arc) return arc;
     }
     const size_t ntiles = units / XPB;
-    size_t blocks = (size_t)ctx->num_cus * WG_PER_CU;
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
-    if (blocks > ntiles) blocks = ntiles;
+    size_t blocks = resident_blocks(ctx->num_cus, WG_PER_CU, ctx->persist_grid_pct, ntiles);
     IO kio = io;
     if constexpr (io_tile_group_tw<IO>::value) {
-        // runs of tiles that share a table: as long as possible while every workgroup still gets a run
+        // runs of tiles that share a table: as long as possible while every workgroup still gets a run (tpg = 1, the table entries
+        // reloaded for every tile, was the A/B alternative)
         size_t tpg = (size_t(1) << kio.JB) / XPB;
         if (tpg < 1 || ((size_t(1) << kio.JB) % XPB) != 0) tpg = 1;
         while (tpg > 1 && ntiles / tpg < blocks) tpg /= 2;
-        if (!ctx->big_mid_group) tpg = 1;
         kio.tpg = (int)tpg;
         if (blocks > ntiles / tpg) blocks = ntiles / tpg;
     }
@@ -78,9 +77,7 @@ int launch_rows_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size
         if (arc) return arc;
     }
     const size_t KT = (size_t(1) << io.LA) / XPB;  // row tiles per transform
-    size_t blocks = (size_t)ctx->num_cus * WG_PER_CU;
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
+    const size_t blocks = resident_blocks(ctx->num_cus, WG_PER_CU, ctx->persist_grid_pct, kNoNeedCap);
     // one row tile per workgroup: whole groups of workgroups per row tile (no more groups than transforms) when the chip
     // has a CU for every row tile, otherwise one launch per slice of `blocks` row tiles
     for (size_t kt0 = 0; kt0 < KT; kt0 += blocks) {
@@ -122,7 +119,8 @@ int launch_sub_one_tile(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size
     constexpr int B0 = big_block<T, IO, LL>();
     constexpr int TPT = (1 << LL) >> rl_for(LL);
     constexpr bool kNarrow = !(sizeof(T) == 4 && LL == 7 && sub_is_rows<IO>::value);
-    const size_t cus = (size_t)ctx->num_cus * (size_t)ctx->big_narrow_per_cu;
+    constexpr size_t kBigNarrowPerCu = 1;  // workgroups per CU the narrowing aims for
+    const size_t cus = (size_t)ctx->num_cus * kBigNarrowPerCu;
     if constexpr (kNarrow && B0 / 2 >= 64 && (B0 / 2) % TPT == 0) {
         if (ctx->big_narrow && units / (B0 / TPT) < cus) {
             IO nio = io;
@@ -156,7 +154,7 @@ template <typename T, class IO>
 int launch_sub(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, int LS, size_t units, bool persist)
 {
     if constexpr (sub_tile_persist_of<IO>::value)
-    if (persist && units >= (size_t)ctx->num_cus * ctx->big_persist_min_units) {  // every resident workgroup gets several tiles
+    if (persist && units >= (size_t)ctx->num_cus * kBigPersistMinUnits) {  // every resident workgroup gets several tiles
         switch (LS) {
 #define KOFFT_CASE(LL) \
     case LL: return launch_tile_persist<T, LL, IO>(ctx, io, tw, units);
@@ -201,7 +199,7 @@ int launch_sub(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, int LS, size_
 template <typename T>
 int launch_mid(kofft_hip_ctx *ctx, const BigMidIO<T> &io, const cpx<T> *tw, int LS, size_t units)
 {
-    if (ctx->big_persist && units >= (size_t)ctx->num_cus * ctx->big_persist_min_units) {
+    if (ctx->big_persist && units >= (size_t)ctx->num_cus * kBigPersistMinUnits) {
         switch (LS) {
         case 7: return launch_tile_persist<T, 7, BigMidIO<T>>(ctx, io, tw, units);
         case 8: return launch_tile_persist<T, 8, BigMidIO<T>>(ctx, io, tw, units);
@@ -224,12 +222,12 @@ int fft_axis2_core(kofft_hip_ctx *ctx, cpx<T> *data, int LT, int I, size_t block
 {
     const size_t len = size_t(1) << LT, block_elems = len << I, block_bytes = block_elems * sizeof(cpx<T>);
     const cpx<T> *tw = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::tw, len, &tw);
+    int rc = twiddle_table<T>(ctx, len, &tw);
     if (rc) return rc;
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, block_bytes, blocks);
-    rc = ensure_real_tmp(ctx, chunk * block_bytes);
+    rc = ensure(ctx, ctx->real_tmp, chunk * block_bytes);
     if (rc) return rc;
-    cpx<T> *mid = static_cast<cpx<T> *>(ctx->real_tmp);
+    cpx<T> *mid = static_cast<cpx<T> *>(ctx->real_tmp.p);
     const int LS = LT - L1;
     const T scale = (T)1 / (T)(float)len;
     for (size_t b0 = 0; b0 < blocks; b0 += chunk) {
@@ -243,7 +241,7 @@ int fft_axis2_core(kofft_hip_ctx *ctx, cpx<T> *data, int LT, int I, size_t block
         rc = KOFFT_ERR_UNSUPPORTED;
         // LS = LT - L1 with L1 = 7 from 4096 points on: 5 .. 7 in f32 (axes up to 2^14 points), 5 / 6 in f64 (up to 2^13) -- fft_axis2_dev
         if constexpr (sizeof(T) == 4) {
-            if (ctx->big_persist && units >= (size_t)ctx->num_cus * ctx->big_persist_min_units && LS == 7)
+            if (ctx->big_persist && units >= (size_t)ctx->num_cus * kBigPersistMinUnits && LS == 7)
                 rc = launch_tile_persist<T, 7, AxisLastIO<T, INVERSE>>(ctx, m, tw, units);
         }
         if (rc == KOFFT_ERR_UNSUPPORTED) {
@@ -352,8 +350,7 @@ int big_probe_pick(kofft_hip_ctx *ctx, size_t need, size_t io_bytes, int K, Run 
         }
     if (got < 2) {
         if (got == 1) {
-            ctx->big_tmp = cand[0];
-            ctx->big_tmp_bytes = need;
+            ctx->big_tmp = DevBuf{cand[0], need};
         }
         cleanup(0);
         return KOFFT_OK;
@@ -399,8 +396,7 @@ int big_probe_pick(kofft_hip_ctx *ctx, size_t need, size_t io_bytes, int K, Run 
     }
     ctx->big_probe_n = got;
     ctx->big_probe_pick = best;
-    ctx->big_tmp = cand[best];
-    ctx->big_tmp_bytes = need;
+    ctx->big_tmp = DevBuf{cand[best], need};
     cleanup(best);
     return KOFFT_OK;
 }
@@ -417,13 +413,13 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
     // on, three factors of 7..9 bits: one more pass over HBM, but every pass keeps full-width tiles (two factors of
     // 11..13 bits shrink the tiles to 4, 2, 1 columns and fall to 0.05..0.16 of the roofline).
     // measured crossover, KOFFT_HIP_BIG_THREE_MIN; from 2^23 always three (two factors would need 2^12-point sub-transforms: tiles of 2 columns)
-    const bool three = (L >= ctx->big_three_min && !ctx->big_two_only) || L >= 23;
+    const bool three = L >= ctx->big_three_min || L >= 23;
     // two factors of an odd L: the larger one first when the persistent first-factor kernel covers it (c32, 2^11 points)
     // (only for batches the persistent kernels take: a single 2^21-point transform is faster as 2^10 x 2^11, 31.7 vs 33.6 us)
     const bool first11 = ctx->big_first11 && ctx->big_persist && L == 21 && !three &&
-                         (batch << 10) >= (size_t)ctx->num_cus * ctx->big_persist_min_units;
-    const bool first_larger = (ctx->big_first_larger >= 0 ? ctx->big_first_larger != 0 : sizeof(T) == 4) && L <= 20 && ctx->big_persist &&
-                              (batch << (L - (L + 1) / 2)) >= (size_t)ctx->num_cus * ctx->big_persist_min_units;  // batches only
+                         (batch << 10) >= (size_t)ctx->num_cus * kBigPersistMinUnits;
+    const bool first_larger = sizeof(T) == 4 && L <= 20 && ctx->big_persist &&
+                              (batch << (L - (L + 1) / 2)) >= (size_t)ctx->num_cus * kBigPersistMinUnits;  // batches only
     // (odd log2 n: the first factor -- the cheaper kernel: one table for all its tiles -- takes the extra bit in f32: 2^15 / 2^17 /
     // 2^19 +1.5..3 % on the same box; c64 shows no difference and keeps the smaller first factor; a single transform
     // -- the one-tile-per-workgroup kernels -- is faster the other way at 2^19, 14.0 vs 15.2 us, and keeps it too)
@@ -433,7 +429,7 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
     const int L2 = three ? (L - L1 + 1) / 2 : 0;
     const int L3 = L - L1 - L2;
     const cpx<T> *tw = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::tw, n, &tw);
+    int rc = twiddle_table<T>(ctx, n, &tw);
     if (rc) return rc;
     const size_t xf_bytes = n * sizeof(cpx<T>);
     size_t chunk = ctx->big_chunk_bytes / xf_bytes;
@@ -448,8 +444,7 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         // first factor: stages 0 .. L1-1 down the columns of a 2^L1 x 2^(L-L1) matrix
         ColsIO a{src, mid, L - L1, L - L1, n};
         fix_cols(a);
-        const bool first_persist = ctx->big_first_persist >= 0 ? ctx->big_first_persist != 0 : ctx->big_persist;
-        const size_t persist_units = (size_t)ctx->num_cus * ctx->big_persist_min_units;
+        const size_t persist_units = (size_t)ctx->num_cus * kBigPersistMinUnits;
         // Both factors on their persistent kernels (the conditions of launch_sub and of the rows branch below): the intermediate
         // is then block-interleaved -- see BigColsIO::out_lane.
         const bool rows_resident = ctx->big_persist && (nb << (L - L3)) >= persist_units && L3 >= 7 && L3 <= 10;
@@ -464,18 +459,18 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         // first factor then interleaves the rows of a pair (blk_r = 1: 256-byte runs per wavefront store).
         bool rows_pairs = false;
         if constexpr (rows_pair_io<RowsIO>::ok) {
-            rows_pairs = ctx->big_row_pairs && !three && first_persist && (nb << (L - L1)) >= persist_units && L1 >= 7 &&
+            rows_pairs = ctx->big_row_pairs && !three && ctx->big_persist && (nb << (L - L1)) >= persist_units && L1 >= 7 &&
                          (L1 <= 10 || (L1 == 11 && first11)) && rows_resident;
             if (rows_pairs) {
                 a.blk_r = 1;
                 a.blk_c = 0;
             }
         }
-        if ((sizeof(T) == 8 || KOFFT_BLOCKED_C32) && ctx->big_blocked && !three && first_persist && (nb << (L - L1)) >= persist_units && L1 >= 7 && L1 <= 10 && rows_resident) {
+        if ((sizeof(T) == 8 || KOFFT_BLOCKED_C32) && ctx->big_blocked && !three && ctx->big_persist && (nb << (L - L1)) >= persist_units && L1 >= 7 && L1 <= 10 && rows_resident) {
             a.blk_c = ilog2((size_t)tile_persist_xpb<T>(L1));
             a.blk_r = ilog2((size_t)rows_persist_xpb<T>(L3));
         }
-        rc = launch_sub<T>(ctx, a, tw, L1, nb << (L - L1), first_persist);
+        rc = launch_sub<T>(ctx, a, tw, L1, nb << (L - L1), ctx->big_persist);
         if (rc) return rc;
         if (ev_mid) KOFFT_HIP_TRY(ctx, hipEventRecord(ev_mid, ctx->stream));  // (the probe below: first factor | the rest)
         const cpx<T> *last_in = mid;
@@ -522,7 +517,7 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
 #else
         const size_t load_piece = (size_t)(64 / big_rows_per_wg<T>(L3)) * sizeof(cpx<T>);
 #endif
-        b.nt_load = ctx->big_mid_nt >= 0 ? ctx->big_mid_nt != 0 : (nb * xf_bytes > (size_t(192) << 20) && load_piece >= 64);
+        b.nt_load = nb * xf_bytes > (size_t(192) << 20) && load_piece >= 64;
         rc = KOFFT_ERR_UNSUPPORTED;
         // last factor: rows resident (table entries per row tile in LDS) for batches, else one tile per workgroup (two 512-thread workgroups
         // per CU at 128 registers).  (The generic persistent tile kernel as a third form was round 4's measurement switch: removed in round 6.)
@@ -541,11 +536,10 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         }
         return rc;
     };
-    if (ctx->big_tmp_bytes < need) {
+    if (ctx->big_tmp.bytes < need) {
         if (ctx->big_tmp_external) return KOFFT_ERR_ALLOC;
-        if (ctx->big_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->big_tmp));
-        ctx->big_tmp = nullptr;
-        ctx->big_tmp_bytes = 0;
+        if (ctx->big_tmp.p) KOFFT_HIP_TRY(ctx, hipFree(ctx->big_tmp.p));
+        ctx->big_tmp = DevBuf{};
         ctx->big_probe_n = 0;
         // (Round 4, tools/exp_c64_alloc.py: a physically contiguous buffer -- hipExtMallocWithFlags(hipDeviceMallocContiguous) -- made
         // the last factor's reads fast on one box (188-192 us per 512 MiB chunk on 16 of 16 buffers against 217-231 us on most plain
@@ -564,14 +558,14 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
             });
             if (prc) return prc;
         }
-        if (!ctx->big_tmp) {
-            KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->big_tmp, need));
-            ctx->big_tmp_bytes = need;
+        if (!ctx->big_tmp.p) {  // (no probe, or one that kept no candidate: the old buffer is gone, this only allocates)
+            const int arc = ensure(ctx, ctx->big_tmp, need);
+            if (arc) return arc;
         }
     }
-    cpx<T> *mid0 = static_cast<cpx<T> *>(ctx->big_tmp);
+    cpx<T> *mid0 = static_cast<cpx<T> *>(ctx->big_tmp.p);
 #ifdef KOFFT_EXP_TMP_PRINT
-    fprintf(stderr, "kofft big_tmp %p mid %p\n", ctx->big_tmp, (void *)mid0);
+    fprintf(stderr, "kofft big_tmp %p mid %p\n", ctx->big_tmp.p, (void *)mid0);
 #endif
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk;
@@ -607,54 +601,33 @@ int fft_big_windowed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d
 template <typename T>
 int get_bluestein(kofft_hip_ctx *ctx, size_t n, size_t m, const cpx<T> **chirp, const cpx<T> **bfft)
 {
-    const int kc = sizeof(T) == 4 ? 5 : 6, kb = sizeof(T) == 4 ? 7 : 8;
-    auto ic = ctx->tables.find(std::make_pair(kc, n));
-    auto ib = ctx->tables.find(std::make_pair(kb, n));
-    if (ic != ctx->tables.end() && ib != ctx->tables.end()) {
-        *chirp = static_cast<const cpx<T> *>(ic->second);
-        *bfft = static_cast<const cpx<T> *>(ib->second);
-        return KOFFT_OK;
-    }
-    std::vector<T> hc(2 * n), hb(2 * m);
-    if constexpr (sizeof(T) == 4) kofft_tables::bluestein_f32(n, m, (float *)hc.data(), (float *)hb.data());
-    else kofft_tables::bluestein_f64(n, m, (double *)hc.data(), (double *)hb.data());
-    void *dc = nullptr, *db = nullptr;
-    // every failure path below frees both tables (nothing is cached until the last step has succeeded)
-    auto fail = [&](const char *what, hipError_t e) {
-        if (dc) (void)hipFree(dc);
-        if (db) (void)hipFree(db);
-        if (e != hipSuccess) ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
-    };
-    hipError_t e = hipMalloc(&dc, hc.size() * sizeof(T));
-    if (e == hipSuccess) e = hipMalloc(&db, hb.size() * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        fail("bluestein tables: hipMalloc", e);
-        return KOFFT_ERR_HIP;
-    }
-    e = hipMemcpy(dc, hc.data(), hc.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, hb.data(), hb.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        fail("bluestein tables: upload", e);
-        return KOFFT_ERR_HIP;
-    }
-    // b_fft = fft(b) with the ordinary power-of-two path (fft.rs:425-427)
-    int rc = fft_dev<T>(ctx, static_cast<T *>(db), static_cast<T *>(db), m, 1, 0);
-    if (rc) {
-        fail("", hipSuccess);
-        return rc;
-    }
-    // the table is cached for every later call, on whatever stream that call uses: finish it first
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        fail("bluestein tables: fft(b)", e);
-        return KOFFT_ERR_HIP;
-    }
-    ctx->tables[std::make_pair(kc, n)] = dc;
-    ctx->tables[std::make_pair(kb, n)] = db;
-    *chirp = static_cast<const cpx<T> *>(dc);
-    *bfft = static_cast<const cpx<T> *>(db);
-    return KOFFT_OK;
+    // both tables or neither: nothing is cached until the last step has succeeded
+    return device_table_pair(
+        ctx, kind_for<T>(kTableBlueChirpF32), kind_for<T>(kTableBlueBfftF32), n, 2 * n * sizeof(T), 2 * m * sizeof(T), "bluestein tables", chirp,
+        bfft, [&](void *dc, void *db, std::string &why) {
+            std::vector<T> hc(2 * n), hb(2 * m);
+            if constexpr (sizeof(T) == 4) kofft_tables::bluestein_f32(n, m, (float *)hc.data(), (float *)hb.data());
+            else kofft_tables::bluestein_f64(n, m, (double *)hc.data(), (double *)hb.data());
+            int rc = upload_table(dc, hc.data(), hc.size() * sizeof(T), why);
+            if (rc == KOFFT_OK) rc = upload_table(db, hb.data(), hb.size() * sizeof(T), why);
+            if (rc) {
+                why = "upload: " + why;
+                return rc;
+            }
+            // b_fft = fft(b) with the ordinary power-of-two path (fft.rs:425-427)
+            rc = fft_dev<T>(ctx, static_cast<T *>(db), static_cast<T *>(db), m, 1, 0);
+            if (rc) {
+                why = "fft(b): " + ctx->last_error;
+                return rc;
+            }
+            // the table is cached for every later call, on whatever stream that call uses: finish it first
+            const hipError_t e = hipStreamSynchronize(ctx->stream);
+            if (e != hipSuccess) {
+                why = std::string("fft(b): ") + hipGetErrorString(e);
+                return KOFFT_ERR_HIP;
+            }
+            return KOFFT_OK;
+        });
 }
 
 // The whole arm in one launch (bluestein_wg_kernel): m = 2^5 .. 2^12 (c32) / 2^10 (c64).
@@ -727,11 +700,7 @@ int launch_bluestein_persist_src(kofft_hip_ctx *ctx, const SRC &src, cpx<T> *out
         const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
         if (arc) return arc;
     }
-    size_t blocks = (size_t)ctx->num_cus * WG;
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
-    const size_t need = (batch + XPB - 1) / XPB;
-    if (blocks > need) blocks = need;
+    const size_t blocks = resident_blocks(ctx->num_cus, WG, ctx->persist_grid_pct, (batch + XPB - 1) / XPB);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BLOCK), lds, ctx->stream, src, out, chirp, bfft, tw, (int)n, scale_m, scale_n, batch);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
@@ -766,7 +735,7 @@ int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, co
     const cpx<T> *chirp = nullptr, *bfft = nullptr, *tw = nullptr;
     int rc = get_bluestein<T>(ctx, n, m, &chirp, &bfft);
     if (rc) return rc;
-    rc = get_table<T>(ctx, Kind<T>::tw, m, &tw);
+    rc = twiddle_table<T>(ctx, m, &tw);
     if (rc) return rc;
     const T sm = (T)1 / (T)(float)m, sn = (T)1 / (T)(float)n;
     const BlueStftSrc src{d_signal, d_window, len, hop, start0, (int)n};
@@ -809,7 +778,7 @@ int dispatch_blue(kofft_hip_ctx *ctx, const IO &io, size_t m, size_t batch)
     if (L == 4) return launch_small<T, 16, EPI_STORE>(ctx, io, batch);
     if (L < (sizeof(T) == 4 ? 13 : 11) || L > max_log2<T>()) return KOFFT_ERR_UNSUPPORTED;
     const cpx<T> *tw = nullptr;
-    const int rc = get_table<T>(ctx, Kind<T>::tw, m, &tw);
+    const int rc = twiddle_table<T>(ctx, m, &tw);
     if (rc) return rc;
     switch (L) {
     case 11:
@@ -842,7 +811,7 @@ int fft_bluestein_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, siz
         // The persistent form (large batches) reaches m = 8192 (c32) / 4096 (c64)
         if (L >= 5 && L <= 13) {
             const cpx<T> *tw = nullptr;
-            rc = get_table<T>(ctx, Kind<T>::tw, m, &tw);
+            rc = twiddle_table<T>(ctx, m, &tw);
             if (rc) return rc;
             const T sm = (T)1 / (T)(float)m, sn = (T)1 / (T)(float)n;
             const cpx<T> *src = reinterpret_cast<const cpx<T> *>(d_in);
@@ -870,14 +839,9 @@ int fft_bluestein_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, siz
     }
     const size_t xf_bytes = m * sizeof(cpx<T>);
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, xf_bytes, batch);
-    if (ctx->blue_tmp_bytes < chunk * xf_bytes) {
-        if (ctx->blue_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->blue_tmp));
-        ctx->blue_tmp = nullptr;
-        ctx->blue_tmp_bytes = 0;
-        KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->blue_tmp, chunk * xf_bytes));
-        ctx->blue_tmp_bytes = chunk * xf_bytes;
-    }
-    cpx<T> *a = static_cast<cpx<T> *>(ctx->blue_tmp);
+    rc = ensure(ctx, ctx->blue_tmp, chunk * xf_bytes);
+    if (rc) return rc;
+    cpx<T> *a = static_cast<cpx<T> *>(ctx->blue_tmp.p);
     const T scale_m = (T)1 / (T)(float)m, scale_n = (T)1 / (T)(float)n;
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk;
@@ -948,7 +912,7 @@ int fft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch,
     if (n == (size_t(2) << max_log2<T>()) && ctx->use_regfile && batch >= (size_t)ctx->num_cus * 2) {
         // 256 KiB per transform: one pass over HBM with the transform in the CU's register file (fft_regfile.hip.h)
         const cpx<T> *tw = nullptr;
-        const int trc = get_table<T>(ctx, Kind<T>::tw, n, &tw);
+        const int trc = twiddle_table<T>(ctx, n, &tw);
         if (trc) return trc;
         const T scale = (T)1 / (T)(float)n;  // fft.rs:1167
         // (c32 as 2^7 x 2^8 -- 128-byte load runs, 64-byte store runs -- measured 0.374-0.378 against 0.396-0.402 for 2^8 x 2^7)
@@ -997,34 +961,21 @@ int fft_radix4_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t
         if (d_in != d_out) KOFFT_HIP_TRY(ctx, hipMemcpyAsync(d_out, d_in, batch * 2 * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
         return KOFFT_OK;
     }
-    // tables: (kind 9 / 10, n) = permutation, (11 / 12, n) = stage triples; O(n) host work once per (context, n)
-    const int kp = sizeof(T) == 4 ? 9 : 10, kw = sizeof(T) == 4 ? 11 : 12;
-    auto ip = ctx->tables.find(std::make_pair(kp, n));
-    auto iw = ctx->tables.find(std::make_pair(kw, n));
-    if (ip == ctx->tables.end() || iw == ctx->tables.end()) {
-        const size_t triples = kofft_tables::radix4_triples(n);
-        std::vector<unsigned> hp(n);
-        std::vector<T> hw(6 * (triples ? triples : 1));
-        if constexpr (sizeof(T) == 4) kofft_tables::radix4_f32(n, hp.data(), (float *)hw.data());
-        else kofft_tables::radix4_f64(n, hp.data(), (double *)hw.data());
-        void *dp = nullptr, *dw = nullptr;
-        hipError_t e = hipMalloc(&dp, hp.size() * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc(&dw, hw.size() * sizeof(T));
-        if (e == hipSuccess) e = hipMemcpy(dp, hp.data(), hp.size() * sizeof(unsigned), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dw, hw.data(), hw.size() * sizeof(T), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (dp) (void)hipFree(dp);
-            if (dw) (void)hipFree(dw);
-            ctx->last_error = std::string("radix4 tables: ") + hipGetErrorString(e);
-            return KOFFT_ERR_HIP;
-        }
-        ctx->tables[std::make_pair(kp, n)] = dp;
-        ctx->tables[std::make_pair(kw, n)] = dw;
-        ip = ctx->tables.find(std::make_pair(kp, n));
-        iw = ctx->tables.find(std::make_pair(kw, n));
-    }
-    const unsigned *perm = static_cast<const unsigned *>(ip->second);
-    const cpx<T> *w = static_cast<const cpx<T> *>(iw->second);
+    // tables: the permutation and the stage triples; O(n) host work once per (context, n)
+    const size_t triples = kofft_tables::radix4_triples(n), wvals = 6 * (triples ? triples : 1);
+    const unsigned *perm = nullptr;
+    const cpx<T> *w = nullptr;
+    const int trc = device_table_pair(
+        ctx, kind_for<T>(kTableRadix4PermF32), kind_for<T>(kTableRadix4TwF32), n, n * sizeof(unsigned), wvals * sizeof(T), "radix4 tables", &perm, &w,
+        [&](void *dp, void *dw, std::string &why) {
+            std::vector<unsigned> hp(n);
+            std::vector<T> hw(wvals);
+            if constexpr (sizeof(T) == 4) kofft_tables::radix4_f32(n, hp.data(), (float *)hw.data());
+            else kofft_tables::radix4_f64(n, hp.data(), (double *)hw.data());
+            const int rc = upload_table(dp, hp.data(), hp.size() * sizeof(unsigned), why);
+            return rc ? rc : upload_table(dw, hw.data(), hw.size() * sizeof(T), why);
+        });
+    if (trc) return trc;
     const T scale = (T)1 / (T)(float)n;  // fft.rs:2048
     auto grid = [](size_t quads) { return dim3((unsigned)((quads + 255) / 256)); };
     auto first = [&](const cpx<T> *src, cpx<T> *dst, size_t quads) {
@@ -1040,9 +991,9 @@ int fft_radix4_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t
     }
     const size_t xf_bytes = n * sizeof(cpx<T>);
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, xf_bytes, batch);
-    const int prc = ensure_real_tmp(ctx, chunk * xf_bytes);
+    const int prc = ensure(ctx, ctx->real_tmp, chunk * xf_bytes);
     if (prc) return prc;
-    cpx<T> *tmp = static_cast<cpx<T> *>(ctx->real_tmp);
+    cpx<T> *tmp = static_cast<cpx<T> *>(ctx->real_tmp.p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk, quads = nb * (n / 4);
         first(in + b0 * n, tmp, quads);

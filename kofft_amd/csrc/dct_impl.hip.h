@@ -187,11 +187,11 @@ inline bool dct2_fused_ok(const kofft_hip_ctx *ctx, const float *d_in, size_t n)
 inline int dct2_fused_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     const cpx<float> *tw = nullptr, *rtab = nullptr, *cs = nullptr;
-    int rc = get_table<float>(ctx, Kind<float>::tw, n, &tw);  // get_twiddles(n), the table of the n-point transform
+    int rc = twiddle_table<float>(ctx, n, &tw);  // get_twiddles(n), the table of the n-point transform
     if (rc) return rc;
-    rc = get_table<float>(ctx, Kind<float>::rt, n, &rtab);
+    rc = rfft_table<float>(ctx, n, &rtab);
     if (rc) return rc;
-    rc = get_table<float>(ctx, Kind<float>::dct2, n, &cs);
+    rc = dct2_table(ctx, n, &cs);
     if (rc) return rc;
     switch (ilog2(n)) {
     case 5: return launch_dct2_fused<5>(ctx, d_in, d_out, tw, rtab, cs, batch);
@@ -209,15 +209,15 @@ inline int dct2_fused_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, s
 inline int dct2_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     const cpx<float> *rtab = nullptr, *cs = nullptr;
-    int rc = get_table<float>(ctx, Kind<float>::rt, n, &rtab);  // build_twiddle_table(m = n) of the 2n-real rfft
+    int rc = rfft_table<float>(ctx, n, &rtab);  // build_twiddle_table(m = n) of the 2n-real rfft
     if (rc) return rc;
-    rc = get_table<float>(ctx, Kind<float>::dct2, n, &cs);
+    rc = dct2_table(ctx, n, &cs);
     if (rc) return rc;
     // rows per chunk as rfft_composed_dev, counted on the mirrored 2n-real rows: scratch_chunk_bytes of scratch at most
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, 2 * n * sizeof(float), batch);
-    rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<float>));
+    rc = ensure(ctx, ctx->real_tmp, chunk * n * sizeof(cpx<float>));
     if (rc) return rc;
-    float *z = static_cast<float *>(ctx->real_tmp);
+    float *z = static_cast<float *>(ctx->real_tmp.p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk;
         const bool flat = n < 512;

@@ -197,40 +197,18 @@ __global__ __launch_bounds__(256) void direct_tiled_kernel(const float *__restri
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-constexpr int kDirectTableKind = 20;  // table-cache kinds 20 .. 27: 20 + 4 * family + (type - 1)
-
 inline size_t direct_ldc(size_t n) { return (n + DT_BN - 1) / DT_BN * DT_BN; }
 
 // The n x direct_ldc(n) table of one kind, built on the host at the first call of a (context, kind, n) and kept until the context
 // is destroyed (kofft_hip_destroy frees the whole cache).
 inline int get_direct_table(kofft_hip_ctx *ctx, int family, int type, size_t n, const float **out)
 {
-    const auto key = std::make_pair(kDirectTableKind + 4 * family + (type - 1), n);
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        *out = static_cast<const float *>(it->second);
-        return KOFFT_OK;
-    }
-    const size_t ldc = direct_ldc(n);
-    std::vector<float> host;
-    try {
-        host.resize(n * ldc);
-    } catch (const std::bad_alloc &) {
-        return KOFFT_ERR_ALLOC;
-    }
-    kofft_tables::direct_table_f32(family, type, n, ldc, host.data());
-    void *d = nullptr;
-    KOFFT_HIP_TRY(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-    // synchronous copy: a table is built once per (context, kind, n)
-    const hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        ctx->last_error = std::string("direct table upload: ") + hipGetErrorString(e);
-        return KOFFT_ERR_HIP;
-    }
-    ctx->tables[key] = d;
-    *out = static_cast<const float *>(d);
-    return KOFFT_OK;
+    const size_t ldc = direct_ldc(n), bytes = n * ldc * sizeof(float);
+    return device_table(ctx, direct_table_kind(family, type), n, bytes, "direct table upload", out, [&](void *d, std::string &why) {
+        std::vector<float> host(n * ldc);
+        kofft_tables::direct_table_f32(family, type, n, ldc, host.data());
+        return upload_table(d, host.data(), bytes, why);
+    });
 }
 
 // Where a tile would be mostly padding the simple kernel runs (the crossover measured with tools/bench_trig_direct.py);

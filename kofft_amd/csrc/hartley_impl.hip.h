@@ -4,7 +4,7 @@
 // (never fused): launch_direct<DIR_ZERO> of direct_impl.hip.h (through direct_zero_sums, k_direct_f32.hip), the route rule and the
 // kernels of the direct DCT / DST unchanged.  What is new is the table: H[i][k] = cosf(a) + sinf(a), a = factor * ((i * k) as f32),
 // factor = (2.0 * PI) / n as f32, with the libm crate's cosf / sinf (libm_trigf.hip.h: f64 polynomials after an f64 reduction), not
-// glibc's.  H is symmetric and depends on n only: one table per (context, n) in the context's table cache (kind kDhtTableKind), n rows
+// glibc's.  H is symmetric and depends on n only: one table per (context, n) in the context's table cache (kind kTableDht), n rows
 // of direct_ldc(n) floats, the padding columns +0.
 //  * dht_table_kernel builds it on the device, asynchronously on the context's stream and with no host buffer: a lane owns four
 //    consecutive columns of one row and writes them with one 16-byte store, so a wavefront writes 1024 consecutive bytes; a
@@ -22,7 +22,6 @@
 namespace kofft {
 namespace host {
 
-constexpr int kDhtTableKind = 28;  // table-cache kind (20 .. 27: the direct DCT / DST tables)
 constexpr int DHT_BLOCK = 256;  // lanes of a workgroup: four columns each, 1024 columns of one row
 
 // grid: (ceil(ldc / (4 * DHT_BLOCK)), n), blockIdx.y = the row i (uniform: its address and i * k need no per-lane multiply-add).

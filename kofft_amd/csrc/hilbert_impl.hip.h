@@ -207,7 +207,7 @@ template <class P, class KernelOf>
 int fused_dev(kofft_hip_ctx *ctx, KernelOf kernel_of, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     const cpx<float> *tw = nullptr;
-    const int rc = get_table<float>(ctx, Kind<float>::tw, n, &tw);  // get_twiddles(n), the table of the n-point transform
+    const int rc = twiddle_table<float>(ctx, n, &tw);  // get_twiddles(n), the table of the n-point transform
     if (rc) return rc;
     using std::integral_constant;
     switch (ilog2(n)) {

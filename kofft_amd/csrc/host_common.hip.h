@@ -24,6 +24,7 @@
 #include "fft_regfile.hip.h"
 #include "fft_split_wide.hip.h"
 #include "fft_wg.hip.h"
+#include "host_cache.h"
 #include "host_layout.h"
 #include "tables.h"
 
@@ -59,27 +60,18 @@ struct kofft_hip_ctx {
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     int persist_claim_pct = -1; // kofft_hip_set_persist_claim_pct: percent of the batch the kClaim persistent kernels hand out by claim, 0 .. 100 (-1: the configuration's; A/B, tests)
     unsigned *persist_claim_counters = nullptr;  // device: [next claim, workgroups done]; zeroed at creation, every kClaim launch leaves them at zero
-    bool big_two_only = false; // (a member only -- no environment variable since round 4) never split into three factors (A/B measurements)
     int big_three_min = 22;    // KOFFT_HIP_BIG_THREE_MIN: smallest log2 n split into three factors
     bool small32 = true;       // KOFFT_HIP_SMALL32=0: f32 n = 32 on the thread-group kernel instead of one thread per transform (A/B)
     bool big_first11 = true;   // KOFFT_HIP_BIG_FIRST11=0: 2^21 as 2^10 x 2^11 with the one-tile-per-workgroup kernel for the 2^11 factor (A/B)
-    bool big_mid_group = true; // (a member only -- no environment variable since round 4) the middle factor reloads its table entries for every tile (A/B)
-    int big_first_larger = -1; // (a member only -- no environment variable since round 4) odd log2 n: which factor takes the extra bit (default: the first in f32)
     bool big_narrow = true;    // KOFFT_HIP_BIG_NARROW=0: full-width tiles even when they leave CUs without a workgroup (A/B)
-    int big_narrow_per_cu = 1; // (a member only -- no environment variable since round 4) workgroups per CU the narrowing aims for
     bool big_persist = true;   // KOFFT_HIP_BIG_PERSIST=0: factors on the one-tile-per-workgroup kernel (A/B measurements)
-    size_t big_persist_min_units = 32;  // (a member only -- no environment variable since round 4) units (columns / rows) per CU from which the persistent factor kernels run
-    int big_first_persist = -1;  // (a member only -- no environment variable since round 4) first factor one tile per workgroup / persistent (default: big_persist)
-    int big_mid_nt = -1;       // (compile-time only since round 4; no getenv) force plain / streaming loads of the intermediate (default: by chunk size)
     bool blue_fused = true;    // KOFFT_HIP_BLUESTEIN_FUSED=0: pointwise steps as separate kernels at every size
     bool blue_one_kernel = true;  // KOFFT_HIP_BLUESTEIN_ONE=0: two launches through a scratch even where one workgroup holds m points
     bool nd_transpose = true;  // KOFFT_HIP_ND_TRANSPOSE=0: long strided axes through the strided kernel
     bool nd_fused = true;      // KOFFT_HIP_ND_FUSED=0: 2-D c32 images with 1024 .. 4096-point rows through rows + two column-tile passes instead of the fused two passes (A/B)
     bool nd_two_pass = true;   // KOFFT_HIP_ND_TWO_PASS=0: power-of-two axes of 4096 .. 16384 points through the transposes instead of two column-tile passes (A/B)
-    int nd_transpose_min = 4096;  // (a member only -- no environment variable since round 4) shortest axis that takes the transpose route (measured: 1024 loses, 2048 ties)
     bool zero_copy = true;     // KOFFT_HIP_ZERO_COPY=0: small host calls through staged copies like large ones
     bool host_pipeline = true; // KOFFT_HIP_HOST_PIPELINE=0: host-pointer batches in one upload / kernel / download
-    int host_chunks = 0;       // (a member only -- no environment variable since round 4) pieces of a pipelined host batch (default 8)
     bool rfft14_wide = true;    // KOFFT_HIP_RFFT14_WIDE=0: rfft / irfft of 32768 reals on the generic kernel
     bool rfft13_persist = true; // KOFFT_HIP_RFFT13_PERSIST=0: rfft / irfft n = 16384 on the generic kernel
     int persist64 = 1;         // KOFFT_HIP_PERSIST64=0: c64 n = 4096 / 8192 on the generic kernel (A/B measurements)
@@ -89,10 +81,8 @@ struct kofft_hip_ctx {
     bool use_regfile = true;   // KOFFT_HIP_REGFILE=0: c32 2^15 / c64 2^14 on the two-factor path instead of the register-file-resident kernel (A/B)
     bool use_split = true;     // KOFFT_HIP_SPLIT=0: n = 8192 on the block-synchronised persistent kernel instead of the wave-split one (A/B)
     std::string last_error;
-    // planner caches: (kind, n) -> device table.  kind 0/1 = FftPlanner twiddles f32/f64,
-    // 2/3 = RfftPlanner post-pass table f32/f64, 13 = DctPlanner (cos, sin) table f32, 20 .. 27 = the direct DCT / DST tables
-    // (direct_impl.hip.h), 28 = the Hartley table (hartley_impl.hip.h).
-    std::map<std::pair<int, size_t>, void *> tables;
+    // planner caches: (kind, n) -> device table, every kind in TableKind (host_cache.h); read and filled by device_table / device_table_pair alone
+    kofft::host::TableCache tables;
     // chirp-Z tables: most recently used first, at most kSpectralSlots; an evicted slot is freed after the stream is synchronised.
     // goertzel_coeff: the device-pointer Goertzel's coefficients (kGoertzelMaxFreqs floats), goertzel_last what it holds.
     // kofft_hip_destroy and kofft_hip_release_scratch drop all of it (spectral_drop)
@@ -100,11 +90,9 @@ struct kofft_hip_ctx {
     void *goertzel_coeff = nullptr;
     std::vector<float> goertzel_last;
     // staging for the host-pointer entry points: one device buffer, laid out by host_layout() (host_layout.h)
-    void *stage = nullptr;
-    size_t stage_bytes = 0;
+    kofft::host::DevBuf stage;
     // intermediate of the two-factor large-n path (fft_big.hip.h): `big_chunk` transforms at a time
-    void *big_tmp = nullptr;
-    size_t big_tmp_bytes = 0;
+    kofft::host::DevBuf big_tmp;
     bool big_row_pairs = true;       // KOFFT_HIP_BIG_ROW_PAIRS=0: c32 last factor one row per thread slot (8-row tiles) instead of row pairs (A/B)
     bool big_blocked = true;         // KOFFT_HIP_BIG_BLOCKED=0: natural layout of the two-factor intermediate (A/B)
     bool big_tmp_external = false;  // KOFFT_EXP_API builds only: the intermediate belongs to the experiment script
@@ -117,12 +105,9 @@ struct kofft_hip_ctx {
     void *pinned = nullptr;      // host address
     void *pinned_dev = nullptr;  // the same memory as the device sees it
     size_t pinned_bytes = 0;
-    void *blue_tmp = nullptr;  // zero-padded work buffer of the Bluestein arm
-    size_t blue_tmp_bytes = 0;
-    void *real_tmp = nullptr;  // the inner complex transform of real / STFT lengths the fused kernels do not cover
-    size_t real_tmp_bytes = 0;
-    void *rows_tmp = nullptr;  // istft_parallel_rows on device pointers: the inverse transforms of the caller's (const) frames
-    size_t rows_tmp_bytes = 0;
+    kofft::host::DevBuf blue_tmp;  // zero-padded work buffer of the Bluestein arm
+    kofft::host::DevBuf real_tmp;  // the inner complex transform of real / STFT lengths the fused kernels do not cover
+    kofft::host::DevBuf rows_tmp;  // istft_parallel_rows on device pointers: the inverse transforms of the caller's (const) frames
     size_t scratch_chunk_bytes = kofft::host::kScratchChunkDefaultBytes;  // KOFFT_HIP_SCRATCH_CHUNK_MB (1 .. 512): the scratch of one pass of every chunk loop but the factor path's (scratch_chunk_rows, host_layout.h); the N-D transpose panels take twice this
     size_t big_chunk_bytes = size_t(512) << 20;  // KOFFT_HIP_BIG_CHUNK_MB; measured on config 5 with the persistent factor kernels: 128 MiB 14.7 ms, 256 13.0, 512 12.1, 1024 12.5, 2048 13.1
 };
@@ -147,45 +132,71 @@ inline int ilog2(size_t n)
     return l;
 }
 
-template <typename T> struct Kind;
-template <> struct Kind<float> { static constexpr int tw = 0, rt = 2, dct2 = 13; };  // (4 .. 12: k_stft.hip, complex_impl.hip.h)
-template <> struct Kind<double> { static constexpr int tw = 1, rt = 3; };
+// The allocator of the table cache and the scratch buffers (host_cache.h).  A failed hipMalloc also leaves its error with the runtime,
+// where the next launch's hipGetLastError would find it: taken away here.
+struct HipAlloc {
+    static const char *alloc(void **p, size_t bytes)
+    {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) return nullptr;
+        (void)hipGetLastError();
+        return hipGetErrorString(e);
+    }
+    static const char *free(void *p)
+    {
+        const hipError_t e = hipFree(p);
+        return e == hipSuccess ? nullptr : hipGetErrorString(e);
+    }
+};
 
-template <typename T>
-int get_table(kofft_hip_ctx *ctx, int kind, size_t n, const cpx<T> **out)
+// cached_table / cached_table_pair on device memory (P, Q: the tables' element types)
+template <typename P, class Build>
+int device_table(kofft_hip_ctx *ctx, TableKind kind, size_t n, size_t bytes, const char *label, const P **out, Build build)
 {
-    auto key = std::make_pair(kind, n);
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        *out = static_cast<const cpx<T> *>(it->second);
-        return KOFFT_OK;
-    }
-    const bool is_dct2 = kind == 13;  // Kind<float>::dct2: (cos, sin) of DctPlanner, n pairs
-    const bool is_rfft = kind == 2 || kind == 3;
-    const size_t entries = (is_rfft || is_dct2) ? n : n / 2;
-    std::vector<T> host(2 * (entries ? entries : 1));
-    if (is_dct2) {
-        if constexpr (sizeof(T) == 4) kofft_tables::dct2_table_f32(n, (float *)host.data());
-        else return KOFFT_ERR_UNSUPPORTED;  // the reference's DCT is f32-only (dct.rs:6)
-    } else if (is_rfft) {
-        if constexpr (sizeof(T) == 4) kofft_tables::rfft_table_f32(n, (float *)host.data());
-        else kofft_tables::rfft_table_f64(n, (double *)host.data());
-    } else {
-        if constexpr (sizeof(T) == 4) kofft_tables::twiddles_f32(n, (float *)host.data());
-        else kofft_tables::twiddles_f64(n, (double *)host.data());
-    }
-    void *d = nullptr;
-    KOFFT_HIP_TRY(ctx, hipMalloc(&d, host.size() * sizeof(T)));
-    // synchronous copy: tables are built once per (context, n), never in a timed region
-    hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        ctx->last_error = std::string("table upload: ") + hipGetErrorString(e);
-        return KOFFT_ERR_HIP;
-    }
-    ctx->tables[key] = d;
-    *out = static_cast<const cpx<T> *>(d);
-    return KOFFT_OK;
+    return cached_table<HipAlloc>(ctx, kind, n, bytes, label, out, build);
+}
+template <typename P, typename Q, class Build>
+int device_table_pair(kofft_hip_ctx *ctx, TableKind kind_a, TableKind kind_b, size_t n, size_t bytes_a, size_t bytes_b, const char *label,
+                      const P **out_a, const Q **out_b, Build build)
+{
+    return cached_table_pair<HipAlloc>(ctx, kind_a, kind_b, n, bytes_a, bytes_b, label, out_a, out_b, build);
+}
+// what most builders end with.  A synchronous copy: tables are built once per (context, n), never in a timed region
+inline int upload_table(void *d, const void *host, size_t bytes, std::string &why)
+{
+    const hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) return KOFFT_OK;
+    why = hipGetErrorString(e);
+    return KOFFT_ERR_HIP;
+}
+
+// The planner tables of one length, n >= 1: `entries` complex values filled by f32 / f64 (tables.h)
+template <typename T>
+int planner_table(kofft_hip_ctx *ctx, TableKind kind, size_t n, size_t entries, void (*f32)(size_t, float *), void (*f64)(size_t, double *),
+                  const cpx<T> **out)
+{
+    const size_t vals = 2 * (entries ? entries : 1);
+    return device_table(ctx, kind, n, vals * sizeof(T), "table upload", out, [&](void *d, std::string &why) {
+        std::vector<T> host(vals);
+        if constexpr (sizeof(T) == 4) f32(n, (float *)host.data());
+        else f64(n, (double *)host.data());
+        return upload_table(d, host.data(), vals * sizeof(T), why);
+    });
+}
+// FftPlanner's twiddles (n / 2 entries), RfftPlanner's post-pass table (n entries), DctPlanner's (cos, sin) pairs (n; f32 only: dct.rs:6)
+template <typename T>
+int twiddle_table(kofft_hip_ctx *ctx, size_t n, const cpx<T> **out)
+{
+    return planner_table<T>(ctx, kind_for<T>(kTableTwF32), n, n / 2, kofft_tables::twiddles_f32, kofft_tables::twiddles_f64, out);
+}
+template <typename T>
+int rfft_table(kofft_hip_ctx *ctx, size_t n, const cpx<T> **out)
+{
+    return planner_table<T>(ctx, kind_for<T>(kTableRfftF32), n, n, kofft_tables::rfft_table_f32, kofft_tables::rfft_table_f64, out);
+}
+inline int dct2_table(kofft_hip_ctx *ctx, size_t n, const cpx<float> **out)
+{
+    return planner_table<float>(ctx, kTableDct2, n, n, kofft_tables::dct2_table_f32, nullptr, out);
 }
 
 constexpr size_t kZeroCopyMax = size_t(512) << 10;  // bytes per direction up to which a host call goes zero-copy
@@ -213,23 +224,13 @@ inline int ensure_pinned(kofft_hip_ctx *ctx, size_t bytes)
     return KOFFT_OK;
 }
 
-inline int ensure_stage(kofft_hip_ctx *ctx, size_t bytes)
+// grow-only device scratch: ensure(ctx, ctx->real_tmp, bytes), then ctx->real_tmp.p
+inline int ensure(kofft_hip_ctx *ctx, DevBuf &buf, size_t bytes) { return ensure_buf<HipAlloc>(ctx, buf, bytes); }
+// every device scratch buffer of a context and the pinned one go (kofft_hip_destroy, kofft_hip_release_scratch)
+inline void drop_buffers(kofft_hip_ctx *ctx)
 {
-    if (ctx->stage_bytes >= bytes) return KOFFT_OK;
-    if (ctx->stage) KOFFT_HIP_TRY(ctx, hipFree(ctx->stage));
-    ctx->stage = nullptr;
-    ctx->stage_bytes = 0;
-    KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->stage, bytes));
-    ctx->stage_bytes = bytes;
-    return KOFFT_OK;
-}
-
-// both buffers of the host staging path go (kofft_hip_destroy, kofft_hip_release_scratch)
-inline void drop_host_buffers(kofft_hip_ctx *ctx)
-{
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    ctx->stage = nullptr;
-    ctx->stage_bytes = 0;
+    if (ctx->big_tmp_external) ctx->big_tmp = DevBuf{};  // (KOFFT_EXP_API builds: the experiment script's own buffer)
+    for (DevBuf *b : {&ctx->stage, &ctx->big_tmp, &ctx->blue_tmp, &ctx->real_tmp, &ctx->rows_tmp}) release_buf<HipAlloc>(*b);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     ctx->pinned = ctx->pinned_dev = nullptr;
     ctx->pinned_bytes = 0;
@@ -474,6 +475,19 @@ template <> struct PersistGrid<10, RfftIO<float>> {
     static int wg_per_cu(int base, size_t input_bytes) { return input_bytes > (size_t(1) << 30) ? base / 2 : base; }
 };
 
+// What the chip-resident launchers below end with: the kernel's LDS attribute (done: the CALLER's function-local static, one per kernel
+// instance), the launch on `blocks` workgroups, its error.
+template <class Kern, class IO, class TW>
+int launch_resident(kofft_hip_ctx *ctx, std::atomic<unsigned long long> &done, Kern kern, size_t blocks, int block, size_t lds, const IO &io,
+                    const TW *tw, size_t batch)
+{
+    const int arc = set_dyn_lds_once(ctx, done, reinterpret_cast<const void *>(kern), lds);
+    if (arc) return arc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(block), lds, ctx->stream, io, tw, batch);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
 template <typename T, int L, int EPI, class IO>
 int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch);
 template <typename T, int L, int EPI, class IO>
@@ -489,20 +503,10 @@ int launch_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t ba
                            (EPI == EPI_RFFT ? (size_t)(1 << L) * sizeof(cpx<T>) : 0) +
                            (Cfg::kTwLastInLds ? (size_t)(1 << L) / 2 * sizeof(cpx<T>) : 0);
     static_assert(lds * Cfg::WG_PER_CU <= 160 * 1024, "LDS budget");
-    auto kern = fft_persist_kernel<T, L, RL, EPI, IO, Cfg>;
-    {
-        static std::atomic<unsigned long long> attr_done{0};
-        const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
-        if (arc) return arc;
-    }
-    size_t blocks = (size_t)ctx->num_cus * PersistGrid<L, IO>::wg_per_cu(Cfg::WG_PER_CU, batch * sizeof(cpx<T>) << L);
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;  // measurement knob
-    if (blocks < 1) blocks = 1;
-    const size_t need = (batch + XPB - 1) / XPB;
-    if (blocks > need) blocks = need;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Cfg::BLOCK), lds, ctx->stream, io, tw, batch);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
+    static std::atomic<unsigned long long> attr_done{0};
+    const size_t blocks = resident_blocks(ctx->num_cus, PersistGrid<L, IO>::wg_per_cu(Cfg::WG_PER_CU, batch * sizeof(cpx<T>) << L),
+                                          ctx->persist_grid_pct, (batch + XPB - 1) / XPB);
+    return launch_resident(ctx, attr_done, fft_persist_kernel<T, L, RL, EPI, IO, Cfg>, blocks, Cfg::BLOCK, lds, io, tw, batch);
     }
 }
 
@@ -522,24 +526,15 @@ int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, siz
         return KOFFT_ERR_ALLOC;
     }
     using KIO = PersistClaimIO<IO>;  // the kernel's policy: `io` plus the hand-out's argument
-    auto kern = fft_persist_kernel<T, L, RL, EPI, KIO, Cfg>;
-    {
-        static std::atomic<unsigned long long> attr_done{0};
-        const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
-        if (arc) return arc;
-    }
-    size_t blocks = (size_t)ctx->num_cus * PersistGrid<L, IO>::wg_per_cu(Cfg::WG_PER_CU, batch * sizeof(cpx<T>) << L);
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;  // measurement knob
-    if (blocks < 1) blocks = 1;
-    const size_t need = (batch + XPB - 1) / XPB;
-    if (blocks > need) blocks = need;  // (every workgroup's first walked row exists)
+    static std::atomic<unsigned long long> attr_done{0};
+    // (no more workgroups than tiles of XPB rows: every workgroup's first walked row exists)
+    const size_t blocks = resident_blocks(ctx->num_cus, PersistGrid<L, IO>::wg_per_cu(Cfg::WG_PER_CU, batch * sizeof(cpx<T>) << L),
+                                          ctx->persist_grid_pct, (batch + XPB - 1) / XPB);
     const size_t stride = blocks * XPB;
     const size_t pct = ctx->persist_claim_pct < 0 ? (size_t)Cfg::kClaimPct : (ctx->persist_claim_pct > 100 ? 100 : (size_t)ctx->persist_claim_pct);
     const size_t claimed = batch / 100 * pct + batch % 100 * pct / 100;
     const KIO kio{io, PersistClaim{ctx->persist_claim_counters, (batch - claimed) / stride * stride}};
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Cfg::BLOCK), lds, ctx->stream, kio, tw, batch);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
+    return launch_resident(ctx, attr_done, fft_persist_kernel<T, L, RL, EPI, KIO, Cfg>, blocks, Cfg::BLOCK, lds, kio, tw, batch);
 }
 
 // The wave-split kernel (fft_split.hip.h): one workgroup per CU, one s_barrier per transform.
@@ -549,19 +544,9 @@ int launch_split(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batc
     using Gm = SplitGeom<LA, LB>;
     constexpr size_t lds = 2 * (size_t)Gm::N * sizeof(cpx<T>) + 16;  // (+ the two counters of KOFFT_SPLIT_COUNTERS)
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fft_split_persist_kernel<T, LA, LB, IO>;
-    {
-        static std::atomic<unsigned long long> attr_done{0};
-        const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
-        if (arc) return arc;
-    }
-    size_t blocks = (size_t)ctx->num_cus;
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
-    if (blocks > batch) blocks = batch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Gm::TPT), lds, ctx->stream, io, tw, batch);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
+    static std::atomic<unsigned long long> attr_done{0};
+    const size_t blocks = resident_blocks(ctx->num_cus, 1, ctx->persist_grid_pct, batch);
+    return launch_resident(ctx, attr_done, fft_split_persist_kernel<T, LA, LB, IO>, blocks, Gm::TPT, lds, io, tw, batch);
 }
 
 
@@ -572,19 +557,9 @@ int launch_split_wide(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t
     using Gm = SplitWideGeom<LA, LB, QB0>;
     constexpr size_t lds = split_wide_lds_bytes<Gm>();
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fft_split_wide_persist_kernel<T, LA, LB, QB0, IO>;
-    {
-        static std::atomic<unsigned long long> attr_done{0};
-        const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
-        if (arc) return arc;
-    }
-    size_t blocks = (size_t)ctx->num_cus * ((160 * 1024) / lds);
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
-    if (blocks > batch) blocks = batch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Gm::TPT), lds, ctx->stream, io, tw, batch);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
+    static std::atomic<unsigned long long> attr_done{0};
+    const size_t blocks = resident_blocks(ctx->num_cus, (int)((160 * 1024) / lds), ctx->persist_grid_pct, batch);
+    return launch_resident(ctx, attr_done, fft_split_wide_persist_kernel<T, LA, LB, QB0, IO>, blocks, Gm::TPT, lds, io, tw, batch);
 }
 
 // c32 n = 2^15 / c64 n = 2^14: the whole transform in the CU's register file (fft_regfile.hip.h), one 1024-thread workgroup per CU
@@ -594,19 +569,9 @@ int launch_regfile(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t ba
     using Gm = RfGeom<T, LA, LB, QB0>;
     constexpr size_t lds = regfile_lds_bytes<Gm, T>();
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fft_regfile_persist_kernel<T, LA, LB, QB0, IO>;
-    {
-        static std::atomic<unsigned long long> attr_done{0};
-        const int arc = set_dyn_lds_once(ctx, attr_done, reinterpret_cast<const void *>(kern), lds);
-        if (arc) return arc;
-    }
-    size_t blocks = (size_t)ctx->num_cus;
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
-    if (blocks > batch) blocks = batch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Gm::TPT), lds, ctx->stream, io, tw, batch);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
+    static std::atomic<unsigned long long> attr_done{0};
+    const size_t blocks = resident_blocks(ctx->num_cus, 1, ctx->persist_grid_pct, batch);
+    return launch_resident(ctx, attr_done, fft_regfile_persist_kernel<T, LA, LB, QB0, IO>, blocks, Gm::TPT, lds, io, tw, batch);
 }
 
 // rfft of 2^15 reals: the same kernel with the post-pass as its epilogue (two instances: with / without a row window)
@@ -617,18 +582,9 @@ int launch_split_wide_rfft(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, s
     constexpr size_t lds = split_wide_lds_bytes<Gm>();
     const bool win = io.window != nullptr;
     auto kern = win ? fft_split_wide_persist_kernel<T, LA, LB, QB0, IO, EPI_RFFT, true> : fft_split_wide_persist_kernel<T, LA, LB, QB0, IO, EPI_RFFT, false>;
-    {
-        static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};
-        const int arc = set_dyn_lds_once(ctx, attr_done[win ? 1 : 0], reinterpret_cast<const void *>(kern), lds);
-        if (arc) return arc;
-    }
-    size_t blocks = (size_t)ctx->num_cus * ((160 * 1024) / lds);
-    if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-    if (blocks < 1) blocks = 1;
-    if (blocks > batch) blocks = batch;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Gm::TPT), lds, ctx->stream, io, tw, batch);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
+    static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};
+    const size_t blocks = resident_blocks(ctx->num_cus, (int)((160 * 1024) / lds), ctx->persist_grid_pct, batch);
+    return launch_resident(ctx, attr_done[win ? 1 : 0], kern, blocks, Gm::TPT, lds, io, tw, batch);
 }
 
 template <typename T, int N, int EPI, class IO>
@@ -687,7 +643,7 @@ int dispatch(kofft_hip_ctx *ctx, const IO &io, size_t n, size_t batch)
     default: break;
     }
     const cpx<T> *tw = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::tw, n, &tw);
+    int rc = twiddle_table<T>(ctx, n, &tw);
     if (rc) return rc;
     // n = 32 in f32: still one thread per transform (64 data registers), IO staged through LDS like the small sizes
     if constexpr (sizeof(T) == 4 && !IO::kSlotMinor) if (L == 5 && ctx->small32) return launch_small<T, 32, EPI>(ctx, io, batch, tw);
@@ -759,39 +715,14 @@ inline bool complex_len_ok(size_t n) { return n <= (size_t(1) << (is_pow2(n) ? 2
 // inner lengths the fused real / STFT kernels cover (one workgroup per transform); the rest is composed (real_impl.hip.h)
 template <typename T> inline bool fused_len_ok(size_t m) { return is_pow2(m) && m <= (size_t(1) << max_log2<T>()); }
 
-inline int ensure_real_tmp(kofft_hip_ctx *ctx, size_t bytes)
-{
-    if (ctx->real_tmp_bytes >= bytes) return KOFFT_OK;
-    if (ctx->real_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->real_tmp));
-    ctx->real_tmp = nullptr;
-    ctx->real_tmp_bytes = 0;
-    KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->real_tmp, bytes));
-    ctx->real_tmp_bytes = bytes;
-    return KOFFT_OK;
-}
-
-// hann(win_len), cached per context like a planner table (kind 4): stft_magnitudes' window, one signal or rows
+// hann(win_len), cached per context like a planner table: stft_magnitudes' window, one signal or rows
 inline int hann_table(kofft_hip_ctx *ctx, size_t win_len, const float **out)
 {
-    auto key = std::make_pair(4, win_len);
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        *out = static_cast<const float *>(it->second);
-        return KOFFT_OK;
-    }
-    std::vector<float> w(win_len);
-    kofft_tables::hann_f32(win_len, w.data());
-    void *d = nullptr;
-    KOFFT_HIP_TRY(ctx, hipMalloc(&d, win_len * sizeof(float)));
-    const hipError_t ce = hipMemcpy(d, w.data(), win_len * sizeof(float), hipMemcpyHostToDevice);
-    if (ce != hipSuccess) {  // nothing is cached, nothing is left behind
-        (void)hipFree(d);
-        ctx->last_error = std::string("stft_magnitudes window upload: ") + hipGetErrorString(ce);
-        return KOFFT_ERR_HIP;
-    }
-    ctx->tables[key] = d;
-    *out = static_cast<const float *>(d);
-    return KOFFT_OK;
+    return device_table(ctx, kTableHann, win_len, win_len * sizeof(float), "stft_magnitudes window upload", out, [&](void *d, std::string &why) {
+        std::vector<float> w(win_len);
+        kofft_tables::hann_f32(win_len, w.data());
+        return upload_table(d, w.data(), win_len * sizeof(float), why);
+    });
 }
 
 // ---- typed device-pointer entry points, one translation unit per family ---------------------------------------------

@@ -20,45 +20,21 @@ int dht_check(size_t n, size_t batch, const void *in, const void *out, const kof
 // on the host and uploaded (kofft_hip_set_dht_table_device(ctx, 0)).
 static int get_dht_table(kofft_hip_ctx *ctx, size_t n, const float **out)
 {
-    const auto key = std::make_pair(kDhtTableKind, n);
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        *out = static_cast<const float *>(it->second);
-        return KOFFT_OK;
-    }
-    const size_t ldc = direct_ldc(n);
-    void *d = nullptr;
-    if (ctx->dht_table_device) {
-        KOFFT_HIP_TRY(ctx, hipMalloc(&d, n * ldc * sizeof(float)));
+    const size_t ldc = direct_ldc(n), bytes = n * ldc * sizeof(float);
+    const bool on_device = ctx->dht_table_device;
+    return device_table(ctx, kTableDht, n, bytes, on_device ? "dht table launch" : "dht table upload", out, [&](void *d, std::string &why) {
+        if (!on_device) {
+            std::vector<float> host(n * ldc);
+            kofft_tables::dht_table_f32(n, ldc, host.data());
+            return upload_table(d, host.data(), bytes, why);
+        }
         const float factor = (2.0f * 3.14159265358979323846f) / (float)n;  // hartley.rs:15
         const dim3 grid((unsigned)((ldc + 4 * DHT_BLOCK - 1) / (4 * DHT_BLOCK)), (unsigned)n);
         hipLaunchKernelGGL(dht_table_kernel, grid, dim3(DHT_BLOCK), 0, ctx->stream, static_cast<float *>(d), (int)n, (int)ldc, factor);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            ctx->last_error = std::string("dht table launch: ") + hipGetErrorString(e);
-            return KOFFT_ERR_HIP;
-        }
-    } else {
-        std::vector<float> host;
-        try {
-            host.resize(n * ldc);
-        } catch (const std::bad_alloc &) {
-            return KOFFT_ERR_ALLOC;
-        }
-        kofft_tables::dht_table_f32(n, ldc, host.data());
-        KOFFT_HIP_TRY(ctx, hipMalloc(&d, host.size() * sizeof(float)));
-        // synchronous copy: a table is built once per (context, n)
-        const hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            ctx->last_error = std::string("dht table upload: ") + hipGetErrorString(e);
-            return KOFFT_ERR_HIP;
-        }
-    }
-    ctx->tables[key] = d;
-    *out = static_cast<const float *>(d);
-    return KOFFT_OK;
+        if (e != hipSuccess) why = hipGetErrorString(e);
+        return e == hipSuccess ? KOFFT_OK : KOFFT_ERR_HIP;
+    });
 }
 
 int dht_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)

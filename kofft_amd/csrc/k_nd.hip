@@ -4,6 +4,8 @@
 namespace kofft {
 namespace host {
 
+constexpr size_t kNdTransposeMin = 4096;  // shortest axis that takes the transpose route (measured: 1024 loses, 2048 ties)
+
 // ndfft::fft2d_inplace / fft3d_inplace (ndfft.rs:74-155): one axis at a time, every line of the axis in one launch.
 template <typename T>
 int fft_axis_dev(kofft_hip_ctx *ctx, T *d_data, size_t len, size_t lines, size_t inner, size_t outer_stride, size_t stride,
@@ -25,7 +27,7 @@ int fft_axis_dev(kofft_hip_ctx *ctx, T *d_data, size_t len, size_t lines, size_t
         lines * len * sizeof(cpx<T>) >= (size_t(16) << 20) && len * inner * sizeof(cpx<T>) <= (size_t(1) << 31)) {  // (32-bit buffer descriptors per block)
         return fft_axis2_dev<T>(ctx, d_data, ilog2(len), ilog2(inner), lines / inner, inverse);
     }
-    if (stride == inner && (!fused_len_ok<T>(len) || (ctx->nd_transpose && len >= (size_t)ctx->nd_transpose_min && lines * len * sizeof(cpx<T>) >= (size_t(16) << 20)))) {
+    if (stride == inner && (!fused_len_ok<T>(len) || (ctx->nd_transpose && len >= kNdTransposeMin && lines * len * sizeof(cpx<T>) >= (size_t(16) << 20)))) {
         const size_t outer = lines / inner;  // dense [len][inner] blocks, outer_stride apart
         const size_t cap = 2 * ctx->scratch_chunk_bytes, col_bytes = len * sizeof(cpx<T>);
         size_t P = cap / col_bytes;
@@ -40,10 +42,10 @@ int fft_axis_dev(kofft_hip_ctx *ctx, T *d_data, size_t len, size_t lines, size_t
         // the panel lives in its own scratch: fft_dev below may use the factor path's intermediate (n > 2^14) or the
         // Bluestein work buffer (other lengths)
         {
-            const int prc = ensure_real_tmp(ctx, need);
+            const int prc = ensure(ctx, ctx->real_tmp, need);
             if (prc) return prc;
         }
-        cpx<T> *panel = static_cast<cpx<T> *>(ctx->real_tmp);
+        cpx<T> *panel = static_cast<cpx<T> *>(ctx->real_tmp.p);
         cpx<T> *data = reinterpret_cast<cpx<T> *>(d_data);
         for (size_t o0 = 0; o0 < outer; o0 += OG) {
             const size_t og = (outer - o0 < OG) ? outer - o0 : OG;

@@ -26,13 +26,13 @@ int fft2d_fused_core(kofft_hip_ctx *ctx, cpx<float> *data, int LT)
 {
     const size_t rows = size_t(1) << LT, cols = size_t(1) << LC, elems = rows * cols;
     const cpx<float> *tw_row = nullptr, *tw_col = nullptr;
-    int rc = get_table<float>(ctx, Kind<float>::tw, cols, &tw_row);
+    int rc = twiddle_table<float>(ctx, cols, &tw_row);
     if (rc) return rc;
-    rc = get_table<float>(ctx, Kind<float>::tw, rows, &tw_col);
+    rc = twiddle_table<float>(ctx, rows, &tw_col);
     if (rc) return rc;
-    rc = ensure_real_tmp(ctx, elems * sizeof(cpx<float>));
+    rc = ensure(ctx, ctx->real_tmp, elems * sizeof(cpx<float>));
     if (rc) return rc;
-    cpx<float> *mid = static_cast<cpx<float> *>(ctx->real_tmp);
+    cpx<float> *mid = static_cast<cpx<float> *>(ctx->real_tmp.p);
     {
         constexpr int BLOCK = (1 << LC) / 16;
         constexpr int WG_PER_CU = 512 / BLOCK;  // two wavefronts per SIMD: 256 registers each (244 .. 256 used, nothing spilled)
@@ -40,10 +40,7 @@ int fft2d_fused_core(kofft_hip_ctx *ctx, cpx<float> *data, int LT)
         static_assert(lds * WG_PER_CU <= 160 * 1024, "LDS budget");
         auto kern = fft2d_rows4_kernel<LC, INVERSE>;
         const size_t groups = rows / 4;
-        size_t blocks = (size_t)ctx->num_cus * WG_PER_CU;
-        if (ctx->persist_grid_pct > 0) blocks = blocks * (size_t)ctx->persist_grid_pct / 100;
-        if (blocks < 1) blocks = 1;
-        if (blocks > groups) blocks = groups;
+        const size_t blocks = resident_blocks(ctx->num_cus, WG_PER_CU, ctx->persist_grid_pct, groups);
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BLOCK), lds, ctx->stream, data, mid, tw_row, tw_col, LT - 2, groups,
                            1.0f / (float)cols);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
@@ -71,7 +68,7 @@ bool fft2d_fused_ok(const kofft_hip_ctx *ctx, size_t rows, size_t cols)
     // (8192 rows, round 6: the column pass runs 2^11-point tiles of 8 columns = 64-byte runs -- 8192 x 2048 0.140 -> 0.124 ms, 8192 x 1024 0.076 -> 0.061; a 256 MiB
     // image, 8192 x 4096, no longer fits the Infinity Cache between the passes and LOSES, 0.307 -> 0.369 ms: it keeps rows + two column-tile passes)
     // (KOFFT_HIP_NO_PERSIST=1 forces the generic kernels here too.  The units-per-CU floor of the factor path's tile kernels
-    // (big_persist_min_units) is NOT applied: its 4 x cols column units are 16 .. 64 per CU, and the route measured faster down to
+    // (kBigPersistMinUnits, complex_impl.hip.h) is NOT applied: its 4 x cols column units are 16 .. 64 per CU, and the route measured faster down to
     // 1024-point rows on images of at least 32 MiB -- 4096 x 1024: 0.044 -> 0.034 ms -- which is the rule below.)
     return ctx->nd_fused && ctx->use_persist && ctx->big_persist && (cols == 1024 || cols == 2048 || cols == 4096) && is_pow2(rows) && rows >= 1024 && (rows <= 4096 || (rows == 8192 && cols <= 2048)) &&
            rows / 4 >= (size_t)ctx->num_cus && rows * cols >= (size_t(1) << 22);  // (16 MiB images: 1024 x 2048 0.031 against 0.029 ms, 1024 x 1024 a tie)

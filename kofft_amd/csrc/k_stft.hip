@@ -109,15 +109,13 @@ static int launch_istft_fused(kofft_hip_ctx *ctx, float *d_frames, size_t frames
     static_assert(lds * WG <= 160 * 1024, "LDS budget");
     *done = false;
     const size_t steps = (frames + XPB - 1) / XPB;
-    size_t grid = (size_t)ctx->num_cus * WG;
-    if (ctx->persist_grid_pct > 0) grid = grid * (size_t)ctx->persist_grid_pct / 100;
-    if (grid < 1) grid = 1;
+    const size_t grid = resident_blocks(ctx->num_cus, WG, ctx->persist_grid_pct, kNoNeedCap);
     const size_t fpw = ((steps + grid - 1) / grid) * XPB;  // frames per workgroup: whole steps
     // (fewer than four steps per run: the two kernels are as fast or faster -- 1024 / 256 x 3000 frames 0.023 against 0.030 ms fused)
     if (fpw < 4 * XPB || fpw < (size_t)(2 * C)) return KOFFT_OK;
     const size_t runs = (frames + fpw - 1) / fpw;
     const cpx<float> *tw = nullptr;
-    int rc = get_table<float>(ctx, Kind<float>::tw, N, &tw);
+    int rc = twiddle_table<float>(ctx, N, &tw);
     if (rc) return rc;
     auto kern = istft_fused_kernel<L, RL, CL, WG>;
     {
@@ -225,9 +223,9 @@ int stft_mag_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t 
     if (!fused_len_ok<float>(win_len)) {
         // any other window length: the composed STFT into scratch, then magnitudes + maximum in one pass (in frame chunks)
         const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, win_len * 8, frames);
-        int rc = ensure_real_tmp(ctx, chunk * win_len * 8);
+        int rc = ensure(ctx, ctx->real_tmp, chunk * win_len * 8);
         if (rc) return rc;
-        float *spec = static_cast<float *>(ctx->real_tmp);
+        float *spec = static_cast<float *>(ctx->real_tmp.p);
         for (size_t f0 = 0; f0 < frames; f0 += chunk) {
             const size_t nf = (frames - f0 < chunk) ? frames - f0 : chunk;
             rc = stft_composed_dev(ctx, d_samples, len, d_win, win_len, f0 * hop, hop, spec, nf);

@@ -69,9 +69,9 @@ int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, si
         // any other window length: the composed frames in the context's scratch, at most scratch_chunk_bytes at a time, then their kept bins
         const size_t chunk = composed_chunk(ctx, win_len, total);
         if ((chunk * bins + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-        int rc = ensure_real_tmp(ctx, chunk * win_len * 8);
+        int rc = ensure(ctx, ctx->real_tmp, chunk * win_len * 8);
         if (rc) return rc;
-        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp);
+        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp.p);
         for (size_t t0 = 0; t0 < total; t0 += chunk) {
             const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
             rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_window, win_len, hop, spec, t0, nt);

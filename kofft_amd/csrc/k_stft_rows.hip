@@ -174,9 +174,9 @@ int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, s
     unsigned *max_bits = reinterpret_cast<unsigned *>(d_max);
     if (!fused_len_ok<float>(win_len)) {
         const size_t chunk = composed_chunk(ctx, win_len, total);
-        rc = ensure_real_tmp(ctx, chunk * win_len * 8);
+        rc = ensure(ctx, ctx->real_tmp, chunk * win_len * 8);
         if (rc) return rc;
-        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp);
+        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp.p);
         const size_t half = win_len / 2;
         for (size_t t0 = 0; t0 < total; t0 += chunk) {
             const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
@@ -239,14 +239,8 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
     size_t rows_per = rows;
     if (keep_frames && frames > 0) {
         rows_per = scratch_chunk_rows(ctx->scratch_chunk_bytes, frames * win_len * 8, rows);
-        const size_t bytes = rows_per * frames * win_len * 8;
-        if (ctx->rows_tmp_bytes < bytes) {
-            if (ctx->rows_tmp) KOFFT_HIP_TRY(ctx, hipFree(ctx->rows_tmp));
-            ctx->rows_tmp = nullptr;
-            ctx->rows_tmp_bytes = 0;
-            KOFFT_HIP_TRY(ctx, hipMalloc(&ctx->rows_tmp, bytes));
-            ctx->rows_tmp_bytes = bytes;
-        }
+        const int trc = ensure(ctx, ctx->rows_tmp, rows_per * frames * win_len * 8);
+        if (trc) return trc;
     }
     if ((rows_per * out_len + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     for (size_t r0 = 0; r0 < rows; r0 += rows_per) {
@@ -255,7 +249,7 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
         if (frames > 0) {
             float *dst = d_frames + r0 * frames * in_frame;
             if (keep_frames) {
-                dst = static_cast<float *>(ctx->rows_tmp);
+                dst = static_cast<float *>(ctx->rows_tmp.p);
                 if (half) {  // the completed frames F[k] = H[k], k <= n/2; conj(H[n - k]) above
                     const int erc = expand_half(ctx, time_frames, dst, nr * frames, win_len);
                     if (erc) return erc;

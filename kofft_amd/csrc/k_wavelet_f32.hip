@@ -242,8 +242,8 @@ int dwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx,
     // per level, through two scratch buffers of batch * lens[1] floats
     float *tmp = nullptr;
     if (levels > 1) {
-        if ((rc = ensure_real_tmp(ctx, 2 * batch * lens[1] * sizeof(float)))) return rc;
-        tmp = static_cast<float *>(ctx->real_tmp);
+        if ((rc = ensure(ctx, ctx->real_tmp, 2 * batch * lens[1] * sizeof(float)))) return rc;
+        tmp = static_cast<float *>(ctx->real_tmp.p);
     }
     const float *src = d_in;
     size_t off = 0;
@@ -278,8 +278,8 @@ int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float
     // per level, coarsest first, through two scratch buffers of batch * total / 2 floats
     float *tmp = nullptr;
     if (levels > 1) {
-        if ((rc = ensure_real_tmp(ctx, batch * total * sizeof(float)))) return rc;
-        tmp = static_cast<float *>(ctx->real_tmp);
+        if ((rc = ensure(ctx, ctx->real_tmp, batch * total * sizeof(float)))) return rc;
+        tmp = static_cast<float *>(ctx->real_tmp.p);
     }
     const float *src = d_approx;
     size_t c = n;

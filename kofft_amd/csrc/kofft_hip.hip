@@ -173,9 +173,9 @@ int stage_host(kofft_hip_ctx *ctx, size_t batch, int n, const HostArray<T> *a, c
             if (a[k].down && bytes(k)) std::memcpy(a[k].down, h + lay.off[k], bytes(k));
         return KOFFT_OK;
     }
-    int rc = ensure_stage(ctx, lay.total);
+    int rc = ensure(ctx, ctx->stage, lay.total);
     if (rc) return rc;
-    const T *d_side = point_at(ctx->stage);
+    const T *d_side = point_at(ctx->stage.p);
     auto side_up = [&] { return side_bytes ? hipMemcpyAsync(const_cast<T *>(d_side), side, side_bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
     // rows [r0, r0 + nr) of every array that travels in this direction
     auto copy_rows = [&](bool up, size_t r0, size_t nr, hipStream_t st) {
@@ -196,7 +196,8 @@ int stage_host(kofft_hip_ctx *ctx, size_t batch, int n, const HostArray<T> *a, c
     }
     if (pipeline_ok && use_host_pipeline(ctx, moved, batch, min_row * sizeof(T))) {
         KOFFT_HIP_TRY(ctx, side_up());
-        const size_t chunk = host_chunk_rows(batch, ctx->host_chunks);
+        constexpr int kHostChunks = 8;  // pieces of a pipelined host batch
+        const size_t chunk = host_chunk_rows(batch, kHostChunks);
         auto rows = [&](size_t c) { return (batch - c * chunk < chunk) ? batch - c * chunk : chunk; };
         const int prc = pipeline_chunks(
             ctx, (batch + chunk - 1) / chunk, [&](size_t c, hipStream_t st) { return copy_rows(true, c * chunk, rows(c), st); },
@@ -643,11 +644,7 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->tables) (void)hipFree(kv.second);
     spectral_drop(ctx);
-    drop_host_buffers(ctx);
-    if (ctx->big_tmp && !ctx->big_tmp_external) (void)hipFree(ctx->big_tmp);
-    if (ctx->blue_tmp) (void)hipFree(ctx->blue_tmp);
-    if (ctx->real_tmp) (void)hipFree(ctx->real_tmp);
-    if (ctx->rows_tmp) (void)hipFree(ctx->rows_tmp);
+    drop_buffers(ctx);
     if (ctx->persist_claim_counters) (void)hipFree(ctx->persist_claim_counters);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -681,9 +678,8 @@ int kofft_hip_synchronize(kofft_hip_ctx *ctx)
 int kofft_hip_exp_set_big_tmp(kofft_hip_ctx *ctx, void *d_ptr, size_t bytes)
 {
     if (!ctx) return KOFFT_ERR_NULL;
-    if (ctx->big_tmp && !ctx->big_tmp_external) (void)hipFree(ctx->big_tmp);
-    ctx->big_tmp = d_ptr;
-    ctx->big_tmp_bytes = bytes;
+    if (!ctx->big_tmp_external) release_buf<HipAlloc>(ctx->big_tmp);
+    ctx->big_tmp = DevBuf{d_ptr, bytes};
     ctx->big_tmp_external = d_ptr != nullptr;
     return KOFFT_OK;
 }
@@ -711,14 +707,7 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
     if (!ctx) return KOFFT_ERR_NULL;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    drop_host_buffers(ctx);
-    void **bufs[] = {&ctx->big_tmp, &ctx->blue_tmp, &ctx->real_tmp, &ctx->rows_tmp};
-    size_t *sizes[] = {&ctx->big_tmp_bytes, &ctx->blue_tmp_bytes, &ctx->real_tmp_bytes, &ctx->rows_tmp_bytes};
-    for (int i = 0; i < 4; ++i) {
-        if (*bufs[i] && !(i == 0 && ctx->big_tmp_external)) (void)hipFree(*bufs[i]);
-        *bufs[i] = nullptr;
-        *sizes[i] = 0;
-    }
+    drop_buffers(ctx);
     spectral_drop(ctx);  // the chirp-Z tables (up to 4 x 128 MiB) and the Goertzel coefficient arrays: rebuilt by the next call that needs them
     ctx->big_tmp_external = false;  // (KOFFT_EXP_API builds: the script's intermediate is forgotten, the next call allocates its own)
     ctx->big_probe_n = 0;

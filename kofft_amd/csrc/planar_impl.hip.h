@@ -108,9 +108,9 @@ int planar_composed_dev(kofft_hip_ctx *ctx, const T *re_in, const T *im_in, T *r
 {
     // rows per chunk as dct2_composed_dev: scratch_chunk_bytes of interleaved scratch at most (one row where a row is longer)
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(cpx<T>), batch);
-    int rc = ensure_real_tmp(ctx, chunk * n * sizeof(cpx<T>));
+    int rc = ensure(ctx, ctx->real_tmp, chunk * n * sizeof(cpx<T>));
     if (rc) return rc;
-    cpx<T> *z = static_cast<cpx<T> *>(ctx->real_tmp);
+    cpx<T> *z = static_cast<cpx<T> *>(ctx->real_tmp.p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk, total = nb * n, off = b0 * n;
         const dim3 grid(planar_flat_blocks(ctx, total));

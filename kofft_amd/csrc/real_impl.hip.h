@@ -121,7 +121,7 @@ int rfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_wi
     // (last factor on row pairs) + 217-227 us (post-pass kernel) at n = 2^17 .. 2^20 -- the mirror of a line-aligned tile starts 8 bytes into
     // a line, and its partial-line stores cost more than the pass they save; commit 2191bc6 has it, DESIGN 10 item 4 the counters.)
     const cpx<T> *rtab = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::rt, m, &rtab);
+    int rc = rfft_table<T>(ctx, m, &rtab);
     if (rc) return rc;
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(T), batch);
     if ((chunk * (m + 1) + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
@@ -134,10 +134,10 @@ int rfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_wi
     const bool fuse_window = d_window && is_pow2(m) && m > (size_t(1) << max_log2<T>()) && ctx->blue_fused;
     // scratch: [windowed input (only with an unfused window)] [Y]
     const size_t zbytes = (d_window && !fuse_window) ? chunk * n * sizeof(T) : 0, ybytes = chunk * m * sizeof(cpx<T>);
-    rc = ensure_real_tmp(ctx, zbytes + ybytes);
+    rc = ensure(ctx, ctx->real_tmp, zbytes + ybytes);
     if (rc) return rc;
-    T *z = static_cast<T *>(ctx->real_tmp);
-    T *y = reinterpret_cast<T *>(static_cast<char *>(ctx->real_tmp) + zbytes);
+    T *z = static_cast<T *>(ctx->real_tmp.p);
+    T *y = reinterpret_cast<T *>(static_cast<char *>(ctx->real_tmp.p) + zbytes);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk;
         const T *src = d_in + b0 * n;
@@ -145,7 +145,7 @@ int rfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_wi
             // Round 6: m = 2^15 (f32) / 2^14 (f64) in ONE pass -- the register-file kernel with the post-pass as its epilogue (fft_regfile.hip.h:
             // RfftRowIO; Y[k] and Y[m - k] are in the same workgroup), the window on its loads: no intermediate, no rfft_post_kernel launch
             const cpx<T> *tw = nullptr;
-            rc = get_table<T>(ctx, Kind<T>::tw, m, &tw);
+            rc = twiddle_table<T>(ctx, m, &tw);
             if (rc) return rc;
             constexpr int RLA = sizeof(T) == 4 ? 8 : 7, RLB = 7, RQB0 = 4;  // as fft_dev routes the plain transform
             cpx<T> *dst = reinterpret_cast<cpx<T> *>(d_out) + b0 * (m + 1);
@@ -161,7 +161,7 @@ int rfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_wi
         }
         if (regfile_window && nb >= (size_t)ctx->num_cus * 2) {
             const cpx<T> *tw = nullptr;
-            rc = get_table<T>(ctx, Kind<T>::tw, m, &tw);
+            rc = twiddle_table<T>(ctx, m, &tw);
             if (rc) return rc;
             constexpr int RLA = sizeof(T) == 4 ? 8 : 7, RLB = 7, RQB0 = 4;  // as fft_dev routes the plain transform
             RowWindowIO<T> io{{{}, reinterpret_cast<const cpx<T> *>(src), reinterpret_cast<cpx<T> *>(y), (int)m, (T)1}, reinterpret_cast<const cpx<T> *>(d_window)};
@@ -196,19 +196,19 @@ int irfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, si
 {
     const size_t m = n / 2;
     const cpx<T> *rtab = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::rt, m, &rtab);
+    int rc = rfft_table<T>(ctx, m, &rtab);
     if (rc) return rc;
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(T), batch);
     if ((chunk * m + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-    rc = ensure_real_tmp(ctx, chunk * m * sizeof(cpx<T>));
+    rc = ensure(ctx, ctx->real_tmp, chunk * m * sizeof(cpx<T>));
     if (rc) return rc;
-    cpx<T> *scratch = static_cast<cpx<T> *>(ctx->real_tmp);
+    cpx<T> *scratch = static_cast<cpx<T> *>(ctx->real_tmp.p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk;
         if (m == (size_t(2) << max_log2<T>()) && ctx->use_regfile && nb >= (size_t)ctx->num_cus * 2) {
             // m = 2^15 (f32) / 2^14 (f64): the pre-pass on the register-file kernel's loads (fft_regfile.hip.h: IrfftRowIO) -- one pass instead of two
             const cpx<T> *tw = nullptr;
-            rc = get_table<T>(ctx, Kind<T>::tw, m, &tw);
+            rc = twiddle_table<T>(ctx, m, &tw);
             if (rc) return rc;
             constexpr int RLA = sizeof(T) == 4 ? 8 : 7, RLB = 7, RQB0 = 4;  // as fft_dev routes the plain transform
             const T scale = (T)1 / (T)(float)m;                              // fft.rs:1167
@@ -243,7 +243,7 @@ int rfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, siz
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!fused_len_ok<T>(m)) return rfft_composed_dev<T>(ctx, d_in, d_out, d_window, n, batch);
     const cpx<T> *rtab = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::rt, m, &rtab);
+    int rc = rfft_table<T>(ctx, m, &rtab);
     if (rc) return rc;
     RfftIO<T> io{{}, d_in, d_window, reinterpret_cast<cpx<T> *>(d_out), rtab, (int)m};
     return dispatch<T, EPI_RFFT>(ctx, io, m, batch);
@@ -261,7 +261,7 @@ int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batc
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!fused_len_ok<T>(m)) return irfft_composed_dev<T>(ctx, d_in, d_out, n, batch);
     const cpx<T> *rtab = nullptr;
-    int rc = get_table<T>(ctx, Kind<T>::rt, m, &rtab);
+    int rc = rfft_table<T>(ctx, m, &rtab);
     if (rc) return rc;
     // threads per transform of the persistent kernels (m/16; m/8 up to m = 512)
     const int tpt = (int)(m <= 64 ? m / 4 : m <= 512 ? m / 8 : m / 16);

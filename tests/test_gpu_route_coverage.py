@@ -29,7 +29,7 @@ def _rdt(dtype):
 
 
 def _persist_batch(log2_len):
-    """Transforms that give the persistent factor kernels their CUs x 32 units (complex_impl.hip.h: big_persist_min_units) at the
+    """Transforms that give the persistent factor kernels their CUs x 32 units (complex_impl.hip.h: kBigPersistMinUnits) at the
     smaller of the two factors' unit counts, plus one so that the batch is not a multiple of anything."""
     return max(9, (8192 >> (log2_len // 2 - 1)) + 1)
 

@@ -1,6 +1,6 @@
 """The row-wise families (DCT-II, the analytic signal, the real cepstrum, the direct DCT / DST, the wavelets) on SHARED context state:
-the composed routes' scratch (ctx->real_tmp, grown by ensure_real_tmp), the table cache (twiddle / rfft kinds 0-3, Bluestein 5-8,
-DCT-II 13, the direct kinds 20-27), the per-process kernel attributes (set_dyn_lds_once), stream switches, release_scratch, hipGraph
+the composed routes' scratch (ctx->real_tmp, grown by ensure), the table cache (host_cache.h, TableKind: the twiddle / rfft, Bluestein,
+DCT-II and direct kinds), the per-process kernel attributes (set_dyn_lds_once), stream switches, release_scratch, hipGraph
 capture, two threads at once and the host pipeline.  Every output is compared bit for bit with the family's oracle, and the host
 calls run twice."""
 import subprocess

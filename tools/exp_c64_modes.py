@@ -2,7 +2,7 @@
   realloc   ONE context, its scratch released and re-allocated --reps times with dummy allocations in between (so the
             intermediate moves while the twiddle table stays): does the mode follow the intermediate?
   env:K=V,K=V   --contexts fresh contexts created under these environment knobs (e.g. KOFFT_HIP_BIG_CHUNK_MB=128,
-            a -DKOFFT_EXP_API build with big_mid_nt forced to 0; the environment knob was removed in round 4), each timed on `batch` transforms per call
+            a -DKOFFT_EXP_API build with the last factor's nt_load forced off in fft_big_core; the environment knob was removed in round 4), each timed on `batch` transforms per call
   dst       one context, the OUTPUT buffer re-allocated --reps times
 Run as `rocprofv3 --kernel-trace ... -- python3 tools/exp_c64_modes.py ...` (python3 itself after `--`: no env / shebang hop), parse with `exp_c64_ctx.py --parse`.
 
