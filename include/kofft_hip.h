@@ -37,6 +37,7 @@
 #define KOFFT_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -251,6 +252,51 @@ int kofft_hip_set_hilbert_fused(kofft_hip_ctx *ctx, int on);
 int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch);
 int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
 int kofft_hip_set_cepstrum_fused(kofft_hip_ctx *ctx, int on);
+
+/* ---- mel filterbank and MFCC ------------------------------------------------------
+ * cepstrum::mel_filterbank / mfcc / mfcc_batch (cepstrum.rs:36-98), f32 only like the reference, on `rows` contiguous rows of n_fft
+ * magnitudes -- what kofft_hip_dev_stft_magnitudes_rows_f32 writes, rows x frames flattened.  The filter edges are an INPUT: bins is
+ * a HOST pointer (in both forms) to num_mel + 2 nondecreasing values, read before the call returns.  Everything after the edges is
+ * the reference's arithmetic bit for bit, all f32, never fused:
+ *   energies (rows x num_mel): filter m has a = bins[m], b = bins[m + 1], c = bins[m + 2].  b == a or c == b: +0 (the reference's
+ *     `continue`).  Otherwise e = +0, then e += ((k - a) as f32 / (b - a) as f32) * x[k] for k = a .. b - 1 and e += ((c - k) as f32 /
+ *     (c - b) as f32) * x[k] for k = b .. c - 1, in that order; terms with k >= n_fft are skipped, their edges still set the
+ *     denominators; the integer conversions round to nearest, the division is correctly rounded.
+ *   coeffs (rows x num_coeffs): l[i] = logf(e[i] + 1e-12f) with the libm crate's logf (as the cepstrum), then out[j] = sum_i l[i] *
+ *     C[i][j], i ascending from a +0 seed, one multiply and one add per term, C the table of kofft_hip_dct_direct_f32(ctx, 2, ..) at
+ *     n = num_mel (dct::dct2, dct.rs:134-146), j < num_coeffs.
+ * NaNs come out in the reference's places.  Checks, in this order and before the context or the device is touched: rows == 0 ->
+ * KOFFT_OK; (mfcc) num_coeffs > num_mel -> INVALID_VALUE (cepstrum.rs:79); bins null -> KOFFT_ERR_NULL; bins not nondecreasing ->
+ * INVALID_VALUE (the reference underflows a usize); n_fft > 2^24 or num_mel > 4096 (the bound of the direct table) ->
+ * KOFFT_ERR_UNSUPPORTED; a null data pointer or context -> KOFFT_ERR_NULL; (device pointers) input and output overlap ->
+ * INVALID_VALUE.  num_mel == 0 and num_coeffs == 0 are KOFFT_OK with nothing written; n_fft == 0 gives +0 energies and the MFCCs of
+ * logf(1e-12f) rows, as the reference.  The kofft_hip_dev_* forms are asynchronous on the context's stream (named so for the reason
+ * given at the chirp-Z entries; their guard-band cases live in tests/test_gpu_mfcc_footprint.py).  A context keeps the plans of its
+ * four most recently used (bins, n_fft, num_mel) on the device until kofft_hip_release_scratch or kofft_hip_destroy.
+ * Routes of the MFCC, the same bytes.  The fused kernel (a lane owns a row from its magnitudes to its coefficients; energies never
+ * reach memory) fits num_mel <= 128: 256 bytes of LDS per filter and workgroup next to the 8.25 KiB staging tile, 40.25 KiB at 128,
+ * three workgroups per CU.  The composed route runs through the context's scratch: filterbank kernel, pointwise log, the direct
+ * DCT-II kernels on rows of num_mel, a copy of the first num_coeffs columns.  kofft_hip_set_mfcc_fused(ctx, mode): 1, the default,
+ * takes the fused kernel where it measured faster (num_mel <= 80 and num_coeffs <= 16: DESIGN 5.21) and the composed route
+ * elsewhere; 0 every call composed; 2 the fused kernel wherever it fits (A/B measurements and tests); anything else ->
+ * INVALID_VALUE. */
+int kofft_hip_mel_filterbank_f32(kofft_hip_ctx *ctx, const float *mags, float *energies, size_t n_fft, size_t rows, const uint64_t *bins,
+                                 size_t num_mel);
+int kofft_hip_dev_mel_filterbank_f32(kofft_hip_ctx *ctx, const float *d_mags, float *d_energies, size_t n_fft, size_t rows,
+                                     const uint64_t *bins, size_t num_mel);
+int kofft_hip_mfcc_f32(kofft_hip_ctx *ctx, const float *mags, float *coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+                       size_t num_coeffs);
+int kofft_hip_dev_mfcc_f32(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins,
+                           size_t num_mel, size_t num_coeffs);
+int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on);
+/* Host only: the edges of cepstrum.rs:38-50, bins = num_filters + 2 values: mel_max = 2595 * log10f(1 + (rate / 2) / 700), point i =
+ * 700 * (powf(10, ((mel_max * i) / (num_filters + 1)) / 2595) - 1), bins[i] = floorf(point * (n_fft + 1) / rate) as usize, all f32 in
+ * Rust's parse order, the cast saturating (NaN and negatives give 0).  log10f and powf are GLIBC's, where the reference calls the
+ * libm crate's: the result equals the crate's edges wherever the exact edge is not within an ulp of an integer.  The known case
+ * that is not pinned: with an odd n_fft the last edge is the integer (n_fft + 1) / 2 in exact arithmetic and hangs on the last bit
+ * of both functions.  A Rust caller should take the edges from the shim (kofft-hip: mel_bins), which computes them with the crate
+ * itself.  num_filters > 4096 -> KOFFT_ERR_UNSUPPORTED; bins null -> KOFFT_ERR_NULL. */
+int kofft_hip_mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins);
 
 /* ---- direct DCT-I..IV and DST-I..IV ---------------------------------------------
  * dct::dct1 .. dct4 (dct.rs:108-176) and dst::dst1 .. dst4 (dst.rs:89-146), f32 only like

@@ -16,6 +16,8 @@
 //   kofft::HipFftImpl<float>::dct2               DctPlanner::plan_dct2, dct.rs:61-105
 //   kofft::HipFftImpl<float>::hilbert_analytic   hilbert::hilbert_analytic, hilbert.rs:13-47
 //   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
+//   kofft::HipFftImpl<float>::mel_filterbank / mfcc, kofft::mel_bins   cepstrum::mel_filterbank / mfcc / mfcc_batch, cepstrum.rs:36-98
+//                                                (the filter edges are an argument; mel_bins computes the reference-shaped ones)
 //   kofft::HipFftImpl<float>::dct_direct         dct::dct1..dct4, dct.rs:108-176 (the direct sums)
 //   kofft::HipFftImpl<float>::dst_direct         dst::dst1..dst4, dst.rs:89-146
 //   kofft::HipFftImpl<float>::dwt / idwt         wavelet::<name>_forward / _inverse, wavelet.rs:12-33, 154-535
@@ -30,6 +32,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -335,6 +338,44 @@ public:
         if (n & (n - 1)) return Result::Err(FftError::NonPowerOfTwoNoStd);
         return st(kofft_hip_cepstrum_f32(ctx_, input.data(), output.data(), n, batch));
     }
+    // cepstrum::mel_filterbank's sums (cepstrum.rs:51-67), f32 only like the reference: `rows` contiguous rows of mags.size() / rows
+    // magnitudes in, rows of bins.size() - 2 energies out, with the filter edges `bins` (num_mel + 2 nondecreasing values; kofft::mel_bins
+    // gives the reference-shaped ones).  MismatchedLengths for rows that do not divide the input, fewer than two edges or an output of
+    // another size; InvalidValue for edges out of order; more than 4096 filters or rows over 2^24 throw DeviceError.
+    Result mel_filterbank(const std::vector<float> &mags, const std::vector<uint64_t> &bins, std::vector<float> &energies, size_t rows = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "the mel filterbank is f32-only (cepstrum.rs:36)");
+        if (rows == 0 || mags.size() % rows != 0 || bins.size() < 2 || energies.size() != rows * (bins.size() - 2))
+            return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_mel_filterbank_f32(ctx_, mags.data(), energies.data(), mags.size() / rows, rows, bins.data(), bins.size() - 2));
+    }
+    // cepstrum::mfcc / mfcc_batch (cepstrum.rs:72-98): the energies, logf(e + 1e-12f) with the libm crate's logf, the first num_coeffs
+    // outputs of dct::dct2; coeffs: rows of num_coeffs.  InvalidValue for num_coeffs > bins.size() - 2 (cepstrum.rs:79), checked first
+    // like the reference; otherwise as mel_filterbank.
+    Result mfcc(const std::vector<float> &mags, const std::vector<uint64_t> &bins, size_t num_coeffs, std::vector<float> &coeffs, size_t rows = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "mfcc is f32-only (cepstrum.rs:72)");
+        if (bins.size() >= 2 && num_coeffs > bins.size() - 2) return Result::Err(FftError::InvalidValue);
+        if (rows == 0 || mags.size() % rows != 0 || bins.size() < 2 || coeffs.size() != rows * num_coeffs)
+            return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_mfcc_f32(ctx_, mags.data(), coeffs.data(), mags.size() / rows, rows, bins.data(), bins.size() - 2, num_coeffs));
+    }
+    // ... on device memory, asynchronous on the context's stream (bins stays a host vector, read before the call returns); input and
+    // output must not overlap (InvalidValue)
+    Result mel_filterbank_dev(const float *d_mags, float *d_energies, size_t n_fft, size_t rows, const std::vector<uint64_t> &bins) const
+    {
+        static_assert(std::is_same<T, float>::value, "the mel filterbank is f32-only (cepstrum.rs:36)");
+        if (bins.size() < 2) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_dev_mel_filterbank_f32(ctx_, d_mags, d_energies, n_fft, rows, bins.data(), bins.size() - 2));
+    }
+    Result mfcc_dev(const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const std::vector<uint64_t> &bins, size_t num_coeffs) const
+    {
+        static_assert(std::is_same<T, float>::value, "mfcc is f32-only (cepstrum.rs:72)");
+        if (bins.size() < 2) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_dev_mfcc_f32(ctx_, d_mags, d_coeffs, n_fft, rows, bins.data(), bins.size() - 2, num_coeffs));
+    }
+    // 1 (the default): the fused kernel where it measured faster (up to 80 filters, 16 coefficients); 0: every MFCC composed; 2: fused wherever it fits (the same bytes)
+    Result set_mfcc_fused(int mode) const { return st(kofft_hip_set_mfcc_fused(ctx_, mode)); }
     // dct::dct1 .. dct4 (dct.rs:108-176; type 1 .. 4), the direct sums, f32 only like the reference: `batch` contiguous rows of n reals
     // in, rows of n reals out.  MismatchedLengths for rows that do not divide the input or an output of another size; InvalidValue for
     // a type outside 1 .. 4; n == 0 is an empty result except for type 3 (EmptyInput: dct3 indexes input[0] unchecked); n > 4096
@@ -780,6 +821,16 @@ inline std::vector<float> tukey(size_t len, float alpha) { return window(KOFFT_W
 inline std::vector<float> bartlett(size_t len) { return window(KOFFT_WINDOW_BARTLETT, len); }
 inline std::vector<float> bohman(size_t len) { return window(KOFFT_WINDOW_BOHMAN, len); }
 inline std::vector<float> nuttall(size_t len) { return window(KOFFT_WINDOW_NUTTALL, len); }
+// The filter edges of cepstrum::mel_filterbank (cepstrum.rs:38-50) for rows of n_fft magnitudes: num_filters + 2 values, f32 in the
+// reference's order with GLIBC's log10f / powf where the reference calls the libm crate's -- equal to the crate's wherever the exact
+// edge is not within an ulp of an integer; the last edge of an odd n_fft is the known case that is not pinned (kofft_hip.h).  More
+// than 4096 filters throw std::invalid_argument.
+inline std::vector<uint64_t> mel_bins(float sample_rate, size_t n_fft, size_t num_filters)
+{
+    std::vector<uint64_t> bins(num_filters + 2);
+    if (kofft_hip_mel_bins_f32(sample_rate, n_fft, num_filters, bins.data()) != 0) throw std::invalid_argument("kofft::mel_bins: more than 4096 filters");
+    return bins;
+}
 
 // stft::stft (stft.rs:76-105): output frames are resized to the window length and overwritten
 inline Result stft(const std::vector<float> &signal, const std::vector<float> &window, size_t hop_size,

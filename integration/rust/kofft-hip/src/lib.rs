@@ -56,6 +56,11 @@ extern "C" {
     fn kofft_hip_set_czt_route(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
     fn kofft_hip_dht_f32(ctx: *mut KofftHipCtx, input: *const f32, out: *mut f32, n: usize, batch: usize) -> c_int;
     fn kofft_hip_set_dht_table_device(ctx: *mut KofftHipCtx, on: c_int) -> c_int;
+    fn kofft_hip_mel_filterbank_f32(ctx: *mut KofftHipCtx, mags: *const f32, energies: *mut f32, n_fft: usize, rows: usize, bins: *const u64,
+                                    num_mel: usize) -> c_int;
+    fn kofft_hip_mfcc_f32(ctx: *mut KofftHipCtx, mags: *const f32, coeffs: *mut f32, n_fft: usize, rows: usize, bins: *const u64,
+                          num_mel: usize, num_coeffs: usize) -> c_int;
+    fn kofft_hip_set_mfcc_fused(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
     fn kofft_hip_window_f32(kind: c_int, len: usize, param: f32, out: *mut f32) -> c_int;
     fn kofft_hip_fftnd_c32(ctx: *mut KofftHipCtx, data: *mut f32, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     fn kofft_hip_fftnd_c64(ctx: *mut KofftHipCtx, data: *mut f64, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
@@ -419,6 +424,101 @@ impl HipFftImpl<f32> {
     /// `true` (the default): the Hartley table of a new length is built by a kernel; `false`: on the host and uploaded (the same bytes).
     pub fn set_dht_table_device(&self, on: bool) -> Result<(), FftError> {
         status(self.ctx, unsafe { kofft_hip_set_dht_table_device(self.ctx, on as c_int) })
+    }
+}
+
+impl HipFftImpl<f32> {
+    /// `cepstrum::mel_filterbank`'s sums (kofft cepstrum.rs:51-67) on every row of `n_fft` magnitudes in `mags`, with the filter
+    /// edges `bins` (`num_mel + 2` nondecreasing values): `out` receives rows of `num_mel` energies, bit for bit.  Edges out of order
+    /// are `InvalidValue` (the reference underflows a `usize`); more than 4096 filters or rows over 2^24 panic.
+    pub fn mel_filterbank_batch(&self, mags: &[f32], n_fft: usize, bins: &[u64], out: &mut [f32]) -> Result<(), FftError> {
+        if bins.len() < 2 || (n_fft != 0 && mags.len() % n_fft != 0) || (n_fft == 0 && !mags.is_empty()) { return Err(FftError::MismatchedLengths); }
+        let num_mel = bins.len() - 2;
+        let rows = if n_fft != 0 { mags.len() / n_fft } else if num_mel != 0 { out.len() / num_mel } else { 0 };
+        if out.len() != rows * num_mel { return Err(FftError::MismatchedLengths); }
+        status(self.ctx, unsafe { kofft_hip_mel_filterbank_f32(self.ctx, mags.as_ptr(), out.as_mut_ptr(), n_fft, rows, bins.as_ptr(), num_mel) })
+    }
+
+    /// `cepstrum::mfcc` (kofft cepstrum.rs:72-85) on every row: `out` receives rows of `num_coeffs` coefficients.  `num_coeffs >
+    /// num_mel` is `InvalidValue`, checked first like the reference (cepstrum.rs:79).
+    pub fn mfcc_rows(&self, mags: &[f32], n_fft: usize, bins: &[u64], num_coeffs: usize, out: &mut [f32]) -> Result<(), FftError> {
+        if bins.len() >= 2 && num_coeffs > bins.len() - 2 { return Err(FftError::InvalidValue); }
+        if bins.len() < 2 || (n_fft != 0 && mags.len() % n_fft != 0) || (n_fft == 0 && !mags.is_empty()) { return Err(FftError::MismatchedLengths); }
+        let rows = if n_fft != 0 { mags.len() / n_fft } else if num_coeffs != 0 { out.len() / num_coeffs } else { 0 };
+        if out.len() != rows * num_coeffs { return Err(FftError::MismatchedLengths); }
+        status(self.ctx, unsafe {
+            kofft_hip_mfcc_f32(self.ctx, mags.as_ptr(), out.as_mut_ptr(), n_fft, rows, bins.as_ptr(), bins.len() - 2, num_coeffs)
+        })
+    }
+
+    /// 1 (the default): the fused kernel where it measured faster; 0: every MFCC composed; 2: fused wherever it fits (the same bytes).
+    pub fn set_mfcc_fused(&self, mode: i32) -> Result<(), FftError> {
+        status(self.ctx, unsafe { kofft_hip_set_mfcc_fused(self.ctx, mode as c_int) })
+    }
+}
+
+/// `kofft::cepstrum`'s mel functions (cepstrum.rs:36-98) on the device, the reference's three functions with a context in front.
+/// The edges are computed HERE, with the `libm` crate's own `log10f` / `powf` / `floorf` -- the functions the reference calls -- and
+/// passed down, so the results are the reference's bit for bit at every setting, the odd `n_fft` whose last edge the library's
+/// glibc-based helper (`kofft_hip_mel_bins_f32`) cannot pin included.
+pub mod cepstrum {
+    use super::HipFftImpl;
+    use kofft::fft::FftError;
+    use libm::{floorf, log10f, powf};
+
+    /// cepstrum.rs:38-50, verbatim: the `num_filters + 2` filter edges for rows of `n_fft` magnitudes.
+    pub fn mel_bins(sample_rate: f32, n_fft: usize, num_filters: usize) -> Vec<u64> {
+        let f_min = 0.0;
+        let f_max = sample_rate / 2.0;
+        let mel_min = 2595.0 * log10f(1.0 + f_min / 700.0);
+        let mel_max = 2595.0 * log10f(1.0 + f_max / 700.0);
+        let mut bins = vec![0u64; num_filters + 2];
+        for (i, bin) in bins.iter_mut().enumerate() {
+            let mut mel_point = mel_min + (mel_max - mel_min) * i as f32 / (num_filters + 1) as f32;
+            mel_point = 700.0 * (powf(10.0, mel_point / 2595.0) - 1.0);
+            *bin = floorf(mel_point * (n_fft as f32 + 1.0) / sample_rate) as usize as u64;
+        }
+        bins
+    }
+
+    /// `cepstrum::mel_filterbank`.
+    pub fn mel_filterbank(fft: &HipFftImpl<f32>, fft_mags: &[f32], sample_rate: f32, num_filters: usize) -> Vec<f32> {
+        let mut out = vec![0.0f32; num_filters];
+        fft.mel_filterbank_batch(fft_mags, fft_mags.len(), &mel_bins(sample_rate, fft_mags.len(), num_filters), &mut out)
+            .expect("one row: the lengths agree and the edges are in order");
+        out
+    }
+
+    /// `cepstrum::mfcc`.
+    pub fn mfcc(fft: &HipFftImpl<f32>, fft_mags: &[f32], sample_rate: f32, num_mel: usize, num_coeffs: usize) -> Result<Vec<f32>, FftError> {
+        let mut out = vec![0.0f32; num_coeffs];
+        fft.mfcc_rows(fft_mags, fft_mags.len(), &mel_bins(sample_rate, fft_mags.len(), num_mel), num_coeffs, &mut out)?;
+        Ok(out)
+    }
+
+    /// `cepstrum::mfcc_batch`: frames of one length go to the device in one call.
+    pub fn mfcc_batch(fft: &HipFftImpl<f32>, batch: &[Vec<f32>], sample_rate: f32, num_mel: usize, num_coeffs: usize) -> Result<Vec<Vec<f32>>, FftError> {
+        if num_coeffs > num_mel { return if batch.is_empty() { Ok(Vec::new()) } else { Err(FftError::InvalidValue) }; }
+        let mut result = vec![Vec::new(); batch.len()];
+        let mut lens: Vec<usize> = batch.iter().map(|b| b.len()).collect();
+        lens.sort_unstable();
+        lens.dedup();
+        for n in lens {
+            let idx: Vec<usize> = (0..batch.len()).filter(|&j| batch[j].len() == n).collect();
+            let flat: Vec<f32> = idx.iter().flat_map(|&j| batch[j].iter().copied()).collect();
+            let mut out = vec![0.0f32; idx.len() * num_coeffs];
+            if n != 0 {
+                fft.mfcc_rows(&flat, n, &mel_bins(sample_rate, n, num_mel), num_coeffs, &mut out)?;
+            } else {
+                // rows without data: every energy is +0 (cepstrum.rs:51), one row stands for all of them
+                let one = mfcc(fft, &[], sample_rate, num_mel, num_coeffs)?;
+                for t in 0..idx.len() { out[t * num_coeffs..(t + 1) * num_coeffs].copy_from_slice(&one); }
+            }
+            for (t, &j) in idx.iter().enumerate() {
+                result[j] = out[t * num_coeffs..(t + 1) * num_coeffs].to_vec();
+            }
+        }
+        Ok(result)
     }
 }
 

@@ -82,6 +82,12 @@ SIGNATURES = {
     "kofft_hip_cepstrum_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_cepstrum_f32_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_cepstrum_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_mel_filterbank_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_mel_filterbank_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_mfcc_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_mel_bins_f32": (C.c_int, [C.c_float, _sz, _sz, C.c_void_p]),
     "kofft_hip_dct_direct_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_dct_direct_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_dst_direct_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),

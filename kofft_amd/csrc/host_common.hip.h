@@ -40,6 +40,15 @@ struct kofft_spectral_slot {
     void *d_table = nullptr;
 };
 constexpr size_t kSpectralSlots = 4;  // a 4096 x 4096 chirp-Z table is 128 MiB
+// One cached filterbank plan (k_mfcc_f32.hip): key = (bins, n_fft, num_mel), compared whole; d_plan = [ints | w] as
+// kofft_tables::mel_plan_build lays them out, uploaded stream-ordered from `staged`, which lives as long as the slot.
+struct kofft_mel_slot {
+    std::vector<uint64_t> bins;
+    size_t n_fft = 0, num_mel = 0;
+    std::vector<int> staged;
+    void *d_plan = nullptr;
+};
+constexpr size_t kMelSlots = 4;
 struct kofft_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -52,6 +61,7 @@ struct kofft_hip_ctx {
     bool hilbert_fused = true; // kofft_hip_set_hilbert_fused(ctx, 0): analytic signals of every length through the composed route (expand, fft_dev, mask, inverse fft_dev; A/B, tests)
     bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
+    int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     bool dht_table_device = true; // kofft_hip_set_dht_table_device(ctx, 0): the Hartley table of a new length built on the host and uploaded instead of by dht_table_kernel (the same bytes; A/B, tests)
     int wavelet_fused = 1;    // kofft_hip_set_wavelet_fused: 1 the measured choice (wavelet_use_fused), 0 every multi-level call level by level, 2 the fused kernels wherever they fit (A/B, tests)
@@ -89,6 +99,8 @@ struct kofft_hip_ctx {
     std::vector<kofft_spectral_slot> czt_slots;
     void *goertzel_coeff = nullptr;
     std::vector<float> goertzel_last;
+    // filterbank plans: most recently used first, at most kMelSlots; dropped with the chirp-Z tables (mel_drop)
+    std::vector<kofft_mel_slot> mel_slots;
     // staging for the host-pointer entry points: one device buffer, laid out by host_layout() (host_layout.h)
     kofft::host::DevBuf stage;
     // intermediate of the two-factor large-n path (fft_big.hip.h): `big_chunk` transforms at a time
@@ -791,6 +803,19 @@ int goertzel_launch(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const f
 int goertzel_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate, const float *target_freqs,
                  size_t nfreq);
 void spectral_drop(kofft_hip_ctx *ctx);  // frees every slot and the coefficient buffer; the caller has synchronised the stream
+// k_mfcc_f32.hip: cepstrum::mel_filterbank / mfcc with the edges as an input (mfcc_impl.hip.h); mel_check: the argument checks alone,
+// mfcc: whether num_coeffs takes part; *_dev return before the edge sizes (num_mel == 0, num_coeffs == 0) touch anything
+constexpr size_t kMelMaxFft = size_t(1) << 24;  // (k - a) as f32 is exact below it
+constexpr size_t kMfccFusedMaxMel = 128;        // the fused kernel's log-mel columns: 256 bytes of LDS per filter and workgroup
+constexpr size_t kMfccFusedDefaultMel = 80;     // the measured choice: the fused kernel up to 80 filters (five workgroups per CU) ...
+constexpr size_t kMfccFusedDefaultCoeffs = 16;  // ... and 16 coefficients (two passes of its DCT)
+int mel_check(bool mfcc, bool dev, const void *mags, const void *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+              size_t num_coeffs, const kofft_hip_ctx *ctx);
+int mel_filterbank_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_energies, size_t n_fft, size_t rows, const uint64_t *bins,
+                       size_t num_mel);
+int mfcc_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+             size_t num_coeffs);
+void mel_drop(kofft_hip_ctx *ctx);  // frees every plan; the caller has synchronised the stream
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

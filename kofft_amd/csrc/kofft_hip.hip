@@ -350,6 +350,20 @@ int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, siz
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return cepstrum_dev(ctx, d_in, d_out, n, rows); });
 }
 
+// cepstrum::mel_filterbank / mfcc on host rows of n_fft magnitudes in, num_mel energies or num_coeffs coefficients out (k_mfcc_f32.hip);
+// the edges stay on the host
+int mel_host(kofft_hip_ctx *ctx, bool mfcc, const float *mags, float *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+             size_t num_coeffs)
+{
+    const int rc = mel_check(mfcc, false, mags, out, n_fft, rows, bins, num_mel, num_coeffs, ctx);
+    if (rc || rows == 0 || num_mel == 0 || (mfcc && num_coeffs == 0)) return rc;
+    return rows_host<float>(ctx, mags, out, rows, n_fft, mfcc ? num_coeffs : num_mel, nullptr, 0, true, true,
+                            [&](float *d_in, float *d_out, const float *, size_t nr) {
+                                return mfcc ? mfcc_dev(ctx, d_in, d_out, n_fft, nr, bins, num_mel, num_coeffs)
+                                            : mel_filterbank_dev(ctx, d_in, d_out, n_fft, nr, bins, num_mel);
+                            });
+}
+
 // dct::dct1..4 / dst::dst1..4 on host rows of n reals in and out
 int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float *out, size_t n, size_t batch)
 {
@@ -644,6 +658,7 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->tables) (void)hipFree(kv.second);
     spectral_drop(ctx);
+    mel_drop(ctx);
     drop_buffers(ctx);
     if (ctx->persist_claim_counters) (void)hipFree(ctx->persist_claim_counters);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -709,6 +724,7 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
     KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     drop_buffers(ctx);
     spectral_drop(ctx);  // the chirp-Z tables (up to 4 x 128 MiB) and the Goertzel coefficient arrays: rebuilt by the next call that needs them
+    mel_drop(ctx);       // the filterbank plans, likewise
     ctx->big_tmp_external = false;  // (KOFFT_EXP_API builds: the script's intermediate is forgotten, the next call allocates its own)
     ctx->big_probe_n = 0;
     ctx->big_probe_pick = -1;
@@ -933,6 +949,40 @@ int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size
 int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     return cepstrum_dev(ctx, d_in, d_out, n, batch);
+}
+int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (on < 0 || on > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->mfcc_fused = on;
+    return KOFFT_OK;
+}
+int kofft_hip_mel_filterbank_f32(kofft_hip_ctx *ctx, const float *mags, float *energies, size_t n_fft, size_t rows, const uint64_t *bins,
+                                 size_t num_mel)
+{
+    return mel_host(ctx, false, mags, energies, n_fft, rows, bins, num_mel, 0);
+}
+int kofft_hip_dev_mel_filterbank_f32(kofft_hip_ctx *ctx, const float *d_mags, float *d_energies, size_t n_fft, size_t rows,
+                                     const uint64_t *bins, size_t num_mel)
+{
+    return mel_filterbank_dev(ctx, d_mags, d_energies, n_fft, rows, bins, num_mel);
+}
+int kofft_hip_mfcc_f32(kofft_hip_ctx *ctx, const float *mags, float *coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+                       size_t num_coeffs)
+{
+    return mel_host(ctx, true, mags, coeffs, n_fft, rows, bins, num_mel, num_coeffs);
+}
+int kofft_hip_dev_mfcc_f32(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins,
+                           size_t num_mel, size_t num_coeffs)
+{
+    return mfcc_dev(ctx, d_mags, d_coeffs, n_fft, rows, bins, num_mel, num_coeffs);
+}
+int kofft_hip_mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins)
+{
+    if (num_filters > kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!bins) return KOFFT_ERR_NULL;
+    kofft_tables::mel_bins_f32(sample_rate, n_fft, num_filters, bins);
+    return KOFFT_OK;
 }
 int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on)
 {

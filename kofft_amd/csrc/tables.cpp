@@ -451,4 +451,38 @@ void window_f32(int kind, size_t len, float param, float *out)
     }
 }
 
+// ---- cepstrum::mel_filterbank: the edges and the kernels' plan ----------------------------------------------------------------------
+void mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins)
+{
+    const float f_min = 0.0f;
+    const float f_max = sample_rate / 2.0f;                          // cepstrum.rs:39
+    const float mel_min = 2595.0f * log10f(1.0f + f_min / 700.0f);   // cepstrum.rs:40
+    const float mel_max = 2595.0f * log10f(1.0f + f_max / 700.0f);   // cepstrum.rs:41
+    for (size_t i = 0; i < num_filters + 2; ++i) {
+        float p = mel_min + (mel_max - mel_min) * (float)i / (float)(num_filters + 1);  // cepstrum.rs:44: ((d * i) / (M + 1))
+        p = 700.0f * (powf(10.0f, p / 2595.0f) - 1.0f);                                 // cepstrum.rs:45
+        bins[i] = saturating_usize(floorf(p * ((float)n_fft + 1.0f) / sample_rate));    // cepstrum.rs:49
+    }
+}
+
+size_t mel_plan_ints(size_t num_mel) { return 2 * (num_mel + 1) + num_mel; }
+
+void mel_plan_build(const uint64_t *bins, size_t n_fft, size_t num_mel, int *ints, float *w)
+{
+    int *seg = ints, *live = ints + 2 * (num_mel + 1);
+    for (size_t k = 0; k < 2 * n_fft; ++k) w[k] = 0.0f;
+    for (size_t s = 0; s <= num_mel; ++s) {
+        const uint64_t a = bins[s], b = bins[s + 1];
+        const uint64_t lo = a < n_fft ? a : n_fft, hi = b < n_fft ? b : n_fft;
+        seg[2 * s] = (int)lo;
+        seg[2 * s + 1] = (int)hi;
+        const float d = (float)(b - a);  // cepstrum.rs:59, 64: `(bins[m] - bins[m - 1]) as f32`
+        for (uint64_t k = lo; k < hi; ++k) {
+            w[2 * k] = (float)(k - a) / d;
+            w[2 * k + 1] = (float)(b - k) / d;
+        }
+    }
+    for (size_t m = 0; m < num_mel; ++m) live[m] = (bins[m + 1] != bins[m] && bins[m + 2] != bins[m + 1]) ? 1 : 0;
+}
+
 }  // namespace kofft_tables

@@ -1,6 +1,7 @@
 // tables.h -- host-side planner recipes (see tables.cpp).
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 namespace kofft_tables {
 void twiddles_f32(size_t n, float *out);   // n/2 complex
 void twiddles_f64(size_t n, double *out);
@@ -46,4 +47,17 @@ void dht_table_f32(size_t n, size_t ldc, float *h);
 // alpha, ignored otherwise.  The caller has checked the kind and, for kaiser, len != 0.
 void window_f32(int kind, size_t len, float param, float *out);
 constexpr int kWindowKinds = 7;
+// cepstrum::mel_filterbank's edges (cepstrum.rs:38-50) in f32 in Rust's parse order, with glibc's log10f / powf where the reference
+// calls the libm crate's, and the saturating `floorf(..) as usize`: bins = num_filters + 2 values.
+void mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins);
+// What the filterbank kernels walk (mfcc_impl.hip.h), from nondecreasing edges bins[0 .. num_mel + 1] and rows of n_fft <= 2^24 values.
+// Segment s = [bins[s], bins[s + 1]) is the rise of filter s and the fall of filter s - 1 (cepstrum.rs:57-66):
+//   seg[2 s], seg[2 s + 1]  its bounds clamped to n_fft (the reference skips k >= n_fft; the unclamped edges still set the denominators)
+//   live[m]                 1 unless bins[m + 1] == bins[m] or bins[m + 2] == bins[m + 1] (cepstrum.rs:54: the filter stays +0)
+//   w[2 k], w[2 k + 1]      for k < n_fft inside a segment s: ((k - bins[s]) as f32) / d and ((bins[s + 1] - k) as f32) / d,
+//                           d = (bins[s + 1] - bins[s]) as f32, conversions rounded to nearest, the division correctly rounded;
+//                           +0 for every k outside [bins[0], bins[num_mel + 1])
+// ints: 2 (num_mel + 1) + num_mel values (seg, then live); w: 2 n_fft floats.
+size_t mel_plan_ints(size_t num_mel);
+void mel_plan_build(const uint64_t *bins, size_t n_fft, size_t num_mel, int *ints, float *w);
 }  // namespace kofft_tables
