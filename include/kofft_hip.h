@@ -298,6 +298,65 @@ int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on);
  * itself.  num_filters > 4096 -> KOFFT_ERR_UNSUPPORTED; bins null -> KOFFT_ERR_NULL. */
 int kofft_hip_mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins);
 
+/* ---- spectrogram colour helpers: magnitudes -> dB -> RGB picture -----------------------------
+ * visual::spectrogram's magnitude_to_db, db_scale, map_color_u8 / _u16, color_from_magnitude_*, map_bin_to_pixel and log_scale_bins
+ * (visual/spectrogram.rs:96-234), f32 only like the reference, on the magnitudes kofft_hip_dev_stft_magnitudes_rows_f32 leaves on the
+ * device.  max_mag is a POINTER to one float: a host pointer in the host forms, a device pointer in the kofft_hip_dev_* forms (the
+ * d_max of the magnitudes call: no host synchronisation in between).
+ * The arithmetic contract.  log10 is the LIBM CRATE's log10f (the musl / FreeBSD e_log10f.c port, restated in
+ * kofft_amd/csrc/libm_log10f.hip.h), which is what a build of the reference without a platform libm computes; with `std` the reference
+ * calls the platform's log10f, and its own bytes differ from platform to platform.  Everything else is the reference's f32 operation
+ * order, one rounding per operation, nothing fused: the correctly rounded divisions `mag / max_mag`, by `dynamic_range`, by `-floor_db`
+ * and by a palette segment's width, `20.0 *`, f32::max (a NaN loses; of two equal values the floor is returned), f32::clamp (a NaN
+ * stays), the palettes, f32::round for Gray, and `as u8` as a truncating, saturating cast with NaN -> 0.
+ *   magnitude_to_db: max_mag <= 0 or mag <= 0 -> floor_db; else max(20 * log10f(mag / max_mag), floor_db).
+ *   db_scale: clamp((20 * log10f(max(mag / max_mag, 1e-10)) + dynamic_range) / dynamic_range, 0, 1).
+ *   render: mags[frames][bins] -> pixels.  mode 0: map_color_u8((magnitude_to_db(mag, max_mag, level) - level) / -level), `level` the
+ *     floor in dB (color_from_magnitude_u8); mode 1: map_color_u8(db_scale(mag, max_mag, level)), `level` the dynamic range.  cmap:
+ *     KOFFT_CMAP_*, the reference's declaration order; Fire, Legacy, Gray and Rainbow are implemented, VIRIDIS / PLASMA / INFERNO (the
+ *     colorous crate's) return INVALID_VALUE.  depth 8: 3 bytes per pixel; depth 16: three native uint16_t, each the 8-bit value * 257
+ *     (map_color_u16); the output needs no alignment.  scale 0: a pixel per bin; scale 1: every frame goes through
+ *     log_scale_bins(frame, bins - 1) first -- pixel p is the sum of the bins b with pix_of_bin[b] == p in increasing order from +0,
+ *     divided once by their count as f32, +0 without bins.  pix_of_bin (bins values, a HOST pointer in both forms, read before the
+ *     call returns; NULL unless scale == 1) is an INPUT: kofft_hip_log_bin_map gives the reference-shaped one with glibc's logf, a
+ *     caller with the libm crate can supply its own.  It must be nondecreasing (map_bin_to_pixel is, for every bins from 2 to 8192).
+ *     layout 0: out[frames][bins][3]; layout 1: the picture out[bins][frames][3], row-major, bin b of frame x at row bins - 1 - b,
+ *     column x (what the reference's programs build with put_pixel(x, height - 1 - y)).
+ * Checks, in this order and before the context or the device is touched: count / frames / bins == 0 -> EMPTY_INPUT; an unknown mode,
+ * cmap, depth, scale or layout, or a colorous palette -> INVALID_VALUE; scale == 1 with a null table, a table entry >= bins or a table
+ * that decreases -> INVALID_VALUE; bins > 2^24 or more than 2^31 - 1 tiles of 64 x 64 -> KOFFT_ERR_UNSUPPORTED; a null pointer or
+ * context -> KOFFT_ERR_NULL; (device pointers) the output overlapping the input or max_mag -> INVALID_VALUE.  level and max_mag are not
+ * validated: the reference validates neither.  The kofft_hip_dev_* forms are asynchronous on the context's stream.  A context keeps
+ * the pixel ranges of its four most recently used tables on the device until kofft_hip_release_scratch or kofft_hip_destroy.
+ * kofft_hip_set_spectrogram_transpose(ctx, on): 1, the default, writes layout 1 through an LDS tile (whole dwords per picture row);
+ * 0 lets every lane store its own bytes; the same bytes (which measured faster). */
+#define KOFFT_CMAP_FIRE 0
+#define KOFFT_CMAP_LEGACY 1
+#define KOFFT_CMAP_GRAY 2
+#define KOFFT_CMAP_VIRIDIS 3
+#define KOFFT_CMAP_PLASMA 4
+#define KOFFT_CMAP_INFERNO 5
+#define KOFFT_CMAP_RAINBOW 6
+int kofft_hip_magnitude_to_db_f32(kofft_hip_ctx *ctx, const float *mags, size_t count, const float *max_mag, float floor_db, float *out);
+int kofft_hip_dev_magnitude_to_db_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t count, const float *d_max_mag, float floor_db,
+                                      float *d_out);
+int kofft_hip_db_scale_f32(kofft_hip_ctx *ctx, const float *mags, size_t count, const float *max_mag, float dynamic_range, float *out);
+int kofft_hip_dev_db_scale_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t count, const float *d_max_mag, float dynamic_range,
+                               float *d_out);
+int kofft_hip_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *mags, size_t frames, size_t bins, const float *max_mag, int mode,
+                                     float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin, void *out);
+int kofft_hip_dev_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max_mag,
+                                         int mode, float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin,
+                                         void *d_out);
+int kofft_hip_set_spectrogram_transpose(kofft_hip_ctx *ctx, int on);
+/* Host only: pix_of_bin[b] = map_bin_to_pixel(b, bins - 1) (spectrogram.rs:209-217) for every b < bins: max_bin == 0 -> 0, else
+ * floor(max_bin as f32 * ln(b as f32 + 1) / ln(max_bin as f32 + 1)) as a saturating cast, f32 in Rust's parse order with GLIBC's logf.
+ * bins == 0 -> EMPTY_INPUT; bins > 2^24 -> KOFFT_ERR_UNSUPPORTED; a null pointer -> KOFFT_ERR_NULL. */
+int kofft_hip_log_bin_map(size_t bins, uint32_t *pix_of_bin);
+/* Host only: map_color_u8(t, cmap) (spectrogram.rs:113-160) for a legend.  A colorous palette or an unknown cmap -> INVALID_VALUE;
+ * rgb null -> KOFFT_ERR_NULL. */
+int kofft_hip_map_color_u8(float t, int cmap, unsigned char *rgb);
+
 /* ---- direct DCT-I..IV and DST-I..IV ---------------------------------------------
  * dct::dct1 .. dct4 (dct.rs:108-176) and dst::dst1 .. dst4 (dst.rs:89-146), f32 only like
  * the reference (there is no f64 direct transform), on `batch` contiguous rows of n reals;

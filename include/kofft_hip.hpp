@@ -18,6 +18,9 @@
 //   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
 //   kofft::HipFftImpl<float>::mel_filterbank / mfcc, kofft::mel_bins   cepstrum::mel_filterbank / mfcc / mfcc_batch, cepstrum.rs:36-98
 //                                                (the filter edges are an argument; mel_bins computes the reference-shaped ones)
+//   kofft::HipFftImpl<float>::magnitude_to_db / db_scale / spectrogram_render, kofft::log_bin_map / map_color_u8
+//                                                visual::spectrogram's colour helpers, visual/spectrogram.rs:96-234 (log10 is the libm
+//                                                crate's log10f; Viridis / Plasma / Inferno are InvalidValue)
 //   kofft::HipFftImpl<float>::dct_direct         dct::dct1..dct4, dct.rs:108-176 (the direct sums)
 //   kofft::HipFftImpl<float>::dst_direct         dst::dst1..dst4, dst.rs:89-146
 //   kofft::HipFftImpl<float>::dwt / idwt         wavelet::<name>_forward / _inverse, wavelet.rs:12-33, 154-535
@@ -31,6 +34,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -376,6 +380,55 @@ public:
     }
     // 1 (the default): the fused kernel where it measured faster (up to 80 filters, 16 coefficients); 0: every MFCC composed; 2: fused wherever it fits (the same bytes)
     Result set_mfcc_fused(int mode) const { return st(kofft_hip_set_mfcc_fused(ctx_, mode)); }
+    // visual::spectrogram::magnitude_to_db / db_scale (spectrogram.rs:96-110) of every value, f32 only like the reference, with the libm
+    // crate's log10f (kofft_hip.h: the arithmetic contract).  EmptyInput for no values, MismatchedLengths for an output of another size.
+    Result magnitude_to_db(const std::vector<float> &mags, float max_mag, float floor_db, std::vector<float> &out) const
+    {
+        static_assert(std::is_same<T, float>::value, "the spectrogram helpers are f32-only (visual/spectrogram.rs)");
+        if (out.size() != mags.size()) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_magnitude_to_db_f32(ctx_, mags.data(), mags.size(), &max_mag, floor_db, out.data()));
+    }
+    Result db_scale(const std::vector<float> &mags, float max_mag, float dynamic_range, std::vector<float> &out) const
+    {
+        static_assert(std::is_same<T, float>::value, "the spectrogram helpers are f32-only (visual/spectrogram.rs)");
+        if (out.size() != mags.size()) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_db_scale_f32(ctx_, mags.data(), mags.size(), &max_mag, dynamic_range, out.data()));
+    }
+    // mags[frames][bins] -> an RGB picture of frames * bins * 3 values (kofft_hip.h: mode, level, cmap = KOFFT_CMAP_*, scale, layout);
+    // Pixel = uint8_t (depth 8) or uint16_t (depth 16, the 8-bit value * 257).  pix_of_bin: the bins values of the log scale (kofft::log_bin_map
+    // gives the reference-shaped ones), empty for the linear scale.  MismatchedLengths for frames that do not divide the input, a table
+    // or an output of another size; InvalidValue for a colorous palette, an unknown enumerator or a table that decreases.
+    template <typename Pixel>
+    Result spectrogram_render(const std::vector<float> &mags, size_t frames, float max_mag, int mode, float level, int cmap, int scale, int layout,
+                              const std::vector<uint32_t> &pix_of_bin, std::vector<Pixel> &out) const
+    {
+        static_assert(std::is_same<T, float>::value, "the spectrogram helpers are f32-only (visual/spectrogram.rs)");
+        static_assert(std::is_same<Pixel, uint8_t>::value || std::is_same<Pixel, uint16_t>::value, "pixels are uint8_t or uint16_t");
+        if (frames == 0 || mags.empty()) return Result::Err(FftError::EmptyInput);
+        if (mags.size() % frames != 0 || out.size() != mags.size() * 3 || (scale == 1 && pix_of_bin.size() != mags.size() / frames))
+            return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_spectrogram_render_f32(ctx_, mags.data(), frames, mags.size() / frames, &max_mag, mode, level, cmap, (int)(8 * sizeof(Pixel)),
+                                                   scale, layout, scale == 1 ? pix_of_bin.data() : nullptr, out.data()));
+    }
+    // ... on device memory, asynchronous on the context's stream: d_max_mag is a device pointer (the d_max of stft_magnitudes), pix_of_bin
+    // stays a host vector, read before the call returns; the output must not overlap the input or d_max_mag (InvalidValue)
+    Result magnitude_to_db_dev(const float *d_mags, size_t count, const float *d_max_mag, float floor_db, float *d_out) const
+    {
+        return st(kofft_hip_dev_magnitude_to_db_f32(ctx_, d_mags, count, d_max_mag, floor_db, d_out));
+    }
+    Result db_scale_dev(const float *d_mags, size_t count, const float *d_max_mag, float dynamic_range, float *d_out) const
+    {
+        return st(kofft_hip_dev_db_scale_f32(ctx_, d_mags, count, d_max_mag, dynamic_range, d_out));
+    }
+    Result spectrogram_render_dev(const float *d_mags, size_t frames, size_t bins, const float *d_max_mag, int mode, float level, int cmap, int depth,
+                                  int scale, int layout, const std::vector<uint32_t> &pix_of_bin, void *d_out) const
+    {
+        if (scale == 1 && pix_of_bin.size() != bins) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_dev_spectrogram_render_f32(ctx_, d_mags, frames, bins, d_max_mag, mode, level, cmap, depth, scale, layout,
+                                                       scale == 1 ? pix_of_bin.data() : nullptr, d_out));
+    }
+    // true (the default): the image layout leaves through an LDS tile, whole dwords per picture row; false: every lane stores its own bytes (the same bytes)
+    Result set_spectrogram_transpose(bool on) const { return st(kofft_hip_set_spectrogram_transpose(ctx_, on ? 1 : 0)); }
     // dct::dct1 .. dct4 (dct.rs:108-176; type 1 .. 4), the direct sums, f32 only like the reference: `batch` contiguous rows of n reals
     // in, rows of n reals out.  MismatchedLengths for rows that do not divide the input or an output of another size; InvalidValue for
     // a type outside 1 .. 4; n == 0 is an empty result except for type 3 (EmptyInput: dct3 indexes input[0] unchecked); n > 4096
@@ -830,6 +883,22 @@ inline std::vector<uint64_t> mel_bins(float sample_rate, size_t n_fft, size_t nu
     std::vector<uint64_t> bins(num_filters + 2);
     if (kofft_hip_mel_bins_f32(sample_rate, n_fft, num_filters, bins.data()) != 0) throw std::invalid_argument("kofft::mel_bins: more than 4096 filters");
     return bins;
+}
+
+// visual::spectrogram::map_bin_to_pixel(b, bins - 1) for every b < bins (spectrogram.rs:209-217), f32 with GLIBC's logf: the table the
+// log-scaled render takes.  bins == 0 or > 2^24 throw std::invalid_argument.
+inline std::vector<uint32_t> log_bin_map(size_t bins)
+{
+    std::vector<uint32_t> table(bins);
+    if (kofft_hip_log_bin_map(bins, table.data()) != 0) throw std::invalid_argument("kofft::log_bin_map: bins must be 1 .. 2^24");
+    return table;
+}
+// visual::spectrogram::map_color_u8 (spectrogram.rs:113-160) on the host; a colorous palette or an unknown cmap throws std::invalid_argument.
+inline std::array<uint8_t, 3> map_color_u8(float t, int cmap)
+{
+    std::array<uint8_t, 3> rgb{};
+    if (kofft_hip_map_color_u8(t, cmap, rgb.data()) != 0) throw std::invalid_argument("kofft::map_color_u8: Fire, Legacy, Gray and Rainbow are implemented");
+    return rgb;
 }
 
 // stft::stft (stft.rs:76-105): output frames are resized to the window length and overwritten

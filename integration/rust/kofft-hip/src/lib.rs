@@ -61,6 +61,12 @@ extern "C" {
     fn kofft_hip_mfcc_f32(ctx: *mut KofftHipCtx, mags: *const f32, coeffs: *mut f32, n_fft: usize, rows: usize, bins: *const u64,
                           num_mel: usize, num_coeffs: usize) -> c_int;
     fn kofft_hip_set_mfcc_fused(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
+    fn kofft_hip_magnitude_to_db_f32(ctx: *mut KofftHipCtx, mags: *const f32, count: usize, max_mag: *const f32, floor_db: f32, out: *mut f32) -> c_int;
+    fn kofft_hip_db_scale_f32(ctx: *mut KofftHipCtx, mags: *const f32, count: usize, max_mag: *const f32, dynamic_range: f32, out: *mut f32) -> c_int;
+    fn kofft_hip_spectrogram_render_f32(ctx: *mut KofftHipCtx, mags: *const f32, frames: usize, bins: usize, max_mag: *const f32, mode: c_int,
+                                        level: f32, cmap: c_int, depth: c_int, scale: c_int, layout: c_int, pix_of_bin: *const u32,
+                                        out: *mut core::ffi::c_void) -> c_int;
+    fn kofft_hip_set_spectrogram_transpose(ctx: *mut KofftHipCtx, on: c_int) -> c_int;
     fn kofft_hip_window_f32(kind: c_int, len: usize, param: f32, out: *mut f32) -> c_int;
     fn kofft_hip_fftnd_c32(ctx: *mut KofftHipCtx, data: *mut f32, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     fn kofft_hip_fftnd_c64(ctx: *mut KofftHipCtx, data: *mut f64, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
@@ -519,6 +525,96 @@ pub mod cepstrum {
             }
         }
         Ok(result)
+    }
+}
+
+impl HipFftImpl<f32> {
+    /// `visual::spectrogram::magnitude_to_db` (kofft visual/spectrogram.rs:96-102) of every value, with the **libm crate's** `log10f`
+    /// (include/kofft_hip.h: the arithmetic contract).  No values: `EmptyInput`.
+    pub fn magnitude_to_db_batch(&self, mags: &[f32], max_mag: f32, floor_db: f32, out: &mut [f32]) -> Result<(), FftError> {
+        if out.len() != mags.len() { return Err(FftError::MismatchedLengths); }
+        status(self.ctx, unsafe { kofft_hip_magnitude_to_db_f32(self.ctx, mags.as_ptr(), mags.len(), &max_mag, floor_db, out.as_mut_ptr()) })
+    }
+
+    /// `visual::spectrogram::db_scale` (spectrogram.rs:107-110) of every value.
+    pub fn db_scale_batch(&self, mags: &[f32], max_mag: f32, dynamic_range: f32, out: &mut [f32]) -> Result<(), FftError> {
+        if out.len() != mags.len() { return Err(FftError::MismatchedLengths); }
+        status(self.ctx, unsafe { kofft_hip_db_scale_f32(self.ctx, mags.as_ptr(), mags.len(), &max_mag, dynamic_range, out.as_mut_ptr()) })
+    }
+
+    /// `frames` rows of `mags.len() / frames` magnitudes -> an RGB8 picture, three bytes per pixel.  `floor_db`: `color_from_magnitude_u8`
+    /// (mode 0); `log_table`: every frame through `log_scale_bins` first, over this bin -> pixel table (`spectrogram::log_bin_map`);
+    /// `image`: `[bins][frames][3]` with bin b at row bins - 1 - b (what the reference's programs build), else `[frames][bins][3]`.
+    /// Viridis, Plasma and Inferno are `InvalidValue`.
+    pub fn spectrogram_rgb8(&self, mags: &[f32], frames: usize, max_mag: f32, floor_db: f32, cmap: spectrogram::Colormap, log_table: Option<&[u32]>,
+                            image: bool, out: &mut [u8]) -> Result<(), FftError> {
+        if frames == 0 || mags.is_empty() { return Err(FftError::EmptyInput); }
+        let bins = mags.len() / frames;
+        if mags.len() % frames != 0 || out.len() != mags.len() * 3 || log_table.map_or(false, |t| t.len() != bins) {
+            return Err(FftError::MismatchedLengths);
+        }
+        status(self.ctx, unsafe {
+            kofft_hip_spectrogram_render_f32(self.ctx, mags.as_ptr(), frames, bins, &max_mag, 0, floor_db, cmap as c_int, 8, log_table.is_some() as c_int,
+                                             image as c_int, log_table.map_or(core::ptr::null(), |t| t.as_ptr()), out.as_mut_ptr() as *mut core::ffi::c_void)
+        })
+    }
+
+    /// `true` (the default): the image layout leaves through an LDS tile; `false`: every lane stores its own bytes (the same bytes).
+    pub fn set_spectrogram_transpose(&self, on: bool) -> Result<(), FftError> {
+        status(self.ctx, unsafe { kofft_hip_set_spectrogram_transpose(self.ctx, on as c_int) })
+    }
+}
+
+/// `kofft::visual::spectrogram`'s colour helpers (visual/spectrogram.rs:96-234) on the device.  The bin -> pixel table of the log
+/// scale is computed HERE with the `libm` crate's `logf` -- a build of the reference without `std` -- and passed down; the library's
+/// own helper (`kofft_hip_log_bin_map`) uses glibc's.  `log10` on the device is the libm crate's `log10f` restated
+/// (`tests/spectrogram_pin.rs` pins the restatement and the four palettes against the crates).
+pub mod spectrogram {
+    use super::HipFftImpl;
+    use kofft::fft::FftError;
+
+    /// `Colormap` in the reference's declaration order: the values of `KOFFT_CMAP_*`.
+    #[derive(Clone, Copy, Debug, PartialEq)]
+    #[repr(i32)]
+    pub enum Colormap { Fire = 0, Legacy = 1, Gray = 2, Viridis = 3, Plasma = 4, Inferno = 5, Rainbow = 6 }
+
+    /// spectrogram.rs:209-217 with `libm::logf`.
+    pub fn map_bin_to_pixel(bin: usize, max_bin: usize) -> usize {
+        if max_bin == 0 { return 0; }
+        let log_max = libm::logf(max_bin as f32 + 1.0);
+        let pos = libm::logf(bin as f32 + 1.0);
+        libm::floorf(max_bin as f32 * pos / log_max) as usize
+    }
+
+    /// `map_bin_to_pixel(b, bins - 1)` for every bin: the table `spectrogram_rgb8` takes.
+    pub fn log_bin_map(bins: usize) -> Vec<u32> {
+        (0..bins).map(|b| map_bin_to_pixel(b, bins - 1).min(u32::MAX as usize) as u32).collect()
+    }
+
+    /// `magnitude_to_db` of every value of a frame set.
+    pub fn magnitude_to_db(fft: &HipFftImpl<f32>, mags: &[f32], max_mag: f32, floor_db: f32) -> Result<Vec<f32>, FftError> {
+        let mut out = vec![0.0f32; mags.len()];
+        fft.magnitude_to_db_batch(mags, max_mag, floor_db, &mut out)?;
+        Ok(out)
+    }
+
+    /// `db_scale` of every value of a frame set.
+    pub fn db_scale(fft: &HipFftImpl<f32>, mags: &[f32], max_mag: f32, dynamic_range: f32) -> Result<Vec<f32>, FftError> {
+        let mut out = vec![0.0f32; mags.len()];
+        fft.db_scale_batch(mags, max_mag, dynamic_range, &mut out)?;
+        Ok(out)
+    }
+
+    /// The picture the reference's `examples/spectrogram.rs` builds pixel by pixel: `[bins][frames][3]`, low frequencies at the bottom.
+    pub fn render_rgb8(fft: &HipFftImpl<f32>, mags: &[Vec<f32>], max_mag: f32, floor_db: f32, cmap: Colormap, log_scale: bool) -> Result<Vec<u8>, FftError> {
+        let frames = mags.len();
+        let bins = mags.first().map_or(0, |f| f.len());
+        if mags.iter().any(|f| f.len() != bins) { return Err(FftError::MismatchedLengths); }
+        let flat: Vec<f32> = mags.iter().flat_map(|f| f.iter().copied()).collect();
+        let mut out = vec![0u8; flat.len() * 3];
+        let table = if log_scale { Some(log_bin_map(bins)) } else { None };
+        fft.spectrogram_rgb8(&flat, frames, max_mag, floor_db, cmap, table.as_deref(), true, &mut out)?;
+        Ok(out)
     }
 }
 

@@ -88,6 +88,17 @@ SIGNATURES = {
     "kofft_hip_dev_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_mfcc_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_mel_bins_f32": (C.c_int, [C.c_float, _sz, _sz, C.c_void_p]),
+    "kofft_hip_magnitude_to_db_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),
+    "kofft_hip_dev_magnitude_to_db_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),
+    "kofft_hip_db_scale_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),
+    "kofft_hip_dev_db_scale_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),
+    "kofft_hip_spectrogram_render_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p]),
+    "kofft_hip_dev_spectrogram_render_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_void_p]),
+    "kofft_hip_set_spectrogram_transpose": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_log_bin_map": (C.c_int, [_sz, C.c_void_p]),
+    "kofft_hip_map_color_u8": (C.c_int, [C.c_float, C.c_int, C.c_void_p]),
     "kofft_hip_dct_direct_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_dct_direct_f32_dev": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_dst_direct_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),

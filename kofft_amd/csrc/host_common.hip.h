@@ -49,6 +49,14 @@ struct kofft_mel_slot {
     void *d_plan = nullptr;
 };
 constexpr size_t kMelSlots = 4;
+// One cached set of pixel ranges of the log-scaled spectrogram render (k_spectrogram_f32.hip): key = the caller's bin -> pixel table,
+// compared whole; d_start = bins + 1 values (kofft_tables::spec_ranges_build), uploaded stream-ordered from `staged`.
+struct kofft_spec_slot {
+    std::vector<uint32_t> table;
+    std::vector<uint32_t> staged;
+    void *d_start = nullptr;
+};
+constexpr size_t kSpecSlots = 4;
 struct kofft_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -62,6 +70,7 @@ struct kofft_hip_ctx {
     bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
+    bool spec_transpose = true; // kofft_hip_set_spectrogram_transpose(ctx, 0): the image layout of the spectrogram render with every lane storing its own bytes instead of the exchange through LDS (the same bytes; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     bool dht_table_device = true; // kofft_hip_set_dht_table_device(ctx, 0): the Hartley table of a new length built on the host and uploaded instead of by dht_table_kernel (the same bytes; A/B, tests)
     int wavelet_fused = 1;    // kofft_hip_set_wavelet_fused: 1 the measured choice (wavelet_use_fused), 0 every multi-level call level by level, 2 the fused kernels wherever they fit (A/B, tests)
@@ -101,6 +110,8 @@ struct kofft_hip_ctx {
     std::vector<float> goertzel_last;
     // filterbank plans: most recently used first, at most kMelSlots; dropped with the chirp-Z tables (mel_drop)
     std::vector<kofft_mel_slot> mel_slots;
+    // pixel ranges of the log-scaled spectrogram render: most recently used first, at most kSpecSlots; dropped with the plans above
+    std::vector<kofft_spec_slot> spec_slots;
     // staging for the host-pointer entry points: one device buffer, laid out by host_layout() (host_layout.h)
     kofft::host::DevBuf stage;
     // intermediate of the two-factor large-n path (fft_big.hip.h): `big_chunk` transforms at a time
@@ -816,6 +827,17 @@ int mel_filterbank_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_energie
 int mfcc_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
              size_t num_coeffs);
 void mel_drop(kofft_hip_ctx *ctx);  // frees every plan; the caller has synchronised the stream
+// k_spectrogram_f32.hip: visual::spectrogram's colour helpers (spectrogram_impl.hip.h).  spec_*_check: the argument checks alone, in
+// the order of include/kofft_hip.h; pix_of_bin is a host pointer in both forms, max_mag a device pointer in the *_dev functions
+constexpr size_t kSpecMaxBins = size_t(1) << 24;
+int spec_db_check(bool dev, const void *mags, size_t count, const void *max_mag, const void *out, const kofft_hip_ctx *ctx);
+int spec_db_dev(kofft_hip_ctx *ctx, int which, const float *d_mags, size_t count, const float *d_max, float level, float *d_out);
+int spec_render_check(bool dev, const void *mags, size_t frames, size_t bins, const void *max_mag, int mode, int cmap, int depth, int scale,
+                      int layout, const uint32_t *pix_of_bin, const void *out, const kofft_hip_ctx *ctx);
+int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max, int mode, float level, int cmap,
+                    int depth, int scale, int layout, const uint32_t *pix_of_bin, void *d_out);
+int spec_map_color_u8(float t, int cmap, unsigned char *rgb);
+void spec_drop(kofft_hip_ctx *ctx);  // frees every range table; the caller has synchronised the stream
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
 int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,

@@ -364,6 +364,32 @@ int mel_host(kofft_hip_ctx *ctx, bool mfcc, const float *mags, float *out, size_
                             });
 }
 
+// visual::spectrogram's magnitude_to_db (which == 0) / db_scale on `count` host magnitudes, max_mag a host float (k_spectrogram_f32.hip):
+// one row of `count` values with max_mag as the side input
+int spec_db_host(kofft_hip_ctx *ctx, int which, const float *mags, size_t count, const float *max_mag, float level, float *out)
+{
+    const int rc = spec_db_check(false, mags, count, max_mag, out, ctx);
+    if (rc) return rc;
+    return rows_host<float>(ctx, mags, out, 1, count, count, max_mag, 1, true, true,
+                            [&](float *d_in, float *d_out, const float *d_max, size_t) { return spec_db_dev(ctx, which, d_in, count, d_max, level, d_out); });
+}
+
+// the render on a host picture: the magnitudes and the picture travel as bytes (one row each), max_mag as the side input; the table
+// stays on the host
+int spec_render_host(kofft_hip_ctx *ctx, const float *mags, size_t frames, size_t bins, const float *max_mag, int mode, float level, int cmap,
+                     int depth, int scale, int layout, const uint32_t *pix_of_bin, void *out)
+{
+    const int rc = spec_render_check(false, mags, frames, bins, max_mag, mode, cmap, depth, scale, layout, pix_of_bin, out, ctx);
+    if (rc) return rc;
+    typedef unsigned char byte;
+    return rows_host<byte>(ctx, reinterpret_cast<const byte *>(mags), static_cast<byte *>(out), 1, frames * bins * sizeof(float),
+                           frames * bins * (depth == 16 ? 6 : 3), reinterpret_cast<const byte *>(max_mag), sizeof(float), true, true,
+                           [&](byte *d_in, byte *d_out, const byte *d_max, size_t) {
+                               return spec_render_dev(ctx, reinterpret_cast<const float *>(d_in), frames, bins, reinterpret_cast<const float *>(d_max),
+                                                      mode, level, cmap, depth, scale, layout, pix_of_bin, d_out);
+                           });
+}
+
 // dct::dct1..4 / dst::dst1..4 on host rows of n reals in and out
 int direct_host(kofft_hip_ctx *ctx, int family, int type, const float *in, float *out, size_t n, size_t batch)
 {
@@ -659,6 +685,7 @@ int kofft_hip_destroy(kofft_hip_ctx *ctx)
     for (auto &kv : ctx->tables) (void)hipFree(kv.second);
     spectral_drop(ctx);
     mel_drop(ctx);
+    spec_drop(ctx);
     drop_buffers(ctx);
     if (ctx->persist_claim_counters) (void)hipFree(ctx->persist_claim_counters);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -725,6 +752,7 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
     drop_buffers(ctx);
     spectral_drop(ctx);  // the chirp-Z tables (up to 4 x 128 MiB) and the Goertzel coefficient arrays: rebuilt by the next call that needs them
     mel_drop(ctx);       // the filterbank plans, likewise
+    spec_drop(ctx);      // and the pixel ranges of the log-scaled spectrogram render
     ctx->big_tmp_external = false;  // (KOFFT_EXP_API builds: the script's intermediate is forgotten, the next call allocates its own)
     ctx->big_probe_n = 0;
     ctx->big_probe_pick = -1;
@@ -984,6 +1012,50 @@ int kofft_hip_mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, 
     kofft_tables::mel_bins_f32(sample_rate, n_fft, num_filters, bins);
     return KOFFT_OK;
 }
+int kofft_hip_magnitude_to_db_f32(kofft_hip_ctx *ctx, const float *mags, size_t count, const float *max_mag, float floor_db, float *out)
+{
+    return spec_db_host(ctx, 0, mags, count, max_mag, floor_db, out);
+}
+int kofft_hip_dev_magnitude_to_db_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t count, const float *d_max_mag, float floor_db,
+                                      float *d_out)
+{
+    return spec_db_dev(ctx, 0, d_mags, count, d_max_mag, floor_db, d_out);
+}
+int kofft_hip_db_scale_f32(kofft_hip_ctx *ctx, const float *mags, size_t count, const float *max_mag, float dynamic_range, float *out)
+{
+    return spec_db_host(ctx, 1, mags, count, max_mag, dynamic_range, out);
+}
+int kofft_hip_dev_db_scale_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t count, const float *d_max_mag, float dynamic_range,
+                               float *d_out)
+{
+    return spec_db_dev(ctx, 1, d_mags, count, d_max_mag, dynamic_range, d_out);
+}
+int kofft_hip_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *mags, size_t frames, size_t bins, const float *max_mag, int mode,
+                                     float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin, void *out)
+{
+    return spec_render_host(ctx, mags, frames, bins, max_mag, mode, level, cmap, depth, scale, layout, pix_of_bin, out);
+}
+int kofft_hip_dev_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max_mag,
+                                         int mode, float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin,
+                                         void *d_out)
+{
+    return spec_render_dev(ctx, d_mags, frames, bins, d_max_mag, mode, level, cmap, depth, scale, layout, pix_of_bin, d_out);
+}
+int kofft_hip_set_spectrogram_transpose(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->spec_transpose = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_log_bin_map(size_t bins, uint32_t *pix_of_bin)
+{
+    if (bins == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (bins > kSpecMaxBins) return KOFFT_ERR_UNSUPPORTED;
+    if (!pix_of_bin) return KOFFT_ERR_NULL;
+    kofft_tables::log_bin_map(bins, pix_of_bin);
+    return KOFFT_OK;
+}
+int kofft_hip_map_color_u8(float t, int cmap, unsigned char *rgb) { return spec_map_color_u8(t, cmap, rgb); }
 int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on)
 {
     if (!ctx) return KOFFT_ERR_NULL;

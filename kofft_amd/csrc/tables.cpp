@@ -485,4 +485,33 @@ void mel_plan_build(const uint64_t *bins, size_t n_fft, size_t num_mel, int *int
     for (size_t m = 0; m < num_mel; ++m) live[m] = (bins[m + 1] != bins[m] && bins[m + 2] != bins[m + 1]) ? 1 : 0;
 }
 
+// ---- visual::spectrogram: the log-frequency map and the kernels' pixel ranges -----------------------------------------------------
+void log_bin_map(size_t bins, uint32_t *pix_of_bin)
+{
+    if (bins == 0) return;
+    const size_t max_bin = bins - 1;
+    const float log_max = logf((float)max_bin + 1.0f);  // spectrogram.rs:213
+    for (size_t b = 0; b < bins; ++b) {
+        if (max_bin == 0) {
+            pix_of_bin[b] = 0;  // spectrogram.rs:210
+            continue;
+        }
+        const float pos = logf((float)b + 1.0f);                                              // spectrogram.rs:214
+        const uint64_t y = saturating_usize(floorf((float)max_bin * pos / log_max));          // spectrogram.rs:215
+        pix_of_bin[b] = y > 0xffffffffull ? 0xffffffffu : (uint32_t)y;
+    }
+}
+
+bool spec_ranges_build(const uint32_t *pix_of_bin, size_t bins, uint32_t *start)
+{
+    size_t p = 0;  // the next pixel whose first bin is not known yet
+    for (size_t b = 0; b < bins; ++b) {
+        const uint32_t y = pix_of_bin[b];
+        if (y >= bins || (b > 0 && y < pix_of_bin[b - 1])) return false;
+        for (; p <= y; ++p) start[p] = (uint32_t)b;
+    }
+    for (; p <= bins; ++p) start[p] = (uint32_t)bins;
+    return true;
+}
+
 }  // namespace kofft_tables

@@ -60,4 +60,11 @@ void mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t 
 // ints: 2 (num_mel + 1) + num_mel values (seg, then live); w: 2 n_fft floats.
 size_t mel_plan_ints(size_t num_mel);
 void mel_plan_build(const uint64_t *bins, size_t n_fft, size_t num_mel, int *ints, float *w);
+// visual::spectrogram::map_bin_to_pixel(b, bins - 1) for every b < bins (spectrogram.rs:209-217): f32 in Rust's parse order with glibc's
+// logf, max_bin == 0 -> 0, the saturating `floor(..) as usize` clamped to 32 bits.
+void log_bin_map(size_t bins, uint32_t *pix_of_bin);
+// The pixel ranges the render kernels walk (spectrogram_impl.hip.h) from a bin -> pixel table: pixel p averages the bins
+// [start[p], start[p + 1]), p < bins; start holds bins + 1 values, start[bins] == bins.  false, with start undefined: an entry >= bins,
+// or a table that is not nondecreasing (its pixels would not be ranges).
+bool spec_ranges_build(const uint32_t *pix_of_bin, size_t bins, uint32_t *start);
 }  // namespace kofft_tables
