@@ -298,6 +298,48 @@ int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on);
  * itself.  num_filters > 4096 -> KOFFT_ERR_UNSUPPORTED; bins null -> KOFFT_ERR_NULL. */
 int kofft_hip_mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins);
 
+/* ---- audio front end: rows of signals -> mel energies / MFCCs in one call ----------------------
+ * stft_magnitudes -> mel_filterbank (-> logf -> dct2) over `rows` signals of `len` samples, row r at signal + r * row_stride, `frames`
+ * frames per row, without the rows * frames * (win_len / 2) magnitudes ever being the caller's to hold.  energies is rows * frames *
+ * num_mel floats, coeffs rows * frames * num_coeffs, both dense and frame-major within a row.  bins is a HOST pointer in both forms,
+ * num_mel + 2 nondecreasing values, read before the call returns, exactly as in kofft_hip_mfcc_f32; n_fft of the mel stage is
+ * win_len / 2, the length of a stft_magnitudes row.
+ * Contract.  Let M be the magnitudes of frame f of row r.  window == NULL: M is what kofft_hip_stft_magnitudes_rows_f32 writes for
+ * that frame (window::hann(win_len), bins 0 .. win_len/2 - 1, sqrt(re*re + im*im) un-fused, the root correctly rounded).  A window
+ * given (win_len values; a device pointer in the kofft_hip_dev_* forms): the same expression over kofft_hip_stft_rows_f32's frames
+ * for that window, bins < win_len/2.  A frame past the end of its row reads +0, never the head of row r + 1.  The output row is then
+ * exactly what kofft_hip_mel_filterbank_f32 / kofft_hip_mfcc_f32 return for M with the same bins: the reference's summation order per
+ * filter, logf(e + 1e-12f) with the libm crate's logf, the truncated dct::dct2 over the direct table of num_mel ascending from +0, one
+ * multiply and one add per term, nothing fused; NaNs land where the two calls put them.  No maximum is computed.
+ * Checks, in this order and before the context or the device is touched -- the STFT rows' first, then the mel ones:
+ *   hop == 0 -> INVALID_HOP_SIZE; frames < ceil(len / hop) -> MISMATCHED_LENGTHS; rows == 0 or frames == 0 -> KOFFT_OK, nothing
+ *   touched; win_len == 0 -> EMPTY_INPUT; win_len beyond the complex limits (kofft_hip_stft_rows_f32's) -> UNSUPPORTED; rows > 1 and
+ *   row_stride < len -> INVALID_VALUE; (mfcc) num_coeffs > num_mel -> INVALID_VALUE; bins null -> KOFFT_ERR_NULL; bins decreasing ->
+ *   INVALID_VALUE; num_mel > 4096 (or win_len / 2 > 2^24, the mel stage's bound) -> UNSUPPORTED; a null data pointer (signal with
+ *   len > 0, the output) or a null context -> KOFFT_ERR_NULL; (device forms) the output overlapping the signal or the window ->
+ *   INVALID_VALUE; num_mel == 0 or (mfcc) num_coeffs == 0 -> KOFFT_OK with nothing written.
+ * win_len == 1 gives n_fft == 0: +0 energies and the MFCCs of logf(1e-12f) rows, as kofft_hip_mfcc_f32 at n_fft == 0.
+ * Routes, the same bytes.  The fused kernel (power-of-two win_len 64 .. 2048, num_mel <= 128) keeps a frame's magnitudes, its log-mel
+ * values and the DCT in LDS; the magnitudes never reach memory.  The composed route writes whole frames of magnitudes into the
+ * context's scratch (KOFFT_HIP_SCRATCH_CHUNK_MB at a time, no maximum) and runs the mel / MFCC device path on them: every other
+ * window length (Bluestein lengths such as 400 too) and more filters.  kofft_hip_set_frontend_fused(ctx, mode): 1, the default, the
+ * measured choice (the composed route at every shape, which measured faster than the fused kernel and never slower than the
+ * two calls); 0 every call composed; 2 the fused kernel wherever it fits (A/B measurements and tests); anything
+ * else -> INVALID_VALUE.  The kofft_hip_dev_* forms are asynchronous on the context's stream (named so for the reason given at the
+ * chirp-Z entries; their guard-band cases live in tests/test_gpu_frontend_footprint.py). */
+int kofft_hip_stft_mel_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                                size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, float *energies);
+int kofft_hip_dev_stft_mel_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                    const float *d_window, size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel,
+                                    float *d_energies);
+int kofft_hip_stft_mfcc_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                                 size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs,
+                                 float *coeffs);
+int kofft_hip_dev_stft_mfcc_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                     const float *d_window, size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel,
+                                     size_t num_coeffs, float *d_coeffs);
+int kofft_hip_set_frontend_fused(kofft_hip_ctx *ctx, int mode);
+
 /* ---- spectrogram colour helpers: magnitudes -> dB -> RGB picture -----------------------------
  * visual::spectrogram's magnitude_to_db, db_scale, map_color_u8 / _u16, color_from_magnitude_*, map_bin_to_pixel and log_scale_bins
  * (visual/spectrogram.rs:96-234), f32 only like the reference, on the magnitudes kofft_hip_dev_stft_magnitudes_rows_f32 leaves on the

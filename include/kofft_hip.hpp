@@ -18,6 +18,8 @@
 //   kofft::HipFftImpl<float>::real_cepstrum      cepstrum::real_cepstrum, cepstrum.rs:12-33
 //   kofft::HipFftImpl<float>::mel_filterbank / mfcc, kofft::mel_bins   cepstrum::mel_filterbank / mfcc / mfcc_batch, cepstrum.rs:36-98
 //                                                (the filter edges are an argument; mel_bins computes the reference-shaped ones)
+//   kofft::HipFftImpl<float>::stft_mel / stft_mfcc   stft_magnitudes -> mel_filterbank (-> logf -> dct2) of rows of signals in one call,
+//                                                the magnitudes never leaving the device (no counterpart in the reference: its pipeline)
 //   kofft::HipFftImpl<float>::magnitude_to_db / db_scale / spectrogram_render, kofft::log_bin_map / map_color_u8
 //                                                visual::spectrogram's colour helpers, visual/spectrogram.rs:96-234 (log10 is the libm
 //                                                crate's log10f; Viridis / Plasma / Inferno are InvalidValue)
@@ -380,6 +382,59 @@ public:
     }
     // 1 (the default): the fused kernel where it measured faster (up to 80 filters, 16 coefficients); 0: every MFCC composed; 2: fused wherever it fits (the same bytes)
     Result set_mfcc_fused(int mode) const { return st(kofft_hip_set_mfcc_fused(ctx_, mode)); }
+    // The audio front end in one call (kofft_hip.h): stft_magnitudes -> mel_filterbank of `rows` signals of signals.size() / rows samples,
+    // `frames` frames per row (0: ceil(len / hop)); energies: rows * frames * (bins.size() - 2), frame-major within a row, bit for bit what
+    // stft_magnitudes_rows followed by mel_filterbank returns; the magnitudes stay on the device.  window empty: hann(win_len), else
+    // win_len values.  InvalidHopSize first; MismatchedLengths for rows that do not divide the input, too few frames, a window of another
+    // length, fewer than two edges or an output of another size; InvalidValue for edges out of order.
+    Result stft_mel(const std::vector<float> &signals, size_t rows, size_t win_len, size_t hop, const std::vector<uint64_t> &bins,
+                    std::vector<float> &energies, const std::vector<float> &window = {}, size_t frames = 0) const
+    {
+        static_assert(std::is_same<T, float>::value, "the audio front end is f32-only (cepstrum.rs:36)");
+        if (hop == 0) return Result::Err(FftError::InvalidHopSize);
+        if (rows == 0 || signals.size() % rows != 0 || bins.size() < 2 || (!window.empty() && window.size() != win_len))
+            return Result::Err(FftError::MismatchedLengths);
+        const size_t len = signals.size() / rows, need = len / hop + (len % hop != 0), nf = frames ? frames : need;
+        if (energies.size() != rows * nf * (bins.size() - 2)) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_stft_mel_f32(ctx_, signals.data(), rows, len, len, window.empty() ? nullptr : window.data(), win_len, hop, nf, bins.data(),
+                                         bins.size() - 2, energies.data()));
+    }
+    // ... through logf(e + 1e-12f) and the first num_coeffs outputs of dct::dct2: coeffs rows * frames * num_coeffs.  InvalidValue for
+    // num_coeffs > bins.size() - 2 (cepstrum.rs:79); otherwise as stft_mel.
+    Result stft_mfcc(const std::vector<float> &signals, size_t rows, size_t win_len, size_t hop, const std::vector<uint64_t> &bins, size_t num_coeffs,
+                     std::vector<float> &coeffs, const std::vector<float> &window = {}, size_t frames = 0) const
+    {
+        static_assert(std::is_same<T, float>::value, "the audio front end is f32-only (cepstrum.rs:72)");
+        if (hop == 0) return Result::Err(FftError::InvalidHopSize);
+        if (bins.size() >= 2 && num_coeffs > bins.size() - 2) return Result::Err(FftError::InvalidValue);
+        if (rows == 0 || signals.size() % rows != 0 || bins.size() < 2 || (!window.empty() && window.size() != win_len))
+            return Result::Err(FftError::MismatchedLengths);
+        const size_t len = signals.size() / rows, need = len / hop + (len % hop != 0), nf = frames ? frames : need;
+        if (coeffs.size() != rows * nf * num_coeffs) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_stft_mfcc_f32(ctx_, signals.data(), rows, len, len, window.empty() ? nullptr : window.data(), win_len, hop, nf, bins.data(),
+                                          bins.size() - 2, num_coeffs, coeffs.data()));
+    }
+    // ... on device memory, asynchronous on the context's stream: row r at d_signal + r * row_stride, d_window null for hann(win_len), bins a
+    // host vector read before the call returns; the output must overlap neither the signal nor the window (InvalidValue)
+    Result stft_mel_dev(const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len, size_t hop,
+                        size_t frames, const std::vector<uint64_t> &bins, float *d_energies) const
+    {
+        static_assert(std::is_same<T, float>::value, "the audio front end is f32-only (cepstrum.rs:36)");
+        if (bins.size() < 2) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_dev_stft_mel_f32(ctx_, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins.data(), bins.size() - 2,
+                                             d_energies));
+    }
+    Result stft_mfcc_dev(const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len, size_t hop,
+                         size_t frames, const std::vector<uint64_t> &bins, size_t num_coeffs, float *d_coeffs) const
+    {
+        static_assert(std::is_same<T, float>::value, "the audio front end is f32-only (cepstrum.rs:72)");
+        if (bins.size() < 2) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_dev_stft_mfcc_f32(ctx_, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins.data(), bins.size() - 2,
+                                              num_coeffs, d_coeffs));
+    }
+    // 1 (the default): the measured choice (the composed route, which measured faster at every shape); 0: every call composed; 2:
+    // the fused kernel wherever it fits (power-of-two windows of 64 .. 2048 samples, up to 128 filters) -- the same bytes
+    Result set_frontend_fused(int mode) const { return st(kofft_hip_set_frontend_fused(ctx_, mode)); }
     // visual::spectrogram::magnitude_to_db / db_scale (spectrogram.rs:96-110) of every value, f32 only like the reference, with the libm
     // crate's log10f (kofft_hip.h: the arithmetic contract).  EmptyInput for no values, MismatchedLengths for an output of another size.
     Result magnitude_to_db(const std::vector<float> &mags, float max_mag, float floor_db, std::vector<float> &out) const

@@ -61,6 +61,12 @@ extern "C" {
     fn kofft_hip_mfcc_f32(ctx: *mut KofftHipCtx, mags: *const f32, coeffs: *mut f32, n_fft: usize, rows: usize, bins: *const u64,
                           num_mel: usize, num_coeffs: usize) -> c_int;
     fn kofft_hip_set_mfcc_fused(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
+    fn kofft_hip_stft_mel_f32(ctx: *mut KofftHipCtx, signal: *const f32, rows: usize, len: usize, row_stride: usize, window: *const f32,
+                              win_len: usize, hop: usize, frames: usize, bins: *const u64, num_mel: usize, energies: *mut f32) -> c_int;
+    fn kofft_hip_stft_mfcc_f32(ctx: *mut KofftHipCtx, signal: *const f32, rows: usize, len: usize, row_stride: usize, window: *const f32,
+                               win_len: usize, hop: usize, frames: usize, bins: *const u64, num_mel: usize, num_coeffs: usize,
+                               coeffs: *mut f32) -> c_int;
+    fn kofft_hip_set_frontend_fused(ctx: *mut KofftHipCtx, mode: c_int) -> c_int;
     fn kofft_hip_magnitude_to_db_f32(ctx: *mut KofftHipCtx, mags: *const f32, count: usize, max_mag: *const f32, floor_db: f32, out: *mut f32) -> c_int;
     fn kofft_hip_db_scale_f32(ctx: *mut KofftHipCtx, mags: *const f32, count: usize, max_mag: *const f32, dynamic_range: f32, out: *mut f32) -> c_int;
     fn kofft_hip_spectrogram_render_f32(ctx: *mut KofftHipCtx, mags: *const f32, frames: usize, bins: usize, max_mag: *const f32, mode: c_int,
@@ -461,6 +467,36 @@ impl HipFftImpl<f32> {
     pub fn set_mfcc_fused(&self, mode: i32) -> Result<(), FftError> {
         status(self.ctx, unsafe { kofft_hip_set_mfcc_fused(self.ctx, mode as c_int) })
     }
+
+    /// The audio front end in one call: `stft_magnitudes` -> `mel_filterbank` (`num_coeffs` `None`) or -> `mfcc` of every row of `len`
+    /// samples in `signals`, `frames` frames per row, with the filter edges `bins` over the `win_len / 2` magnitudes of a frame.  `out`
+    /// receives rows * frames rows of `num_mel` energies or `num_coeffs` coefficients, bit for bit what the two calls return; the
+    /// magnitudes stay on the device.  `window` `None` is `window::hann(win_len)`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn stft_mel_rows(&self, signals: &[f32], len: usize, window: Option<&[f32]>, win_len: usize, hop: usize, frames: usize, bins: &[u64],
+                         num_coeffs: Option<usize>, out: &mut [f32]) -> Result<(), FftError> {
+        if hop == 0 { return Err(FftError::InvalidHopSize); }
+        if let Some(nc) = num_coeffs { if bins.len() >= 2 && nc > bins.len() - 2 { return Err(FftError::InvalidValue); } }
+        if bins.len() < 2 || (len != 0 && signals.len() % len != 0) || (len == 0 && !signals.is_empty()) { return Err(FftError::MismatchedLengths); }
+        if let Some(w) = window { if w.len() != win_len { return Err(FftError::MismatchedLengths); } }
+        let num_mel = bins.len() - 2;
+        let width = num_coeffs.unwrap_or(num_mel);
+        let rows = if len != 0 { signals.len() / len } else if frames * width != 0 { out.len() / (frames * width) } else { 0 };
+        if out.len() != rows * frames * width { return Err(FftError::MismatchedLengths); }
+        let win = window.map_or(std::ptr::null(), |w| w.as_ptr());
+        status(self.ctx, unsafe {
+            match num_coeffs {
+                None => kofft_hip_stft_mel_f32(self.ctx, signals.as_ptr(), rows, len, len, win, win_len, hop, frames, bins.as_ptr(), num_mel, out.as_mut_ptr()),
+                Some(nc) => kofft_hip_stft_mfcc_f32(self.ctx, signals.as_ptr(), rows, len, len, win, win_len, hop, frames, bins.as_ptr(), num_mel, nc,
+                                                    out.as_mut_ptr()),
+            }
+        })
+    }
+
+    /// 1 (the default): the measured choice; 0: every front-end call composed; 2: the fused kernel wherever it fits (the same bytes).
+    pub fn set_frontend_fused(&self, mode: i32) -> Result<(), FftError> {
+        status(self.ctx, unsafe { kofft_hip_set_frontend_fused(self.ctx, mode as c_int) })
+    }
 }
 
 /// `kofft::cepstrum`'s mel functions (cepstrum.rs:36-98) on the device, the reference's three functions with a context in front.
@@ -499,6 +535,31 @@ pub mod cepstrum {
     pub fn mfcc(fft: &HipFftImpl<f32>, fft_mags: &[f32], sample_rate: f32, num_mel: usize, num_coeffs: usize) -> Result<Vec<f32>, FftError> {
         let mut out = vec![0.0f32; num_coeffs];
         fft.mfcc_rows(fft_mags, fft_mags.len(), &mel_bins(sample_rate, fft_mags.len(), num_mel), num_coeffs, &mut out)?;
+        Ok(out)
+    }
+
+    /// Mel energies of every frame of every row of `len` samples: `stft_magnitudes` (Hann, `ceil(len / hop)` frames per row) followed by
+    /// `cepstrum::mel_filterbank` over the `win_len / 2` magnitudes of each frame, in one device call; rows * frames rows of
+    /// `num_filters` energies.  The edges are `mel_bins(sample_rate, win_len / 2, num_filters)`, the crate's own.
+    pub fn mel_from_audio(fft: &HipFftImpl<f32>, signals: &[f32], len: usize, sample_rate: f32, win_len: usize, hop: usize,
+                          num_filters: usize) -> Result<Vec<f32>, FftError> {
+        if hop == 0 { return Err(FftError::InvalidHopSize); }
+        let frames = len / hop + (len % hop != 0) as usize;
+        let rows = if len != 0 { signals.len() / len } else { 0 };
+        let mut out = vec![0.0f32; rows * frames * num_filters];
+        fft.stft_mel_rows(signals, len, None, win_len, hop, frames, &mel_bins(sample_rate, win_len / 2, num_filters), None, &mut out)?;
+        Ok(out)
+    }
+
+    /// ... through `logf(e + 1e-12)` and the first `num_coeffs` outputs of `dct::dct2`: rows * frames rows of `num_coeffs` coefficients,
+    /// what `cepstrum::mfcc` returns for each frame's magnitudes.
+    pub fn mfcc_from_audio(fft: &HipFftImpl<f32>, signals: &[f32], len: usize, sample_rate: f32, win_len: usize, hop: usize, num_mel: usize,
+                           num_coeffs: usize) -> Result<Vec<f32>, FftError> {
+        if hop == 0 { return Err(FftError::InvalidHopSize); }
+        let frames = len / hop + (len % hop != 0) as usize;
+        let rows = if len != 0 { signals.len() / len } else { 0 };
+        let mut out = vec![0.0f32; rows * frames * num_coeffs];
+        fft.stft_mel_rows(signals, len, None, win_len, hop, frames, &mel_bins(sample_rate, win_len / 2, num_mel), Some(num_coeffs), &mut out)?;
         Ok(out)
     }
 

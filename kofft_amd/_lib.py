@@ -88,6 +88,12 @@ SIGNATURES = {
     "kofft_hip_dev_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_mfcc_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_mel_bins_f32": (C.c_int, [C.c_float, _sz, _sz, C.c_void_p]),
+    "kofft_hip_stft_mel_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, C.c_void_p]),
+    "kofft_hip_dev_stft_mel_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, C.c_void_p]),
+    "kofft_hip_stft_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p]),
+    "kofft_hip_dev_stft_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz,
+                                                   C.c_void_p]),
+    "kofft_hip_set_frontend_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_magnitude_to_db_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),
     "kofft_hip_dev_magnitude_to_db_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),
     "kofft_hip_db_scale_f32": (C.c_int, [_ctx, C.c_void_p, _sz, C.c_void_p, C.c_float, C.c_void_p]),

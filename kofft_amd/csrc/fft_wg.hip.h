@@ -740,7 +740,7 @@ struct IrfftIO : PlainTw {
     }
 };
 
-enum : int { EPI_STORE = 0, EPI_RFFT = 1 };
+enum : int { EPI_STORE = 0, EPI_RFFT = 1, EPI_MEL = 2 };  // EPI_MEL: the policy finishes its transforms from LDS (frontend_impl.hip.h)
 
 // ---- LDS exchange layouts --------------------------------------------------------------------------------------
 // Plain (threads of a transform contiguous in the wave): each transform slot owns lds_elems(n) padded elements.
@@ -1119,6 +1119,11 @@ __global__ __launch_bounds__(BLOCK, (IO::kMinWaves > 1 && BLOCK == 512 && L == 9
                 }
             }
         }
+    } else if constexpr (EPI == EPI_MEL) {
+        // the audio front end: magnitudes, filterbank, log and DCT of the workgroup's XPB frames without leaving LDS
+        static_assert(!SPLIT && !SM, "the front end's epilogue owns a plain slot per transform");
+        if (NP > 1) __syncthreads();  // every gather of the last exchange is done: the slots are free
+        io.template mel_epilogue<L, RL, BLOCK>(v, smem_raw, blk, batch, tau, slot);
     } else {
         if constexpr (io_has_acc<IO>::value) {
             typename IO::Acc acc = io.acc_init();

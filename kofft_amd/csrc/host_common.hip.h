@@ -70,6 +70,7 @@ struct kofft_hip_ctx {
     bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
+    int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
     bool spec_transpose = true; // kofft_hip_set_spectrogram_transpose(ctx, 0): the image layout of the spectrogram render with every lane storing its own bytes instead of the exchange through LDS (the same bytes; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     bool dht_table_device = true; // kofft_hip_set_dht_table_device(ctx, 0): the Hartley table of a new length built on the host and uploaded instead of by dht_table_kernel (the same bytes; A/B, tests)
@@ -827,6 +828,14 @@ int mel_filterbank_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_energie
 int mfcc_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
              size_t num_coeffs);
 void mel_drop(kofft_hip_ctx *ctx);  // frees every plan; the caller has synchronised the stream
+// the device plan [seg | live | w] of (bins, n_fft, num_mel) from the context's cache, built and uploaded stream-ordered on a miss
+int get_mel_plan(kofft_hip_ctx *ctx, const uint64_t *bins, size_t n_fft, size_t num_mel, const int **out);
+// k_frontend_f32.hip: rows of audio -> stft_magnitudes -> mel_filterbank (-> logf -> dct2) in one call (frontend_impl.hip.h; DESIGN.md
+// 5.23); d_window null: window::hann(win_len).  frontend_check: the argument checks alone, the STFT rows' first, then the mel ones
+int frontend_check(bool mfcc, bool dev, const void *signal, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
+                   size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, const kofft_hip_ctx *ctx);
+int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                 size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *d_out);
 // k_spectrogram_f32.hip: visual::spectrogram's colour helpers (spectrogram_impl.hip.h).  spec_*_check: the argument checks alone, in
 // the order of include/kofft_hip.h; pix_of_bin is a host pointer in both forms, max_mag a device pointer in the *_dev functions
 constexpr size_t kSpecMaxBins = size_t(1) << 24;

@@ -1,0 +1,188 @@
+// k_frontend_f32.hip -- rows of audio to mel energies or MFCCs in one call (frontend_impl.hip.h): every kernel
+// instance of the family, the argument checks and the two routes.
+#include "frontend_impl.hip.h"
+
+#include "direct_impl.hip.h"
+
+namespace kofft {
+namespace host {
+
+// the magnitudes kernels without a maximum run their parents' configurations
+template <> struct PersistCfg<10, StftMagRowsNoMaxIO> : PersistCfg<10, StftMagIO> {};
+template <> struct PersistCfg<11, StftMagRowsNoMaxIO> : PersistCfg<11, StftMagIO> {};
+template <> struct PersistCfg<12, StftMagRowsNoMaxIO> : PersistCfg<12, StftMagIO> {};
+
+// Checks in the order of include/kofft_hip.h, all before the context or the device is touched: the STFT rows' first, then the mel ones.
+int frontend_check(bool mfcc, bool dev, const void *signal, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
+                   size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, const kofft_hip_ctx *ctx)
+{
+    const int crc = stft_rows_check(true, true, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (mfcc && num_coeffs > num_mel) return KOFFT_ERR_INVALID_VALUE;  // cepstrum.rs:79
+    if (!bins) return KOFFT_ERR_NULL;
+    for (size_t i = 0; i < num_mel + 1 && i + 1 != 0; ++i)
+        if (bins[i + 1] < bins[i]) return KOFFT_ERR_INVALID_VALUE;
+    if (win_len / 2 > kMelMaxFft || num_mel > kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !out || (!signal && len)) return KOFFT_ERR_NULL;
+    if (dev) {
+        const size_t out_row = mfcc ? num_coeffs : num_mel;
+        const float *o = static_cast<const float *>(out), *oe = o + rows * frames * out_row;
+        const float *s = static_cast<const float *>(signal), *w = static_cast<const float *>(window);
+        const size_t span = len ? (rows - 1) * (rows > 1 ? row_stride : 0) + len : 0;
+        if (o < oe && span && s < oe && o < s + span) return KOFFT_ERR_INVALID_VALUE;
+        if (o < oe && w && w < oe && o < w + win_len) return KOFFT_ERR_INVALID_VALUE;
+    }
+    return KOFFT_OK;
+}
+
+// ---- the fused route ---------------------------------------------------------------------------------------------------------------
+constexpr size_t kFrontendFusedMinWin = 64, kFrontendFusedMaxWin = 2048;  // fft_wg_kernel's window lengths with room for the log-mel rows
+
+static bool frontend_fused_fits(size_t win_len, size_t num_mel)
+{
+    return is_pow2(win_len) && win_len >= kFrontendFusedMinWin && win_len <= kFrontendFusedMaxWin && num_mel <= kMfccFusedMaxMel;
+}
+
+// Mode 1 takes the fused kernel only where it beat the two-call chain by more than the spread of the runs at every batch measured
+// AND is not slower than the composed route.  Measured on an MI355X: it beats the chain at win_len 64 .. 512 with
+// 40 x 13 (10-14 % at 1024 rows), loses to it at config 4's stream (0.315 against 0.220 ms) and loses to the composed route at every
+// shape by 21-51 % (the generic workgroup kernel against the persistent magnitudes kernels, and an epilogue that leaves most lanes
+// idle).  So no shape takes it by default; it stays behind mode 2.
+static bool frontend_use_fused(const kofft_hip_ctx *ctx, size_t win_len, size_t num_mel, size_t num_coeffs)
+{
+    (void)num_coeffs;
+    if (ctx->frontend_fused == 0 || !frontend_fused_fits(win_len, num_mel)) return false;
+    return ctx->frontend_fused == 2;
+}
+
+template <int L, bool MFCC>
+static int launch_frontend(kofft_hip_ctx *ctx, const FrontendIO<MFCC> &io, const cpx<float> *tw, size_t batch)
+{
+    constexpr int RL = rl_for(L), TPT = (1 << L) >> RL, BLOCK = TPT > 256 ? TPT : 256, XPB = BLOCK / TPT;
+    constexpr size_t slots = lds_wg_bytes<float, false, false, XPB>(1 << L);
+    static_assert(slots + XPB * kMfccFusedMaxMel * sizeof(float) <= 64 * 1024, "LDS without an attribute");
+    const size_t lds = slots + (MFCC ? (size_t)XPB * io.num_mel * sizeof(float) : 0);
+    const size_t blocks = (batch + XPB - 1) / XPB;
+    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((fft_wg_kernel<float, L, RL, BLOCK, EPI_MEL, FrontendIO<MFCC>>), dim3((unsigned)blocks), dim3(BLOCK), lds, ctx->stream, io,
+                       tw, batch);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
+template <bool MFCC>
+static int frontend_fused(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_win,
+                          size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t nc, float *d_out)
+{
+    const int *plan = nullptr;
+    int rc = get_mel_plan(ctx, bins, win_len / 2, num_mel, &plan);
+    if (rc) return rc;
+    const float *table = nullptr;
+    if (MFCC) {
+        rc = get_direct_table(ctx, 0, 2, num_mel, &table);  // the cache entry of kofft_hip_dct_direct_f32(ctx, 2, ..) at n = num_mel
+        if (rc) return rc;
+    }
+    const cpx<float> *tw = nullptr;
+    rc = twiddle_table<float>(ctx, win_len, &tw);
+    if (rc) return rc;
+    FrontendIO<MFCC> io{};
+    fill_rows_io(io, d_signal, rows, len, row_stride, d_win, win_len, hop, frames);
+    io.plan = plan;
+    io.dct = table;
+    io.res = d_out;
+    io.num_mel = (int)num_mel;
+    io.nc = (int)nc;
+    io.ldc = (int)direct_ldc(num_mel);
+    const size_t batch = rows * frames;
+    switch (ilog2(win_len)) {
+    case 6: return launch_frontend<6, MFCC>(ctx, io, tw, batch);
+    case 7: return launch_frontend<7, MFCC>(ctx, io, tw, batch);
+    case 8: return launch_frontend<8, MFCC>(ctx, io, tw, batch);
+    case 9: return launch_frontend<9, MFCC>(ctx, io, tw, batch);
+    case 10: return launch_frontend<10, MFCC>(ctx, io, tw, batch);
+    case 11: return launch_frontend<11, MFCC>(ctx, io, tw, batch);
+    default: return KOFFT_ERR_UNSUPPORTED;  // (never: frontend_fused_fits)
+    }
+}
+
+// ---- the composed route ------------------------------------------------------------------------------------------------------------
+// magnitudes of frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_mags, no maximum
+static int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_win, size_t win_len,
+                      size_t hop, size_t f0, size_t nf, float *d_mags)
+{
+    StftMagRowsNoMaxIO io{};
+    fill_rows_io(io, d_signal, nrows, len, row_stride, d_win, win_len, hop, nf);
+    io.start0 = (f0 && hop > len / f0) ? len : f0 * hop;  // (a start at or past len: silence, as every frame after it)
+    io.mags = d_mags;
+    io.max_bits = nullptr;
+    return dispatch<float, EPI_STORE>(ctx, io, win_len, nrows * nf);
+}
+
+// Whole frames of the flat index t = row * frames + frame, scratch_chunk_bytes of scratch at a time: [magnitudes | (window lengths the
+// magnitudes kernels do not cover) the composed frames].  A chunk may begin and end inside a row: it is cut into the rest of its
+// first row, whole rows, and the head of its last row.
+static int frontend_composed(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_win,
+                             size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t nc, float *d_out)
+{
+    const size_t half = win_len / 2, total = rows * frames, out_row = mfcc ? nc : num_mel;
+    const bool kernels = fused_len_ok<float>(win_len);
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, half * sizeof(float) + (kernels ? 0 : win_len * sizeof(cpx<float>)), total);
+    const size_t mags_bytes = (chunk * half * sizeof(float) + 15) & ~size_t(15);
+    int rc = ensure(ctx, ctx->rows_tmp, mags_bytes + (kernels ? 0 : chunk * win_len * sizeof(cpx<float>)) + 16);
+    if (rc) return rc;
+    float *mags = static_cast<float *>(ctx->rows_tmp.p);
+    cpx<float> *spec = reinterpret_cast<cpx<float> *>(static_cast<char *>(ctx->rows_tmp.p) + mags_bytes);
+    if (rows == 1) row_stride = 0;
+    for (size_t t0 = 0; t0 < total; t0 += chunk) {
+        const size_t nt = total - t0 < chunk ? total - t0 : chunk, end = t0 + nt;
+        if (half && !kernels) {
+            rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_win, win_len, hop, spec, t0, nt);
+            if (rc) return rc;
+            const size_t blocks = (nt * half + 255) / 256;
+            if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL(frontend_mag_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, mags, win_len, nt * half);
+            KOFFT_HIP_TRY(ctx, hipGetLastError());
+        } else if (half) {
+            for (size_t t = t0; t < end;) {
+                const size_t r = t / frames, f = t - r * frames;
+                const float *sig = d_signal ? d_signal + r * row_stride : nullptr;
+                size_t done;
+                if (f != 0 || end - t < frames) {  // part of row r
+                    done = frames - f < end - t ? frames - f : end - t;
+                    rc = mags_piece(ctx, sig, 1, len, 0, d_win, win_len, hop, f, done, mags + (t - t0) * half);
+                } else {
+                    const size_t nr = (end - t) / frames;
+                    done = nr * frames;
+                    rc = mags_piece(ctx, sig, nr, len, row_stride, d_win, win_len, hop, 0, frames, mags + (t - t0) * half);
+                }
+                if (rc) return rc;
+                t += done;
+            }
+        }
+        rc = mfcc ? mfcc_dev(ctx, mags, d_out + t0 * out_row, half, nt, bins, num_mel, nc)
+                  : mel_filterbank_dev(ctx, mags, d_out + t0 * out_row, half, nt, bins, num_mel);
+        if (rc) return rc;
+    }
+    return KOFFT_OK;
+}
+
+int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                 size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *d_out)
+{
+    const int crc = frontend_check(mfcc, true, d_signal, d_window, d_out, rows, len, row_stride, win_len, hop, frames, bins, num_mel, num_coeffs, ctx);
+    if (crc || rows == 0 || frames == 0 || num_mel == 0 || (mfcc && num_coeffs == 0)) return crc;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const float *d_win = d_window;
+    if (!d_win && win_len >= 2) {  // window::hann(win_len), stft_magnitudes' own (a one-sample window has no magnitude bins)
+        const int rc = hann_table(ctx, win_len, &d_win);
+        if (rc) return rc;
+    }
+    if (frontend_use_fused(ctx, win_len, num_mel, num_coeffs)) {
+        return mfcc ? frontend_fused<true>(ctx, d_signal, rows, len, row_stride, d_win, win_len, hop, frames, bins, num_mel, num_coeffs, d_out)
+                    : frontend_fused<false>(ctx, d_signal, rows, len, row_stride, d_win, win_len, hop, frames, bins, num_mel, 0, d_out);
+    }
+    return frontend_composed(ctx, mfcc, d_signal, rows, len, row_stride, d_win, win_len, hop, frames, bins, num_mel, num_coeffs, d_out);
+}
+
+}  // namespace host
+}  // namespace kofft

@@ -36,7 +36,7 @@ void mel_drop(kofft_hip_ctx *ctx)
 // The device plan of (bins, n_fft, num_mel): a hit moves its slot to the front; a miss builds the plan on the host, uploads it on the
 // context's stream (from the slot's own staging vector, which outlives the copy) and, with kMelSlots plans already there, frees the
 // least recently used one after a stream synchronisation.
-static int get_mel_plan(kofft_hip_ctx *ctx, const uint64_t *bins, size_t n_fft, size_t num_mel, const int **out)
+int get_mel_plan(kofft_hip_ctx *ctx, const uint64_t *bins, size_t n_fft, size_t num_mel, const int **out)
 {
     auto &slots = ctx->mel_slots;
     for (size_t j = 0; j < slots.size(); ++j) {

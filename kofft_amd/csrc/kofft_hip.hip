@@ -1356,6 +1356,56 @@ int kofft_hip_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *samples,
     });
 }
 
+// ---- rows of audio to mel energies / MFCCs (k_frontend_f32.hip) --------------------------------------------------
+// The signal goes up, the energies or coefficients come down (whole rows per chunk of the pipeline); the magnitudes stay on the device.
+static int frontend_host(kofft_hip_ctx *ctx, bool mfcc, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                         size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *out)
+{
+    const int crc = frontend_check(mfcc, false, signal, window, out, rows, len, row_stride, win_len, hop, frames, bins, num_mel, num_coeffs, ctx);
+    if (crc || rows == 0 || frames == 0 || num_mel == 0 || (mfcc && num_coeffs == 0)) return crc;
+    std::vector<float> packed;
+    const float *src = pack_rows(signal, rows, len, row_stride, packed);
+    return rows_host<float>(ctx, src, out, rows, len, frames * (mfcc ? num_coeffs : num_mel), window, window ? win_len : 0, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return frontend_dev(ctx, mfcc, d_in, nb, len, len, d_win, win_len, hop, frames, bins, num_mel, num_coeffs, d_out);
+                            });
+}
+
+int kofft_hip_stft_mel_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                                size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, float *energies)
+{
+    return frontend_host(ctx, false, signal, rows, len, row_stride, window, win_len, hop, frames, bins, num_mel, 0, energies);
+}
+
+int kofft_hip_dev_stft_mel_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                    const float *d_window, size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel,
+                                    float *d_energies)
+{
+    return frontend_dev(ctx, false, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins, num_mel, 0, d_energies);
+}
+
+int kofft_hip_stft_mfcc_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                                 size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs,
+                                 float *coeffs)
+{
+    return frontend_host(ctx, true, signal, rows, len, row_stride, window, win_len, hop, frames, bins, num_mel, num_coeffs, coeffs);
+}
+
+int kofft_hip_dev_stft_mfcc_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                     const float *d_window, size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel,
+                                     size_t num_coeffs, float *d_coeffs)
+{
+    return frontend_dev(ctx, true, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins, num_mel, num_coeffs, d_coeffs);
+}
+
+int kofft_hip_set_frontend_fused(kofft_hip_ctx *ctx, int mode)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (mode < 0 || mode > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->frontend_fused = mode;
+    return KOFFT_OK;
+}
+
 int kofft_hip_dev_istft_rows_f32(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len,
                                  size_t hop, float *d_output, size_t out_len, float *d_scratch, size_t scratch_len)
 {
