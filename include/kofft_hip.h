@@ -391,6 +391,43 @@ int kofft_hip_dev_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *d_mags
                                          int mode, float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin,
                                          void *d_out);
 int kofft_hip_set_spectrogram_transpose(kofft_hip_ctx *ctx, int on);
+/* ---- rows of audio -> spectrogram pictures in one call --------------------------
+ * What examples/spectrogram.rs and sanity-check do (stft_magnitudes, its maximum, a colour per bin) and what web-spectrogram's
+ * State::compute_frame does a frame at a time with a running maximum, for `rows` signals at once: the magnitudes never belong to
+ * the caller (they pass through the context's scratch, at most KOFFT_HIP_SCRATCH_CHUNK_MB of it at a time).
+ * Let M[r][f][o], o < win_len/2, be the magnitudes kofft_hip_stft_mel_f32 defines for the same signal, window (NULL: hann(win_len)),
+ * win_len, hop and frames (+0 past the end of a row, never the head of row r + 1).  Picture r is, byte for byte, what
+ * kofft_hip_spectrogram_render_f32 writes for M[r] with the same mode, level, cmap, depth, scale, layout and pix_of_bin (a HOST
+ * pointer in both forms) and the maximum that max_mode chooses; pictures are dense, picture r at out + r * frames * (win_len/2) *
+ * bytes_per_pixel.  channels 3: RGB as in the render; channels 4 (depth 8 only): R, G, B, 255 -- in layout 0 compute_frame's rows.
+ * The output needs no alignment.
+ *   max_mode 0, the row's maximum: stft_magnitudes' (`if mag > max` from +0: a NaN is never selected); max_out[r] is
+ *     kofft_hip_stft_magnitudes_rows_f32's max_mag[r] bit for bit (there: Hann, frames == ceil(len / hop)).
+ *   max_mode 1, the running maximum: compute_frame's.  Per row m starts at 1e-12f; walking frames, then bins, in ascending order,
+ *     `if mag > m { m = mag }` runs BEFORE the pixel is coloured with m (an inclusive prefix); max_out[r] is the final m.  scale == 1
+ *     is refused: the reference defines no position for the maximum under log_scale_bins.
+ *   max_mode 2, given: max_in[r] is used unvalidated, as in the render; max_out, if given, receives a copy; nothing is computed.
+ * max_out may be NULL in every mode; max_in is read in mode 2 only.  In the kofft_hip_dev_* forms signal, window, max_in, max_out
+ * and out are device pointers, the call is asynchronous on the context's stream and nothing synchronises with the host.
+ * Checks, in this order and before the context or the device is touched:
+ *   1. kofft_hip_stft_mel_f32's STFT checks: hop == 0 -> INVALID_HOP_SIZE; frames < ceil(len / hop) -> MISMATCHED_LENGTHS; rows == 0
+ *      or frames == 0 -> KOFFT_OK, nothing written; win_len == 0 -> EMPTY_INPUT; its limits -> KOFFT_ERR_UNSUPPORTED; rows > 1 with
+ *      row_stride < len -> INVALID_VALUE;
+ *   2. the render's: an unknown mode, cmap, depth, scale or layout, a colorous palette, scale == 1 with a null table, an entry
+ *      >= win_len/2 or a table that decreases -> INVALID_VALUE;
+ *   3. an unknown max_mode, channels not 3 or 4, channels == 4 with depth 16, max_mode == 1 with scale == 1 -> INVALID_VALUE;
+ *      win_len/2 > 2^24 -> KOFFT_ERR_UNSUPPORTED;
+ *   4. win_len == 1 (no bins) -> KOFFT_OK with nothing written but max_out: +0 (mode 0), 1e-12f (mode 1), max_in's copy (mode 2; a
+ *      null max_in is KOFFT_ERR_NULL; the device form needs the context to write and returns KOFFT_ERR_NULL without one);
+ *   5. a null context, out, signal (len > 0) or (mode 2) max_in -> KOFFT_ERR_NULL;
+ *   6. (device forms) out overlapping the signal, the window, max_in or max_out -> INVALID_VALUE. */
+int kofft_hip_stft_picture_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                               size_t win_len, size_t hop, size_t frames, int max_mode, const float *max_in, float *max_out, int mode,
+                               float level, int cmap, int depth, int channels, int scale, int layout, const uint32_t *pix_of_bin, void *out);
+int kofft_hip_dev_stft_picture_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                   const float *d_window, size_t win_len, size_t hop, size_t frames, int max_mode, const float *d_max_in,
+                                   float *d_max_out, int mode, float level, int cmap, int depth, int channels, int scale, int layout,
+                                   const uint32_t *pix_of_bin, void *d_out);
 /* Host only: pix_of_bin[b] = map_bin_to_pixel(b, bins - 1) (spectrogram.rs:209-217) for every b < bins: max_bin == 0 -> 0, else
  * floor(max_bin as f32 * ln(b as f32 + 1) / ln(max_bin as f32 + 1)) as a saturating cast, f32 in Rust's parse order with GLIBC's logf.
  * bins == 0 -> EMPTY_INPUT; bins > 2^24 -> KOFFT_ERR_UNSUPPORTED; a null pointer -> KOFFT_ERR_NULL. */

@@ -21,6 +21,8 @@
 //   kofft::HipFftImpl<float>::stft_mel / stft_mfcc   stft_magnitudes -> mel_filterbank (-> logf -> dct2) of rows of signals in one call,
 //                                                the magnitudes never leaving the device (no counterpart in the reference: its pipeline)
 //   kofft::HipFftImpl<float>::magnitude_to_db / db_scale / spectrogram_render, kofft::log_bin_map / map_color_u8
+//   kofft::HipFftImpl<float>::stft_picture / stft_picture_dev   audio -> stft_magnitudes -> the row's, the running (web-spectrogram's
+//                                                compute_frame) or a given maximum -> one picture per row, in one call
 //                                                visual::spectrogram's colour helpers, visual/spectrogram.rs:96-234 (log10 is the libm
 //                                                crate's log10f; Viridis / Plasma / Inferno are InvalidValue)
 //   kofft::HipFftImpl<float>::dct_direct         dct::dct1..dct4, dct.rs:108-176 (the direct sums)
@@ -431,6 +433,44 @@ public:
         if (bins.size() < 2) return Result::Err(FftError::MismatchedLengths);
         return st(kofft_hip_dev_stft_mfcc_f32(ctx_, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins.data(), bins.size() - 2,
                                               num_coeffs, d_coeffs));
+    }
+    // Audio -> spectrogram pictures in one call (kofft_hip.h): stft_magnitudes of `rows` signals of signals.size() / rows samples,
+    // the maximum max_mode chooses (0: the row's, stft_magnitudes' own; 1: web-spectrogram's compute_frame's running maximum from 1e-12; 2:
+    // max_in[r]) and spectrogram_render's colours, one dense picture per row: rows * frames * (win_len / 2) * channels Pixels, byte for byte
+    // what stft_magnitudes_rows followed by spectrogram_render gives per row; the magnitudes stay on the device.  channels 4 (uint8_t only):
+    // R, G, B, 255.  max_out receives the maximum used, one per row.  window empty: hann(win_len); frames 0: ceil(len / hop).
+    // InvalidHopSize first; MismatchedLengths for rows that do not divide the input, too few frames, a window, a table, max_in or pictures
+    // of another size; InvalidValue for the enums, channels 4 at 16 bits and max_mode 1 with scale 1.
+    template <typename Pixel>
+    Result stft_picture(const std::vector<float> &signals, size_t rows, size_t win_len, size_t hop, int max_mode, const std::vector<float> &max_in,
+                        std::vector<float> &max_out, int mode, float level, int cmap, int channels, int scale, int layout,
+                        const std::vector<uint32_t> &pix_of_bin, std::vector<Pixel> &out, const std::vector<float> &window = {},
+                        size_t frames = 0) const
+    {
+        static_assert(std::is_same<T, float>::value, "the spectrogram pictures are f32-only (visual/spectrogram.rs)");
+        static_assert(std::is_same<Pixel, uint8_t>::value || std::is_same<Pixel, uint16_t>::value, "pixels are uint8_t or uint16_t");
+        if (hop == 0) return Result::Err(FftError::InvalidHopSize);
+        if (rows == 0 || signals.size() % rows != 0 || (!window.empty() && window.size() != win_len)) return Result::Err(FftError::MismatchedLengths);
+        const size_t len = signals.size() / rows, need = len / hop + (len % hop != 0), nf = frames ? frames : need;
+        if (channels != 3 && channels != 4) return Result::Err(FftError::InvalidValue);
+        if (out.size() != rows * nf * (win_len / 2) * (size_t)channels || (scale == 1 && pix_of_bin.size() != win_len / 2) ||
+            (max_mode == 2 && max_in.size() != rows))
+            return Result::Err(FftError::MismatchedLengths);
+        max_out.assign(rows, 0.0f);
+        return st(kofft_hip_stft_picture_f32(ctx_, signals.data(), rows, len, len, window.empty() ? nullptr : window.data(), win_len, hop, nf, max_mode,
+                                             max_mode == 2 ? max_in.data() : nullptr, max_out.data(), mode, level, cmap, (int)(8 * sizeof(Pixel)),
+                                             channels, scale, layout, scale == 1 ? pix_of_bin.data() : nullptr, out.data()));
+    }
+    // ... on device memory, asynchronous on the context's stream: d_window null for hann(win_len), d_max_in (max_mode 2) and d_max_out (null:
+    // not wanted) device pointers to rows floats, pix_of_bin a host vector read before the call returns; d_out must overlap none of the others
+    Result stft_picture_dev(const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len, size_t hop,
+                            size_t frames, int max_mode, const float *d_max_in, float *d_max_out, int mode, float level, int cmap, int depth,
+                            int channels, int scale, int layout, const std::vector<uint32_t> &pix_of_bin, void *d_out) const
+    {
+        static_assert(std::is_same<T, float>::value, "the spectrogram pictures are f32-only (visual/spectrogram.rs)");
+        if (scale == 1 && pix_of_bin.size() != win_len / 2) return Result::Err(FftError::MismatchedLengths);
+        return st(kofft_hip_dev_stft_picture_f32(ctx_, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, max_mode, d_max_in, d_max_out,
+                                                 mode, level, cmap, depth, channels, scale, layout, scale == 1 ? pix_of_bin.data() : nullptr, d_out));
     }
     // 1 (the default): the measured choice (the composed route, which measured faster at every shape); 0: every call composed; 2:
     // the fused kernel wherever it fits (power-of-two windows of 64 .. 2048 samples, up to 128 filters) -- the same bytes

@@ -73,6 +73,10 @@ extern "C" {
                                         level: f32, cmap: c_int, depth: c_int, scale: c_int, layout: c_int, pix_of_bin: *const u32,
                                         out: *mut core::ffi::c_void) -> c_int;
     fn kofft_hip_set_spectrogram_transpose(ctx: *mut KofftHipCtx, on: c_int) -> c_int;
+    fn kofft_hip_stft_picture_f32(ctx: *mut KofftHipCtx, signal: *const f32, rows: usize, len: usize, row_stride: usize, window: *const f32,
+                                  win_len: usize, hop: usize, frames: usize, max_mode: c_int, max_in: *const f32, max_out: *mut f32, mode: c_int,
+                                  level: f32, cmap: c_int, depth: c_int, channels: c_int, scale: c_int, layout: c_int, pix_of_bin: *const u32,
+                                  out: *mut core::ffi::c_void) -> c_int;
     fn kofft_hip_window_f32(kind: c_int, len: usize, param: f32, out: *mut f32) -> c_int;
     fn kofft_hip_fftnd_c32(ctx: *mut KofftHipCtx, data: *mut f32, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
     fn kofft_hip_fftnd_c64(ctx: *mut KofftHipCtx, data: *mut f64, depth: usize, rows: usize, cols: usize, inverse: c_int) -> c_int;
@@ -620,6 +624,35 @@ impl HipFftImpl<f32> {
         })
     }
 
+    /// Rows of audio -> one 8-bit picture per row in one call (include/kofft_hip.h): `stft_magnitudes` with
+    /// `window::hann(win_len)`, the maximum `max` chooses, `color_from_magnitude_u8` per bin; the magnitudes stay on the device.
+    /// `rgba`: four bytes per pixel, alpha 255 (`compute_frame`'s rows when `image` is false).  `out`: `rows * frames * (win_len / 2) *
+    /// (3 or 4)` bytes; `max_out`: the maximum used, one per row.
+    pub fn stft_picture_rows(&self, signals: &[f32], len: usize, win_len: usize, hop: usize, frames: usize, max: spectrogram::Maximum<'_>,
+                             floor_db: f32, cmap: spectrogram::Colormap, rgba: bool, log_table: Option<&[u32]>, image: bool, max_out: &mut [f32],
+                             out: &mut [u8]) -> Result<(), FftError> {
+        if hop == 0 { return Err(FftError::InvalidHopSize); }
+        let rows = if len == 0 { max_out.len() } else { signals.len() / len };
+        let px = if rgba { 4 } else { 3 };
+        if signals.len() != rows * len || max_out.len() != rows || out.len() != rows * frames * (win_len / 2) * px
+            || log_table.map_or(false, |t| t.len() != win_len / 2) {
+            return Err(FftError::MismatchedLengths);
+        }
+        let (max_mode, max_in) = match max {
+            spectrogram::Maximum::Row => (0, core::ptr::null()),
+            spectrogram::Maximum::Running => (1, core::ptr::null()),
+            spectrogram::Maximum::Given(m) => {
+                if m.len() != rows { return Err(FftError::MismatchedLengths); }
+                (2, m.as_ptr())
+            }
+        };
+        status(self.ctx, unsafe {
+            kofft_hip_stft_picture_f32(self.ctx, signals.as_ptr(), rows, len, len, core::ptr::null(), win_len, hop, frames, max_mode, max_in,
+                                       max_out.as_mut_ptr(), 0, floor_db, cmap as c_int, 8, px as c_int, log_table.is_some() as c_int, image as c_int,
+                                       log_table.map_or(core::ptr::null(), |t| t.as_ptr()), out.as_mut_ptr() as *mut core::ffi::c_void)
+        })
+    }
+
     /// `true` (the default): the image layout leaves through an LDS tile; `false`: every lane stores its own bytes (the same bytes).
     pub fn set_spectrogram_transpose(&self, on: bool) -> Result<(), FftError> {
         status(self.ctx, unsafe { kofft_hip_set_spectrogram_transpose(self.ctx, on as c_int) })
@@ -638,6 +671,11 @@ pub mod spectrogram {
     #[derive(Clone, Copy, Debug, PartialEq)]
     #[repr(i32)]
     pub enum Colormap { Fire = 0, Legacy = 1, Gray = 2, Viridis = 3, Plasma = 4, Inferno = 5, Rainbow = 6 }
+
+    /// Which maximum `from_audio` colours against: the row's (`stft_magnitudes`' own: examples/spectrogram.rs, sanity-check), the running
+    /// one of web-spectrogram's `State::compute_frame` (from 1e-12, updated before each pixel), or one value per row given by the caller.
+    #[derive(Clone, Copy, Debug)]
+    pub enum Maximum<'a> { Row, Running, Given(&'a [f32]) }
 
     /// spectrogram.rs:209-217 with `libm::logf`.
     pub fn map_bin_to_pixel(bin: usize, max_bin: usize) -> usize {
@@ -676,6 +714,22 @@ pub mod spectrogram {
         let table = if log_scale { Some(log_bin_map(bins)) } else { None };
         fft.spectrogram_rgb8(&flat, frames, max_mag, floor_db, cmap, table.as_deref(), true, &mut out)?;
         Ok(out)
+    }
+
+    /// Audio -> pictures in one call: what examples/spectrogram.rs and sanity-check do with `stft_magnitudes`, its maximum and
+    /// `color_from_magnitude_u8` (`Maximum::Row`, `image` true), and what web-spectrogram's `compute_frame` does a frame at a time
+    /// (`Maximum::Running`, `rgba` true, `image` false, Rainbow, a floor of -80 dB), for `signals.len() / len` rows at once; the
+    /// magnitudes never reach the caller.  Returns (the pictures, `ceil(len / hop)` frames each, and the maximum used per row).
+    pub fn from_audio(fft: &HipFftImpl<f32>, signals: &[f32], len: usize, win_len: usize, hop: usize, max: Maximum<'_>, floor_db: f32,
+                      cmap: Colormap, rgba: bool, log_scale: bool, image: bool) -> Result<(Vec<u8>, Vec<f32>), FftError> {
+        if hop == 0 { return Err(FftError::InvalidHopSize); }
+        if len == 0 || signals.len() % len != 0 { return Err(FftError::MismatchedLengths); }
+        let (rows, frames, bins) = (signals.len() / len, (len + hop - 1) / hop, win_len / 2);
+        let mut out = vec![0u8; rows * frames * bins * if rgba { 4 } else { 3 }];
+        let mut max_out = vec![0.0f32; rows];
+        let table = if log_scale { Some(log_bin_map(bins)) } else { None };
+        fft.stft_picture_rows(signals, len, win_len, hop, frames, max, floor_db, cmap, rgba, table.as_deref(), image, &mut max_out, &mut out)?;
+        Ok((out, max_out))
     }
 }
 

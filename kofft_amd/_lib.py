@@ -103,6 +103,10 @@ SIGNATURES = {
     "kofft_hip_dev_spectrogram_render_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                                        C.c_void_p, C.c_void_p]),
     "kofft_hip_set_spectrogram_transpose": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_stft_picture_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "kofft_hip_dev_stft_picture_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "kofft_hip_log_bin_map": (C.c_int, [_sz, C.c_void_p]),
     "kofft_hip_map_color_u8": (C.c_int, [C.c_float, C.c_int, C.c_void_p]),
     "kofft_hip_dct_direct_f32": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, _sz, _sz]),

@@ -846,6 +846,20 @@ int spec_render_check(bool dev, const void *mags, size_t frames, size_t bins, co
 int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max, int mode, float level, int cmap,
                     int depth, int scale, int layout, const uint32_t *pix_of_bin, void *d_out);
 int spec_map_color_u8(float t, int cmap, unsigned char *rgb);
+// the device ranges [start[p], start[p + 1]) of a checked log_scale_bins table, from the context's cache (uploaded stream-ordered on a miss)
+int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins, const uint32_t **out);
+// k_frontend_f32.hip: magnitudes of frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_mags, no maximum
+int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_win, size_t win_len,
+               size_t hop, size_t f0, size_t nf, float *d_mags);
+// k_picture_f32.hip: rows of audio -> stft_magnitudes -> the maximum (max_mode 0: of the row, 1: compute_frame's running one, 2: given)
+// -> one picture per row (picture_impl.hip.h).  picture_check: the argument checks alone, in the order of
+// include/kofft_hip.h; *empty is set where the call has no bins (win_len == 1) and only max_out is written
+int picture_check(bool dev, const void *signal, size_t rows, size_t len, size_t row_stride, const void *window, size_t win_len, size_t hop,
+                  size_t frames, int max_mode, const void *max_in, const void *max_out, int mode, int cmap, int depth, int channels, int scale,
+                  int layout, const uint32_t *pix_of_bin, const void *out, const kofft_hip_ctx *ctx, bool *empty);
+int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
+                size_t hop, size_t frames, int max_mode, const float *d_max_in, float *d_max_out, int mode, float level, int cmap, int depth,
+                int channels, int scale, int layout, const uint32_t *pix_of_bin, void *d_out);
 void spec_drop(kofft_hip_ctx *ctx);  // frees every range table; the caller has synchronised the stream
 int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
                        float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)

@@ -107,7 +107,7 @@ static int frontend_fused(kofft_hip_ctx *ctx, const float *d_signal, size_t rows
 
 // ---- the composed route ------------------------------------------------------------------------------------------------------------
 // magnitudes of frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_mags, no maximum
-static int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_win, size_t win_len,
+int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_win, size_t win_len,
                       size_t hop, size_t f0, size_t nf, float *d_mags)
 {
     StftMagRowsNoMaxIO io{};

@@ -58,7 +58,7 @@ void spec_drop(kofft_hip_ctx *ctx)
 // The device ranges of a (checked) table: a hit moves its slot to the front; a miss builds the ranges on the host, uploads them on the
 // context's stream (from the slot's own staging vector, which outlives the copy) and, with kSpecSlots tables already there, frees the
 // least recently used one after a stream synchronisation.
-static int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins, const uint32_t **out)
+int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins, const uint32_t **out)
 {
     auto &slots = ctx->spec_slots;
     for (size_t j = 0; j < slots.size(); ++j) {

@@ -145,8 +145,8 @@ __host__ __device__ __forceinline__ uint32_t spec_color(float mag, float max_mag
     return spec_map_color(t, cmap);
 }
 
-// which == 0: magnitude_to_db, else db_scale
-__global__ __launch_bounds__(256) void spec_db_kernel(const float *__restrict__ mags, float *__restrict__ out, const size_t count,
+// which == 0: magnitude_to_db, else db_scale (internal linkage: picture_impl.hip.h includes this header into a second unit)
+static __global__ __launch_bounds__(256) void spec_db_kernel(const float *__restrict__ mags, float *__restrict__ out, const size_t count,
                                                       const float *__restrict__ max_mag, const float level, const int which)
 {
     const float mx = *max_mag;
