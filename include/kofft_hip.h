@@ -253,6 +253,33 @@ int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size
 int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
 int kofft_hip_set_cepstrum_fused(kofft_hip_ctx *ctx, int on);
 
+/* ---- FFT convolution and correlation of rows (overlap-save) ------------------------
+ * `rows` contiguous signals x of nx f32 samples, a filter h of nh f32 taps -- one for all rows (filters == 1) or one per row (filters ==
+ * rows, rows * nh floats) -- and a power-of-two block >= nh.  With hop = block - nh + 1, full = nx + nh - 1 and nb = ceil(full / hop),
+ * every value is a composition of the reference's operations, bit for bit:
+ *   H = fft((h[i], +0) zero-padded to block) (fft.rs:1054-1132); flags bit 0 (correlate): the taps in reverse order, h[nh - 1 - i],
+ *     so that the result is numpy.correlate(x, h, "full") for real data;
+ *   for block b of a row: frame[i] = (x[b * hop - (nh - 1) + i], +0) where that sample exists, (+0, +0) elsewhere; X = fft(frame);
+ *   Y[k] = X[k] * H[k], Complex::mul un-fused (num.rs:162-165); y = ifft(Y) (fft.rs:1134-1174: conj, fft, conj, * 1 / block);
+ *   full_out[b * hop + j] = y[nh - 1 + j].re for j < hop.
+ * out receives full_out[out_first .. out_first + out_len) of every row, dense, out_len floats per row ("full": 0, full; "same":
+ * (nh - 1) / 2, nx; "valid": nh - 1, nx - nh + 1); blocks wholly outside that window are not computed.  The result's bits depend on
+ * block (the reference's table recurrence makes long transforms less accurate).  block == 0: the library's choice, which
+ * kofft_hip_convolve_block(nx, nh, &block) returns without a context (EMPTY_INPUT for nx == 0 or nh == 0).  Checks, in this order and
+ * before the context or a device is touched: rows == 0 or out_len == 0 -> KOFFT_OK; nx == 0 or nh == 0 -> EMPTY_INPUT; block not a
+ * power of two -> NON_POWER_OF_TWO_NO_STD; block < nh -> MISMATCHED_LENGTHS; filters not 1 or rows -> MISMATCHED_LENGTHS; out_first +
+ * out_len > full -> MISMATCHED_LENGTHS; a flag bit other than bit 0 -> INVALID_VALUE; block > 65536 -> KOFFT_ERR_UNSUPPORTED; a null
+ * pointer or context -> KOFFT_ERR_NULL.  kofft_hip_convolve_f32: host pointers; kofft_hip_dev_convolve_f32: device pointers,
+ * asynchronous on the context's stream; out must not overlap x or h.  Blocks 32 .. 4096 run one fused kernel (4-byte aligned x);
+ * kofft_hip_set_convolve_fused(ctx, 0) sends every block of that context through the composed route instead (frames into the
+ * context's scratch, transform, multiply, inverse transform, gather: the same bytes; A/B measurements and tests). */
+int kofft_hip_convolve_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh,
+                           size_t block, unsigned flags, float *out, size_t out_first, size_t out_len);
+int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh,
+                               size_t block, unsigned flags, float *d_out, size_t out_first, size_t out_len);
+int kofft_hip_set_convolve_fused(kofft_hip_ctx *ctx, int on);
+int kofft_hip_convolve_block(size_t nx, size_t nh, size_t *block);
+
 /* ---- mel filterbank and MFCC ------------------------------------------------------
  * cepstrum::mel_filterbank / mfcc / mfcc_batch (cepstrum.rs:36-98), f32 only like the reference, on `rows` contiguous rows of n_fft
  * magnitudes -- what kofft_hip_dev_stft_magnitudes_rows_f32 writes, rows x frames flattened.  The filter edges are an INPUT: bins is

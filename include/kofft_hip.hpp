@@ -346,6 +346,25 @@ public:
         if (n & (n - 1)) return Result::Err(FftError::NonPowerOfTwoNoStd);
         return st(kofft_hip_cepstrum_f32(ctx_, input.data(), output.data(), n, batch));
     }
+    // Overlap-save FFT convolution of `rows` contiguous rows of x.size() / rows samples with h: nh taps for all rows (h.size() == nh)
+    // or per row (h.size() == rows * nh).  out is resized to rows * count: values first .. first + count of each row's full result
+    // of nx + nh - 1 values (count == SIZE_MAX: up to its end).  block: the power-of-two transform length >= nh, 0: the library's
+    // choice (kofft_hip_convolve_block).  MismatchedLengths for rows that do not divide x or taps of another size; then the C
+    // entry's checks in its order.
+    Result convolve_rows(const std::vector<float> &x, const std::vector<float> &h, size_t nh, std::vector<float> &out, size_t rows = 1,
+                         size_t block = 0, size_t first = 0, size_t count = SIZE_MAX) const
+    {
+        return convolve_impl(x, h, nh, out, rows, block, first, count, 0u);
+    }
+    // false: every convolution of this context through frames in the scratch, transform, multiply, inverse transform, gather (the
+    // same bytes; A/B, tests)
+    Result set_convolve_fused(bool on) const { return st(kofft_hip_set_convolve_fused(ctx_, on ? 1 : 0)); }
+    // The cross-correlation of the same rows: convolve_rows with the taps reversed (numpy.correlate's "full" order for real data).
+    Result correlate_rows(const std::vector<float> &x, const std::vector<float> &h, size_t nh, std::vector<float> &out, size_t rows = 1,
+                          size_t block = 0, size_t first = 0, size_t count = SIZE_MAX) const
+    {
+        return convolve_impl(x, h, nh, out, rows, block, first, count, 1u);
+    }
     // cepstrum::mel_filterbank's sums (cepstrum.rs:51-67), f32 only like the reference: `rows` contiguous rows of mags.size() / rows
     // magnitudes in, rows of bins.size() - 2 energies out, with the filter edges `bins` (num_mel + 2 nondecreasing values; kofft::mel_bins
     // gives the reference-shaped ones).  MismatchedLengths for rows that do not divide the input, fewer than two edges or an output of
@@ -725,6 +744,24 @@ public:
 
 private:
     static T *fp(std::vector<C> &v) { return reinterpret_cast<T *>(v.data()); }
+    Result convolve_impl(const std::vector<float> &x, const std::vector<float> &h, size_t nh, std::vector<float> &out, size_t rows,
+                         size_t block, size_t first, size_t count, unsigned flags) const
+    {
+        static_assert(std::is_same<T, float>::value, "convolve_rows / correlate_rows are f32-only");
+        if (rows == 0 || x.size() % rows != 0 || (h.size() != nh && h.size() != rows * nh)) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows;
+        if (nx == 0 || nh == 0) return Result::Err(FftError::EmptyInput);
+        const size_t full = nx + nh - 1;
+        if (count == SIZE_MAX) {
+            if (first > full) return Result::Err(FftError::MismatchedLengths);
+            count = full - first;
+        }
+        if (first > full || count > full - first) return Result::Err(FftError::MismatchedLengths);
+        out.resize(rows * count);
+        float dummy = 0.0f;  // (count == 0: the C entry returns before it looks at the pointer)
+        return st(kofft_hip_convolve_f32(ctx_, x.data(), rows, nx, h.data(), h.size() == nh ? 1 : rows, nh, block, flags,
+                                         out.empty() ? &dummy : out.data(), first, count));
+    }
     Result oop_strided(const std::vector<C> &input, size_t in_stride, std::vector<C> &output, size_t out_stride,
                        bool inverse) const  // fft.rs:1261-1336
     {

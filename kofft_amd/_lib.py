@@ -82,6 +82,10 @@ SIGNATURES = {
     "kofft_hip_cepstrum_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_cepstrum_f32_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_cepstrum_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_convolve_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_convolve_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_convolve_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_convolve_block": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),
     "kofft_hip_mel_filterbank_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_dev_mel_filterbank_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),

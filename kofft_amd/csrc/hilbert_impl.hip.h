@@ -25,14 +25,15 @@ namespace host {
 
 // ---- composed route ---------------------------------------------------------------------------------------------------------
 // Flat grids over the whole batch (rows back to back; n is a power of two, so a sample's bin is its index's low bits): short rows
-// leave no thread idle, and the grid strides over batches larger than it.
-__global__ __launch_bounds__(256) void hilbert_expand_kernel(const float *__restrict__ x, cpx<float> *__restrict__ z, const size_t total)
+// leave no thread idle, and the grid strides over batches larger than it.  (static: k_hilbert_f32.hip and k_convolve_f32.hip both
+// include this header.)
+static __global__ __launch_bounds__(256) void hilbert_expand_kernel(const float *__restrict__ x, cpx<float> *__restrict__ z, const size_t total)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) st_stream(z + i, mk<float>(x[i], 0.0f));
 }
 
 // hilbert.rs:28-34 (n even, n >= 4): bins 0 and n/2 untouched, 1 .. n/2-1 doubled part by part, n/2+1 .. n-1 = Complex32::zero()
-__global__ __launch_bounds__(256) void hilbert_mask_kernel(cpx<float> *__restrict__ z, const size_t n, const size_t total)
+static __global__ __launch_bounds__(256) void hilbert_mask_kernel(cpx<float> *__restrict__ z, const size_t n, const size_t total)
 {
     const size_t h = n / 2;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {

@@ -69,6 +69,7 @@ struct kofft_hip_ctx {
     bool hilbert_fused = true; // kofft_hip_set_hilbert_fused(ctx, 0): analytic signals of every length through the composed route (expand, fft_dev, mask, inverse fft_dev; A/B, tests)
     bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
+    bool convolve_fused = true; // kofft_hip_set_convolve_fused(ctx, 0): overlap-save convolutions of every block through the composed route (expand, fft_dev, multiply, inverse fft_dev, gather; A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
     int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
     bool spec_transpose = true; // kofft_hip_set_spectrogram_transpose(ctx, 0): the image layout of the spectrogram render with every lane storing its own bytes instead of the exchange through LDS (the same bytes; A/B, tests)
@@ -767,6 +768,13 @@ int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batc
 int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
 int hilbert_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: hilbert::hilbert_analytic
 int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: cepstrum::real_cepstrum
+// k_convolve_f32.hip: overlap-save FFT convolution / correlation of rows (convolve_impl.hip.h).  convolve_check: the
+// argument checks alone, in the order of include/kofft_hip.h; *block == 0 is resolved to the default block
+size_t convolve_default_block(size_t nx, size_t nh);  // nx, nh >= 1
+int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *block, unsigned flags, size_t out_first, size_t out_len,
+                   const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx);
+int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
+                 unsigned flags, float *d_out, size_t out_first, size_t out_len);
 // k_planar_f32/f64.hip: FftImpl::fft_split / ifft_split on planes of batch * n reals (planar_impl.hip.h); planar_check: the argument
 // checks alone, in the order of fft_dev and before the context or a device is touched
 inline int planar_check(size_t n, size_t batch, const void *p0, const void *p1, const void *p2, const void *p3, const kofft_hip_ctx *ctx)

@@ -350,6 +350,25 @@ int cepstrum_host(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, siz
                             [&](float *d_in, float *d_out, const float *, size_t rows) { return cepstrum_dev(ctx, d_in, d_out, n, rows); });
 }
 
+// overlap-save convolution / correlation on host rows: nx samples in, out_len values out (k_convolve_f32.hip).  One filter for all
+// rows is the side input, uploaded once; one filter per row is a third array, so that a pipelined chunk carries its own rows' taps
+int convolve_host(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh, size_t block,
+                  unsigned flags, float *out, size_t out_first, size_t out_len)
+{
+    const int rc = convolve_check(rows, nx, nh, filters, &block, flags, out_first, out_len, x, h, out, ctx);
+    if (rc || rows == 0 || out_len == 0) return rc;
+    if (filters == rows && rows > 1) {
+        const HostArray<float> a[3] = {{x, nullptr, nx}, {h, nullptr, nh}, {nullptr, out, out_len}};
+        return rows_host_n<float>(ctx, rows, 3, a, nullptr, 0, true, true, [&](float *const *d, const float *, size_t nr) {
+            return convolve_dev(ctx, d[0], nr, nx, d[1], nr, nh, block, flags, d[2], out_first, out_len);
+        });
+    }
+    return rows_host<float>(ctx, x, out, rows, nx, out_len, h, nh, true, true,
+                            [&](float *d_in, float *d_out, const float *d_h, size_t nr) {
+                                return convolve_dev(ctx, d_in, nr, nx, d_h, 1, nh, block, flags, d_out, out_first, out_len);
+                            });
+}
+
 // cepstrum::mel_filterbank / mfcc on host rows of n_fft magnitudes in, num_mel energies or num_coeffs coefficients out (k_mfcc_f32.hip);
 // the edges stay on the host
 int mel_host(kofft_hip_ctx *ctx, bool mfcc, const float *mags, float *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
@@ -977,6 +996,30 @@ int kofft_hip_cepstrum_f32(kofft_hip_ctx *ctx, const float *in, float *out, size
 int kofft_hip_cepstrum_f32_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     return cepstrum_dev(ctx, d_in, d_out, n, batch);
+}
+int kofft_hip_set_convolve_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->convolve_fused = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_convolve_block(size_t nx, size_t nh, size_t *block)
+{
+    if (nx == 0 || nh == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (nx > (SIZE_MAX >> 2) || nh > (SIZE_MAX >> 2)) return KOFFT_ERR_UNSUPPORTED;
+    if (!block) return KOFFT_ERR_NULL;
+    *block = convolve_default_block(nx, nh);
+    return KOFFT_OK;
+}
+int kofft_hip_convolve_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh, size_t block,
+                           unsigned flags, float *out, size_t out_first, size_t out_len)
+{
+    return convolve_host(ctx, x, rows, nx, h, filters, nh, block, flags, out, out_first, out_len);
+}
+int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh,
+                               size_t block, unsigned flags, float *d_out, size_t out_first, size_t out_len)
+{
+    return convolve_dev(ctx, d_x, rows, nx, d_h, filters, nh, block, flags, d_out, out_first, out_len);
 }
 int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on)
 {
