@@ -280,6 +280,54 @@ int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows
 int kofft_hip_set_convolve_fused(kofft_hip_ctx *ctx, int on);
 int kofft_hip_convolve_block(size_t nx, size_t nh, size_t *block);
 
+/* ---- Welch power spectra and cross spectra of rows ------------------------------------------
+ * The sum over frames of |X[k]|^2 (welch) or conj(X[k]) Y[k] (csd) of `rows` signals of `len` f32 samples, row r at signal + r *
+ * row_stride, `frames` frames per row; no frame ever reaches the caller.  psd is rows * K floats, pxy rows * K interleaved complex,
+ * K = win_len / 2 + 1.  f32 only.  There is no detrending and no median.
+ * Arithmetic contract, met bit for bit by every route, grid, chunk size and device:
+ *   Frames and bins.  Frame f of row r has the spectrum X[k], k < K, that kofft_hip_stft_onesided_f32 writes for it: the same window
+ *     product, +0 past the end of the row and never the head of row r + 1, the reference's FFT or its Bluestein arm, every win_len that
+ *     call takes.  window == NULL: window::hann(win_len), as in kofft_hip_stft_mel_f32.  csd: X and Y are the spectra of frame f of row
+ *     r of x and of y, two signals with the same len, row_stride, window and hop.
+ *   Per frame and bin, nothing fused.  welch: p = re * re + im * im.  csd: c.re = xr * yr + xi * yi, c.im = xr * yi - xi * yr
+ *     (conj(X) Y, scipy.signal.csd's sign).
+ *   Summation order.  The frames of a row are cut into groups of KOFFT_HIP_WELCH_GROUP = 32 consecutive frames counted from frame 0
+ *     of that row; the last group is shorter when 32 does not divide `frames`.  A group's partial is the f32 sum of its frames' values
+ *     in ascending frame order, seeded with +0.  The row's total is the f32 sum of its partials in ascending group order, seeded with
+ *     +0.  No atomics, no trees.
+ *   Output.  out[k] = total[k] * scale, one f32 multiplication (csd: both parts).  With KOFFT_HIP_PSD_DOUBLE in flags the interior
+ *     bins are then multiplied by 2.0f: (total * scale) * 2.0f.  Interior: 1 <= k < K - 1 for even win_len, 1 <= k < K for odd.
+ * `frames` is the caller's and has no lower bound (kofft_amd.psd passes the number of whole segments); frames wholly past the row
+ * contribute +0.  Checks, in this order and before the context or the device is touched: hop == 0 -> INVALID_HOP_SIZE; rows == 0 or
+ * frames == 0 -> KOFFT_OK, nothing touched; win_len == 0 -> EMPTY_INPUT; win_len beyond the complex limits (kofft_hip_stft_rows_f32's)
+ * -> UNSUPPORTED; rows > 1 and row_stride < len -> INVALID_VALUE; sizes that overflow -> UNSUPPORTED; then a flag bit other than
+ * KOFFT_HIP_PSD_DOUBLE -> INVALID_VALUE; a null data pointer (a signal with len > 0, the output) or a null context -> KOFFT_ERR_NULL;
+ * the output overlapping a signal or the window -> INVALID_VALUE.
+ * Routes, the same bytes.  The fused kernel (power-of-two win_len 64 .. 4096) gives a group of frames to a slot of threads that keeps
+ * the running sums of its bins in registers while it walks the frames through LDS; rows of more than one group leave their partials
+ * in the context's scratch for a second small kernel.  The composed route (every other win_len, Bluestein lengths such as 400 too)
+ * writes the one-sided frames of whole groups into the context's scratch (KOFFT_HIP_SCRATCH_CHUNK_MB at a time) and sums them there.
+ * kofft_hip_set_welch_fused(ctx, mode): 1, the default, the measured choice; 0 every call composed; 2 the fused kernel
+ * wherever it exists (A/B measurements and tests); anything else -> INVALID_VALUE.  The kofft_hip_dev_* forms take device pointers and
+ * are asynchronous on the context's stream (named so for the reason given at the chirp-Z entries; their guard-band cases live in
+ * tests/test_gpu_welch_footprint.py).
+ * kofft_hip_welch_scale_f32, host only, no context: scaling 0 (density) 1 / (fs * sum w[i]^2 * frames), scaling 1 (spectrum) 1 /
+ * ((sum w[i])^2 * frames); the sums ascending in double over the f32 window (NULL: window::hann(win_len)), the result rounded to f32
+ * once.  scale null -> KOFFT_ERR_NULL; win_len == 0 -> EMPTY_INPUT; another scaling, fs <= 0 (or NaN), frames == 0 or a zero sum ->
+ * INVALID_VALUE.  Coherence and transfer functions are compositions: |csd(x, y)|^2 / (welch(x) welch(y)) and csd(x, y) / welch(x). */
+#define KOFFT_HIP_WELCH_GROUP 32
+#define KOFFT_HIP_PSD_DOUBLE 1
+int kofft_hip_welch_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                        size_t win_len, size_t hop, size_t frames, float scale, int flags, float *psd);
+int kofft_hip_dev_welch_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                            size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_psd);
+int kofft_hip_csd_f32(kofft_hip_ctx *ctx, const float *x, const float *y, size_t rows, size_t len, size_t row_stride, const float *window,
+                      size_t win_len, size_t hop, size_t frames, float scale, int flags, float *pxy);
+int kofft_hip_dev_csd_f32(kofft_hip_ctx *ctx, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
+                          const float *d_window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_pxy);
+int kofft_hip_set_welch_fused(kofft_hip_ctx *ctx, int mode);
+int kofft_hip_welch_scale_f32(const float *window, size_t win_len, double fs, size_t frames, int scaling, float *scale);
+
 /* ---- mel filterbank and MFCC ------------------------------------------------------
  * cepstrum::mel_filterbank / mfcc / mfcc_batch (cepstrum.rs:36-98), f32 only like the reference, on `rows` contiguous rows of n_fft
  * magnitudes -- what kofft_hip_dev_stft_magnitudes_rows_f32 writes, rows x frames flattened.  The filter edges are an INPUT: bins is

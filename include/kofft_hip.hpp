@@ -365,6 +365,46 @@ public:
     {
         return convolve_impl(x, h, nh, out, rows, block, first, count, 1u);
     }
+    // Welch power spectra of `rows` contiguous rows of x.size() / rows samples (kofft_hip_welch_f32): psd is resized to rows *
+    // (win_len / 2 + 1) floats, (total * scale) (* 2 on the interior bins with `twice`) in the summation order the C header fixes
+    // (groups of KOFFT_HIP_WELCH_GROUP frames).  window: win_len values, or empty for window::hann(win_len).  MismatchedLengths for rows
+    // that do not divide x or a window of another size; then the C entry's checks in its order.  No detrending.
+    Result welch(const std::vector<float> &x, const std::vector<float> &window, size_t win_len, size_t hop, size_t frames,
+                 std::vector<float> &psd, size_t rows = 1, float scale = 1.0f, bool twice = false) const
+    {
+        static_assert(std::is_same<T, float>::value, "welch / csd are f32-only");
+        if (rows == 0 || x.size() % rows != 0 || (!window.empty() && window.size() != win_len)) return Result::Err(FftError::MismatchedLengths);
+        const size_t len = x.size() / rows;
+        psd.assign(rows * (win_len / 2 + 1), 0.0f);
+        return st(kofft_hip_welch_f32(ctx_, x.data(), rows, len, len, window.empty() ? nullptr : window.data(), win_len, hop, frames, scale,
+                                      twice ? KOFFT_HIP_PSD_DOUBLE : 0, psd.data()));
+    }
+    // Cross spectra conj(X) Y of the rows of x and y (kofft_hip_csd_f32): pxy is resized to rows * (win_len / 2 + 1) complex values.
+    Result csd(const std::vector<float> &x, const std::vector<float> &y, const std::vector<float> &window, size_t win_len, size_t hop,
+               size_t frames, std::vector<Complex<float>> &pxy, size_t rows = 1, float scale = 1.0f, bool twice = false) const
+    {
+        static_assert(std::is_same<T, float>::value, "welch / csd are f32-only");
+        if (rows == 0 || x.size() % rows != 0 || y.size() != x.size() || (!window.empty() && window.size() != win_len))
+            return Result::Err(FftError::MismatchedLengths);
+        const size_t len = x.size() / rows;
+        pxy.assign(rows * (win_len / 2 + 1), Complex<float>{0.0f, 0.0f});
+        return st(kofft_hip_csd_f32(ctx_, x.data(), y.data(), rows, len, len, window.empty() ? nullptr : window.data(), win_len, hop, frames,
+                                    scale, twice ? KOFFT_HIP_PSD_DOUBLE : 0, reinterpret_cast<float *>(pxy.data())));
+    }
+    // 1: the measured choice (the default), 0: every welch / csd of this context through the composed route, 2: the fused kernel
+    // wherever it exists (the same bytes; A/B, tests)
+    Result set_welch_fused(int mode) const { return st(kofft_hip_set_welch_fused(ctx_, mode)); }
+    // kofft_hip_welch_scale_f32, no device: density 1 / (fs * sum w^2 * frames), spectrum 1 / ((sum w)^2 * frames); an empty window is
+    // window::hann(win_len).  Returns 0 and sets `err` on an error (a zero sum, fs <= 0, frames == 0, win_len == 0).
+    static float welch_scale(const std::vector<float> &window, size_t win_len, double fs, size_t frames, bool spectrum = false, int *err = nullptr)
+    {
+        float s = 0.0f;
+        const int rc = (!window.empty() && window.size() != win_len)
+                           ? KOFFT_ERR_MISMATCHED_LENGTHS
+                           : kofft_hip_welch_scale_f32(window.empty() ? nullptr : window.data(), win_len, fs, frames, spectrum ? 1 : 0, &s);
+        if (err) *err = rc;
+        return rc ? 0.0f : s;
+    }
     // cepstrum::mel_filterbank's sums (cepstrum.rs:51-67), f32 only like the reference: `rows` contiguous rows of mags.size() / rows
     // magnitudes in, rows of bins.size() - 2 energies out, with the filter edges `bins` (num_mel + 2 nondecreasing values; kofft::mel_bins
     // gives the reference-shaped ones).  MismatchedLengths for rows that do not divide the input, fewer than two edges or an output of

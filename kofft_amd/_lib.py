@@ -86,6 +86,12 @@ SIGNATURES = {
     "kofft_hip_dev_convolve_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_convolve_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_convolve_block": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),
+    "kofft_hip_welch_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
+    "kofft_hip_dev_welch_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
+    "kofft_hip_csd_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
+    "kofft_hip_dev_csd_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
+    "kofft_hip_set_welch_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_welch_scale_f32": (C.c_int, [C.c_void_p, _sz, C.c_double, _sz, C.c_int, C.POINTER(C.c_float)]),
     "kofft_hip_mel_filterbank_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_dev_mel_filterbank_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_mfcc_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz]),

@@ -72,6 +72,7 @@ struct kofft_hip_ctx {
     bool convolve_fused = true; // kofft_hip_set_convolve_fused(ctx, 0): overlap-save convolutions of every block through the composed route (expand, fft_dev, multiply, inverse fft_dev, gather; A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
     int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
+    int welch_fused = 1;      // kofft_hip_set_welch_fused: 1 the measured choice (welch_use_fused), 0 every Welch / cross-spectrum call through the composed route (one-sided frames into the scratch, then the sums), 2 the fused kernel wherever it exists (A/B, tests)
     bool spec_transpose = true; // kofft_hip_set_spectrogram_transpose(ctx, 0): the image layout of the spectrogram render with every lane storing its own bytes instead of the exchange through LDS (the same bytes; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     bool dht_table_device = true; // kofft_hip_set_dht_table_device(ctx, 0): the Hartley table of a new length built on the host and uploaded instead of by dht_table_kernel (the same bytes; A/B, tests)
@@ -916,6 +917,15 @@ int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, si
                       size_t win_len, size_t hop, float *d_out, size_t frames);
 int istft_onesided_dev(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
                        float *d_output, size_t out_len);
+// the same kernels on frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_out; no checks
+int stft_onesided_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_window,
+                        size_t win_len, size_t hop, size_t f0, size_t nf, float *d_out);
+// k_welch_f32.hip: Welch power spectra (d_y null) and cross spectra of rows (welch_impl.hip.h).  welch_check: the argument
+// checks alone, in the order of include/kofft_hip.h
+int welch_check(bool csd, const void *x, const void *y, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
+                size_t win_len, size_t hop, size_t frames, int flags, const kofft_hip_ctx *ctx);
+int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
+              const float *d_window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_out);
 // dst[t][k] = src[t][k] for k <= win_len/2, conj(src[t][win_len - k]) above: nt frames of win_len/2 + 1 bins -> nt frames of win_len
 int expand_half(kofft_hip_ctx *ctx, const float *d_half, float *d_full, size_t nt, size_t win_len);
 template <typename T>

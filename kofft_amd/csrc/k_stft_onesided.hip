@@ -88,6 +88,18 @@ int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, si
     return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
 }
 
+// frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row; f0 * hop < len or len == 0), dense at d_out: stft_onesided_dev's kernels
+// on a rectangle of the batch, for the chunk walks that keep the frames in the context's scratch (k_welch_f32.hip)
+int stft_onesided_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_window,
+                        size_t win_len, size_t hop, size_t f0, size_t nf, float *d_out)
+{
+    StftHalfRowsIO io{};
+    fill_rows_io(io, d_signal, nrows, len, row_stride, d_window, win_len, hop, nf);
+    io.start0 = f0 * hop;
+    io.out = reinterpret_cast<cpx<float> *>(d_out);
+    return dispatch<float, EPI_STORE>(ctx, io, win_len, nrows * nf);
+}
+
 // istft_rows_dev's mode 2 walk with the Hermitian completion in the place of its copy: d_half is never written
 int istft_onesided_dev(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
                        float *d_output, size_t out_len)

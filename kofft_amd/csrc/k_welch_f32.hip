@@ -1,0 +1,227 @@
+// k_welch_f32.hip -- Welch power spectra and cross spectra of rows (welch_impl.hip.h): every kernel instance of the
+// family, the argument checks and the two routes.
+#include "welch_impl.hip.h"
+
+namespace kofft {
+namespace host {
+
+static bool ranges_overlap(const float *a, size_t na, const float *b, size_t nb) { return na && nb && a < b + nb && b < a + na; }
+
+// Checks in the order of include/kofft_hip.h, all before the context or the device is touched: the STFT rows' without the frame count,
+// then the flags, the pointers, the overlaps.
+int welch_check(bool csd, const void *x, const void *y, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
+                size_t win_len, size_t hop, size_t frames, int flags, const kofft_hip_ctx *ctx)
+{
+    const int crc = stft_rows_check(false, false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (flags & ~KOFFT_HIP_PSD_DOUBLE) return KOFFT_ERR_INVALID_VALUE;
+    if (!ctx || !out || (len && (!x || (csd && !y)))) return KOFFT_ERR_NULL;
+    const float *o = static_cast<const float *>(out);
+    const size_t no = rows * (win_len / 2 + 1) * (csd ? 2 : 1);
+    const size_t span = len ? (rows - 1) * (rows > 1 ? row_stride : 0) + len : 0;
+    if (ranges_overlap(o, no, static_cast<const float *>(x), span)) return KOFFT_ERR_INVALID_VALUE;
+    if (csd && ranges_overlap(o, no, static_cast<const float *>(y), span)) return KOFFT_ERR_INVALID_VALUE;
+    if (window && ranges_overlap(o, no, static_cast<const float *>(window), win_len)) return KOFFT_ERR_INVALID_VALUE;
+    return KOFFT_OK;
+}
+
+// ---- the fused route ---------------------------------------------------------------------------------------------------------------
+constexpr size_t kWelchFusedMinWin = 64, kWelchFusedMaxWin = 4096;
+
+static bool welch_fused_fits(size_t win_len)
+{
+    return is_pow2(win_len) && win_len >= kWelchFusedMinWin && win_len <= kWelchFusedMaxWin;
+}
+
+// Mode 1: the measured choice per window length: the fused kernel wherever it was not slower than the composed route
+// beyond the spread of the runs at every shape tried.  Measured on an MI355X: it is 1.05 to 3.2 times faster at win_len 64 .. 1024 and
+// 4096 (power and cross spectrum, every shape), and loses at 2048 -- the power spectrum at all four shapes tried (0.175 against 0.157 ms
+// at 64 x 480 000, 0.150 against 0.086 at 16 x 1 000 000: two waves per workgroup and few groups against the persistent STFT kernel's
+// frame-level parallelism), the cross spectrum at one of them (0.192 against 0.158).  So 2048 stays behind mode 2.
+static bool welch_use_fused(const kofft_hip_ctx *ctx, size_t win_len)
+{
+    if (ctx->welch_fused == 0 || !welch_fused_fits(win_len)) return false;
+    return ctx->welch_fused == 2 || win_len != 2048;
+}
+
+struct WelchCall {
+    const float *x, *y;  // y: the cross spectrum only
+    bool csd;
+    const float *win;
+    size_t rows, len, row_stride, win_len, hop, frames /* the frames that can hold a sample, at least 1 */, ngroups;
+    float scale;
+    int twice;
+    float *out;
+};
+
+static int launch_total(kofft_hip_ctx *ctx, const WelchCall &c, const float *part, size_t g_first, size_t g_count)
+{
+    const size_t K = c.win_len / 2 + 1, vals = K * (c.csd ? 2 : 1);
+    const size_t nrows = (g_first + g_count - 1) / c.ngroups - g_first / c.ngroups + 1;
+    const size_t blocks = (nrows * vals + 255) / 256;
+    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(welch_total_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, part, c.out, vals, c.csd ? 2 : 1, c.ngroups, g_first,
+                       g_count, c.scale, c.twice, (c.win_len & 1) ? K : K - 1, nrows * vals);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
+template <int L, bool CSD>
+static int launch_fused(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float> *tw, size_t g_first, size_t g_count, float *dst, bool final)
+{
+    constexpr int RL = rl_for(L), TPT = (1 << L) >> RL, BLOCK = TPT > 64 ? TPT : 64, XPB = BLOCK / TPT;
+    constexpr size_t lds = lds_wg_bytes<float, false, false, XPB>(1 << L);
+    static_assert(lds <= 64 * 1024, "LDS without an attribute");
+    const size_t blocks = (g_count + XPB - 1) / XPB;
+    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+    StftIO io{};
+    io.signal = c.x;
+    io.window = c.win;
+    io.out = nullptr;
+    io.len = c.len;
+    io.hop = c.hop;
+    io.start0 = 0;
+    io.n = 1 << L;
+    hipLaunchKernelGGL((welch_fused_kernel<L, RL, BLOCK, CSD>), dim3((unsigned)blocks), dim3(BLOCK), lds, ctx->stream, io, c.y, tw, c.row_stride,
+                       c.frames, c.ngroups, g_first, g_count, dst, c.scale, c.twice, final ? 1 : 0);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
+template <bool CSD>
+static int launch_fused_l(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float> *tw, size_t g_first, size_t g_count, float *dst, bool final)
+{
+    switch (ilog2(c.win_len)) {
+    case 6: return launch_fused<6, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    case 7: return launch_fused<7, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    case 8: return launch_fused<8, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    case 9: return launch_fused<9, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    case 10: return launch_fused<10, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    case 11: return launch_fused<11, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    case 12: return launch_fused<12, CSD>(ctx, c, tw, g_first, g_count, dst, final);
+    default: return KOFFT_ERR_UNSUPPORTED;  // (never: welch_fused_fits)
+    }
+}
+
+// Rows of one group: one launch, scaled from the kernel.  Otherwise the partials of at most scratch_chunk_bytes of groups at a time,
+// then their rows' totals.
+static int welch_fused(kofft_hip_ctx *ctx, const WelchCall &c)
+{
+    const cpx<float> *tw = nullptr;
+    int rc = twiddle_table<float>(ctx, c.win_len, &tw);
+    if (rc) return rc;
+    const size_t vals = (c.win_len / 2 + 1) * (c.csd ? 2 : 1), total = c.rows * c.ngroups;
+    if (c.ngroups == 1) {
+        const size_t step = size_t(1) << 30;
+        for (size_t g0 = 0; g0 < total && !rc; g0 += step)
+            rc = c.csd ? launch_fused_l<true>(ctx, c, tw, g0, total - g0 < step ? total - g0 : step, c.out, true)
+                     : launch_fused_l<false>(ctx, c, tw, g0, total - g0 < step ? total - g0 : step, c.out, true);
+        return rc;
+    }
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, vals * sizeof(float), total);
+    rc = ensure(ctx, ctx->rows_tmp, chunk * vals * sizeof(float));
+    if (rc) return rc;
+    float *part = static_cast<float *>(ctx->rows_tmp.p);
+    for (size_t g0 = 0; g0 < total; g0 += chunk) {
+        const size_t ng = total - g0 < chunk ? total - g0 : chunk;
+        rc = c.csd ? launch_fused_l<true>(ctx, c, tw, g0, ng, part, false) : launch_fused_l<false>(ctx, c, tw, g0, ng, part, false);
+        if (rc) return rc;
+        rc = launch_total(ctx, c, part, g0, ng);
+        if (rc) return rc;
+    }
+    return KOFFT_OK;
+}
+
+// ---- the composed route ------------------------------------------------------------------------------------------------------------
+// the one-sided frames (window lengths the STFT kernels cover) or the full composed frames of flat indices [t0, t0 + nt) of one signal
+static int welch_frames(kofft_hip_ctx *ctx, const WelchCall &c, const float *sig, bool kernels, size_t t0, size_t nt, cpx<float> *spec)
+{
+    if (!kernels) return stft_rows_composed(ctx, sig, c.len, c.row_stride, c.frames, c.win, c.win_len, c.hop, spec, t0, nt);
+    const size_t K = c.win_len / 2 + 1;
+    PicPiece p[3];
+    const int np = picture_cut(t0, nt, c.frames, p);
+    for (int i = 0; i < np; ++i) {
+        const int rc = stft_onesided_piece(ctx, sig ? sig + p[i].row * c.row_stride : nullptr, p[i].nr, c.len, c.row_stride, c.win, c.win_len,
+                                           c.hop, p[i].f0, p[i].nf, reinterpret_cast<float *>(spec + p[i].at * K));
+        if (rc) return rc;
+    }
+    return KOFFT_OK;
+}
+
+// Chunks of whole groups (welch_cut.h) through the scratch: [frames of x | frames of y | partials], at most scratch_chunk_bytes (one
+// group where a group alone is larger).
+static int welch_composed(kofft_hip_ctx *ctx, const WelchCall &c)
+{
+    const bool kernels = fused_len_ok<float>(c.win_len), csd = c.csd;
+    const size_t K = c.win_len / 2 + 1, vals = K * (csd ? 2 : 1), fstride = kernels ? K : c.win_len, total = c.rows * c.frames;
+    const size_t per_frame = fstride * sizeof(cpx<float>) * (csd ? 2 : 1) + (vals * sizeof(float) + kWelchGroup - 1) / kWelchGroup;
+    size_t cap = scratch_chunk_rows(ctx->scratch_chunk_bytes, per_frame, total);
+    if (cap < kWelchGroup) cap = kWelchGroup < total ? kWelchGroup : total;
+    size_t max_groups = cap / kWelchGroup + cap / c.frames + 2;  // whole groups, one short group per row end, the two ends
+    if (max_groups > c.rows * c.ngroups) max_groups = c.rows * c.ngroups;
+    const size_t spec_bytes = (cap * fstride * sizeof(cpx<float>) + 15) & ~size_t(15);
+    int rc = ensure(ctx, ctx->rows_tmp, spec_bytes * (csd ? 2 : 1) + max_groups * vals * sizeof(float));
+    if (rc) return rc;
+    char *base = static_cast<char *>(ctx->rows_tmp.p);
+    cpx<float> *spec_x = reinterpret_cast<cpx<float> *>(base), *spec_y = csd ? reinterpret_cast<cpx<float> *>(base + spec_bytes) : nullptr;
+    float *part = reinterpret_cast<float *>(base + spec_bytes * (csd ? 2 : 1));
+    for (size_t t0 = 0; t0 < total;) {
+        const size_t end = welch_chunk_end(t0, cap, c.frames, total), nt = end - t0;
+        const size_t g0 = welch_group_at(t0, c.frames), ng = (end == total ? c.rows * c.ngroups : welch_group_at(end, c.frames)) - g0;
+        if (ng > max_groups) return KOFFT_ERR_UNSUPPORTED;  // (never: the bound above)
+        rc = welch_frames(ctx, c, c.x, kernels, t0, nt, spec_x);
+        if (rc) return rc;
+        if (csd) {
+            rc = welch_frames(ctx, c, c.y, kernels, t0, nt, spec_y);
+            if (rc) return rc;
+        }
+        const size_t blocks = (ng * K + 255) / 256;
+        if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+        if (csd)
+            hipLaunchKernelGGL(welch_partial_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec_x, spec_y, part, fstride, K,
+                               c.frames, c.ngroups, t0, g0, ng * K);
+        else
+            hipLaunchKernelGGL(welch_partial_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec_x, spec_y, part, fstride, K,
+                               c.frames, c.ngroups, t0, g0, ng * K);
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+        rc = launch_total(ctx, c, part, g0, ng);
+        if (rc) return rc;
+        t0 = end;
+    }
+    return KOFFT_OK;
+}
+
+int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
+              const float *d_window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_out)
+{
+    const int crc = welch_check(csd, d_x, d_y, d_window, d_out, rows, len, row_stride, win_len, hop, frames, flags, ctx);
+    if (crc || rows == 0 || frames == 0) return crc;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WelchCall c{};
+    c.win = d_window;
+    if (!c.win) {  // window::hann(win_len), as the front end's
+        const int rc = hann_table(ctx, win_len, &c.win);
+        if (rc) return rc;
+    }
+    // A frame that begins at or past the end of its row is all +0: its terms are +-0 and change no sum (a sum seeded with +0 is never -0).
+    // Only the frames that can hold a sample are walked, at least one, so that a row without samples still stores +0 * scale.
+    const size_t holding = len ? (len - 1) / hop + 1 : 1;
+    c.x = d_x;
+    c.y = csd ? d_y : nullptr;
+    c.rows = rows;
+    c.len = len;
+    c.row_stride = rows > 1 ? row_stride : 0;
+    c.win_len = win_len;
+    c.hop = hop;
+    c.frames = frames < holding ? frames : holding;
+    c.ngroups = welch_groups(c.frames);
+    c.scale = scale;
+    c.twice = (flags & KOFFT_HIP_PSD_DOUBLE) ? 1 : 0;
+    c.out = d_out;
+    c.csd = csd;
+    if (welch_use_fused(ctx, win_len)) return welch_fused(ctx, c);
+    return welch_composed(ctx, c);
+}
+
+}  // namespace host
+}  // namespace kofft
