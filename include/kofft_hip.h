@@ -280,6 +280,45 @@ int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows
 int kofft_hip_set_convolve_fused(kofft_hip_ctx *ctx, int on);
 int kofft_hip_convolve_block(size_t nx, size_t nh, size_t *block);
 
+/* ---- polyphase resampling of rows (upfirdn, resample_poly) -----------------------------------
+ * Sample-rate conversion by up / down of `rows` dense rows of nx f32 samples through one FIR filter of nh taps: out_len values per row
+ * from up-sampled time t0 on, the decimating or interpolating filter computed directly in the time domain (with up == down == 1 a
+ * plain FIR).  f32 only; one filter for all rows; no gcd reduction: up and down are used as given.
+ * Definition, met bit for bit by every route, grid and device.  Let xu be x with up - 1 zeros after every sample (xu[i * up] = x[i]);
+ * the full filtered length is full_up = (nx - 1) * up + nh.  Output m of a row sits at up-sampled time t = t0 + m * down:
+ *   p = t mod up;  i0 = t div up;  acc = +0.0f
+ *   for j = 0, 1, 2, .. while p + j * up < nh:       (ascending j, one accumulator)
+ *       i = i0 - j;  if 0 <= i < nx:  acc = acc + (h[p + j * up] * x[i])      (one f32 product, then one f32 sum: never fused)
+ *   out[m] = acc
+ * Terms whose sample does not exist are skipped, not multiplied by zero: a NaN or Inf of x reaches exactly the outputs whose term set
+ * holds it, and an output without terms is +0.  All position arithmetic (t, i0, p + j * up) is 64-bit.
+ * This is scipy.signal.upfirdn(h, x, up, down) for t0 = 0 and out_len = ceil(full_up / down), and scipy.signal.resample_poly's
+ * alignment (the taps already multiplied by up) for t0 = (nh - 1) / 2 and out_len = ceil(nx * up / down).
+ * Checks, in this order and before the context or a device is touched: rows == 0 or out_len == 0 -> KOFFT_OK, nothing touched;
+ * nx == 0 or nh == 0 -> EMPTY_INPUT; up == 0 or down == 0 -> INVALID_VALUE; full_up, t0 + (out_len - 1) * down or a byte count
+ * beyond 64 bits -> KOFFT_ERR_UNSUPPORTED; t0 + (out_len - 1) * down >= full_up (an output wholly past the result) ->
+ * MISMATCHED_LENGTHS; a null pointer or context -> KOFFT_ERR_NULL; out overlapping x or h -> INVALID_VALUE.
+ * Routes, the same bytes.  The plain kernel takes every shape: one thread per output, samples and taps from global memory.  The tiled
+ * kernel gives a 256-thread workgroup up to KOFFT_HIP_RESAMPLE_TILE consecutive outputs of one row at a time: the samples their terms name
+ * and the taps in phase-major order lie in LDS, one pass over HBM; it exists where both fit 52 KiB.  kofft_hip_set_resample_tiled(ctx,
+ * on): 1, the default, the measured choice; 0 every call of the context on the plain kernel; 2 the tiled kernel
+ * wherever its tables fit (A/B measurements and tests); anything else -> INVALID_VALUE.  kofft_hip_resample_route, no context: *route = 1 where a default context runs the tiled kernel, 0 where the plain one; for
+ * fixed up and down it is 1 up to some nh and 0 beyond.  nh == 0 -> EMPTY_INPUT, up == 0 or down == 0 -> INVALID_VALUE, route null ->
+ * KOFFT_ERR_NULL.  kofft_hip_dev_resample_f32 takes device pointers and is asynchronous on the context's stream.
+ * kofft_hip_resample_taps_f32, host only, no context: what scipy.signal.resample_poly designs by default (zeros = 10, beta = 5.0).
+ * half = zeros * max(up, down), *nh = 2 * half + 1; the sinc of cutoff 1 / max(up, down) under a Kaiser window of `beta`, normalised to
+ * unit sum, times up; everything in double (I0 by its power series), rounded to f32 once.  taps == NULL: *nh alone.  taps and nh both
+ * null -> KOFFT_ERR_NULL; up, down or zeros == 0, beta < 0 or NaN -> INVALID_VALUE; a length beyond 2^28 taps -> KOFFT_ERR_UNSUPPORTED.
+ * The device contract never depends on this helper: the taps are an input, as the mel edges are. */
+#define KOFFT_HIP_RESAMPLE_TILE 1024
+int kofft_hip_resample_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t nh, size_t up, size_t down,
+                           size_t t0, float *out, size_t out_len);
+int kofft_hip_dev_resample_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t nh, size_t up,
+                               size_t down, size_t t0, float *d_out, size_t out_len);
+int kofft_hip_set_resample_tiled(kofft_hip_ctx *ctx, int on);
+int kofft_hip_resample_route(size_t nh, size_t up, size_t down, int *route);
+int kofft_hip_resample_taps_f32(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh);
+
 /* ---- Welch power spectra and cross spectra of rows ------------------------------------------
  * The sum over frames of |X[k]|^2 (welch) or conj(X[k]) Y[k] (csd) of `rows` signals of `len` f32 samples, row r at signal + r *
  * row_stride, `frames` frames per row; no frame ever reaches the caller.  psd is rows * K floats, pxy rows * K interleaved complex,

@@ -365,6 +365,48 @@ public:
     {
         return convolve_impl(x, h, nh, out, rows, block, first, count, 1u);
     }
+    // Polyphase resampling of `rows` contiguous rows of x.size() / rows samples through the taps h (kofft_hip_resample_f32): out is
+    // resized to rows * count values, output m of a row at up-sampled time t0 + m * down, in the arithmetic the C header fixes.  count
+    // SIZE_MAX: every output from t0 to the end of the full result of (nx - 1) * up + h.size() values (scipy.signal.upfirdn's length at
+    // t0 = 0).  MismatchedLengths for rows that do not divide x; then the C entry's checks in its order.
+    Result resample_rows(const std::vector<float> &x, const std::vector<float> &h, size_t up, size_t down, std::vector<float> &out,
+                         size_t rows = 1, size_t t0 = 0, size_t count = SIZE_MAX) const
+    {
+        static_assert(std::is_same<T, float>::value, "resample_rows is f32-only");
+        if (rows == 0 || x.size() % rows != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows, nh = h.size();
+        if (count == SIZE_MAX) {
+            if (nx == 0 || nh == 0) return Result::Err(FftError::EmptyInput);
+            if (up == 0 || down == 0) return Result::Err(FftError::InvalidValue);
+            size_t full_up = 0;
+            if (__builtin_mul_overflow(nx - 1, up, &full_up) || __builtin_add_overflow(full_up, nh, &full_up))
+                return st(KOFFT_ERR_UNSUPPORTED);
+            count = t0 < full_up ? (full_up - t0 - 1) / down + 1 : 0;
+        }
+        size_t total = 0;
+        if (__builtin_mul_overflow(rows, count, &total)) return st(KOFFT_ERR_UNSUPPORTED);
+        out.assign(total, 0.0f);
+        float dummy = 0.0f;
+        return st(kofft_hip_resample_f32(ctx_, x.data(), rows, nx, h.data(), nh, up, down, t0, out.empty() ? &dummy : out.data(), count));
+    }
+    // 1: the measured choice (the default), 0: every resampling call of this context on the plain kernel, 2: the tiled kernel wherever
+    // its tables fit (the same bytes; A/B, tests)
+    Result set_resample_tiled(int mode) const { return st(kofft_hip_set_resample_tiled(ctx_, mode)); }
+    // kofft_hip_resample_taps_f32, no device: scipy.signal.resample_poly's default filter for up / down (2 * zeros * max(up, down) + 1
+    // taps).  Returns an empty vector and sets `err` on an error.
+    static std::vector<float> resample_taps(size_t up, size_t down, size_t zeros = 10, double beta = 5.0, int *err = nullptr)
+    {
+        size_t nh = 0;
+        int rc = kofft_hip_resample_taps_f32(up, down, zeros, beta, nullptr, &nh);
+        std::vector<float> taps;
+        if (!rc) {
+            taps.resize(nh);
+            rc = kofft_hip_resample_taps_f32(up, down, zeros, beta, taps.data(), &nh);
+        }
+        if (err) *err = rc;
+        if (rc) taps.clear();
+        return taps;
+    }
     // Welch power spectra of `rows` contiguous rows of x.size() / rows samples (kofft_hip_welch_f32): psd is resized to rows *
     // (win_len / 2 + 1) floats, (total * scale) (* 2 on the interior bins with `twice`) in the summation order the C header fixes
     // (groups of KOFFT_HIP_WELCH_GROUP frames).  window: win_len values, or empty for window::hann(win_len).  MismatchedLengths for rows

@@ -16,9 +16,10 @@ from . import mfcc  # noqa: E402  (kofft::cepstrum::mel_filterbank / mfcc / mfcc
 from . import spectrogram  # noqa: E402  (kofft::visual::spectrogram: magnitude_to_db, db_scale, the colour maps, log_scale_bins)
 from . import convolve  # noqa: E402  (overlap-save FFT convolution / correlation of rows: convolve, correlate, default_block)
 from . import psd  # noqa: E402  (Welch power spectra and cross spectra of rows: welch, csd, segments)
+from . import resample  # noqa: E402  (polyphase resampling of rows: upfirdn, resample_poly, design_taps)
 
 __all__ = ["DctPlanner", "DeviceError", "fft2d_inplace", "fft3d_inplace", "flatten_2d", "flatten_3d", "FftError", "FftPlan", "FftPlanner", "FftStrategy", "HipFftImpl", "HipMulti", "IstftStream", "RfftPlanner", "StftStream",
            "batch", "batch_inverse", "frame", "hann", "hilbert_analytic", "inverse_frame", "inverse_parallel", "irfft_packed", "istft", "istft_onesided", "multi_channel", "multi_channel_inverse", "new_fft_impl",
-           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_magnitudes_rows", "stft_multi", "stft_onesided", "stft_rows", "LibraryMissing", "load_library", "dct", "dst", "wavelet", "czt", "goertzel", "hartley", "window", "mfcc", "spectrogram", "convolve", "psd",
+           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_magnitudes_rows", "stft_multi", "stft_onesided", "stft_rows", "LibraryMissing", "load_library", "dct", "dst", "wavelet", "czt", "goertzel", "hartley", "window", "mfcc", "spectrogram", "convolve", "psd", "resample",
            "ComplexVec", "SplitComplex", "fft_complex_vec", "fft_split", "fft_split_complex", "ifft_complex_vec", "ifft_split", "ifft_split_complex"]
 __version__ = "0.1.0"

@@ -86,6 +86,11 @@ SIGNATURES = {
     "kofft_hip_dev_convolve_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_convolve_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_convolve_block": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),
+    "kofft_hip_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_set_resample_tiled": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_resample_route": (C.c_int, [_sz, _sz, _sz, C.POINTER(C.c_int)]),
+    "kofft_hip_resample_taps_f32": (C.c_int, [_sz, _sz, _sz, C.c_double, C.c_void_p, C.POINTER(_sz)]),
     "kofft_hip_welch_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
     "kofft_hip_dev_welch_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
     "kofft_hip_csd_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),

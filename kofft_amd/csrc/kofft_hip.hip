@@ -2,6 +2,7 @@
 // include/kofft_hip.h.  The kernels live in the k_*.hip translation units (host_common.hip.h).
 #include "host_common.hip.h"
 #include "host_layout.h"
+#include "resample_plan.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -1020,6 +1021,42 @@ int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows
                                size_t block, unsigned flags, float *d_out, size_t out_first, size_t out_len)
 {
     return convolve_dev(ctx, d_x, rows, nx, d_h, filters, nh, block, flags, d_out, out_first, out_len);
+}
+// ---- polyphase resampling of rows (k_resample_f32.hip) -----------------------------------------------------------
+// nx samples per row go up, out_len values come down; the one filter is the side input, uploaded once
+int kofft_hip_resample_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t nh, size_t up, size_t down,
+                           size_t t0, float *out, size_t out_len)
+{
+    const int rc = resample_check(rows, nx, nh, up, down, t0, out_len, x, h, out, ctx);
+    if (rc || rows == 0 || out_len == 0) return rc;
+    return rows_host<float>(ctx, x, out, rows, nx, out_len, h, nh, true, true,
+                            [&](float *d_in, float *d_out, const float *d_h, size_t nr) {
+                                return resample_dev(ctx, d_in, nr, nx, d_h, nh, up, down, t0, d_out, out_len);
+                            });
+}
+int kofft_hip_dev_resample_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t nh, size_t up,
+                               size_t down, size_t t0, float *d_out, size_t out_len)
+{
+    return resample_dev(ctx, d_x, rows, nx, d_h, nh, up, down, t0, d_out, out_len);
+}
+int kofft_hip_set_resample_tiled(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (on < 0 || on > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->resample_tiled = on;
+    return KOFFT_OK;
+}
+int kofft_hip_resample_route(size_t nh, size_t up, size_t down, int *route)
+{
+    if (!route) return KOFFT_ERR_NULL;
+    if (nh == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (up == 0 || down == 0) return KOFFT_ERR_INVALID_VALUE;
+    *route = resample_route(nh, up, down);
+    return KOFFT_OK;
+}
+int kofft_hip_resample_taps_f32(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh)
+{
+    return resample_taps(up, down, zeros, beta, taps, nh);
 }
 int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on)
 {
