@@ -590,6 +590,11 @@ int kofft_hip_set_direct_tiled(kofft_hip_ctx *ctx, int on);
  * it; 0: only what the grid's stride leaves over); pct < 0: the library's measured default;
  * pct > 100 -> INVALID_VALUE.  The same bytes at every setting (A/B measurements and tests). */
 int kofft_hip_set_persist_claim_pct(kofft_hip_ctx *ctx, int pct);
+/* Tests only: waits for the context's stream, then reads back the first word of each of the nine
+ * 128-byte lines of the claim hand-out (the claim words, one per piece of the claimed rows, in the
+ * first lines; the arrival word in the last), which every launch leaves at zero.  ctx or out null ->
+ * KOFFT_ERR_NULL. */
+int kofft_hip_persist_claim_debug(kofft_hip_ctx *ctx, unsigned out[9]);
 /* The tables of the direct transforms, host only (tests): C = n * n floats, C[i * n + k] as
  * above; rows outside the kind's i range are +0.  type not 1 .. 4 -> INVALID_VALUE; n == 0 ->
  * KOFFT_OK; n > 4096 -> KOFFT_ERR_UNSUPPORTED; C null -> KOFFT_ERR_NULL. */

@@ -171,13 +171,28 @@ template <class CFG>
 struct persist_claim<CFG, decltype((void)CFG::kClaim)> { static constexpr bool value = CFG::kClaim; };
 
 // The claim hand-out's kernel argument: rows [0, split) are walked with the grid's stride (split is a multiple of the stride), rows
-// [split, batch) are claimed XPB at a time with one fetch-add on counters[0].  counters[1] counts the workgroups that have made their
-// one failing claim; the last of them stores zeros to both, so that the next launch on the context's stream starts from zero without
-// any host-side reset (launch_persist; the context zeroes them once when it allocates them).
+// [split, batch) are claimed XPB at a time with one fetch-add.  The claimed rows are cut into kPersistClaimShards contiguous pieces of
+// whole units (the last piece takes the remainder), each with a claim word of its own on its own 128-byte line: ONE word answers about
+// 80 fetch-adds per microsecond (round 8: tools/ubench_copy4.hip, and the kernel itself with every row claimed), and the kernel asks for
+// 90.  A workgroup starts at shard blockIdx.x % kPersistClaimShards, and when a claim there fails it moves on to the next shard and never
+// returns to an exhausted one: at most kPersistClaimShards failing claims per workgroup, and nobody waits for anybody.
+// TWO words (round 8): as few as keep each word well below its rate.  More pieces are more separate streams through the
+// batch, and measured slower at every share -- eight (one per XCD) no faster than the one word was, three and four in between.
+// The context owns kPersistClaimMaxShards + 1 lines: the claim words first, the LAST line's word counts the workgroups that have found
+// every shard empty; the last of them stores zeros to every word the kernel uses, so that the next launch on the context's stream starts
+// from zero without any host-side reset (launch_persist; the context zeroes them once when it allocates them).
+#ifndef KOFFT_C12_CLAIM_SHARDS
+#define KOFFT_C12_CLAIM_SHARDS 2  // (A/B: 1 .. 8)
+#endif
+constexpr unsigned kPersistClaimShards = KOFFT_C12_CLAIM_SHARDS, kPersistClaimMaxShards = 8, kPersistClaimLine = 128 / sizeof(unsigned);
+static_assert(kPersistClaimShards >= 1 && kPersistClaimShards <= kPersistClaimMaxShards, "claim words");
+constexpr size_t kPersistClaimBytes = (kPersistClaimMaxShards + 1) * 128;
 struct PersistClaim {
-    unsigned *counters;
-    size_t split;
+    unsigned *counters;  // shard s: counters[s * kPersistClaimLine]; arrivals: counters[kPersistClaimMaxShards * kPersistClaimLine]
+    size_t split;        // (batch - split < 2^32: launch_persist_claim)
 };
+// "this shard is exhausted", in the LDS word a claimed row travels through (no row: rows are below 2^63)
+constexpr unsigned long long kPersistClaimEmpty = ~0ull;
 // the IO policy of a kClaim configuration's kernel: the configuration's own policy plus the hand-out's argument
 template <class IO>
 struct PersistClaimIO : IO {
@@ -602,6 +617,36 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     // (claim hand-out) the row after `base`, and the LDS words the claims travel through
     [[maybe_unused]] size_t nbase = 0;
     [[maybe_unused]] unsigned long long *claim_word = nullptr;
+    // (claim hand-out) the claiming lane's own: the shard it claims from, and how many shards it has found exhausted.  The pieces: shard s
+    // owns the units [s * piece, s * piece + len(s)) of the claimed rows, as row offsets from split.
+    [[maybe_unused]] unsigned claim_shard = blockIdx.x % kPersistClaimShards, claim_exhausted = 0;
+    [[maybe_unused]] unsigned claim_index = 0;  // (opaque: see the loop below)
+    [[maybe_unused]] unsigned claim_total = 0, claim_piece = 0;
+    if constexpr (CLAIMS) {
+        asm volatile("" : "+v"(claim_index));
+        claim_total = (unsigned)(batch - io.claim.split);
+        claim_piece = claim_total / XPB / kPersistClaimShards * XPB;
+    }
+    [[maybe_unused]] auto claim_counter = [&](const unsigned s) -> unsigned * {
+        if constexpr (CLAIMS) return io.claim.counters + (claim_index + s * kPersistClaimLine);
+        else return nullptr;
+    };
+    [[maybe_unused]] auto claim_len = [&](const unsigned s) -> unsigned {
+        return s + 1 == kPersistClaimShards ? claim_total - (kPersistClaimShards - 1) * claim_piece : claim_piece;
+    };
+    // (lane 0, outside the pipeline) one row, waiting for every answer: the current shard, then -- each failing claim retires a shard for
+    // good -- its successors; `batch` once all of them are exhausted
+    [[maybe_unused]] auto claim_now = [&]() -> size_t {
+        if constexpr (CLAIMS) {
+            while (claim_exhausted < kPersistClaimShards) {
+                const unsigned off = XPB * atomicAdd(claim_counter(claim_shard), 1u);
+                if (off < claim_len(claim_shard)) return io.claim.split + (size_t)claim_shard * claim_piece + off;
+                ++claim_exhausted;
+                claim_shard = (claim_shard + 1) % kPersistClaimShards;
+            }
+        }
+        return batch;
+    };
     if constexpr (CLAIMS) {
         static_assert(NP == 3 && NBUF == 1 && !WAVE && G == 1 && persist_depth<CFG>::value == 1 && !persist_tw_global<CFG>::value &&
                           !(RawSel::pair || RawSel::pair_lds) && !CFG::kInvInLds && !CFG::kTwLastInLds && EPI != EPI_RFFT,
@@ -615,8 +660,8 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         if (!second_walked) {  // workgroup-uniform
             if (tid == 0) {
                 size_t r0 = base, r1 = batch;
-                if (!first_walked) r0 = io.claim.split + (size_t)XPB * atomicAdd(io.claim.counters, 1u);
-                if (r0 < batch) r1 = io.claim.split + (size_t)XPB * atomicAdd(io.claim.counters, 1u);  // (never a second claim after a failed one)
+                if (!first_walked) r0 = claim_now();
+                if (r0 < batch) r1 = claim_now();  // (never another claim once every shard has failed)
                 claim_word[0] = r0;
                 claim_word[1] = r1;
             }
@@ -625,13 +670,19 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
             nbase = claim_word[1];  // (claim_word[0] is next written behind three barriers of the first transform)
         }
     }
-    // (claim hand-out) a workgroup makes exactly ONE failing claim and counts itself here afterwards; the last one to arrive has seen
-    // every claim of the launch completed and resets both counters for the next launch
+    // (claim hand-out) a workgroup leaves only when it has no next row, and a claimed "no next row" is `batch` from claim_now(): one failing
+    // claim on every shard.  It counts itself here afterwards.  Every fetch-add of a workgroup is made by its lane 0, which has used the
+    // answer -- the decision to leave depends on each of them -- before it arrives: all of a workgroup's claims are complete when it is
+    // counted, so the last one to arrive has seen every claim of the launch completed, none can be in flight, and it resets the claim
+    // words and the arrival word for the next launch.
     [[maybe_unused]] auto claim_leave = [&]() {
         if constexpr (CLAIMS) {
-            if (tid == 0 && atomicAdd(io.claim.counters + 1, 1u) == gridDim.x - 1) {
-                __hip_atomic_store(io.claim.counters, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(io.claim.counters + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned *const arrivals = io.claim.counters + kPersistClaimMaxShards * kPersistClaimLine;
+            if (tid == 0 && atomicAdd(arrivals, 1u) == gridDim.x - 1) {
+#pragma unroll
+                for (unsigned s = 0; s < kPersistClaimShards; ++s)
+                    __hip_atomic_store(io.claim.counters + s * kPersistClaimLine, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     };
@@ -697,22 +748,36 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         // and hands the result round with v_readfirstlane -- behind an s_waitcnt vmcnt(0) right at the claim)
         // (an opaque INDEX, not an opaque pointer: that one would lose its address space, and behind a flat_atomic every counted vmcnt wait
         // of the loop becomes vmcnt(0))
-        unsigned claim_index = 0;
-        asm volatile("" : "+v"(claim_index));
-        unsigned *const claim_next = io.claim.counters + claim_index;
+        // (claim_index above; the shard's part of the address is the claiming lane's own, a VGPR as well)
         // (the ticket stays a bare register until put(): anything computed from it next to the fetch-add would wait for it there, in front
         // of the prefetch, with vmcnt(0) -- the previous transform's stores included)
         struct ClaimXchg {
             unsigned long long *word;
-            size_t split;
+            size_t first;  // the shard's first row
+            unsigned len;  // and its rows
             const unsigned *ticket;
             size_t *claimed;
             bool writer;  // the claiming lane, in a step that claims
             __device__ __forceinline__ void put() const
             {
-                if (writer) *word = split + (size_t)XPB * *ticket;
+                if (writer) {
+                    const unsigned off = XPB * *ticket;
+                    *word = off < len ? first + off : kPersistClaimEmpty;
+                }
             }
             __device__ __forceinline__ void get() const { *claimed = *word; }
+        };
+        // A claim that found its shard exhausted (workgroup-uniform: the word every lane has read): lane 0 retires the shard and claims from
+        // the next ones until one answers with a row, waiting for each answer -- each shard at most once in a workgroup's life -- and hands the
+        // row, or `batch`, round through the second LDS word (last read before the first transform; three barriers between two uses).
+        auto claim_walk_on = [&]() -> size_t {
+            if (tid == 0) {
+                ++claim_exhausted;
+                claim_shard = (claim_shard + 1) % kPersistClaimShards;
+                claim_word[1] = claim_now();
+            }
+            __syncthreads();
+            return claim_word[1];
         };
 #define KOFFT_PERSIST_STEP_CLAIM(CUR, NXT, LEAVE)                                                                    \
     {                                                                                                                \
@@ -721,17 +786,19 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         const bool claims = more && !walked && tid == 0;                                                             \
         unsigned ticket; /* (no initial value: merging one with the fetch-add's result would be a copy, and a wait, at the claim) */ \
         size_t claimed = batch;                                                                                      \
-        if (claims) ticket = atomicAdd(claim_next, 1u);                                                              \
+        if (claims) ticket = atomicAdd(claim_counter(claim_shard), 1u);                                              \
         __builtin_amdgcn_sched_barrier(0); /* the claim in front of the prefetch */                                  \
         issue(NXT, nbase);                                                                                           \
         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of CUR's first use */                          \
         KOFFT_PERSIST_STEP_STAMP                                                                                     \
-        const ClaimXchg xchg{claim_word, io.claim.split, &ticket, &claimed, claims};                                 \
+        const ClaimXchg xchg{claim_word, io.claim.split + (size_t)claim_shard * claim_piece, claim_len(claim_shard), &ticket, &claimed, claims}; \
         persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, base + wslot, group_cnt(base), sub, tau, acc, NoPrefetchParts{}, xchg); \
         KOFFT_PERSIST_STAMP_ROW()                                                                                    \
         if (!more) LEAVE;                                                                                            \
+        /* (workgroup-uniform, and said so: the upper half of the word every lane has read; no row has all its bits set) */ \
+        if (!walked && __builtin_amdgcn_readfirstlane((unsigned)(claimed >> 32)) == ~0u) claimed = claim_walk_on();   \
         base = nbase;                                                                                                \
-        nbase = walked ? nbase + step : (size_t)claimed; /* (a failed claim: at or beyond the end) */                \
+        nbase = walked ? nbase + step : (size_t)claimed; /* (every shard exhausted: batch) */                        \
     }
 #define KOFFT_PERSIST_STEP_STAMP KOFFT_PERSIST_STAMP_LANDED()
         KOFFT_PERSIST_STEP_CLAIM(ra, rb, { finish(); return; })

@@ -82,7 +82,7 @@ struct kofft_hip_ctx {
     bool blue_persist = true; // KOFFT_HIP_BLUESTEIN_PERSIST=0: the one-launch Bluestein arm always as one workgroup per XPB transforms
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     int persist_claim_pct = -1; // kofft_hip_set_persist_claim_pct: percent of the batch the kClaim persistent kernels hand out by claim, 0 .. 100 (-1: the configuration's; A/B, tests)
-    unsigned *persist_claim_counters = nullptr;  // device: [next claim, workgroups done]; zeroed at creation, every kClaim launch leaves them at zero
+    unsigned *persist_claim_counters = nullptr;  // device: nine 128-byte lines, the claim words in the first ones and the arrival word in the last (fft_persist.hip.h, PersistClaim); zeroed at creation, every kClaim launch leaves them at zero
     int big_three_min = 22;    // KOFFT_HIP_BIG_THREE_MIN: smallest log2 n split into three factors
     bool small32 = true;       // KOFFT_HIP_SMALL32=0: f32 n = 32 on the thread-group kernel instead of one thread per transform (A/B)
     bool big_first11 = true;   // KOFFT_HIP_BIG_FIRST11=0: 2^21 as 2^10 x 2^11 with the one-tile-per-workgroup kernel for the 2^11 factor (A/B)
@@ -368,11 +368,12 @@ template <bool INV> struct PersistCfg<12, ComplexIO<double, INV>> {
 template <class IO> struct PersistCfg<12, IO> : PersistCfgBase<IO> { static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_C12_DEPTH; };
 // c32 n = 4096 (round 7): the last kClaimPct percent of the batch are claimed row by row instead of walked (fft_persist.hip.h,
 // PersistClaim), so that a workgroup that falls behind leaves rows to the others; the table of fractions is in DESIGN.md 5.2.
+// (round 8: 87 percent through two claim words; 25 was the largest share ONE word could hand out below its own rate)
 #ifndef KOFFT_C12_CLAIM
 #define KOFFT_C12_CLAIM true
 #endif
 #ifndef KOFFT_C12_CLAIM_PCT
-#define KOFFT_C12_CLAIM_PCT 25
+#define KOFFT_C12_CLAIM_PCT 87
 #endif
 template <bool INV> struct PersistCfg<12, ComplexIO<float, INV>> : PersistCfgBase<ComplexIO<float, INV>> {
     static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_C12_DEPTH, kClaimPct = KOFFT_C12_CLAIM_PCT;
@@ -538,7 +539,7 @@ int launch_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t ba
 }
 
 // The same for a kClaim configuration.  Rows [0, split) are walked as above, split a multiple of the grid's stride; rows [split, batch)
-// are claimed through the context's two counters, which every launch leaves at zero (no reset here, nothing a captured graph's replay
+// are claimed through the context's claim words, which every launch leaves at zero (no reset here, nothing a captured graph's replay
 // would miss: pointer and split are plain kernel arguments that depend on the batch alone).  They ride in the kernel's IO policy.
 template <typename T, int L, int EPI, class IO>
 int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch)
@@ -559,7 +560,8 @@ int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, siz
                                           ctx->persist_grid_pct, (batch + XPB - 1) / XPB);
     const size_t stride = blocks * XPB;
     const size_t pct = ctx->persist_claim_pct < 0 ? (size_t)Cfg::kClaimPct : (ctx->persist_claim_pct > 100 ? 100 : (size_t)ctx->persist_claim_pct);
-    const size_t claimed = batch / 100 * pct + batch % 100 * pct / 100;
+    size_t claimed = batch / 100 * pct + batch % 100 * pct / 100;
+    if (claimed > (size_t(1) << 31)) claimed = size_t(1) << 31;  // (row offsets from split travel as 32-bit tickets)
     const KIO kio{io, PersistClaim{ctx->persist_claim_counters, (batch - claimed) / stride * stride}};
     return launch_resident(ctx, attr_done, fft_persist_kernel<T, L, RL, EPI, KIO, Cfg>, blocks, Cfg::BLOCK, lds, kio, tw, batch);
 }

@@ -686,8 +686,9 @@ int kofft_hip_create(int device, kofft_hip_ctx **out)
     }
     ctx->stream = ctx->own_stream;
     // the claim counters of the kClaim persistent kernels (fft_persist.hip.h): zero once, here; every launch leaves them at zero
-    if (hipMalloc(reinterpret_cast<void **>(&ctx->persist_claim_counters), 64) != hipSuccess ||
-        hipMemsetAsync(ctx->persist_claim_counters, 0, 64, ctx->own_stream) != hipSuccess) {
+    // (room for eight claim words, and the arrival word, each on a 128-byte line of its own)
+    if (hipMalloc(reinterpret_cast<void **>(&ctx->persist_claim_counters), kofft::kPersistClaimBytes) != hipSuccess ||
+        hipMemsetAsync(ctx->persist_claim_counters, 0, kofft::kPersistClaimBytes, ctx->own_stream) != hipSuccess) {
         if (ctx->persist_claim_counters) (void)hipFree(ctx->persist_claim_counters);
         (void)hipStreamDestroy(ctx->own_stream);
         delete ctx;
@@ -1147,6 +1148,16 @@ int kofft_hip_set_persist_claim_pct(kofft_hip_ctx *ctx, int pct)
     if (!ctx) return KOFFT_ERR_NULL;
     if (pct > 100) return KOFFT_ERR_INVALID_VALUE;
     ctx->persist_claim_pct = pct < 0 ? -1 : pct;
+    return KOFFT_OK;
+}
+int kofft_hip_persist_claim_debug(kofft_hip_ctx *ctx, unsigned out[9])
+{
+    if (!ctx || !out) return KOFFT_ERR_NULL;
+    if (!ctx->persist_claim_counters) return KOFFT_ERR_ALLOC;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    KOFFT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (unsigned s = 0; s <= kofft::kPersistClaimMaxShards; ++s)
+        KOFFT_HIP_TRY(ctx, hipMemcpy(out + s, ctx->persist_claim_counters + s * kofft::kPersistClaimLine, sizeof(unsigned), hipMemcpyDeviceToHost));
     return KOFFT_OK;
 }
 int kofft_hip_set_wavelet_fused(kofft_hip_ctx *ctx, int on)
