@@ -98,20 +98,4 @@ struct FrontendIO : StftRowsOf<StftIO> {
     }
 };
 
-namespace host {
-
-// magnitudes of bins 0 .. n/2-1 of composed frames (any window length), no maximum: mag_rows_kernel's values
-// (internal linkage: k_frontend_f32.hip and k_picture_f32.hip both include this header and each launches its own copy)
-static __global__ __launch_bounds__(256) void frontend_mag_kernel(const cpx<float> *__restrict__ spec, float *__restrict__ mags, const size_t win_len,
-                                                           const size_t total /* transforms * (win_len/2) */)
-{
-    const size_t half = win_len / 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const size_t t = idx / half;
-    const cpx<float> c = spec[t * win_len + (idx - t * half)];
-    mags[idx] = sqrtf(c.re * c.re + c.im * c.im);
-}
-
-}  // namespace host
 }  // namespace kofft

@@ -867,7 +867,8 @@ int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size
 int spec_map_color_u8(float t, int cmap, unsigned char *rgb);
 // the device ranges [start[p], start[p + 1]) of a checked log_scale_bins table, from the context's cache (uploaded stream-ordered on a miss)
 int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins, const uint32_t **out);
-// k_frontend_f32.hip: magnitudes of frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_mags, no maximum
+// k_frontend_f32.hip: magnitudes of frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_mags, no maximum; no
+// checks (framed_produce's leaf for FRAMES_MAGS)
 int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_win, size_t win_len,
                size_t hop, size_t f0, size_t nf, float *d_mags);
 // k_picture_f32.hip: rows of audio -> stft_magnitudes -> the maximum (max_mode 0: of the row, 1: compute_frame's running one, 2: given)
@@ -900,10 +901,22 @@ int istft_rows_check(size_t rows, size_t frames, size_t win_len, size_t hop, siz
 // walk's copy into the context's scratch is then the Hermitian completion (expand_half, k_stft_onesided.hip)
 int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
                    float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, bool keep_frames, bool half = false);
-// transforms t0 .. t0 + nt of the flat index row * frames + frame, composed (any window length): framing product into dst, fft_dev in place
-int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
-                       size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt);
 size_t composed_chunk(const kofft_hip_ctx *ctx, size_t win_len, size_t count);  // transforms per pass through at most ctx->scratch_chunk_bytes of scratch
+// k_stft_rows.hip, for every family that cuts rows into frames.  What a framed call reads: `rows` signals cut into `frames` frames each, the flat index t = row * frames + frame.  framed_src is
+// the one place that fills it: a null d_window becomes hann_table's (on the context: its only use of ctx)
+struct FramedSrc {
+    const float *signal, *win;
+    size_t rows, len, row_stride /* 0 when rows == 1 */, win_len, hop, frames;
+    bool kernels;  // the rows kernels cover win_len (fused_len_ok); otherwise stft_rows_composed
+};
+int framed_src(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
+               size_t hop, size_t frames, FramedSrc *src);
+// Frames [t0, t0 + nt) of the flat index, dense at dst, as win_len complex values (FRAMES_FULL; composed lengths only), bins
+// 0 .. win_len/2 (FRAMES_HALF) or the magnitudes of bins 0 .. win_len/2 - 1 without a maximum (FRAMES_MAGS; win_len >= 2).  The rows
+// kernels run per rectangle of the chunk (frame_cut.h) through the two leaves below; the composed lengths go through
+// stft_rows_composed -- into dst for FRAMES_FULL, otherwise into `spec` (nt * win_len complex, the caller's) and a per-element tail.
+enum FramedForm { FRAMES_FULL, FRAMES_HALF, FRAMES_MAGS };
+int framed_produce(kofft_hip_ctx *ctx, const FramedSrc &s, FramedForm form, size_t t0, size_t nt, void *dst, cpx<float> *spec);
 // the input side of a StftRowsOf policy (row_stride: 0 when rows == 1)
 template <class IO>
 inline void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
@@ -920,6 +933,10 @@ inline void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len,
     io.row_stride = rows > 1 ? row_stride : 0;
     io.frames32 = rows * frames < (size_t(1) << 31) ? (unsigned)frames : 0u;
 }
+template <class IO> inline void fill_rows_io(IO &io, const FramedSrc &s)
+{
+    fill_rows_io(io, s.signal, s.rows, s.len, s.row_stride, s.win, s.win_len, s.hop, s.frames);
+}
 // k_stft_onesided.hip: the STFT with bins 0 .. win_len/2 of every frame kept, rows * frames * (win_len/2 + 1) complex, bit for bit the
 // prefix of stft_rows_dev's frames, and inverse_parallel of the Hermitian completion of such frames
 int stft_onesided_check(bool host_form, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames);
@@ -927,7 +944,8 @@ int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, si
                       size_t win_len, size_t hop, float *d_out, size_t frames);
 int istft_onesided_dev(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
                        float *d_output, size_t out_len);
-// the same kernels on frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_out; no checks
+// the same kernels on frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_out; no checks (framed_produce's leaf
+// for FRAMES_HALF)
 int stft_onesided_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_window,
                         size_t win_len, size_t hop, size_t f0, size_t nf, float *d_out);
 // k_welch_f32.hip: Welch power spectra (d_y null) and cross spectra of rows (welch_impl.hip.h).  welch_check: the argument

@@ -1,7 +1,9 @@
-// host_layout.h -- where the arrays of one host-pointer call lie in its staging buffer (kofft_hip.hip: stage_host).
-// Arithmetic only, no HIP: tests/cpp/host_layout_check.cpp includes this file alone.
+// host_layout.h -- where the arrays of one host-pointer call lie in its staging buffer (kofft_hip.hip: stage_host), the scratch chunks
+// and their walk, and the overlap test of the device forms.  Arithmetic only, no HIP: tests/cpp/host_layout_check.cpp and
+// tests/cpp/sanitize_frame_cut.cpp include this file alone.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 
 namespace kofft {
 namespace host {
@@ -51,6 +53,29 @@ inline size_t scratch_chunk_rows(size_t cap_bytes, size_t row_bytes, size_t coun
     if (chunk < 1) chunk = 1;
     return chunk > count ? count : chunk;
 }
+
+// The chunk walk: body(t0, nt) for the pieces [t0, t0 + nt) of [0, total), `chunk` at a time (chunk >= 1 where total > 0), in order;
+// it ends at the first body that returns non-zero and returns that, otherwise 0.
+template <class Body>
+inline int for_chunks(size_t total, size_t chunk, Body &&body)
+{
+    for (size_t t0 = 0; t0 < total; t0 += chunk) {
+        const int rc = body(t0, total - t0 < chunk ? total - t0 : chunk);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- the overlap checks of the device forms ----
+// the bytes [a, a + a_bytes) and [b, b + b_bytes) share one; a null pointer or an empty range never does
+inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return p && q && a_bytes && b_bytes && p < q + b_bytes && q < p + a_bytes;
+}
+
+// elements from the first of row 0 to the last of row rows - 1 of a strided batch (row_stride >= len; it does not count when rows == 1)
+inline size_t rows_span(size_t rows, size_t len, size_t row_stride) { return rows && len ? (rows - 1) * row_stride + len : 0; }
 
 // KOFFT_HIP_SCRATCH_CHUNK_MB: a whole number of MiB from 1 to kScratchChunkMaxMb, nothing before or after it.  true: *bytes is set;
 // false (empty, not a number, trailing text, out of range): *bytes is left alone.

@@ -26,11 +26,9 @@ int frontend_check(bool mfcc, bool dev, const void *signal, const void *window, 
     if (!ctx || !out || (!signal && len)) return KOFFT_ERR_NULL;
     if (dev) {
         const size_t out_row = mfcc ? num_coeffs : num_mel;
-        const float *o = static_cast<const float *>(out), *oe = o + rows * frames * out_row;
-        const float *s = static_cast<const float *>(signal), *w = static_cast<const float *>(window);
-        const size_t span = len ? (rows - 1) * (rows > 1 ? row_stride : 0) + len : 0;
-        if (o < oe && span && s < oe && o < s + span) return KOFFT_ERR_INVALID_VALUE;
-        if (o < oe && w && w < oe && o < w + win_len) return KOFFT_ERR_INVALID_VALUE;
+        const size_t out_bytes = rows * frames * out_row * sizeof(float);
+        if (overlaps(out, out_bytes, signal, rows_span(rows, len, row_stride) * sizeof(float))) return KOFFT_ERR_INVALID_VALUE;
+        if (overlaps(out, out_bytes, window, win_len * sizeof(float))) return KOFFT_ERR_INVALID_VALUE;
     }
     return KOFFT_OK;
 }
@@ -71,9 +69,9 @@ static int launch_frontend(kofft_hip_ctx *ctx, const FrontendIO<MFCC> &io, const
 }
 
 template <bool MFCC>
-static int frontend_fused(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_win,
-                          size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t nc, float *d_out)
+static int frontend_fused(kofft_hip_ctx *ctx, const FramedSrc &s, const uint64_t *bins, size_t num_mel, size_t nc, float *d_out)
 {
+    const size_t win_len = s.win_len;
     const int *plan = nullptr;
     int rc = get_mel_plan(ctx, bins, win_len / 2, num_mel, &plan);
     if (rc) return rc;
@@ -86,14 +84,14 @@ static int frontend_fused(kofft_hip_ctx *ctx, const float *d_signal, size_t rows
     rc = twiddle_table<float>(ctx, win_len, &tw);
     if (rc) return rc;
     FrontendIO<MFCC> io{};
-    fill_rows_io(io, d_signal, rows, len, row_stride, d_win, win_len, hop, frames);
+    fill_rows_io(io, s);
     io.plan = plan;
     io.dct = table;
     io.res = d_out;
     io.num_mel = (int)num_mel;
     io.nc = (int)nc;
     io.ldc = (int)direct_ldc(num_mel);
-    const size_t batch = rows * frames;
+    const size_t batch = s.rows * s.frames;
     switch (ilog2(win_len)) {
     case 6: return launch_frontend<6, MFCC>(ctx, io, tw, batch);
     case 7: return launch_frontend<7, MFCC>(ctx, io, tw, batch);
@@ -119,51 +117,22 @@ int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t l
 }
 
 // Whole frames of the flat index t = row * frames + frame, scratch_chunk_bytes of scratch at a time: [magnitudes | (window lengths the
-// magnitudes kernels do not cover) the composed frames].  A chunk may begin and end inside a row: it is cut into the rest of its
-// first row, whole rows, and the head of its last row.
-static int frontend_composed(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_win,
-                             size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t nc, float *d_out)
+// magnitudes kernels do not cover) the composed frames].  A chunk may begin and end inside a row (framed_produce cuts it).
+static int frontend_composed(kofft_hip_ctx *ctx, bool mfcc, const FramedSrc &s, const uint64_t *bins, size_t num_mel, size_t nc, float *d_out)
 {
-    const size_t half = win_len / 2, total = rows * frames, out_row = mfcc ? nc : num_mel;
-    const bool kernels = fused_len_ok<float>(win_len);
-    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, half * sizeof(float) + (kernels ? 0 : win_len * sizeof(cpx<float>)), total);
+    const size_t win_len = s.win_len, half = win_len / 2, total = s.rows * s.frames, out_row = mfcc ? nc : num_mel;
+    const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, half * sizeof(float) + (s.kernels ? 0 : win_len * sizeof(cpx<float>)), total);
     const size_t mags_bytes = (chunk * half * sizeof(float) + 15) & ~size_t(15);
-    int rc = ensure(ctx, ctx->rows_tmp, mags_bytes + (kernels ? 0 : chunk * win_len * sizeof(cpx<float>)) + 16);
-    if (rc) return rc;
+    const int erc = ensure(ctx, ctx->rows_tmp, mags_bytes + (s.kernels ? 0 : chunk * win_len * sizeof(cpx<float>)) + 16);
+    if (erc) return erc;
     float *mags = static_cast<float *>(ctx->rows_tmp.p);
     cpx<float> *spec = reinterpret_cast<cpx<float> *>(static_cast<char *>(ctx->rows_tmp.p) + mags_bytes);
-    if (rows == 1) row_stride = 0;
-    for (size_t t0 = 0; t0 < total; t0 += chunk) {
-        const size_t nt = total - t0 < chunk ? total - t0 : chunk, end = t0 + nt;
-        if (half && !kernels) {
-            rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_win, win_len, hop, spec, t0, nt);
-            if (rc) return rc;
-            const size_t blocks = (nt * half + 255) / 256;
-            if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL(frontend_mag_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, mags, win_len, nt * half);
-            KOFFT_HIP_TRY(ctx, hipGetLastError());
-        } else if (half) {
-            for (size_t t = t0; t < end;) {
-                const size_t r = t / frames, f = t - r * frames;
-                const float *sig = d_signal ? d_signal + r * row_stride : nullptr;
-                size_t done;
-                if (f != 0 || end - t < frames) {  // part of row r
-                    done = frames - f < end - t ? frames - f : end - t;
-                    rc = mags_piece(ctx, sig, 1, len, 0, d_win, win_len, hop, f, done, mags + (t - t0) * half);
-                } else {
-                    const size_t nr = (end - t) / frames;
-                    done = nr * frames;
-                    rc = mags_piece(ctx, sig, nr, len, row_stride, d_win, win_len, hop, 0, frames, mags + (t - t0) * half);
-                }
-                if (rc) return rc;
-                t += done;
-            }
-        }
-        rc = mfcc ? mfcc_dev(ctx, mags, d_out + t0 * out_row, half, nt, bins, num_mel, nc)
-                  : mel_filterbank_dev(ctx, mags, d_out + t0 * out_row, half, nt, bins, num_mel);
+    return for_chunks(total, chunk, [&](size_t t0, size_t nt) {
+        const int rc = half ? framed_produce(ctx, s, FRAMES_MAGS, t0, nt, mags, spec) : KOFFT_OK;  // (a one-sample window has no bins)
         if (rc) return rc;
-    }
-    return KOFFT_OK;
+        return mfcc ? mfcc_dev(ctx, mags, d_out + t0 * out_row, half, nt, bins, num_mel, nc)
+                    : mel_filterbank_dev(ctx, mags, d_out + t0 * out_row, half, nt, bins, num_mel);
+    });
 }
 
 int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
@@ -172,16 +141,12 @@ int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t ro
     const int crc = frontend_check(mfcc, true, d_signal, d_window, d_out, rows, len, row_stride, win_len, hop, frames, bins, num_mel, num_coeffs, ctx);
     if (crc || rows == 0 || frames == 0 || num_mel == 0 || (mfcc && num_coeffs == 0)) return crc;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const float *d_win = d_window;
-    if (!d_win && win_len >= 2) {  // window::hann(win_len), stft_magnitudes' own (a one-sample window has no magnitude bins)
-        const int rc = hann_table(ctx, win_len, &d_win);
-        if (rc) return rc;
-    }
-    if (frontend_use_fused(ctx, win_len, num_mel, num_coeffs)) {
-        return mfcc ? frontend_fused<true>(ctx, d_signal, rows, len, row_stride, d_win, win_len, hop, frames, bins, num_mel, num_coeffs, d_out)
-                    : frontend_fused<false>(ctx, d_signal, rows, len, row_stride, d_win, win_len, hop, frames, bins, num_mel, 0, d_out);
-    }
-    return frontend_composed(ctx, mfcc, d_signal, rows, len, row_stride, d_win, win_len, hop, frames, bins, num_mel, num_coeffs, d_out);
+    FramedSrc s;
+    const int rc = framed_src(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, &s);
+    if (rc) return rc;
+    if (frontend_use_fused(ctx, win_len, num_mel, num_coeffs))
+        return mfcc ? frontend_fused<true>(ctx, s, bins, num_mel, num_coeffs, d_out) : frontend_fused<false>(ctx, s, bins, num_mel, 0, d_out);
+    return frontend_composed(ctx, mfcc, s, bins, num_mel, num_coeffs, d_out);
 }
 
 }  // namespace host

@@ -2,7 +2,7 @@
 // the family, the argument checks and the routes of the three maximum modes.
 #include "picture_impl.hip.h"
 
-#include "picture_cut.h"
+#include "frame_cut.h"
 
 namespace kofft {
 namespace host {
@@ -11,12 +11,6 @@ namespace host {
 template <> struct PersistCfg<10, StftMagRowsMaxOnlyIO> : PersistCfg<10, StftMagIO> {};
 template <> struct PersistCfg<11, StftMagRowsMaxOnlyIO> : PersistCfg<11, StftMagIO> {};
 template <> struct PersistCfg<12, StftMagRowsMaxOnlyIO> : PersistCfg<12, StftMagIO> {};
-
-static bool pic_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const char *p = static_cast<const char *>(a), *q = static_cast<const char *>(b);
-    return p && q && a_bytes && b_bytes && p < q + b_bytes && q < p + a_bytes;
-}
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
 int picture_check(bool dev, const void *signal, size_t rows, size_t len, size_t row_stride, const void *window, size_t win_len, size_t hop,
@@ -54,9 +48,8 @@ int picture_check(bool dev, const void *signal, size_t rows, size_t len, size_t 
     if (dev) {
         const size_t px = channels == 4 ? 4 : (depth == 16 ? 6 : 3);
         const size_t out_bytes = rows * frames * bins * px;
-        const size_t span = len ? (rows - 1) * (rows > 1 ? row_stride : 0) + len : 0;
-        if (pic_overlap(out, out_bytes, signal, span * sizeof(float)) || pic_overlap(out, out_bytes, window, win_len * sizeof(float)) ||
-            (max_mode == 2 && pic_overlap(out, out_bytes, max_in, rows * sizeof(float))) || pic_overlap(out, out_bytes, max_out, rows * sizeof(float)))
+        if (overlaps(out, out_bytes, signal, rows_span(rows, len, row_stride) * sizeof(float)) || overlaps(out, out_bytes, window, win_len * sizeof(float)) ||
+            (max_mode == 2 && overlaps(out, out_bytes, max_in, rows * sizeof(float))) || overlaps(out, out_bytes, max_out, rows * sizeof(float)))
             return KOFFT_ERR_INVALID_VALUE;
     }
     return KOFFT_OK;
@@ -71,9 +64,8 @@ static unsigned pic_blocks(const kofft_hip_ctx *ctx, size_t items)
 // what one call works with
 struct PicCall {
     kofft_hip_ctx *ctx;
-    const float *signal, *win;
-    size_t rows, len, row_stride, win_len, hop, frames, half;
-    bool kernels;  // the window length is one of the magnitudes kernels'
+    FramedSrc src;
+    size_t half;  // src.win_len / 2
     float *mags, *pmax, *fmax;
     cpx<float> *spec;
     const float *row_max;  // the maximum the render reads per row (modes 0 and 2)
@@ -84,28 +76,7 @@ struct PicCall {
 };
 
 // magnitudes of frames [t0, t0 + nt) of the flat index, dense at c.mags
-static int pic_produce(const PicCall &c, size_t t0, size_t nt)
-{
-    kofft_hip_ctx *ctx = c.ctx;
-    if (!c.kernels) {
-        const int rc = stft_rows_composed(ctx, c.signal, c.len, c.row_stride, c.frames, c.win, c.win_len, c.hop, c.spec, t0, nt);
-        if (rc) return rc;
-        const size_t blocks = (nt * c.half + 255) / 256;
-        if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(frontend_mag_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, c.spec, c.mags, c.win_len, nt * c.half);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-        return KOFFT_OK;
-    }
-    PicPiece p[3];
-    const int np = picture_cut(t0, nt, c.frames, p);
-    for (int k = 0; k < np; ++k) {
-        const float *sig = c.signal ? c.signal + p[k].row * c.row_stride : nullptr;
-        const int rc = mags_piece(ctx, sig, p[k].nr, c.len, p[k].nr > 1 ? c.row_stride : 0, c.win, c.win_len, c.hop, p[k].f0, p[k].nf,
-                                  c.mags + p[k].at * c.half);
-        if (rc) return rc;
-    }
-    return KOFFT_OK;
-}
+static int pic_produce(const PicCall &c, size_t t0, size_t nt) { return framed_produce(c.ctx, c.src, FRAMES_MAGS, t0, nt, c.mags, c.spec); }
 
 template <int FMT, bool PMAX>
 static int pic_render_as(const PicCall &c, size_t t0, size_t nt)
@@ -113,21 +84,22 @@ static int pic_render_as(const PicCall &c, size_t t0, size_t nt)
     kofft_hip_ctx *ctx = c.ctx;
     constexpr size_t PX = pic_px(FMT);
     const int bins = (int)c.half;
+    const size_t frames = c.src.frames;
     if (c.layout == 0) {
         hipLaunchKernelGGL((pic_flat_kernel<FMT, PMAX>), dim3(pic_blocks(ctx, (nt * c.half + 3) / 4)), dim3(256), 0, ctx->stream, c.mags, c.pmax,
-                           c.out + t0 * c.half * PX, nt, bins, c.row_max, t0 / c.frames, (t0 % c.frames) * c.half, c.frames * c.half, c.mode, c.level, c.cmap,
+                           c.out + t0 * c.half * PX, nt, bins, c.row_max, t0 / frames, (t0 % frames) * c.half, frames * c.half, c.mode, c.level, c.cmap,
                            c.start);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         return KOFFT_OK;
     }
-    PicPiece p[3];
-    const int np = picture_cut(t0, nt, c.frames, p);
+    FramePiece p[3];
+    const int np = frame_cut(t0, nt, frames, p);
     for (int k = 0; k < np; ++k) {
         const size_t tiles_b = (c.half + SPEC_TB - 1) / SPEC_TB, tiles_f = (p[k].nf + SPEC_TF - 1) / SPEC_TF;
         if (tiles_f > 0x7fffffffULL / tiles_b || p[k].nr > 0x7fffffffULL / (tiles_b * tiles_f)) return KOFFT_ERR_UNSUPPORTED;
         auto kern = ctx->spec_transpose ? pic_image_kernel<FMT, true, PMAX> : pic_image_kernel<FMT, false, PMAX>;
         hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_b * tiles_f * p[k].nr)), dim3(SPEC_THREADS), 0, ctx->stream, c.mags + p[k].at * c.half,
-                           PMAX ? c.pmax + p[k].at * c.half : nullptr, c.out, p[k].row, p[k].f0, p[k].nf, c.frames, bins, c.row_max, c.mode,
+                           PMAX ? c.pmax + p[k].at * c.half : nullptr, c.out, p[k].row, p[k].f0, p[k].nf, frames, bins, c.row_max, c.mode,
                            c.level, c.cmap, c.start, (unsigned)tiles_b, (unsigned)tiles_f);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
     }
@@ -146,7 +118,7 @@ static int pic_render(const PicCall &c, bool per_pixel, size_t t0, size_t nt)
 // the row maxima of the chunk at c.mags into max_bits
 static int pic_row_max(const PicCall &c, unsigned *max_bits, size_t t0, size_t nt)
 {
-    hipLaunchKernelGGL(pic_row_max_kernel, dim3(pic_blocks(c.ctx, nt * c.half)), dim3(256), 0, c.ctx->stream, c.mags, max_bits, c.frames, c.half, t0,
+    hipLaunchKernelGGL(pic_row_max_kernel, dim3(pic_blocks(c.ctx, nt * c.half)), dim3(256), 0, c.ctx->stream, c.mags, max_bits, c.src.frames, c.half, t0,
                        nt * c.half);
     KOFFT_HIP_TRY(c.ctx, hipGetLastError());
     return KOFFT_OK;
@@ -159,9 +131,9 @@ static int pic_running(const PicCall &c, float *carry, size_t t0, size_t nt)
     const unsigned per_frame = (unsigned)((nt + 3) / 4);  // (nt <= 2^27: a chunk holds at most 2^27 floats)
     hipLaunchKernelGGL(pic_frame_max_kernel, dim3(per_frame), dim3(256), 0, ctx->stream, c.mags, c.fmax, nt, (int)c.half);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
-    const size_t nrows = (t0 + nt - 1) / c.frames - t0 / c.frames + 1;
+    const size_t nrows = (t0 + nt - 1) / c.src.frames - t0 / c.src.frames + 1;
     if (nrows > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(pic_frame_scan_kernel, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, c.fmax, carry, c.frames, t0, nt);
+    hipLaunchKernelGGL(pic_frame_scan_kernel, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, c.fmax, carry, c.src.frames, t0, nt);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(pic_pixel_max_kernel, dim3(per_frame), dim3(256), 0, ctx->stream, c.mags, c.fmax, c.pmax, nt, (int)c.half);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
@@ -199,18 +171,11 @@ int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t l
         return pic_fill(ctx, d_max_out, rows, max_mode == 1 ? kPicSeed : 0.0f);
     }
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const float *d_win = d_window;
-    if (!d_win) {  // window::hann(win_len), stft_magnitudes' own
-        rc = hann_table(ctx, win_len, &d_win);
-        if (rc) return rc;
-    }
     PicCall c{};
     c.ctx = ctx;
-    c.signal = d_signal;
-    c.win = d_win;
-    c.rows = rows, c.len = len, c.row_stride = rows == 1 ? 0 : row_stride, c.win_len = win_len, c.hop = hop, c.frames = frames;
+    rc = framed_src(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, &c.src);
+    if (rc) return rc;
     c.half = win_len / 2;
-    c.kernels = fused_len_ok<float>(win_len);
     c.mode = mode, c.level = level, c.cmap = cmap, c.layout = layout;
     c.fmt = channels == 4 ? 2 : (depth == 16 ? 1 : 0);
     c.out = static_cast<unsigned char *>(d_out);
@@ -222,10 +187,10 @@ int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t l
     // scratch: [magnitudes | (mode 1) the per-pixel maxima | (composed window lengths) the frames | a float per row | (mode 1) a float per frame]
     const size_t total = rows * frames;
     const bool running = max_mode == 1;
-    const size_t frame_bytes = c.half * sizeof(float) * (running ? 2 : 1) + (c.kernels ? 0 : win_len * sizeof(cpx<float>));
+    const size_t frame_bytes = c.half * sizeof(float) * (running ? 2 : 1) + (c.src.kernels ? 0 : win_len * sizeof(cpx<float>));
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, frame_bytes, total);
     const size_t mags_bytes = pad16(chunk * c.half * sizeof(float));
-    const size_t spec_bytes = c.kernels ? 0 : pad16(chunk * win_len * sizeof(cpx<float>));
+    const size_t spec_bytes = c.src.kernels ? 0 : pad16(chunk * win_len * sizeof(cpx<float>));
     const size_t per_row_bytes = pad16(rows * sizeof(float));
     rc = ensure(ctx, ctx->rows_tmp, mags_bytes * (running ? 2 : 1) + spec_bytes + per_row_bytes + (running ? pad16(chunk * sizeof(float)) : 0) + 16);
     if (rc) return rc;
@@ -242,17 +207,9 @@ int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t l
     base += per_row_bytes;
     c.fmax = reinterpret_cast<float *>(base);
 
-    auto for_chunks = [&](auto &&body) {
-        for (size_t t0 = 0; t0 < total; t0 += chunk) {
-            const int brc = body(t0, total - t0 < chunk ? total - t0 : chunk);
-            if (brc) return brc;
-        }
-        return (int)KOFFT_OK;
-    };
-
     if (max_mode == 2) {
         c.row_max = d_max_in;
-        rc = for_chunks([&](size_t t0, size_t nt) {
+        rc = for_chunks(total, chunk, [&](size_t t0, size_t nt) {
             const int prc = pic_produce(c, t0, nt);
             return prc ? prc : pic_render(c, false, t0, nt);
         });
@@ -265,7 +222,7 @@ int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t l
     if (running) {
         rc = pic_fill(ctx, per_row, rows, kPicSeed);
         if (rc) return rc;
-        rc = for_chunks([&](size_t t0, size_t nt) {
+        rc = for_chunks(total, chunk, [&](size_t t0, size_t nt) {
             int prc = pic_produce(c, t0, nt);
             if (!prc) prc = pic_running(c, per_row, t0, nt);
             return prc ? prc : pic_render(c, true, t0, nt);
@@ -286,20 +243,20 @@ int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t l
             } else {
                 // two passes.  The first keeps nothing but the maxima: the magnitudes kernels without their stores over the whole batch,
                 // or (composed window lengths) chunk after chunk through the scratch
-                if (c.kernels) {
+                if (c.src.kernels) {
                     StftMagRowsMaxOnlyIO io{};
-                    fill_rows_io(io, d_signal, rows, len, row_stride, d_win, win_len, hop, frames);
+                    fill_rows_io(io, c.src);
                     io.mags = nullptr;
                     io.max_bits = max_bits;
                     rc = dispatch<float, EPI_STORE>(ctx, io, win_len, total);
                 } else {
-                    rc = for_chunks([&](size_t t0, size_t nt) {
+                    rc = for_chunks(total, chunk, [&](size_t t0, size_t nt) {
                         const int prc = pic_produce(c, t0, nt);
                         return prc ? prc : pic_row_max(c, max_bits, t0, nt);
                     });
                 }
                 if (!rc)
-                    rc = for_chunks([&](size_t t0, size_t nt) {
+                    rc = for_chunks(total, chunk, [&](size_t t0, size_t nt) {
                         const int prc = pic_produce(c, t0, nt);
                         return prc ? prc : pic_render(c, false, t0, nt);
                     });

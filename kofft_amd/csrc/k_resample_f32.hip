@@ -11,8 +11,6 @@ namespace host {
 
 static_assert(kResampleTile == KOFFT_HIP_RESAMPLE_TILE, "include/kofft_hip.h names the tile");
 
-static bool ranges_overlap(const float *a, size_t na, const float *b, size_t nb) { return na && nb && a < b + nb && b < a + na; }
-
 // The argument checks alone, in the order of include/kofft_hip.h and before the context or a device is touched.  KOFFT_OK with
 // rows == 0 or out_len == 0: nothing to do.
 int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, size_t t0, size_t out_len, const void *x, const void *h,
@@ -30,10 +28,7 @@ int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, si
         return KOFFT_ERR_UNSUPPORTED;
     if (last >= full_up) return KOFFT_ERR_MISMATCHED_LENGTHS;
     if (!ctx || !x || !h || !out) return KOFFT_ERR_NULL;
-    const float *o = static_cast<const float *>(out);
-    if (ranges_overlap(o, rows * out_len, static_cast<const float *>(x), rows * nx) ||
-        ranges_overlap(o, rows * out_len, static_cast<const float *>(h), nh))
-        return KOFFT_ERR_INVALID_VALUE;
+    if (overlaps(out, out_bytes, x, in_bytes) || overlaps(out, out_bytes, h, h_bytes)) return KOFFT_ERR_INVALID_VALUE;
     return KOFFT_OK;
 }
 

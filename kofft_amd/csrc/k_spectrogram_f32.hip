@@ -7,19 +7,13 @@
 namespace kofft {
 namespace host {
 
-static bool spec_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const char *p = static_cast<const char *>(a), *q = static_cast<const char *>(b);
-    return a_bytes && b_bytes && p < q + b_bytes && q < p + a_bytes;
-}
-
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
 int spec_db_check(bool dev, const void *mags, size_t count, const void *max_mag, const void *out, const kofft_hip_ctx *ctx)
 {
     if (count == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (count > SIZE_MAX / sizeof(float)) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !mags || !max_mag || !out) return KOFFT_ERR_NULL;
-    if (dev && (spec_overlap(mags, count * sizeof(float), out, count * sizeof(float)) || spec_overlap(max_mag, sizeof(float), out, count * sizeof(float))))
+    if (dev && (overlaps(mags, count * sizeof(float), out, count * sizeof(float)) || overlaps(max_mag, sizeof(float), out, count * sizeof(float))))
         return KOFFT_ERR_INVALID_VALUE;
     return KOFFT_OK;
 }
@@ -44,7 +38,7 @@ int spec_render_check(bool dev, const void *mags, size_t frames, size_t bins, co
     if (tiles_f > 0x7fffffffULL / tiles_b) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !mags || !max_mag || !out) return KOFFT_ERR_NULL;
     const size_t in_bytes = frames * bins * sizeof(float), out_bytes = frames * bins * px;
-    if (dev && (spec_overlap(mags, in_bytes, out, out_bytes) || spec_overlap(max_mag, sizeof(float), out, out_bytes))) return KOFFT_ERR_INVALID_VALUE;
+    if (dev && (overlaps(mags, in_bytes, out, out_bytes) || overlaps(max_mag, sizeof(float), out, out_bytes))) return KOFFT_ERR_INVALID_VALUE;
     return KOFFT_OK;
 }
 

@@ -7,16 +7,6 @@
 namespace kofft {
 namespace host {
 
-// composed frames (any window length) -> their kept bins: dst[t][k] = src[t][k], k < bins.  One bin per thread.
-__global__ __launch_bounds__(256) void pack_half_kernel(const cpx<float> *__restrict__ src, cpx<float> *__restrict__ dst, const size_t win_len,
-                                                        const size_t bins, const size_t total /* transforms * bins */)
-{
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const size_t t = idx / bins, k = idx - t * bins;
-    dst[idx] = src[t * win_len + k];
-}
-
 // the completed frame F[k] = H[k] for k < bins, (H[n - k].re, -H[n - k].im) above; the imaginary parts of H[0] and H[n/2] as given.
 // One bin of F per thread; `half` is only read.
 __global__ __launch_bounds__(256) void expand_half_kernel(const cpx<float> *__restrict__ half, cpx<float> *__restrict__ full,
@@ -64,38 +54,31 @@ int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, si
     if (!ctx || (!d_signal && len) || !d_window || !d_out) return KOFFT_ERR_NULL;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t total = rows * frames, bins = win_len / 2 + 1;
-    if (rows == 1) row_stride = 0;
-    if (!fused_len_ok<float>(win_len)) {
+    FramedSrc s;
+    (void)framed_src(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, &s);  // (the caller's window: nothing to fail)
+    if (!s.kernels) {
         // any other window length: the composed frames in the context's scratch, at most scratch_chunk_bytes at a time, then their kept bins
         const size_t chunk = composed_chunk(ctx, win_len, total);
-        if ((chunk * bins + 255) / 256 > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-        int rc = ensure(ctx, ctx->real_tmp, chunk * win_len * 8);
+        const int rc = ensure(ctx, ctx->real_tmp, chunk * win_len * 8);
         if (rc) return rc;
-        cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp.p);
-        for (size_t t0 = 0; t0 < total; t0 += chunk) {
-            const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
-            rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_window, win_len, hop, spec, t0, nt);
-            if (rc) return rc;
-            hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)((nt * bins + 255) / 256)), dim3(256), 0, ctx->stream, spec,
-                               reinterpret_cast<cpx<float> *>(d_out) + t0 * bins, win_len, bins, nt * bins);
-            KOFFT_HIP_TRY(ctx, hipGetLastError());
-        }
-        return KOFFT_OK;
+        return for_chunks(total, chunk, [&](size_t t0, size_t nt) {
+            return framed_produce(ctx, s, FRAMES_HALF, t0, nt, d_out + t0 * bins * 2, static_cast<cpx<float> *>(ctx->real_tmp.p));
+        });
     }
     StftHalfRowsIO io{};
-    fill_rows_io(io, d_signal, rows, len, row_stride, d_window, win_len, hop, frames);
+    fill_rows_io(io, s);
     io.out = reinterpret_cast<cpx<float> *>(d_out);
     return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
 }
 
-// frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row; f0 * hop < len or len == 0), dense at d_out: stft_onesided_dev's kernels
-// on a rectangle of the batch, for the chunk walks that keep the frames in the context's scratch (k_welch_f32.hip)
+// frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_out: stft_onesided_dev's kernels on a rectangle of the
+// batch, for the chunk walks that keep the frames in the context's scratch (framed_produce; k_welch_f32.hip)
 int stft_onesided_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_window,
                         size_t win_len, size_t hop, size_t f0, size_t nf, float *d_out)
 {
     StftHalfRowsIO io{};
     fill_rows_io(io, d_signal, nrows, len, row_stride, d_window, win_len, hop, nf);
-    io.start0 = f0 * hop;
+    io.start0 = (f0 && hop > len / f0) ? len : f0 * hop;  // (a start at or past len: silence, as every frame after it; mags_piece's form)
     io.out = reinterpret_cast<cpx<float> *>(d_out);
     return dispatch<float, EPI_STORE>(ctx, io, win_len, nrows * nf);
 }

@@ -1,7 +1,10 @@
 // k_stft_rows.hip -- STFT (stft.rs:76-105), stft_magnitudes (visual/spectrogram.rs:52-76) and ISTFT (stft.rs:117-156, 289-343) over
 // ROWS of signals on device pointers.  Row r of every output is what k_stft.hip's single-signal entry returns for
-// signal r alone; one launch chain serves all rows.
+// signal r alone; one launch chain serves all rows.  Also the framed families' shared host side: framed_src (what a framed call reads)
+// and framed_produce (frames t0 .. of the flat index densely into scratch: full, their kept bins, or their magnitudes).
 #include "host_common.hip.h"
+
+#include "frame_cut.h"
 
 namespace kofft {
 namespace host {
@@ -39,6 +42,28 @@ __global__ __launch_bounds__(256) void mag_rows_kernel(const cpx<float> *__restr
         row = (unsigned)((t0 + t) / frames);
     }
     row_max_commit(max_bits, row, v, false);  // (`if mag > max_mag`: a NaN is never a candidate)
+}
+
+// ... without a maximum: mag_rows_kernel's values (framed_produce, FRAMES_MAGS)
+__global__ __launch_bounds__(256) void frontend_mag_kernel(const cpx<float> *__restrict__ spec, float *__restrict__ mags, const size_t win_len,
+                                                           const size_t total /* transforms * (win_len/2) */)
+{
+    const size_t half = win_len / 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const size_t t = idx / half;
+    const cpx<float> c = spec[t * win_len + (idx - t * half)];
+    mags[idx] = sqrtf(c.re * c.re + c.im * c.im);
+}
+
+// composed frames -> their kept bins: dst[t][k] = src[t][k], k < bins.  One bin per thread (framed_produce, FRAMES_HALF).
+__global__ __launch_bounds__(256) void pack_half_kernel(const cpx<float> *__restrict__ src, cpx<float> *__restrict__ dst, const size_t win_len,
+                                                        const size_t bins, const size_t total /* transforms * bins */)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const size_t t = idx / bins, k = idx - t * bins;
+    dst[idx] = src[t * win_len + k];
 }
 
 // The ordered overlap-add of istft_ola_kernel over rows: one thread per output sample of rows * out_len, the same sums in the same
@@ -95,9 +120,9 @@ int stft_rows_check(bool host_form, bool mags, size_t rows, size_t len, size_t r
     return KOFFT_OK;
 }
 
-// transforms t0 .. t0 + nt of the flat index, composed: framing product into dst, fft_dev in place
-int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
-                       size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt)
+// transforms t0 .. t0 + nt of the flat index, composed (any window length): framing product into dst, fft_dev in place
+static int stft_rows_composed(kofft_hip_ctx *ctx, const float *d_signal, size_t len, size_t row_stride, size_t frames, const float *d_window,
+                              size_t win_len, size_t hop, cpx<float> *dst, size_t t0, size_t nt)
 {
     const size_t blocks = (nt * win_len + 255) / 256;
     if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
@@ -112,6 +137,45 @@ size_t composed_chunk(const kofft_hip_ctx *ctx, size_t win_len, size_t count)
     return scratch_chunk_rows(ctx->scratch_chunk_bytes, win_len * 8, count);
 }
 
+int framed_src(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
+               size_t hop, size_t frames, FramedSrc *src)
+{
+    *src = FramedSrc{d_signal, d_window, rows, len, rows == 1 ? 0 : row_stride, win_len, hop, frames, fused_len_ok<float>(win_len)};
+    return d_window ? KOFFT_OK : hann_table(ctx, win_len, &src->win);  // window::hann(win_len), stft_magnitudes' own
+}
+
+int framed_produce(kofft_hip_ctx *ctx, const FramedSrc &s, FramedForm form, size_t t0, size_t nt, void *dst, cpx<float> *spec)
+{
+    const size_t half = s.win_len / 2, per = form == FRAMES_HALF ? half + 1 : half;  // values per frame of the two packed forms
+    if (!s.kernels) {
+        const size_t blocks = (nt * per + 255) / 256;
+        if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+        cpx<float> *frames = form == FRAMES_FULL ? static_cast<cpx<float> *>(dst) : spec;
+        const int rc = stft_rows_composed(ctx, s.signal, s.len, s.row_stride, s.frames, s.win, s.win_len, s.hop, frames, t0, nt);
+        if (rc || form == FRAMES_FULL) return rc;
+        if (form == FRAMES_HALF)
+            hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, static_cast<cpx<float> *>(dst), s.win_len,
+                               per, nt * per);
+        else
+            hipLaunchKernelGGL(frontend_mag_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, static_cast<float *>(dst), s.win_len,
+                               nt * per);
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+        return KOFFT_OK;
+    }
+    if (form == FRAMES_FULL) return KOFFT_ERR_UNSUPPORTED;  // (never: the full frames of these lengths are one dispatch, stft_rows_dev)
+    FramePiece p[3];
+    const int np = frame_cut(t0, nt, s.frames, p);
+    for (int k = 0; k < np; ++k) {
+        const float *sig = s.signal ? s.signal + p[k].row * s.row_stride : nullptr;
+        const int rc = form == FRAMES_HALF ? stft_onesided_piece(ctx, sig, p[k].nr, s.len, s.row_stride, s.win, s.win_len, s.hop, p[k].f0, p[k].nf,
+                                                                 static_cast<float *>(dst) + p[k].at * per * 2)
+                                           : mags_piece(ctx, sig, p[k].nr, s.len, s.row_stride, s.win, s.win_len, s.hop, p[k].f0, p[k].nf,
+                                                        static_cast<float *>(dst) + p[k].at * per);
+        if (rc) return rc;
+    }
+    return KOFFT_OK;
+}
+
 int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
                   size_t win_len, size_t hop, float *d_out, size_t frames)
 {
@@ -120,20 +184,14 @@ int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t
     if (!ctx || (!d_signal && len) || !d_window || !d_out) return KOFFT_ERR_NULL;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t total = rows * frames;
-    if (rows == 1) row_stride = 0;
-    if (!fused_len_ok<float>(win_len)) {
-        // any other window length: composed over all rows at once (BlueStftSrc knows one signal only)
-        const size_t chunk = composed_chunk(ctx, win_len, total);
-        for (size_t t0 = 0; t0 < total; t0 += chunk) {
-            const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
-            const int rc = stft_rows_composed(ctx, d_signal, len, row_stride, frames, d_window, win_len, hop,
-                                              reinterpret_cast<cpx<float> *>(d_out) + t0 * win_len, t0, nt);
-            if (rc) return rc;
-        }
-        return KOFFT_OK;
-    }
+    FramedSrc s;
+    (void)framed_src(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, &s);  // (the caller's window: nothing to fail)
+    if (!s.kernels)  // any other window length: composed over all rows at once (BlueStftSrc knows one signal only)
+        return for_chunks(total, composed_chunk(ctx, win_len, total), [&](size_t t0, size_t nt) {
+            return framed_produce(ctx, s, FRAMES_FULL, t0, nt, reinterpret_cast<cpx<float> *>(d_out) + t0 * win_len, nullptr);
+        });
     StftRowsIO io{};
-    fill_rows_io(io, d_signal, rows, len, row_stride, d_window, win_len, hop, frames);
+    fill_rows_io(io, s);
     io.out = reinterpret_cast<cpx<float> *>(d_out);
     return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
 }
@@ -166,44 +224,40 @@ int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, s
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     KOFFT_HIP_TRY(ctx, hipMemsetAsync(d_max, 0, rows * sizeof(float), ctx->stream));  // every max_mag starts at 0.0
     if (frames == 0) return KOFFT_OK;
-    const float *d_win = nullptr;
-    int rc = hann_table(ctx, win_len, &d_win);
+    FramedSrc s;
+    int rc = framed_src(ctx, d_samples, rows, len, row_stride, nullptr, win_len, hop, frames, &s);
     if (rc) return rc;
     const size_t total = rows * frames;
-    if (rows == 1) row_stride = 0;
     unsigned *max_bits = reinterpret_cast<unsigned *>(d_max);
-    if (!fused_len_ok<float>(win_len)) {
+    if (!s.kernels) {
         const size_t chunk = composed_chunk(ctx, win_len, total);
         rc = ensure(ctx, ctx->real_tmp, chunk * win_len * 8);
         if (rc) return rc;
         cpx<float> *spec = static_cast<cpx<float> *>(ctx->real_tmp.p);
         const size_t half = win_len / 2;
-        for (size_t t0 = 0; t0 < total; t0 += chunk) {
-            const size_t nt = (total - t0 < chunk) ? total - t0 : chunk;
-            rc = stft_rows_composed(ctx, d_samples, len, row_stride, frames, d_win, win_len, hop, spec, t0, nt);
-            if (rc) return rc;
-            if (nt * half) {
-                const size_t blocks = (nt * half + 255) / 256;
-                if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-                hipLaunchKernelGGL(mag_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, d_mags + t0 * half, max_bits,
-                                   frames, win_len, t0, nt * half);
-                KOFFT_HIP_TRY(ctx, hipGetLastError());
-            }
-        }
-        return KOFFT_OK;
+        return for_chunks(total, chunk, [&](size_t t0, size_t nt) {
+            const int prc = framed_produce(ctx, s, FRAMES_FULL, t0, nt, spec, nullptr);
+            if (prc || nt * half == 0) return prc;
+            const size_t blocks = (nt * half + 255) / 256;  // its own tail: the magnitudes and the row maximum in one kernel
+            if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL(mag_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, d_mags + t0 * half, max_bits, frames,
+                               win_len, t0, nt * half);
+            KOFFT_HIP_TRY(ctx, hipGetLastError());
+            return KOFFT_OK;
+        });
     }
     // Rows long enough to reach dispatch()'s persistent kernels on their own run the single-signal kernel row by row: there the
     // maximum costs one atomicMax per wavefront and KERNEL, here one per wavefront and TRANSFORM, and with few rows those pile up on a few
     // addresses (measured, n = 1024: 8 rows x 14 063 frames 1.30 ms against the loop's 0.42; 256 x 1875 1.53 against 7.37 -- DESIGN.md 5.18).
     if (rows <= kMagRowsLoopMaxRows && frames >= mag_rows_loop_frames(ctx, win_len, hop)) {
         for (size_t r = 0; r < rows; ++r) {
-            rc = stft_mag_dev(ctx, d_samples + r * row_stride, len, win_len, hop, d_mags + r * frames * (win_len / 2), frames, d_max + r);
+            rc = stft_mag_dev(ctx, d_samples + r * s.row_stride, len, win_len, hop, d_mags + r * frames * (win_len / 2), frames, d_max + r);
             if (rc) return rc;
         }
         return KOFFT_OK;
     }
     StftMagRowsIO io{};
-    fill_rows_io(io, d_samples, rows, len, row_stride, d_win, win_len, hop, frames);
+    fill_rows_io(io, s);
     io.mags = d_mags;
     io.max_bits = max_bits;
     return dispatch<float, EPI_STORE>(ctx, io, win_len, total);

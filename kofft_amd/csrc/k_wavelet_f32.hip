@@ -25,12 +25,6 @@ int dispatch(int w, Fn fn)
     }
 }
 
-bool overlaps(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
-    return abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-
 // any two of the ranges (pointer, bytes) overlap
 bool any_overlap(std::initializer_list<std::pair<const void *, size_t>> r)
 {

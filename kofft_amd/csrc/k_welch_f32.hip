@@ -5,8 +5,6 @@
 namespace kofft {
 namespace host {
 
-static bool ranges_overlap(const float *a, size_t na, const float *b, size_t nb) { return na && nb && a < b + nb && b < a + na; }
-
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched: the STFT rows' without the frame count,
 // then the flags, the pointers, the overlaps.
 int welch_check(bool csd, const void *x, const void *y, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
@@ -16,12 +14,10 @@ int welch_check(bool csd, const void *x, const void *y, const void *window, cons
     if (crc || rows == 0 || frames == 0) return crc;
     if (flags & ~KOFFT_HIP_PSD_DOUBLE) return KOFFT_ERR_INVALID_VALUE;
     if (!ctx || !out || (len && (!x || (csd && !y)))) return KOFFT_ERR_NULL;
-    const float *o = static_cast<const float *>(out);
-    const size_t no = rows * (win_len / 2 + 1) * (csd ? 2 : 1);
-    const size_t span = len ? (rows - 1) * (rows > 1 ? row_stride : 0) + len : 0;
-    if (ranges_overlap(o, no, static_cast<const float *>(x), span)) return KOFFT_ERR_INVALID_VALUE;
-    if (csd && ranges_overlap(o, no, static_cast<const float *>(y), span)) return KOFFT_ERR_INVALID_VALUE;
-    if (window && ranges_overlap(o, no, static_cast<const float *>(window), win_len)) return KOFFT_ERR_INVALID_VALUE;
+    const size_t out_bytes = rows * (win_len / 2 + 1) * (csd ? 2 : 1) * sizeof(float), in_bytes = rows_span(rows, len, row_stride) * sizeof(float);
+    if (overlaps(out, out_bytes, x, in_bytes)) return KOFFT_ERR_INVALID_VALUE;
+    if (csd && overlaps(out, out_bytes, y, in_bytes)) return KOFFT_ERR_INVALID_VALUE;
+    if (overlaps(out, out_bytes, window, win_len * sizeof(float))) return KOFFT_ERR_INVALID_VALUE;
     return KOFFT_OK;
 }
 
@@ -45,10 +41,10 @@ static bool welch_use_fused(const kofft_hip_ctx *ctx, size_t win_len)
 }
 
 struct WelchCall {
-    const float *x, *y;  // y: the cross spectrum only
+    FramedSrc src;   // of x; src.frames: the frames that can hold a sample, at least 1
+    const float *y;  // the cross spectrum only
     bool csd;
-    const float *win;
-    size_t rows, len, row_stride, win_len, hop, frames /* the frames that can hold a sample, at least 1 */, ngroups;
+    size_t ngroups;
     float scale;
     int twice;
     float *out;
@@ -56,12 +52,12 @@ struct WelchCall {
 
 static int launch_total(kofft_hip_ctx *ctx, const WelchCall &c, const float *part, size_t g_first, size_t g_count)
 {
-    const size_t K = c.win_len / 2 + 1, vals = K * (c.csd ? 2 : 1);
+    const size_t win_len = c.src.win_len, K = win_len / 2 + 1, vals = K * (c.csd ? 2 : 1);
     const size_t nrows = (g_first + g_count - 1) / c.ngroups - g_first / c.ngroups + 1;
     const size_t blocks = (nrows * vals + 255) / 256;
     if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(welch_total_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, part, c.out, vals, c.csd ? 2 : 1, c.ngroups, g_first,
-                       g_count, c.scale, c.twice, (c.win_len & 1) ? K : K - 1, nrows * vals);
+                       g_count, c.scale, c.twice, (win_len & 1) ? K : K - 1, nrows * vals);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
 }
@@ -75,15 +71,15 @@ static int launch_fused(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float>
     const size_t blocks = (g_count + XPB - 1) / XPB;
     if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
     StftIO io{};
-    io.signal = c.x;
-    io.window = c.win;
+    io.signal = c.src.signal;
+    io.window = c.src.win;
     io.out = nullptr;
-    io.len = c.len;
-    io.hop = c.hop;
+    io.len = c.src.len;
+    io.hop = c.src.hop;
     io.start0 = 0;
     io.n = 1 << L;
-    hipLaunchKernelGGL((welch_fused_kernel<L, RL, BLOCK, CSD>), dim3((unsigned)blocks), dim3(BLOCK), lds, ctx->stream, io, c.y, tw, c.row_stride,
-                       c.frames, c.ngroups, g_first, g_count, dst, c.scale, c.twice, final ? 1 : 0);
+    hipLaunchKernelGGL((welch_fused_kernel<L, RL, BLOCK, CSD>), dim3((unsigned)blocks), dim3(BLOCK), lds, ctx->stream, io, c.y, tw, c.src.row_stride,
+                       c.src.frames, c.ngroups, g_first, g_count, dst, c.scale, c.twice, final ? 1 : 0);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
 }
@@ -91,7 +87,7 @@ static int launch_fused(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float>
 template <bool CSD>
 static int launch_fused_l(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float> *tw, size_t g_first, size_t g_count, float *dst, bool final)
 {
-    switch (ilog2(c.win_len)) {
+    switch (ilog2(c.src.win_len)) {
     case 6: return launch_fused<6, CSD>(ctx, c, tw, g_first, g_count, dst, final);
     case 7: return launch_fused<7, CSD>(ctx, c, tw, g_first, g_count, dst, final);
     case 8: return launch_fused<8, CSD>(ctx, c, tw, g_first, g_count, dst, final);
@@ -108,57 +104,39 @@ static int launch_fused_l(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<floa
 static int welch_fused(kofft_hip_ctx *ctx, const WelchCall &c)
 {
     const cpx<float> *tw = nullptr;
-    int rc = twiddle_table<float>(ctx, c.win_len, &tw);
+    int rc = twiddle_table<float>(ctx, c.src.win_len, &tw);
     if (rc) return rc;
-    const size_t vals = (c.win_len / 2 + 1) * (c.csd ? 2 : 1), total = c.rows * c.ngroups;
-    if (c.ngroups == 1) {
-        const size_t step = size_t(1) << 30;
-        for (size_t g0 = 0; g0 < total && !rc; g0 += step)
-            rc = c.csd ? launch_fused_l<true>(ctx, c, tw, g0, total - g0 < step ? total - g0 : step, c.out, true)
-                     : launch_fused_l<false>(ctx, c, tw, g0, total - g0 < step ? total - g0 : step, c.out, true);
-        return rc;
-    }
+    const size_t vals = (c.src.win_len / 2 + 1) * (c.csd ? 2 : 1), total = c.src.rows * c.ngroups;
+    const auto launch = c.csd ? launch_fused_l<true> : launch_fused_l<false>;
+    if (c.ngroups == 1)
+        return for_chunks(total, size_t(1) << 30, [&](size_t g0, size_t ng) { return launch(ctx, c, tw, g0, ng, c.out, true); });
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, vals * sizeof(float), total);
     rc = ensure(ctx, ctx->rows_tmp, chunk * vals * sizeof(float));
     if (rc) return rc;
     float *part = static_cast<float *>(ctx->rows_tmp.p);
-    for (size_t g0 = 0; g0 < total; g0 += chunk) {
-        const size_t ng = total - g0 < chunk ? total - g0 : chunk;
-        rc = c.csd ? launch_fused_l<true>(ctx, c, tw, g0, ng, part, false) : launch_fused_l<false>(ctx, c, tw, g0, ng, part, false);
-        if (rc) return rc;
-        rc = launch_total(ctx, c, part, g0, ng);
-        if (rc) return rc;
-    }
-    return KOFFT_OK;
+    return for_chunks(total, chunk, [&](size_t g0, size_t ng) {
+        const int lrc = launch(ctx, c, tw, g0, ng, part, false);
+        return lrc ? lrc : launch_total(ctx, c, part, g0, ng);
+    });
 }
 
 // ---- the composed route ------------------------------------------------------------------------------------------------------------
-// the one-sided frames (window lengths the STFT kernels cover) or the full composed frames of flat indices [t0, t0 + nt) of one signal
-static int welch_frames(kofft_hip_ctx *ctx, const WelchCall &c, const float *sig, bool kernels, size_t t0, size_t nt, cpx<float> *spec)
-{
-    if (!kernels) return stft_rows_composed(ctx, sig, c.len, c.row_stride, c.frames, c.win, c.win_len, c.hop, spec, t0, nt);
-    const size_t K = c.win_len / 2 + 1;
-    PicPiece p[3];
-    const int np = picture_cut(t0, nt, c.frames, p);
-    for (int i = 0; i < np; ++i) {
-        const int rc = stft_onesided_piece(ctx, sig ? sig + p[i].row * c.row_stride : nullptr, p[i].nr, c.len, c.row_stride, c.win, c.win_len,
-                                           c.hop, p[i].f0, p[i].nf, reinterpret_cast<float *>(spec + p[i].at * K));
-        if (rc) return rc;
-    }
-    return KOFFT_OK;
-}
-
 // Chunks of whole groups (welch_cut.h) through the scratch: [frames of x | frames of y | partials], at most scratch_chunk_bytes (one
-// group where a group alone is larger).
+// group where a group alone is larger).  The frames are framed_produce's: the one-sided frames where the STFT kernels cover the window
+// length, otherwise the full composed frames, read in place.
 static int welch_composed(kofft_hip_ctx *ctx, const WelchCall &c)
 {
-    const bool kernels = fused_len_ok<float>(c.win_len), csd = c.csd;
-    const size_t K = c.win_len / 2 + 1, vals = K * (csd ? 2 : 1), fstride = kernels ? K : c.win_len, total = c.rows * c.frames;
+    const FramedSrc &sx = c.src;
+    FramedSrc sy = c.src;
+    sy.signal = c.y;
+    const bool kernels = sx.kernels, csd = c.csd;
+    const FramedForm form = kernels ? FRAMES_HALF : FRAMES_FULL;
+    const size_t K = sx.win_len / 2 + 1, vals = K * (csd ? 2 : 1), fstride = kernels ? K : sx.win_len, total = sx.rows * sx.frames;
     const size_t per_frame = fstride * sizeof(cpx<float>) * (csd ? 2 : 1) + (vals * sizeof(float) + kWelchGroup - 1) / kWelchGroup;
     size_t cap = scratch_chunk_rows(ctx->scratch_chunk_bytes, per_frame, total);
     if (cap < kWelchGroup) cap = kWelchGroup < total ? kWelchGroup : total;
-    size_t max_groups = cap / kWelchGroup + cap / c.frames + 2;  // whole groups, one short group per row end, the two ends
-    if (max_groups > c.rows * c.ngroups) max_groups = c.rows * c.ngroups;
+    size_t max_groups = cap / kWelchGroup + cap / sx.frames + 2;  // whole groups, one short group per row end, the two ends
+    if (max_groups > sx.rows * c.ngroups) max_groups = sx.rows * c.ngroups;
     const size_t spec_bytes = (cap * fstride * sizeof(cpx<float>) + 15) & ~size_t(15);
     int rc = ensure(ctx, ctx->rows_tmp, spec_bytes * (csd ? 2 : 1) + max_groups * vals * sizeof(float));
     if (rc) return rc;
@@ -166,23 +144,23 @@ static int welch_composed(kofft_hip_ctx *ctx, const WelchCall &c)
     cpx<float> *spec_x = reinterpret_cast<cpx<float> *>(base), *spec_y = csd ? reinterpret_cast<cpx<float> *>(base + spec_bytes) : nullptr;
     float *part = reinterpret_cast<float *>(base + spec_bytes * (csd ? 2 : 1));
     for (size_t t0 = 0; t0 < total;) {
-        const size_t end = welch_chunk_end(t0, cap, c.frames, total), nt = end - t0;
-        const size_t g0 = welch_group_at(t0, c.frames), ng = (end == total ? c.rows * c.ngroups : welch_group_at(end, c.frames)) - g0;
+        const size_t end = welch_chunk_end(t0, cap, sx.frames, total), nt = end - t0;
+        const size_t g0 = welch_group_at(t0, sx.frames), ng = (end == total ? sx.rows * c.ngroups : welch_group_at(end, sx.frames)) - g0;
         if (ng > max_groups) return KOFFT_ERR_UNSUPPORTED;  // (never: the bound above)
-        rc = welch_frames(ctx, c, c.x, kernels, t0, nt, spec_x);
+        rc = framed_produce(ctx, sx, form, t0, nt, spec_x, nullptr);
         if (rc) return rc;
         if (csd) {
-            rc = welch_frames(ctx, c, c.y, kernels, t0, nt, spec_y);
+            rc = framed_produce(ctx, sy, form, t0, nt, spec_y, nullptr);
             if (rc) return rc;
         }
         const size_t blocks = (ng * K + 255) / 256;
         if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
         if (csd)
             hipLaunchKernelGGL(welch_partial_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec_x, spec_y, part, fstride, K,
-                               c.frames, c.ngroups, t0, g0, ng * K);
+                               sx.frames, c.ngroups, t0, g0, ng * K);
         else
             hipLaunchKernelGGL(welch_partial_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec_x, spec_y, part, fstride, K,
-                               c.frames, c.ngroups, t0, g0, ng * K);
+                               sx.frames, c.ngroups, t0, g0, ng * K);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         rc = launch_total(ctx, c, part, g0, ng);
         if (rc) return rc;
@@ -198,23 +176,13 @@ int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, 
     if (crc || rows == 0 || frames == 0) return crc;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     WelchCall c{};
-    c.win = d_window;
-    if (!c.win) {  // window::hann(win_len), as the front end's
-        const int rc = hann_table(ctx, win_len, &c.win);
-        if (rc) return rc;
-    }
     // A frame that begins at or past the end of its row is all +0: its terms are +-0 and change no sum (a sum seeded with +0 is never -0).
     // Only the frames that can hold a sample are walked, at least one, so that a row without samples still stores +0 * scale.
     const size_t holding = len ? (len - 1) / hop + 1 : 1;
-    c.x = d_x;
+    const int rc = framed_src(ctx, d_x, rows, len, row_stride, d_window, win_len, hop, frames < holding ? frames : holding, &c.src);
+    if (rc) return rc;
     c.y = csd ? d_y : nullptr;
-    c.rows = rows;
-    c.len = len;
-    c.row_stride = rows > 1 ? row_stride : 0;
-    c.win_len = win_len;
-    c.hop = hop;
-    c.frames = frames < holding ? frames : holding;
-    c.ngroups = welch_groups(c.frames);
+    c.ngroups = welch_groups(c.src.frames);
     c.scale = scale;
     c.twice = (flags & KOFFT_HIP_PSD_DOUBLE) ? 1 : 0;
     c.out = d_out;

@@ -23,7 +23,6 @@
 //    batch (or per pixel), a first column f0 and the picture's own pitch in layout 1, and the 4-channel pixel R, G, B, 255.
 #pragma once
 
-#include "frontend_impl.hip.h"
 #include "spectrogram_impl.hip.h"
 
 namespace kofft {

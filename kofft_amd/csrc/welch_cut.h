@@ -1,13 +1,13 @@
 // welch_cut.h -- the chunks of the composed Welch / cross-spectrum route.  The frames of `rows` rows carry the flat index
 // t = row * frames + frame; every row is cut into groups of KOFFT_HIP_WELCH_GROUP consecutive frames counted from its frame 0 (the last
 // one shorter), and a group's partial sum must be formed in one piece.  A chunk [t0, end) of at most `cap` frames therefore begins and
-// ends at a group seam: welch_chunk_end cuts it, picture_cut (picture_cut.h) cuts the chunk into rectangles of the batch, and the
+// ends at a group seam: welch_chunk_end cuts it, frame_cut (frame_cut.h) cuts the chunk into rectangles of the batch, and the
 // rectangles are whole groups because the chunk is.  Arithmetic only, no HIP: tests/cpp/sanitize_welch_cut.cpp includes this file
 // alone and compares it with an enumeration of every frame.
 #pragma once
 #include <cstddef>
 
-#include "picture_cut.h"
+#include "frame_cut.h"
 
 #ifndef KOFFT_HIP_WELCH_GROUP
 #define KOFFT_HIP_WELCH_GROUP 32

@@ -1,7 +1,7 @@
 // sanitize_welch_cut.cpp -- kofft_amd/csrc/welch_cut.h against an enumeration of every frame, in a stand-alone program that
 // tests/test_welch_cpu.py builds with -fsanitize=address,undefined.  For hand-made shapes and a few hundred random (frames per row,
 // rows, cap): the chunks welch_chunk_end cuts cover every frame of the flat index exactly once in order, each holds at most
-// max(cap, 32) frames, each begins and ends at a group seam, its pieces (picture_cut) are at most three rectangles that name every
+// max(cap, 32) frames, each begins and ends at a group seam, its pieces (frame_cut) are at most three rectangles that name every
 // frame of the chunk once, every piece is made of whole groups, and welch_group_at counts the groups the chunk holds.
 #include <cstdio>
 #include <vector>
@@ -37,8 +37,8 @@ static void walk(size_t frames, size_t rows, size_t cap)
         const size_t g0 = welch_group_at(t0, frames), g1 = end == total ? rows * ngroups : welch_group_at(end, frames);
         if (g0 != groups || g1 <= g0) ++problems;
         groups = g1;
-        PicPiece p[3];
-        const int n = picture_cut(t0, nt, frames, p);
+        FramePiece p[3];
+        const int n = frame_cut(t0, nt, frames, p);
         if (n < 1 || n > 3) {
             ++problems;
             return;

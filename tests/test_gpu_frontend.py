@@ -387,3 +387,37 @@ def test_chunk_seams_inside_a_row(monkeypatch, seam_case, mode):
         assert_rows_equal(got.reshape(-1, 26), we.reshape(-1, 26), f"mode {mode}: win_len 400 across the seams", nan_safe=True)
     finally:
         f.close()
+
+
+# (win_len, hop, rows, frames per row, filters, the scratch bytes of a frame, the one chunk with all three kinds of rectangle)
+THREE_KINDS = [(64, 4, 7, 3000, 8, 32 * 4, (8192, 8192)),                  # the magnitudes kernels: [magnitudes]
+               (1000, 300, 7, 40, 20, 500 * 4 + 1000 * 8, (104, 104))]      # composed: [magnitudes | composed frames]
+
+
+@pytest.mark.parametrize("win_len,hop,rows,frames,filters,frame_bytes,chunk", THREE_KINDS, ids=["kernels-64", "composed-1000"])
+def test_a_chunk_with_the_tail_of_a_row_whole_rows_and_the_head_of_a_row(monkeypatch, fft32, oracle, win_len, hop, rows, frames, filters,
+                                                                        frame_bytes, chunk):
+    """KOFFT_HIP_SCRATCH_CHUNK_MB=1: 7 rows whose second chunk holds the tail of row 2, rows 3 and 4 and the head of row 5 -- the
+    producer's magnitudes per rectangle (808 + 2 x 3000 + 1384 frames of 64) and its composed magnitudes (16 + 2 x 40 + 8 frames of
+    1000).  Energies and coefficients against the oracle and against the same call on a default context, bit for bit."""
+    import kofft_amd
+    from test_gpu_scratch_seams import chunk_kinds, three_kind_chunks
+
+    assert three_kind_chunks(1, frame_bytes, rows, frames) == [chunk]
+    assert chunk_kinds(*chunk, frames) == ((808, 6000, 1384) if win_len == 64 else (16, 80, 8))
+    x = fo.signal(seeded(51000 + win_len), rows, frames * hop - hop // 2)
+    bins = _ref_bins(16000, win_len // 2, filters)
+    want_e, want_c = fo.expected(oracle, x, win_len, hop, frames, bins)
+    nc = min(13, filters)
+    monkeypatch.setenv(KNOB, "1")
+    f = kofft_amd.HipFftImpl(F)
+    try:
+        f.set_frontend_fused(0)
+        got_e, got_c = f.stft_mel_rows(x, win_len, hop, bins), f.stft_mfcc_rows(x, win_len, hop, bins, nc)
+        assert_rows_equal(got_e.reshape(-1, filters), want_e.reshape(-1, filters), f"win_len {win_len}: energies", nan_safe=True)
+        assert_rows_equal(got_c.reshape(-1, nc), np.ascontiguousarray(want_c[:, :, :nc]).reshape(-1, nc), f"win_len {win_len}: coefficients",
+                          nan_safe=True)
+        assert bits_equal(got_e, fft32.stft_mel_rows(x, win_len, hop, bins)), "energies differ from the default context's"
+        assert bits_equal(got_c, fft32.stft_mfcc_rows(x, win_len, hop, bins, nc)), "coefficients differ from the default context's"
+    finally:
+        f.close()

@@ -65,6 +65,7 @@ def _dev(f, x, h, up, down, t0, out_len, off=0):
     res = []
     for _ in range(2):
         out = torch.full((rows * out_len + off,), float("nan"), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # (torch's copies and fills run on its stream, the call on the context's own)
         f.resample_dev(dx.data_ptr() + 4 * off, rows, nx, dh.data_ptr() + 4 * off, h.size, up, down, t0, out.data_ptr() + 4 * off, out_len)
         f.synchronize()
         res.append(out[off:].cpu().numpy().reshape(rows, out_len))

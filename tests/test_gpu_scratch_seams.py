@@ -31,6 +31,29 @@ def pieces(cap_mb, row_bytes, count):
     return [min(chunk, count - b0) for b0 in range(0, count, chunk)]
 
 
+def chunk_kinds(t0, nt, frames):
+    """The frames of the three kinds of rectangle that frame_cut (kofft_amd/csrc/frame_cut.h) makes of the chunk [t0, t0 + nt) of the
+    flat index t = row * frames + frame: (the tail of a row the chunk does not begin, whole rows, the head of a row it does not end).
+    A chunk inside one row counts as a tail (it begins inside the row) or a head (it begins the row)."""
+    end, first = t0 + nt, -(-t0 // frames) * frames  # `first`: the first row start at or after t0
+    if first >= end:
+        return (nt, 0, 0) if t0 % frames else (0, 0, nt)
+    whole = (end - first) // frames * frames
+    return first - t0, whole, end - first - whole
+
+
+def three_kind_chunks(cap_mb, frame_bytes, rows, frames):
+    """The chunks (t0, nt) of scratch_chunk_rows(cap, frame_bytes, rows * frames) frames that hold all three kinds of rectangle, the
+    whole rows being at least one.  A seam test of a framed family asserts that its geometry has one: a later change of a scratch
+    layout then fails that precondition instead of quietly leaving the seam untested."""
+    out, t0 = [], 0
+    for nt in pieces(cap_mb, frame_bytes, rows * frames):
+        if all(chunk_kinds(t0, nt, frames)):
+            out.append((t0, nt))
+        t0 += nt
+    return out
+
+
 def make(monkeypatch, dtype=F32, mb=1, **env):
     """A context created with the scratch cap at `mb` MiB (and further switches, e.g. BLUESTEIN_FUSED="0")."""
     import kofft_amd
@@ -432,6 +455,9 @@ def test_composed_stft_rows_across_chunk_seams_inside_rows(oracle, monkeypatch):
 
     win_len, hop, rows, frames = 1000, 300, 7, 50
     assert pieces(1, win_len * 8, rows * frames) == [131, 131, 88] and 131 // frames == 2 and 262 // frames == 5
+    # the second piece holds all three kinds of rectangle: the tail of row 2, rows 3 and 4, the head of row 5 (framed_produce's cells
+    # "full frames, composed" and "kept bins, composed")
+    assert three_kind_chunks(1, win_len * 8, rows, frames) == [(131, 131)] and chunk_kinds(131, 131, frames) == (19, 100, 12)
     f = make(monkeypatch)
     try:
         rng = seeded(81000)

@@ -265,6 +265,39 @@ def test_module_functions(routes, oracle):
     assert np.max(np.abs(p1 - want64)) <= 4 * 9.893e-7 * np.max(want64)  # tests/test_welch_cpu.py's bound at 256
 
 
+@pytest.mark.parametrize("csd,rows,frames,want", [(False, 7, 1500, (3896, 3892, (604, 3000, 288))), (True, 8, 600, (1928, 1928, (472, 1200, 256)))],
+                         ids=["welch-7x1500", "csd-8x600"])
+def test_a_chunk_with_the_tail_of_a_row_whole_rows_and_the_head_of_a_row(monkeypatch, fft32, csd, rows, frames, want):
+    """KOFFT_HIP_SCRATCH_CHUNK_MB=1, win_len 64 on the composed route (set_welch_fused(0)): the one-sided frames come from the STFT
+    kernels per rectangle of the chunk, and the second chunk holds the tail of a row, two whole rows and the head of a row (its ends
+    are group seams).  Against the oracle and against the same call on a default context, bit for bit."""
+    import framed_cases as fc
+    import kofft_amd
+    from oracle import pyoracle
+    from test_gpu_scratch_seams import chunk_kinds
+
+    win_len, hop, total = 64, 4, rows * frames
+    cap = fc.welch_composed_cap(win_len, csd, 1 << 20, total)
+    t0 = fc.welch_chunk_end(0, cap, frames, total)
+    nt = fc.welch_chunk_end(t0, cap, frames, total) - t0
+    assert (t0, nt, chunk_kinds(t0, nt, frames)) == want and all(want[2])
+    length = (frames - 1) * hop + win_len - 3
+    assert fc.welch_frames_walked(length, hop, frames) == frames
+    rng = seeded(26500 + rows)
+    x = rng.standard_normal((rows, length)).astype(F)
+    y = rng.standard_normal((rows, length)).astype(F) if csd else None
+    ref = wo.welch_ref(x, pyoracle.hann(win_len), hop, frames, 0.3, True, y=y)
+    monkeypatch.setenv("KOFFT_HIP_SCRATCH_CHUNK_MB", "1")
+    f = kofft_amd.HipFftImpl(F)
+    try:
+        f.set_welch_fused(0)
+        got = _host(f, x, y, win_len, hop, frames, None, 0.3, True)
+        assert_rows_equal(got, ref, f"three kinds of rectangle in one chunk, csd={csd}")
+        assert bits_equal(got, _host(fft32, x, y, win_len, hop, frames, None, 0.3, True)), "differs from the default context's"
+    finally:
+        f.close()
+
+
 def test_chunk_seams_in_a_fresh_process():
     """KOFFT_HIP_SCRATCH_CHUNK_MB=1 in a child process (tests/welch_seams_child.py): 5 rows x 700 frames at win_len 256, so the composed
     route's chunks (about 999 frames) begin and end inside rows; and 3 rows x 800 groups, more partials than the fused route's scratch

@@ -2,7 +2,7 @@
 with their declared argument order, every argument check of the C ABI in the header's order through a null context (each case is
 reachable only if the earlier checks passed: a check that came later would give NULL, the last one), the Python module's errors before
 any device is touched, the oracle's running maximum against a literal restatement of compute_frame, and the chunk cutting
-(kofft_amd/csrc/picture_cut.h) in a stand-alone program under sanitizers."""
+(kofft_amd/csrc/frame_cut.h, with the chunk walk and the overlap test of host_layout.h) in a stand-alone program under sanitizers."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -148,11 +148,11 @@ def test_running_maximum_against_compute_frame_restated():
 
 
 def test_the_chunk_cutting_under_asan_ubsan(tmp_path):
-    """picture_cut.h against an enumeration of every frame of every chunk, in a stand-alone program under AddressSanitizer +
-    UndefinedBehaviorSanitizer."""
-    exe = tmp_path / "sanitize_picture_cut"
+    """frame_cut.h against an enumeration of every frame of every chunk that for_chunks hands out, and overlaps / rows_span against
+    enumerations of bytes, in a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer."""
+    exe = tmp_path / "sanitize_frame_cut"
     flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
-    subprocess.run(["g++", "-std=c++17", *flags, str(ROOT / "tests" / "cpp" / "sanitize_picture_cut.cpp"), "-o", str(exe)], check=True,
+    subprocess.run(["g++", "-std=c++17", *flags, str(ROOT / "tests" / "cpp" / "sanitize_frame_cut.cpp"), "-o", str(exe)], check=True,
                    capture_output=True, text=True)
     res = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
                          env={"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
