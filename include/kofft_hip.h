@@ -319,6 +319,48 @@ int kofft_hip_set_resample_tiled(kofft_hip_ctx *ctx, int on);
 int kofft_hip_resample_route(size_t nh, size_t up, size_t down, int *route);
 int kofft_hip_resample_taps_f32(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh);
 
+/* ---- IIR filtering of rows by a cascade of biquads (sosfilt) -----------------------------------
+ * scipy.signal.sosfilt on `rows` dense rows of nx f32 samples: `sections` >= 1 second-order sections sos[sections][6] =
+ * b0 b1 b2 a0 a1 a2 (scipy's layout), one cascade for all rows.  f32 only.  zi[rows][sections][2]: the initial state of every row
+ * and section, null for all +0; zf[rows][sections][2]: the final state, null for not stored.  The state is row-major so that batches
+ * can be cut by rows (scipy's is [sections][rows][2]; the Python wrapper transposes).  flags: bit 0 KOFFT_HIP_SOSFILT_REVERSE, the
+ * row is walked from its last sample to its first (the filter of the flipped row, flipped back; zi / zf are then the state before
+ * sample nx - 1 / after sample 0).
+ * Definition, met bit for bit by every route, grid and device.  Per row and per section s in ascending s, the section's input v is
+ * the previous section's output (x for s = 0); with the section's state (z0, z1), for t = 0 .. nx - 1 (nx - 1 .. 0 with the flag):
+ *   y  = (b0 * v[t]) + z0
+ *   z0 = ((b1 * v[t]) - (a1 * y)) + z1
+ *   z1 = (b2 * v[t]) - (a2 * y)
+ *   out[t] = y
+ * Every product and every sum is one rounded f32 operation in exactly this association (never fused; f32 subnormals are kept); NaN
+ * and Inf propagate as the recurrence says.  The nesting of the loops over sections and samples is not part of the contract: either
+ * order gives the same bits.  a0 is not divided by: it must be 1.0f, as scipy demands.  A rounded recurrence cannot be cut along
+ * time without changing bits: a row is walked sequentially and the parallelism is across rows.
+ * Checks, in this order and before the context or a device is touched: rows == 0 or nx == 0 -> KOFFT_OK, nothing touched (zf is not
+ * written either); sections == 0 -> EMPTY_INPUT; an unknown flag bit -> INVALID_VALUE; a byte count beyond 64 bits ->
+ * KOFFT_ERR_UNSUPPORTED; x, sos, out or the context null -> KOFFT_ERR_NULL; out overlapping x other than out == x exactly, or zf
+ * overlapping zi other than zf == zi exactly -> INVALID_VALUE; an output (out, zf) overlapping sos, the other output, or the input
+ * that is not its own (zf over x, out over zi) -> INVALID_VALUE; host form only, where sos can be read: some a0 != 1.0f ->
+ * INVALID_VALUE (the device form requires it and does not read device memory to check).  Filtering in place (out == x, zf == zi) is
+ * allowed.
+ * Routes, the same bytes.  The plain kernel: one thread per row walks its row in global memory.  The tiled kernel: a wavefront owns 64
+ * rows and walks them in tiles of KOFFT_HIP_SOSFILT_TILE samples staged through LDS with coalesced loads and stores.  Either holds
+ * at most KOFFT_HIP_SOSFILT_GROUP sections per pass; a longer cascade runs further passes in place over out.
+ * kofft_hip_set_sosfilt_tiled(ctx, on): 1, the default, the measured choice; 0 every call of the context on the plain
+ * kernel; 2 the tiled kernel wherever it exists (A/B measurements and tests); anything else -> INVALID_VALUE.
+ * kofft_hip_sosfilt_route, no context: *route = 1 where a default context runs the tiled kernel, 0 where the plain one; the measured
+ * rule depends on `rows` alone (the tiled kernel from 16 rows on).  route null -> KOFFT_ERR_NULL.
+ * kofft_hip_dev_sosfilt_f32 takes device pointers and is asynchronous on the context's stream. */
+#define KOFFT_HIP_SOSFILT_REVERSE 1u
+#define KOFFT_HIP_SOSFILT_TILE 32
+#define KOFFT_HIP_SOSFILT_GROUP 8
+int kofft_hip_sosfilt_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *sos, size_t sections, const float *zi,
+                          float *zf, unsigned flags, float *out);
+int kofft_hip_dev_sosfilt_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections,
+                              const float *d_zi, float *d_zf, unsigned flags, float *d_out);
+int kofft_hip_set_sosfilt_tiled(kofft_hip_ctx *ctx, int on);
+int kofft_hip_sosfilt_route(size_t rows, int *route);
+
 /* ---- Welch power spectra and cross spectra of rows ------------------------------------------
  * The sum over frames of |X[k]|^2 (welch) or conj(X[k]) Y[k] (csd) of `rows` signals of `len` f32 samples, row r at signal + r *
  * row_stride, `frames` frames per row; no frame ever reaches the caller.  psd is rows * K floats, pxy rows * K interleaved complex,

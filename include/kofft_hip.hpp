@@ -407,6 +407,30 @@ public:
         if (rc) taps.clear();
         return taps;
     }
+    // IIR filtering of `rows` contiguous rows of x.size() / rows samples by the cascade of sos.size() / 6 biquads (kofft_hip_sosfilt_f32:
+    // b0 b1 b2 a0 a1 a2 per section, a0 == 1): out is resized to x.size() values, in the arithmetic the C header fixes.  zi: the initial
+    // state [rows][sections][2], or null for zeros; zf: resized to rows * sections * 2 final-state values, or null for none; zf == zi
+    // updates the state in place, and &out == &x filters in place.  reverse: every row is walked from its last sample.  MismatchedLengths
+    // for rows that do not divide x, a sos that is no multiple of 6 values or a zi of another size; then the C entry's checks in its order.
+    Result sosfilt_rows(const std::vector<float> &x, const std::vector<float> &sos, std::vector<float> &out, size_t rows = 1,
+                        const std::vector<float> *zi = nullptr, std::vector<float> *zf = nullptr, bool reverse = false) const
+    {
+        static_assert(std::is_same<T, float>::value, "sosfilt_rows is f32-only");
+        if (rows == 0 || x.size() % rows != 0 || sos.size() % 6 != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows, sections = sos.size() / 6;
+        size_t state = 0;
+        if (__builtin_mul_overflow(rows, sections, &state) || __builtin_mul_overflow(state, (size_t)2, &state)) return st(KOFFT_ERR_UNSUPPORTED);
+        if (zi && zi->size() != state) return Result::Err(FftError::MismatchedLengths);
+        if (&out != &x) out.assign(x.size(), 0.0f);
+        if (zf && zf != zi) zf->assign(state, 0.0f);
+        float dummy = 0.0f;
+        return st(kofft_hip_sosfilt_f32(ctx_, x.empty() ? &dummy : x.data(), rows, nx, sos.empty() ? &dummy : sos.data(), sections,
+                                        zi && !zi->empty() ? zi->data() : nullptr, zf && !zf->empty() ? zf->data() : nullptr,
+                                        reverse ? KOFFT_HIP_SOSFILT_REVERSE : 0u, out.empty() ? &dummy : out.data()));
+    }
+    // 1: the measured choice (the default), 0: every sosfilt call of this context on the plain kernel, 2: the tiled kernel wherever it
+    // exists (the same bytes; A/B, tests)
+    Result set_sosfilt_tiled(int mode) const { return st(kofft_hip_set_sosfilt_tiled(ctx_, mode)); }
     // Welch power spectra of `rows` contiguous rows of x.size() / rows samples (kofft_hip_welch_f32): psd is resized to rows *
     // (win_len / 2 + 1) floats, (total * scale) (* 2 on the interior bins with `twice`) in the summation order the C header fixes
     // (groups of KOFFT_HIP_WELCH_GROUP frames).  window: win_len values, or empty for window::hann(win_len).  MismatchedLengths for rows

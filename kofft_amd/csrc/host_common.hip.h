@@ -74,6 +74,7 @@ struct kofft_hip_ctx {
     int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
     int welch_fused = 1;      // kofft_hip_set_welch_fused: 1 the measured choice (welch_use_fused), 0 every Welch / cross-spectrum call through the composed route (one-sided frames into the scratch, then the sums), 2 the fused kernel wherever it exists (A/B, tests)
     int resample_tiled = 1;   // kofft_hip_set_resample_tiled: 1 the measured choice (resample_route), 0 polyphase resampling of every shape on the plain kernel (one thread per output, global loads), 2 the tiled kernel wherever its tables fit the LDS budget (the same bytes; A/B, tests)
+    int sosfilt_tiled = 1;    // kofft_hip_set_sosfilt_tiled: 1 the measured choice (sosfilt_use_tiled), 0 IIR filtering of every shape on the plain kernel (one thread per row, global loads), 2 the tiled kernel wherever it exists (the same bytes; A/B, tests)
     bool spec_transpose = true; // kofft_hip_set_spectrogram_transpose(ctx, 0): the image layout of the spectrogram render with every lane storing its own bytes instead of the exchange through LDS (the same bytes; A/B, tests)
     bool direct_tiled = true; // kofft_hip_set_direct_tiled(ctx, 0): direct DCT / DST sums of every shape on the simple kernel (one lane per output; A/B, tests)
     bool dht_table_device = true; // kofft_hip_set_dht_table_device(ctx, 0): the Hartley table of a new length built on the host and uploaded instead of by dht_table_kernel (the same bytes; A/B, tests)
@@ -786,6 +787,12 @@ int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, si
 int resample_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t nh, size_t up, size_t down, size_t t0,
                  float *d_out, size_t out_len);
 int resample_taps(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh);
+// k_sosfilt_f32.hip: IIR filtering of rows by a cascade of biquads (sosfilt_impl.hip.h, sosfilt_plan.h).  sosfilt_check:
+// the argument checks alone, in the order of include/kofft_hip.h; host_sos: sos is host memory and every a0 is compared with 1.0f
+int sosfilt_check(size_t rows, size_t nx, size_t sections, unsigned flags, const void *x, const void *sos, const void *zi, const void *zf,
+                  const void *out, const kofft_hip_ctx *ctx, bool host_sos);
+int sosfilt_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
+                float *d_zf, unsigned flags, float *d_out);
 // k_planar_f32/f64.hip: FftImpl::fft_split / ifft_split on planes of batch * n reals (planar_impl.hip.h); planar_check: the argument
 // checks alone, in the order of fft_dev and before the context or a device is touched
 inline int planar_check(size_t n, size_t batch, const void *p0, const void *p1, const void *p2, const void *p3, const kofft_hip_ctx *ctx)

@@ -1,0 +1,89 @@
+// k_sosfilt_f32.hip -- batched IIR filtering of float rows (sosfilt_impl.hip.h, sosfilt_plan.h): the two kernels'
+// instances, the argument checks and the device-pointer entry point.
+#include "sosfilt_impl.hip.h"
+
+namespace kofft {
+namespace host {
+
+#ifndef KOFFT_SOSFILT_MEASURE_TILE
+static_assert(kSosTile == KOFFT_HIP_SOSFILT_TILE, "include/kofft_hip.h names the tile");
+#endif
+static_assert(kSosGroup == KOFFT_HIP_SOSFILT_GROUP, "include/kofft_hip.h names the group");
+static_assert(kSosGroup == 8, "sosfilt_launch dispatches 1 .. 8 sections");
+
+// The argument checks alone, in the order of include/kofft_hip.h and before the context or a device is touched.  KOFFT_OK with
+// rows == 0 or nx == 0: nothing to do.  host_sos: sos is host memory, so a0 can be read.
+int sosfilt_check(size_t rows, size_t nx, size_t sections, unsigned flags, const void *x, const void *sos, const void *zi, const void *zf,
+                  const void *out, const kofft_hip_ctx *ctx, bool host_sos)
+{
+    if (rows == 0 || nx == 0) return KOFFT_OK;
+    if (sections == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (flags & ~(unsigned)KOFFT_HIP_SOSFILT_REVERSE) return KOFFT_ERR_INVALID_VALUE;
+    size_t x_bytes = 0, z_bytes = 0, sos_bytes = 0;
+    if (__builtin_mul_overflow(rows, nx, &x_bytes) || __builtin_mul_overflow(x_bytes, sizeof(float), &x_bytes) ||
+        __builtin_mul_overflow(rows, sections, &z_bytes) || __builtin_mul_overflow(z_bytes, 2 * sizeof(float), &z_bytes) ||
+        __builtin_mul_overflow(sections, 6 * sizeof(float), &sos_bytes))
+        return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !x || !sos || !out) return KOFFT_ERR_NULL;
+    if (out != x && overlaps(out, x_bytes, x, x_bytes)) return KOFFT_ERR_INVALID_VALUE;
+    if (zi && zf && zf != zi && overlaps(zf, z_bytes, zi, z_bytes)) return KOFFT_ERR_INVALID_VALUE;
+    if (overlaps(out, x_bytes, sos, sos_bytes) || (zf && overlaps(zf, z_bytes, sos, sos_bytes)) || (zf && overlaps(zf, z_bytes, out, x_bytes)) ||
+        (zf && overlaps(zf, z_bytes, x, x_bytes)) || (zi && overlaps(out, x_bytes, zi, z_bytes)))
+        return KOFFT_ERR_INVALID_VALUE;
+    if (host_sos)
+        for (size_t s = 0; s < sections; ++s)
+            if (!(static_cast<const float *>(sos)[6 * s + 3] == 1.0f)) return KOFFT_ERR_INVALID_VALUE;
+    return KOFFT_OK;
+}
+
+template <int NS>
+static void sosfilt_launch_ns(kofft_hip_ctx *ctx, bool tiled, const float *src, const float *d_sos, const float *d_zi, float *d_zf, float *d_out,
+                              const SosShape &s)
+{
+    if (tiled) {
+        const size_t want = sos_row_groups(s.rows), cap = (size_t)ctx->num_cus * 64;
+        hipLaunchKernelGGL((sosfilt_tiled_kernel<NS, kSosPrefetch>), dim3((unsigned)(want < cap ? want : cap)), dim3(64), 0, ctx->stream, src, d_sos,
+                           d_zi, d_zf, d_out, s);
+    } else {
+        const size_t want = (s.rows + kSosPlainThreads - 1) / kSosPlainThreads, cap = (size_t)ctx->num_cus * 64;
+        hipLaunchKernelGGL(sosfilt_plain_kernel<NS>, dim3((unsigned)(want < cap ? want : cap)), dim3(kSosPlainThreads), 0, ctx->stream, src, d_sos,
+                           d_zi, d_zf, d_out, s);
+    }
+}
+
+// mode 2: the tiled kernel wherever it exists, which is everywhere; mode 1: the measured rule (sos_route); mode 0: never
+static bool sosfilt_use_tiled(const kofft_hip_ctx *ctx, size_t rows) { return ctx->sosfilt_tiled == 2 || (ctx->sosfilt_tiled == 1 && sos_route(rows) == 1); }
+
+int sosfilt_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
+                float *d_zf, unsigned flags, float *d_out)
+{
+    const int crc = sosfilt_check(rows, nx, sections, flags, d_x, d_sos, d_zi, d_zf, d_out, ctx, false);
+    if (crc || rows == 0 || nx == 0) return crc;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool tiled = sosfilt_use_tiled(ctx, rows);
+    SosShape s{};
+    s.rows = rows;
+    s.nx = nx;
+    s.sections = sections;
+    s.reverse = (flags & KOFFT_HIP_SOSFILT_REVERSE) ? 1 : 0;
+    const size_t passes = sos_passes(sections, kSosGroup);
+    for (size_t p = 0; p < passes; ++p) {  // pass p filters what pass p - 1 left in `out`
+        s.first = p * kSosGroup;
+        const float *src = p == 0 ? d_x : d_out;
+        switch (sos_pass_sections(p, sections, kSosGroup)) {
+        case 1: sosfilt_launch_ns<1>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        case 2: sosfilt_launch_ns<2>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        case 3: sosfilt_launch_ns<3>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        case 4: sosfilt_launch_ns<4>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        case 5: sosfilt_launch_ns<5>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        case 6: sosfilt_launch_ns<6>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        case 7: sosfilt_launch_ns<7>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        default: sosfilt_launch_ns<8>(ctx, tiled, src, d_sos, d_zi, d_zf, d_out, s); break;
+        }
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+    }
+    return KOFFT_OK;
+}
+
+}  // namespace host
+}  // namespace kofft

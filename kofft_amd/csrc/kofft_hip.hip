@@ -3,6 +3,7 @@
 #include "host_common.hip.h"
 #include "host_layout.h"
 #include "resample_plan.h"
+#include "sosfilt_plan.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -1058,6 +1059,37 @@ int kofft_hip_resample_route(size_t nh, size_t up, size_t down, int *route)
 int kofft_hip_resample_taps_f32(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh)
 {
     return resample_taps(up, down, zeros, beta, taps, nh);
+}
+// ---- IIR filtering of rows by a cascade of biquads (k_sosfilt_f32.hip) -------------------------------------------
+// up to four row arrays: x up, out down, zi up, zf down (an absent state is an empty array and reaches the device as null); the
+// coefficients are the side input, uploaded once
+int kofft_hip_sosfilt_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *sos, size_t sections, const float *zi,
+                          float *zf, unsigned flags, float *out)
+{
+    const int rc = sosfilt_check(rows, nx, sections, flags, x, sos, zi, zf, out, ctx, true);
+    if (rc || rows == 0 || nx == 0) return rc;
+    const HostArray<float> a[4] = {{x, nullptr, nx}, {nullptr, out, nx}, {zi, nullptr, zi ? 2 * sections : 0}, {nullptr, zf, zf ? 2 * sections : 0}};
+    return rows_host_n<float>(ctx, rows, 4, a, sos, 6 * sections, true, true, [&](float *const *d, const float *d_sos, size_t nr) {
+        return sosfilt_dev(ctx, d[0], nr, nx, d_sos, sections, zi ? d[2] : nullptr, zf ? d[3] : nullptr, flags, d[1]);
+    });
+}
+int kofft_hip_dev_sosfilt_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections,
+                              const float *d_zi, float *d_zf, unsigned flags, float *d_out)
+{
+    return sosfilt_dev(ctx, d_x, rows, nx, d_sos, sections, d_zi, d_zf, flags, d_out);
+}
+int kofft_hip_sosfilt_route(size_t rows, int *route)
+{
+    if (!route) return KOFFT_ERR_NULL;
+    *route = sos_route(rows);
+    return KOFFT_OK;
+}
+int kofft_hip_set_sosfilt_tiled(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (on < 0 || on > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->sosfilt_tiled = on;
+    return KOFFT_OK;
 }
 int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on)
 {
