@@ -637,6 +637,26 @@ int kofft_hip_set_persist_claim_pct(kofft_hip_ctx *ctx, int pct);
  * first lines; the arrival word in the last), which every launch leaves at zero.  ctx or out null ->
  * KOFFT_ERR_NULL. */
 int kofft_hip_persist_claim_debug(kofft_hip_ctx *ctx, unsigned out[9]);
+/* Which way that kernel walks a batch.  Rows are independent, so every setting computes the same
+ * bytes; only the order in which rows are taken and the cache policy of some stores differ.
+ *   mode -1 (default): a call whose input range or output range is exactly the range the context's
+ *           previous call of this kernel wrote walks the batch from the other end than that call
+ *           did (the rows written last are read first); any other call walks ascending.  Other
+ *           calls through the context do not clear what is remembered: a stale record costs at
+ *           most one needless change of direction.  A captured graph replays the directions it
+ *           was captured with.
+ *   mode 0: always ascending, no kept zone: the kernel as it was before this knob existed.
+ *   mode 1 / 2: always ascending / descending, with the kept zone (A/B measurements and tests).
+ * The kept zone is the end of a walk, `bytes` long, stored with the default cache policy instead of
+ * the streaming one; 0 switches it off, and under mode -1 it is off for batches smaller than twice
+ * the zone (modes 1 and 2 clamp it to the batch).  mode outside -1 .. 2 -> INVALID_VALUE.
+ * Calls, not environment variables, like kofft_hip_set_persist_claim_pct. */
+int kofft_hip_set_persist_walk(kofft_hip_ctx *ctx, int mode);
+int kofft_hip_set_persist_keep_bytes(kofft_hip_ctx *ctx, size_t bytes);
+/* Tests only, host-side state, no synchronisation: out[0] = launches of that kernel through the
+ * context so far; of the last one: out[1] = 1 if it walked descending, out[2] = the first walk index
+ * of its kept zone (= its batch: none), out[3] = its batch.  ctx or out null -> KOFFT_ERR_NULL. */
+int kofft_hip_persist_walk_debug(kofft_hip_ctx *ctx, unsigned long long out[4]);
 /* The tables of the direct transforms, host only (tests): C = n * n floats, C[i * n + k] as
  * above; rows outside the kind's i range are +0.  type not 1 .. 4 -> INVALID_VALUE; n == 0 ->
  * KOFFT_OK; n > 4096 -> KOFFT_ERR_UNSUPPORTED; C null -> KOFFT_ERR_NULL. */

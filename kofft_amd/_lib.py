@@ -135,6 +135,9 @@ SIGNATURES = {
     "kofft_hip_set_direct_tiled": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_set_persist_claim_pct": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_persist_claim_debug": (C.c_int, [_ctx, C.c_void_p]),
+    "kofft_hip_set_persist_walk": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_set_persist_keep_bytes": (C.c_int, [_ctx, C.c_size_t]),
+    "kofft_hip_persist_walk_debug": (C.c_int, [_ctx, C.c_void_p]),
     "kofft_hip_dct_direct_table_f32": (C.c_int, [C.c_int, _sz, C.c_void_p]),
     "kofft_hip_dst_direct_table_f32": (C.c_int, [C.c_int, _sz, C.c_void_p]),
     "kofft_hip_dst_planner_table_f32": (C.c_int, [C.c_int, _sz, C.c_void_p]),

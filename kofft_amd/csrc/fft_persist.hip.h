@@ -187,9 +187,15 @@ struct persist_claim<CFG, decltype((void)CFG::kClaim)> { static constexpr bool v
 constexpr unsigned kPersistClaimShards = KOFFT_C12_CLAIM_SHARDS, kPersistClaimMaxShards = 8, kPersistClaimLine = 128 / sizeof(unsigned);
 static_assert(kPersistClaimShards >= 1 && kPersistClaimShards <= kPersistClaimMaxShards, "claim words");
 constexpr size_t kPersistClaimBytes = (kPersistClaimMaxShards + 1) * 128;
+// (round 9) Everything above speaks of WALK indices w in [0, batch): the stride walk, split, the shards and the tickets.  The memory row
+// of w is w, or batch - 1 - w when the launch is mirrored (persist_walk.h: a launch on the buffer its predecessor wrote walks the other
+// way); it is resolved where the row's descriptors are made and nowhere else (XPB == 1 and G == 1: a unit is one row).  Rows with
+// w >= keep_from are stored with the default cache policy instead of the streaming one (keep_from == batch: none).
 struct PersistClaim {
     unsigned *counters;  // shard s: counters[s * kPersistClaimLine]; arrivals: counters[kPersistClaimMaxShards * kPersistClaimLine]
     size_t split;        // (batch - split < 2^32: launch_persist_claim)
+    size_t keep_from;    // first walk index of the kept zone
+    unsigned mirror;     // 0 / 1
 };
 // "this shard is exhausted", in the LDS word a claimed row travels through (no row: rows are below 2^63)
 constexpr unsigned long long kPersistClaimEmpty = ~0ull;
@@ -202,6 +208,7 @@ struct PersistClaimIO : IO {
 // it, get() behind it (the claimed row travels from the claiming
 // lane to the workgroup through one LDS word)
 struct NoXchg {
+    static constexpr bool keep = false;
     __device__ __forceinline__ void put() const {}
     __device__ __forceinline__ void get() const {}
 };
@@ -505,6 +512,22 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
                 else if (LastG::out_index(0, u) == N / 2) io.store_d_nyquist(od, tau, LastG::out_index(0, u), cur[u], row_off);
             }
         } else {
+        if constexpr (persist_claim<CFG>::value) {
+            // (round 9) the cache policy is an instruction bit: a workgroup-uniform branch round two copies of the R stores.  The compiler
+            // lays the two arms out one behind the other, each skipped by a branch of its own, and no longer counts on either arm's stores
+            // having been issued: the next step's waits for its inputs are vmcnt(8) and vmcnt(23 .. 16) where the kernel without the
+            // branch had vmcnt(24) and vmcnt(39 .. 32) -- a step waits for its predecessor's stores.  MEASURED, not assumed harmless
+            // (DESIGN.md 5.2, round 9): with the zone off this kernel runs 1.6 .. 1.8 % FASTER than the one without the branch, in two
+            // interleaved runs; the form that keeps the old waits -- no branch, both copies issued, one through an empty descriptor, vmcnt(40) and
+            // vmcnt(55 .. 48) -- runs 2.3 % slower than the kernel without the branch and 4 % slower than this one.
+            if (xchg.keep) {
+#pragma unroll
+                for (int u = 0; u < R; ++u) io.template store_d<AUX_DEFAULT>(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
+            } else {
+#pragma unroll
+                for (int u = 0; u < R; ++u) io.template store_d<KOFFT_STORE_AUX>(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
+            }
+        } else {
 #ifdef KOFFT_PERSIST_ACTIVE_BRANCH /* measurement only (tools/build_variant.sh): rounds 1-4's branch around the stores, for same-box A/Bs */
         if (active)
 #endif
@@ -512,6 +535,7 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
         for (int u = 0; u < R; ++u) {
             if constexpr (io_has_acc<IO>::value) io.store_d_acc(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off, acc);
             else io.store_d(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
+        }
         }
         }
     }
@@ -634,6 +658,12 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     [[maybe_unused]] auto claim_len = [&](const unsigned s) -> unsigned {
         return s + 1 == kPersistClaimShards ? claim_total - (kPersistClaimShards - 1) * claim_piece : claim_piece;
     };
+    // (claim hand-out, round 9) the memory row of walk index w; w >= batch ("no row") maps to nothing that is used: such a row's descriptor is
+    // empty whatever its base
+    [[maybe_unused]] auto mem_row = [&](const size_t w) -> size_t {
+        if constexpr (CLAIMS) return io.claim.mirror ? batch - 1 - w : w;
+        else return w;
+    };
     // (lane 0, outside the pipeline) one row, waiting for every answer: the current shard, then -- each failing claim retires a shard for
     // good -- its successors; `batch` once all of them are exhausted
     [[maybe_unused]] auto claim_now = [&]() -> size_t {
@@ -707,7 +737,7 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     // transform -- the bounds check then returns zeros without touching memory; no branch, so the loads carry no
     // register shuffles behind them).
     auto issue = [&](Raw *dst, const size_t b) {
-        const rsrc_t d = io.in_desc_n(b + wslot, group_cnt(b));
+        const rsrc_t d = io.in_desc_n(mem_row(b) + wslot, group_cnt(b));
         if constexpr (RawSel::pair || RawSel::pair_lds) {
 #pragma unroll
             for (int u = 0; u < R; ++u) dst[u] = io.fetch_pair_d(d, in_lane_bytes, FirstG::in_index(0, u), in_row_off);
@@ -758,6 +788,7 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
             const unsigned *ticket;
             size_t *claimed;
             bool writer;  // the claiming lane, in a step that claims
+            bool keep;    // the row in CUR lies in the kept zone (workgroup-uniform, and said so)
             __device__ __forceinline__ void put() const
             {
                 if (writer) {
@@ -791,8 +822,9 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         issue(NXT, nbase);                                                                                           \
         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of CUR's first use */                          \
         KOFFT_PERSIST_STEP_STAMP                                                                                     \
-        const ClaimXchg xchg{claim_word, io.claim.split + (size_t)claim_shard * claim_piece, claim_len(claim_shard), &ticket, &claimed, claims}; \
-        persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, base + wslot, group_cnt(base), sub, tau, acc, NoPrefetchParts{}, xchg); \
+        const ClaimXchg xchg{claim_word, io.claim.split + (size_t)claim_shard * claim_piece, claim_len(claim_shard), &ticket, &claimed, claims, \
+                             __builtin_amdgcn_readfirstlane((unsigned)(base >= io.claim.keep_from)) != 0u}; \
+        persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, mem_row(base) + wslot, group_cnt(base), sub, tau, acc, NoPrefetchParts{}, xchg); \
         KOFFT_PERSIST_STAMP_ROW()                                                                                    \
         if (!more) LEAVE;                                                                                            \
         /* (workgroup-uniform, and said so: the upper half of the word every lane has read; no row has all its bits set) */ \

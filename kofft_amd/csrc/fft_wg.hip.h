@@ -130,6 +130,8 @@ struct ComplexIO : PlainTw {
     {
         return buf_load_cpx<T, KOFFT_C_LOAD_AUX>(d, row_off + lane_bytes, iu * (int)sizeof(cpx<T>));
     }
+    // (AUX: the store's cache policy, a template argument like the load helper's; the kClaim persistent kernel's kept zone alone passes another)
+    template <int AUX = KOFFT_STORE_AUX>
     __device__ __forceinline__ void store_d(rsrc_t d, int lane_bytes, int ou, cpx<T> v, int row_off = 0) const
     {
         if (INVERSE) {
@@ -137,7 +139,8 @@ struct ComplexIO : PlainTw {
             v.re = v.re * scale;
             v.im = im * scale;
         }
-        buf_store_cpx<T>(v, d, row_off + lane_bytes, ou * (int)sizeof(cpx<T>));
+        if constexpr (AUX == KOFFT_STORE_AUX) buf_store_cpx<T>(v, d, row_off + lane_bytes, ou * (int)sizeof(cpx<T>));
+        else buf_store_cpx_aux<T, AUX>(v, d, row_off + lane_bytes, ou * (int)sizeof(cpx<T>));
     }
     __device__ __forceinline__ Inv invariant(int) const { return {}; }
     __device__ __forceinline__ cpx<T> finish(size_t, int, Raw v, Inv) const

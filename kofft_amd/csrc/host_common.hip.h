@@ -26,6 +26,7 @@
 #include "fft_wg.hip.h"
 #include "host_cache.h"
 #include "host_layout.h"
+#include "persist_walk.h"
 #include "tables.h"
 
 // ---------------------------------------------------------------------------------
@@ -84,6 +85,12 @@ struct kofft_hip_ctx {
     int persist_grid_pct = 0; // KOFFT_HIP_PERSIST_GRID_PCT: scale the persistent grids (measurements only)
     int persist_claim_pct = -1; // kofft_hip_set_persist_claim_pct: percent of the batch the kClaim persistent kernels hand out by claim, 0 .. 100 (-1: the configuration's; A/B, tests)
     unsigned *persist_claim_counters = nullptr;  // device: nine 128-byte lines, the claim words in the first ones and the arrival word in the last (fft_persist.hip.h, PersistClaim); zeroed at creation, every kClaim launch leaves them at zero
+    int persist_walk_mode = kofft::host::kPersistWalkRule;  // kofft_hip_set_persist_walk: -1 a kClaim launch on the buffer its predecessor wrote walks the other way (persist_walk.h), 0 ascending and no kept zone (the kernel of round 8), 1 / 2 ascending / descending with the kept zone (A/B, tests)
+    size_t persist_keep_bytes = kofft::host::kPersistKeepDefaultBytes;  // kofft_hip_set_persist_keep_bytes: the end of a kClaim walk that is stored with the default cache policy
+    kofft::host::PersistWalkRecord persist_walk_last;  // what the last kClaim launch wrote and which way it walked (launch_persist_claim)
+    unsigned long long persist_walk_launches = 0;      // kofft_hip_persist_walk_debug: kClaim launches so far, and the last one's plan
+    kofft::host::PersistWalkPlan persist_walk_plan_last{false, 0};
+    size_t persist_walk_batch_last = 0;
     int big_three_min = 22;    // KOFFT_HIP_BIG_THREE_MIN: smallest log2 n split into three factors
     bool small32 = true;       // KOFFT_HIP_SMALL32=0: f32 n = 32 on the thread-group kernel instead of one thread per transform (A/B)
     bool big_first11 = true;   // KOFFT_HIP_BIG_FIRST11=0: 2^21 as 2^10 x 2^11 with the one-tile-per-workgroup kernel for the 2^11 factor (A/B)
@@ -563,7 +570,19 @@ int launch_persist_claim(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, siz
     const size_t pct = ctx->persist_claim_pct < 0 ? (size_t)Cfg::kClaimPct : (ctx->persist_claim_pct > 100 ? 100 : (size_t)ctx->persist_claim_pct);
     size_t claimed = batch / 100 * pct + batch % 100 * pct / 100;
     if (claimed > (size_t(1) << 31)) claimed = size_t(1) << 31;  // (row offsets from split travel as 32-bit tickets)
-    const KIO kio{io, PersistClaim{ctx->persist_claim_counters, (batch - claimed) / stride * stride}};
+    // (round 9) Direction and kept zone: persist_walk.h.  The context remembers the range this launch writes and the way it walks, for
+    // the next one.  Mirror and keep_from are plain kernel arguments too, but they depend on the CALL HISTORY: a captured graph replays
+    // the directions it was captured with, whatever ran on the buffer in between -- correct by construction (any direction computes the
+    // same rows), and a graph of an even number of calls on one buffer keeps alternating across its replays.
+    const size_t row_bytes = sizeof(cpx<T>) << L, bytes = batch * row_bytes;
+    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(io.in), out_lo = reinterpret_cast<uintptr_t>(io.out);
+    const kofft::host::PersistWalkPlan plan = kofft::host::persist_walk_plan(ctx->persist_walk_mode, ctx->persist_walk_last, in_lo, bytes, out_lo,
+                                                                             bytes, batch, row_bytes, ctx->persist_keep_bytes);
+    ctx->persist_walk_last = kofft::host::PersistWalkRecord{out_lo, bytes, plan.mirror};
+    ctx->persist_walk_plan_last = plan;
+    ctx->persist_walk_batch_last = batch;
+    ++ctx->persist_walk_launches;
+    const KIO kio{io, PersistClaim{ctx->persist_claim_counters, (batch - claimed) / stride * stride, plan.keep_from, plan.mirror ? 1u : 0u}};
     return launch_resident(ctx, attr_done, fft_persist_kernel<T, L, RL, EPI, KIO, Cfg>, blocks, Cfg::BLOCK, lds, kio, tw, batch);
 }
 

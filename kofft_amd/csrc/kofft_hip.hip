@@ -1192,6 +1192,28 @@ int kofft_hip_persist_claim_debug(kofft_hip_ctx *ctx, unsigned out[9])
         KOFFT_HIP_TRY(ctx, hipMemcpy(out + s, ctx->persist_claim_counters + s * kofft::kPersistClaimLine, sizeof(unsigned), hipMemcpyDeviceToHost));
     return KOFFT_OK;
 }
+int kofft_hip_set_persist_walk(kofft_hip_ctx *ctx, int mode)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (mode < -1 || mode > 2) return KOFFT_ERR_INVALID_VALUE;
+    ctx->persist_walk_mode = mode;
+    return KOFFT_OK;
+}
+int kofft_hip_set_persist_keep_bytes(kofft_hip_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->persist_keep_bytes = bytes;
+    return KOFFT_OK;
+}
+int kofft_hip_persist_walk_debug(kofft_hip_ctx *ctx, unsigned long long out[4])
+{
+    if (!ctx || !out) return KOFFT_ERR_NULL;
+    out[0] = ctx->persist_walk_launches;  // host-side state only: no synchronisation
+    out[1] = ctx->persist_walk_plan_last.mirror ? 1u : 0u;
+    out[2] = ctx->persist_walk_plan_last.keep_from;
+    out[3] = ctx->persist_walk_batch_last;
+    return KOFFT_OK;
+}
 int kofft_hip_set_wavelet_fused(kofft_hip_ctx *ctx, int on)
 {
     if (!ctx) return KOFFT_ERR_NULL;

@@ -7,7 +7,10 @@ given with --libs (name=path) over --rounds rounds, so box drift lands on every 
 with --parse (the cells file records how many library dispatches each cell made).
 
 usage (GPU box): python3 tools/exp_inplace_ab.py [--libs head=kofft_amd/lib/libkofft_hip.so ld0=kofft_amd/lib_ld0/libkofft_hip.so]
-                 (name=path@PCT: that build with PCT percent of the batch handed out by claim, kofft_hip_set_persist_claim_pct)
+                 (name=path@PCT: that build with PCT percent of the batch handed out by claim, kofft_hip_set_persist_claim_pct;
+                  name=path@wMODE and name=path@wMODE,kMIB: that build with kofft_hip_set_persist_walk(MODE) and a kept zone of MIB MiB,
+                  kofft_hip_set_persist_keep_bytes; the options combine, comma-separated: head=...so@87,w-1,k128)
+                 form inplace_rot: in place on src and dst in turn -- no call runs on the buffer the previous call touched
                  python3 tools/exp_inplace_ab.py --parse <kernel_trace.csv> [--counters <counter_collection.csv>] --cells <cells.json>"""
 import argparse
 import csv
@@ -22,7 +25,7 @@ N, BATCH = 4096, 65536
 
 
 class Lib:
-    def __init__(self, path, claim_pct=None):
+    def __init__(self, path, claim_pct=None, walk=None, keep_mib=None):
         self.lib = C.CDLL(str(path))
         self.lib.kofft_hip_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         self.lib.kofft_hip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -33,6 +36,13 @@ class Lib:
         if claim_pct is not None:  # name=path@PCT: the share of the batch handed out by claim (kofft_hip_set_persist_claim_pct)
             self.lib.kofft_hip_set_persist_claim_pct.argtypes = [C.c_void_p, C.c_int]
             assert self.lib.kofft_hip_set_persist_claim_pct(self.ctx, int(claim_pct)) == 0
+
+        if walk is not None:  # name=path@wMODE: which way the kClaim kernel walks the batch (kofft_hip_set_persist_walk)
+            self.lib.kofft_hip_set_persist_walk.argtypes = [C.c_void_p, C.c_int]
+            assert self.lib.kofft_hip_set_persist_walk(self.ctx, int(walk)) == 0
+        if keep_mib is not None:  # name=path@kMIB: the kept zone (kofft_hip_set_persist_keep_bytes)
+            self.lib.kofft_hip_set_persist_keep_bytes.argtypes = [C.c_void_p, C.c_size_t]
+            assert self.lib.kofft_hip_set_persist_keep_bytes(self.ctx, int(keep_mib) << 20) == 0
 
     def set_stream(self, s):
         assert self.lib.kofft_hip_set_stream(self.ctx, C.c_void_p(s)) == 0
@@ -104,8 +114,16 @@ def main():
     libs = []
     for spec in args.libs:
         name, path = spec.split("=", 1)
-        path, _, pct = path.partition("@")
-        lib = Lib(path, int(pct) if pct else None)
+        path, _, opts = path.partition("@")
+        pct = walk = keep = None
+        for o in filter(None, opts.split(",")):
+            if o[0] == "w":
+                walk = int(o[1:])
+            elif o[0] == "k":
+                keep = int(o[1:])
+            else:
+                pct = int(o)
+        lib = Lib(path, pct, walk, keep)
         lib.set_stream(stream.cuda_stream)
         libs.append((name, lib))
     cells, summary = [], defaultdict(list)
@@ -119,6 +137,12 @@ def main():
                     call = lambda: lib.oop(src.data_ptr(), dst.data_ptr())  # noqa: E731
                 elif form == "inplace_dst":
                     call = lambda: lib.inplace(dst.data_ptr())  # noqa: E731
+                elif form == "inplace_rot":
+                    turn = [0]
+
+                    def call():
+                        turn[0] ^= 1
+                        lib.inplace((src, dst)[turn[0]].data_ptr())
                 else:
                     call = lambda: lib.inplace(src.data_ptr())  # noqa: E731
                 for _ in range(args.warm):
