@@ -361,6 +361,46 @@ int kofft_hip_dev_sosfilt_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows,
 int kofft_hip_set_sosfilt_tiled(kofft_hip_ctx *ctx, int on);
 int kofft_hip_sosfilt_route(size_t rows, int *route);
 
+/* ---- the same cascade as a scan along time (sosfilt_scan) ---------------------------------------
+ * kofft_hip_sosfilt_f32 walks a row sequentially; few long rows leave the device idle.  kofft_hip_sosfilt_scan_f32 takes the same
+ * arguments plus `chunk`, cuts every row into chunks of `chunk` samples and filters all chunks of all rows in parallel.  It has its
+ * own bit-exact definition: the same recurrence inside a chunk, but the state at a seam is computed, not walked, so the bits differ
+ * from kofft_hip_sosfilt_f32's after the first chunk (by the rounding of an f32 recurrence: DESIGN 5.30 has the accuracy table).
+ * Definition, met bit for bit by every batch size, grid and entry point.  The cascade runs in groups of KOFFT_HIP_SOSFILT_GROUP
+ * sections; group g filters the output of group g - 1.  For one group of S sections: D = 2 S, component i = 2 s + k of a state vector
+ * is z_k of section s; C = ceil(nx / chunk); chunk c holds samples [c * chunk, min(nx, (c + 1) * chunk)); "the walk" is the
+ * recurrence of kofft_hip_sosfilt_f32, every product and sum one rounded f32 operation, never fused, subnormals kept.
+ *   1. M[i][j] is component i of the group's state after walking `chunk` samples of +0.0f from the state e_j (component j 1.0f, the
+ *      others +0.0f); the walk is followed literally, b * 0 terms included.
+ *   2. p_c, c = 0 .. C - 2, is the group's state after walking chunk c from the all +0 state.
+ *   3. Z_0 is the row's zi (all +0 without one).  For c = 0 .. C - 2 and every i, with J = 2 * (i / 2) + 2:
+ *        Z_{c+1}[i] = ((((M[i][0] * Z_c[0]) + (M[i][1] * Z_c[1])) + ...) + (M[i][J-1] * Z_c[J-1])) + p_c[i]
+ *      in ascending j, every product and sum one rounded f32 operation.  Only the columns of the sections <= i / 2 enter: the others
+ *      are exact zeros of M, and leaving them out keeps an Inf in a later section's state from making an earlier component NaN.
+ *   4. Chunk c of out is the walk of chunk c from Z_c; zf is the state at the end of the walk of chunk C - 1.
+ * With C == 1 the bytes are kofft_hip_sosfilt_f32's, and chunk 0 of any call equals its first `chunk` samples.  With
+ * KOFFT_HIP_SOSFILT_REVERSE the result is the forward definition applied to the time-reversed row: chunk c holds samples
+ * [max(0, nx - (c + 1) * chunk), nx - c * chunk), walked downwards; the short chunk is the last in walk order in both directions.
+ * `chunk` is part of the contract: another chunk gives other bits.  Cutting a row into two calls (zf -> zi) is correct to the same
+ * accuracy but not bit-identical to one call: the seam state of one call is M Z + p, not a walked state.
+ * Checks: those of kofft_hip_sosfilt_f32 in its order, with one added directly after the flag check -- chunk == 0 or not a multiple
+ * of KOFFT_HIP_SOSFILT_TILE -> INVALID_VALUE -- and the byte count of the state scratch added to the 64-bit overflow checks
+ * (KOFFT_ERR_UNSUPPORTED).  In place (out == x, zf == zi) is allowed: the walk that stores zf takes every chunk's initial state from the
+ * scratch, where an earlier launch has copied zi, so no launch reads zi while another part of it writes zf.  The host form checks a0 == 1.0f; the device form requires it.
+ * Three launches per group: a walk of all chunks from +0 that keeps only the final states (and M, from 2 S further walks of zeros),
+ * a sequential carry over the C - 1 seams of every row, a walk of all chunks from their true states that stores out.  The states,
+ * rows * C * D floats, live in the context's scratch; a batch whose states exceed KOFFT_HIP_SCRATCH_CHUNK_MB goes in pieces of
+ * whole rows.  Two reads and one write of every sample instead of one and one; faster than kofft_hip_sosfilt_f32 on few long rows,
+ * slower on many short ones (DESIGN 5.30 says where).
+ * kofft_hip_sosfilt_scan_chunk, no context: *chunk = the measured choice for the shape, never below 1024 (shorter chunks are legal
+ * but cost accuracy where poles lie within ~1e-3 of the unit circle).  chunk null -> KOFFT_ERR_NULL.
+ * kofft_hip_dev_sosfilt_scan_f32 takes device pointers and is asynchronous on the context's stream. */
+int kofft_hip_sosfilt_scan_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *sos, size_t sections, const float *zi,
+                               float *zf, size_t chunk, unsigned flags, float *out);
+int kofft_hip_dev_sosfilt_scan_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections,
+                                   const float *d_zi, float *d_zf, size_t chunk, unsigned flags, float *d_out);
+int kofft_hip_sosfilt_scan_chunk(size_t rows, size_t nx, size_t sections, size_t *chunk);
+
 /* ---- Welch power spectra and cross spectra of rows ------------------------------------------
  * The sum over frames of |X[k]|^2 (welch) or conj(X[k]) Y[k] (csd) of `rows` signals of `len` f32 samples, row r at signal + r *
  * row_stride, `frames` frames per row; no frame ever reaches the caller.  psd is rows * K floats, pxy rows * K interleaved complex,

@@ -428,6 +428,32 @@ public:
                                         zi && !zi->empty() ? zi->data() : nullptr, zf && !zf->empty() ? zf->data() : nullptr,
                                         reverse ? KOFFT_HIP_SOSFILT_REVERSE : 0u, out.empty() ? &dummy : out.data()));
     }
+    // sosfilt_rows as a scan along time (kofft_hip_sosfilt_scan_f32): every row is cut into chunks of `chunk` samples (a multiple of
+    // KOFFT_HIP_SOSFILT_TILE) that are filtered in parallel, in the scan's own bit-exact definition of the C header -- sosfilt_rows'
+    // bits in the first chunk, others after it.  The arguments, sizes and errors of sosfilt_rows; chunk == 0 or no multiple of the tile:
+    // InvalidValue.  scan_chunk: kofft_hip_sosfilt_scan_chunk's measured choice for a shape.
+    Result sosfilt_scan_rows(const std::vector<float> &x, const std::vector<float> &sos, std::vector<float> &out, size_t chunk, size_t rows = 1,
+                             const std::vector<float> *zi = nullptr, std::vector<float> *zf = nullptr, bool reverse = false) const
+    {
+        static_assert(std::is_same<T, float>::value, "sosfilt_scan_rows is f32-only");
+        if (rows == 0 || x.size() % rows != 0 || sos.size() % 6 != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows, sections = sos.size() / 6;
+        size_t state = 0;
+        if (__builtin_mul_overflow(rows, sections, &state) || __builtin_mul_overflow(state, (size_t)2, &state)) return st(KOFFT_ERR_UNSUPPORTED);
+        if (zi && zi->size() != state) return Result::Err(FftError::MismatchedLengths);
+        if (&out != &x) out.assign(x.size(), 0.0f);
+        if (zf && zf != zi) zf->assign(state, 0.0f);
+        float dummy = 0.0f;
+        return st(kofft_hip_sosfilt_scan_f32(ctx_, x.empty() ? &dummy : x.data(), rows, nx, sos.empty() ? &dummy : sos.data(), sections,
+                                             zi && !zi->empty() ? zi->data() : nullptr, zf && !zf->empty() ? zf->data() : nullptr, chunk,
+                                             reverse ? KOFFT_HIP_SOSFILT_REVERSE : 0u, out.empty() ? &dummy : out.data()));
+    }
+    static size_t sosfilt_scan_chunk(size_t rows, size_t nx, size_t sections)
+    {
+        size_t chunk = 0;
+        (void)kofft_hip_sosfilt_scan_chunk(rows, nx, sections, &chunk);
+        return chunk;
+    }
     // 1: the measured choice (the default), 0: every sosfilt call of this context on the plain kernel, 2: the tiled kernel wherever it
     // exists (the same bytes; A/B, tests)
     Result set_sosfilt_tiled(int mode) const { return st(kofft_hip_set_sosfilt_tiled(ctx_, mode)); }

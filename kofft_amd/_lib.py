@@ -95,6 +95,9 @@ SIGNATURES = {
     "kofft_hip_dev_sosfilt_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]),
     "kofft_hip_set_sosfilt_tiled": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_sosfilt_route": (C.c_int, [_sz, C.POINTER(C.c_int)]),
+    "kofft_hip_sosfilt_scan_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, _sz, C.c_uint, C.c_void_p]),
+    "kofft_hip_dev_sosfilt_scan_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, _sz, C.c_uint, C.c_void_p]),
+    "kofft_hip_sosfilt_scan_chunk": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
     "kofft_hip_welch_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
     "kofft_hip_dev_welch_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),
     "kofft_hip_csd_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_int, C.c_void_p]),

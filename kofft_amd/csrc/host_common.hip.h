@@ -809,9 +809,12 @@ int resample_taps(size_t up, size_t down, size_t zeros, double beta, float *taps
 // k_sosfilt_f32.hip: IIR filtering of rows by a cascade of biquads (sosfilt_impl.hip.h, sosfilt_plan.h).  sosfilt_check:
 // the argument checks alone, in the order of include/kofft_hip.h; host_sos: sos is host memory and every a0 is compared with 1.0f
 int sosfilt_check(size_t rows, size_t nx, size_t sections, unsigned flags, const void *x, const void *sos, const void *zi, const void *zf,
-                  const void *out, const kofft_hip_ctx *ctx, bool host_sos);
+                  const void *out, const kofft_hip_ctx *ctx, bool host_sos, const size_t *scan_chunk = nullptr);
 int sosfilt_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
                 float *d_zf, unsigned flags, float *d_out);
+// the scan along time: sosfilt_check with scan_chunk, rows * C chunks walked in parallel, the states in ctx->real_tmp
+int sosfilt_scan_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
+                     float *d_zf, size_t chunk, unsigned flags, float *d_out);
 // k_planar_f32/f64.hip: FftImpl::fft_split / ifft_split on planes of batch * n reals (planar_impl.hip.h); planar_check: the argument
 // checks alone, in the order of fft_dev and before the context or a device is touched
 inline int planar_check(size_t n, size_t batch, const void *p0, const void *p1, const void *p2, const void *p3, const kofft_hip_ctx *ctx)

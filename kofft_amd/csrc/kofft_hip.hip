@@ -1078,6 +1078,28 @@ int kofft_hip_dev_sosfilt_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows,
 {
     return sosfilt_dev(ctx, d_x, rows, nx, d_sos, sections, d_zi, d_zf, flags, d_out);
 }
+// ---- the same cascade as a scan along time (k_sosfilt_f32.hip): the same staging, rows are independent -------------
+int kofft_hip_sosfilt_scan_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *sos, size_t sections, const float *zi,
+                               float *zf, size_t chunk, unsigned flags, float *out)
+{
+    const int rc = sosfilt_check(rows, nx, sections, flags, x, sos, zi, zf, out, ctx, true, &chunk);
+    if (rc || rows == 0 || nx == 0) return rc;
+    const HostArray<float> a[4] = {{x, nullptr, nx}, {nullptr, out, nx}, {zi, nullptr, zi ? 2 * sections : 0}, {nullptr, zf, zf ? 2 * sections : 0}};
+    return rows_host_n<float>(ctx, rows, 4, a, sos, 6 * sections, true, true, [&](float *const *d, const float *d_sos, size_t nr) {
+        return sosfilt_scan_dev(ctx, d[0], nr, nx, d_sos, sections, zi ? d[2] : nullptr, zf ? d[3] : nullptr, chunk, flags, d[1]);
+    });
+}
+int kofft_hip_dev_sosfilt_scan_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections,
+                                   const float *d_zi, float *d_zf, size_t chunk, unsigned flags, float *d_out)
+{
+    return sosfilt_scan_dev(ctx, d_x, rows, nx, d_sos, sections, d_zi, d_zf, chunk, flags, d_out);
+}
+int kofft_hip_sosfilt_scan_chunk(size_t rows, size_t nx, size_t sections, size_t *chunk)
+{
+    if (!chunk) return KOFFT_ERR_NULL;
+    *chunk = (size_t)sos_scan_chunk_rule(rows, nx, sections);
+    return KOFFT_OK;
+}
 int kofft_hip_sosfilt_route(size_t rows, int *route)
 {
     if (!route) return KOFFT_ERR_NULL;

@@ -83,5 +83,73 @@ KOFFT_SOS_HD void sos_tile_elem(unsigned k, unsigned T, unsigned *r, unsigned *t
 // floats of one row of the tile in LDS: T + 1, odd for every even T, so that lane r reading [r][t] hits bank (r + t) mod 32
 constexpr unsigned sos_lds_stride(unsigned T) { return T | 1; }
 
+// ---- the scan along time (sosfilt_scan) ----
+// A row of nx samples is cut into C = sos_scan_chunks chunks of `chunk` samples (a multiple of the tile) counted in walk order: chunk c
+// holds walk steps [c * chunk, min(nx, (c + 1) * chunk)) of the row, so the short chunk is the last one walked in both directions.  A
+// "virtual row" v of a batch cut into `per_row` chunks a row is chunk v % per_row of row v / per_row; a wavefront owns kSosRows
+// consecutive virtual rows.  Walk step i of a chunk lies in tile i / T of that chunk: the tile grid starts at the chunk's first walked
+// sample, which with the reverse flag is its highest address.
+
+// chunks of a row of nx samples (nx >= 1, chunk >= 1)
+KOFFT_SOS_HD unsigned long long sos_scan_chunks(unsigned long long nx, unsigned long long chunk) { return (nx - 1) / chunk + 1; }
+
+// virtual row v -> (row, chunk) with per_row >= 1 chunks a row
+KOFFT_SOS_HD void sos_scan_vrow(unsigned long long v, unsigned long long per_row, unsigned long long *row, unsigned long long *c)
+{
+    *row = v / per_row;
+    *c = v - *row * per_row;
+}
+
+// samples of chunk c < sos_scan_chunks(nx, chunk): `chunk`, or what is left of the row in the last one.  Never 0.
+KOFFT_SOS_HD unsigned long long sos_scan_len(unsigned long long c, unsigned long long nx, unsigned long long chunk)
+{
+    const unsigned long long left = nx - c * chunk;
+    return left < chunk ? left : chunk;
+}
+
+// the element of the batch (row * nx + sample) that walk step i < sos_scan_len of chunk c of row `row` touches: ascending from sample
+// c * chunk, or with the reverse flag descending from sample nx - 1 - c * chunk
+KOFFT_SOS_HD unsigned long long sos_scan_at(unsigned long long row, unsigned long long c, unsigned long long i, unsigned long long nx,
+                                            unsigned long long chunk, bool reverse)
+{
+    const unsigned long long step = c * chunk + i;
+    return row * nx + (reverse ? nx - 1 - step : step);
+}
+
+// samples of tile k of a chunk of `len` samples: T, what is left in the chunk's last tile, 0 past it
+KOFFT_SOS_HD unsigned sos_scan_tile_len(unsigned long long len, unsigned long long k, unsigned T)
+{
+    if (k * T >= len) return 0;
+    const unsigned long long left = len - k * T;
+    return left < T ? (unsigned)left : T;
+}
+
+// Floats of the state scratch of one pass over `rows` rows of C chunks with a state of D = 2 * sections components: one slot of D floats
+// for each of the C - 1 seams of a row (slot row * (C - 1) + c: p_c after the first walk, Z_{c+1} after the carry), then D slots for
+// the transition matrix, slot j holding column j (M[0 .. D)[j]), then one slot a row for Z_0 (sos_scan_z0_slot): the carry kernel copies
+// zi there, so that the storing walk never reads zi, which zf may alias.
+KOFFT_SOS_HD unsigned long long sos_scan_state_floats(unsigned long long rows, unsigned long long C, unsigned D)
+{
+    return (rows * C + D) * D;
+}
+KOFFT_SOS_HD unsigned long long sos_scan_z0_slot(unsigned long long row, unsigned long long rows, unsigned long long C, unsigned D)
+{
+    return rows * (C - 1) + D + row;
+}
+
+// The measured rule behind kofft_hip_sosfilt_scan_chunk (profiles/sosfilt_scan_bench.txt).  Two costs pull apart: the
+// carry is sequential over the nx / chunk seams of a row, and the walks need rows * nx / chunk / 64 wavefronts to fill the device.  Rows
+// of 2^20 samples and fewer (64 x 2^20, 4096 x 48 000, 65 536 x 3000) measured fastest at 1024 at every section count; rows of 2^24 and
+// 28.8 M samples (16 and 1 of them) at 2048, except the single row through 8 and 12 sections, which measured faster at 4096 outside the
+// spread (16 x 2^24 through 8 sections: 4096 faster by 3 % in one run, a tie in another).  Between 2^20 and 2^24 samples a row nothing was measured: the line is drawn at 2^22.  Never below kSosScanMinChunk: shorter
+// chunks cost accuracy with poles close to the unit circle.
+constexpr unsigned long long kSosScanMinChunk = 1024;
+constexpr unsigned long long kSosScanLongRow = 1ull << 22;
+KOFFT_SOS_HD unsigned long long sos_scan_chunk_rule(unsigned long long rows, unsigned long long nx, unsigned long long sections)
+{
+    if (nx < kSosScanLongRow) return kSosScanMinChunk;
+    return rows == 1 && sections >= 8 ? 4 * kSosScanMinChunk : 2 * kSosScanMinChunk;
+}
+
 }  // namespace host
 }  // namespace kofft

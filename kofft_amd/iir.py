@@ -14,6 +14,13 @@ forward-backward filter **defined as this composition**: scipy's default ``padle
 product, one difference), a forward call with state float32(zi) * ext[0], a reverse call with state float32(zi) * y[last], the middle
 nx samples.  Padding and the state products are numpy on the host; the two filter passes are the device calls.
 
+``sosfilt_scan(sos, x, zi=None, chunk=None)`` is the same filter as a scan along time: every row is cut into chunks of
+``chunk`` samples that are filtered in parallel, which is what makes a few long rows fast.  It has its own bit-exact definition
+(include/kofft_hip.h): inside a chunk the recurrence above, at a seam the state M Z + p of the chunk's transition matrix, so its bits
+differ from ``sosfilt``'s after the first chunk and depend on ``chunk``; it is as close to float64 scipy as ``sosfilt`` is.  ``chunk=None``
+asks ``scan_chunk(rows, nx, sections)``, the measured choice (never below 1024).  Filtering a signal in two calls (zf -> zi) is correct but
+not bit-identical to one call.  ``sosfiltfilt(..., chunk=...)`` runs its two passes through the scan.
+
 ``fft=`` names the f32 HipFftImpl to run on; without one, a context on device 0 is created at the first call and kept.  Shape and
 value errors are raised before any context is created."""
 from __future__ import annotations
@@ -27,7 +34,7 @@ import ctypes as C
 from . import _lib, api
 from .api import FftError, HipFftImpl
 
-__all__ = ["sosfilt", "sosfilt_zi", "sosfiltfilt", "default_padlen", "route"]
+__all__ = ["sosfilt", "sosfilt_scan", "scan_chunk", "sosfilt_zi", "sosfiltfilt", "default_padlen", "route"]
 
 _default: Optional[HipFftImpl] = None
 
@@ -42,6 +49,26 @@ def route(rows: int) -> int:
     if rc:
         raise api.DeviceError(rc, "kofft_hip_sosfilt_route")
     return int(r.value)
+
+
+def scan_chunk(rows: int, nx: int, sections: int) -> int:
+    """kofft_hip_sosfilt_scan_chunk: the measured chunk for ``rows`` rows of ``nx`` samples through ``sections`` sections.  No device."""
+    if min(int(rows), int(nx), int(sections)) < 0:
+        raise ValueError("sizes are usize: they cannot be negative")
+    r = C.c_size_t()
+    rc = _lib.load().kofft_hip_sosfilt_scan_chunk(int(rows), int(nx), int(sections), C.byref(r))
+    if rc:
+        raise api.DeviceError(rc, "kofft_hip_sosfilt_scan_chunk")
+    return int(r.value)
+
+
+def _chunk(chunk, rows: int, nx: int, sections: int) -> int:
+    if chunk is None:
+        return scan_chunk(rows, nx, sections)
+    k = int(chunk)
+    if k <= 0 or k % 32:
+        raise FftError(FftError.InvalidValue)  # (a multiple of KOFFT_HIP_SOSFILT_TILE)
+    return k
 
 
 def _sos(sos) -> np.ndarray:
@@ -73,11 +100,23 @@ def _ctx(fft):
 
 def sosfilt(sos, x, zi=None, reverse: bool = False, fft: Optional[HipFftImpl] = None):
     """scipy.signal.sosfilt(sos, x, axis=-1, zi=zi) in float32: y, or (y, zf) when ``zi`` is given."""
+    return _filter(sos, x, zi, reverse, fft, False, None)
+
+
+def sosfilt_scan(sos, x, zi=None, chunk: Optional[int] = None, reverse: bool = False, fft: Optional[HipFftImpl] = None):
+    """``sosfilt`` as a scan along time in chunks of ``chunk`` samples (a multiple of 32; None: ``scan_chunk``'s choice): the arguments,
+    the state layout and the results of ``sosfilt``, the bits of kofft_hip_sosfilt_scan_f32's definition."""
+    return _filter(sos, x, zi, reverse, fft, True, chunk)
+
+
+def _filter(sos, x, zi, reverse, fft, scan: bool, chunk):
     c = _sos(sos)
     a = _rows(x)
     sections = c.shape[0]
     rows, nx = int(np.prod(a.shape[:-1], dtype=np.int64)), a.shape[-1]
     rows2d = a.reshape(rows, nx)
+    if scan:
+        chunk = _chunk(chunk, rows, nx, sections)
     st = None
     if zi is not None:
         z = np.asarray(zi, np.float32)
@@ -88,9 +127,10 @@ def sosfilt(sos, x, zi=None, reverse: bool = False, fft: Optional[HipFftImpl] = 
         y = np.empty(a.shape, np.float32)
         return y if zi is None else (y, np.array(zi, np.float32))
     fft = _ctx(fft)
+    run = (lambda *p, **k: fft.sosfilt_scan_rows(*p, chunk, **k)) if scan else fft.sosfilt_rows
     if st is None:
-        return fft.sosfilt_rows(rows2d, c, reverse=reverse).reshape(a.shape)
-    y, zf = fft.sosfilt_rows(rows2d, c, zi=st, zf=True, reverse=reverse)
+        return run(rows2d, c, reverse=reverse).reshape(a.shape)
+    y, zf = run(rows2d, c, zi=st, zf=True, reverse=reverse)
     return y.reshape(a.shape), np.ascontiguousarray(zf.transpose(1, 0, 2)).reshape((sections,) + a.shape[:-1] + (2,))
 
 
@@ -129,11 +169,14 @@ def odd_ext(a: np.ndarray, n: int) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([left, a, right], axis=1))
 
 
-def sosfiltfilt(sos, x, padlen: Optional[int] = None, fft: Optional[HipFftImpl] = None) -> np.ndarray:
+def sosfiltfilt(sos, x, padlen: Optional[int] = None, fft: Optional[HipFftImpl] = None, chunk: Optional[int] = None) -> np.ndarray:
     """The zero-phase forward-backward filter of every row (scipy.signal.sosfiltfilt with padtype "odd"), as the composition the
-    module's docstring fixes."""
+    module's docstring fixes.  ``chunk`` (a multiple of 32): both passes run through the scan in chunks of that many samples; without
+    it, the sequential filter, as ever."""
     c = _sos(sos)
     a = _rows(x)
+    if chunk is not None:
+        chunk = _chunk(chunk, 0, 0, 0)
     edge = default_padlen(c) if padlen is None else int(padlen)
     if edge < 0:
         raise ValueError("padlen cannot be negative")
@@ -146,6 +189,7 @@ def sosfiltfilt(sos, x, padlen: Optional[int] = None, fft: Optional[HipFftImpl] 
     zi = sosfilt_zi(c).astype(np.float32)  # [sections, 2]
     ext = odd_ext(rows2d, edge)
     fft = _ctx(fft)
-    y = fft.sosfilt_rows(ext, c, zi=np.ascontiguousarray(zi[None, :, :] * ext[:, :1, None]))
-    y = fft.sosfilt_rows(y, c, zi=np.ascontiguousarray(zi[None, :, :] * y[:, -1:, None]), reverse=True)
+    run = fft.sosfilt_rows if chunk is None else (lambda *p, **k: fft.sosfilt_scan_rows(*p, chunk, **k))
+    y = run(ext, c, zi=np.ascontiguousarray(zi[None, :, :] * ext[:, :1, None]))
+    y = run(y, c, zi=np.ascontiguousarray(zi[None, :, :] * y[:, -1:, None]), reverse=True)
     return np.ascontiguousarray(y[:, edge:edge + nx]).reshape(a.shape)
