@@ -280,6 +280,40 @@ int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows
 int kofft_hip_set_convolve_fused(kofft_hip_ctx *ctx, int on);
 int kofft_hip_convolve_block(size_t nx, size_t nh, size_t *block);
 
+/* ---- filter-bank convolution and correlation of rows (overlap-save) ------------------------
+ * The convolution above with `filters` filters of nh taps that every row shares: each frame is loaded and transformed once, then
+ * multiplied and transformed back once per filter (filters + 1 transforms per frame where `filters` calls above cost 2 * filters).
+ * block, hop, full, nb and the frame are the ones above.  For row r, filter f and block b:
+ *   H_f = fft((re, im) of tap i, zero-padded to block).  Real taps: (h[f][i], +0), h holds filters * nh floats.  flags bit 1 (complex
+ *     taps): h holds filters * nh interleaved (re, im) f32 pairs.  flags bit 0 (correlate): the taps reversed, complex taps conjugated
+ *     as well, conj(h[f][nh - 1 - i]), so that the result is numpy.correlate(x, h_f, "full");
+ *   X = fft(frame), once per (row, block);  Y_f[k] = X[k] * H_f[k], Complex::mul un-fused (num.rs:162-165);
+ *   y_f = ifft(Y_f) (fft.rs:1134-1174): re = v.re * (1 / block), im = (-v.im) * (1 / block);
+ *   element b * hop + j of (row, filter), j < hop, comes from y_f[nh - 1 + j] by the output kind in flags bits 2-3: 0 the real part
+ *     (f32), 1 the complex value (an (re, im) f32 pair), 2 the magnitude sqrtf(re * re + im * im) of the scaled values (the sum
+ *     un-fused, the root correctly rounded).
+ * out is dense [rows][filters][out_len] elements of 4 bytes (kinds 0 and 2) or 8 bytes (kind 1), aligned to its element, and holds
+ * full_out[out_first .. out_first + out_len) of every (row, filter); blocks wholly outside that window are not computed.  With real
+ * taps and kind 0, (row, filter) has the bits kofft_hip_convolve_f32 gives for that filter alone.  block == 0: kofft_hip_convolve_block(nx,
+ * nh).  Checks, in this order and before the context or a device is touched: rows == 0, filters == 0 or out_len == 0 -> KOFFT_OK;
+ * nx == 0 or nh == 0 -> EMPTY_INPUT; block not a power of two -> NON_POWER_OF_TWO_NO_STD; block < nh -> MISMATCHED_LENGTHS; out_first +
+ * out_len > full -> MISMATCHED_LENGTHS; a flag bit above bit 3, or output kind 3 -> INVALID_VALUE; block > 65536 ->
+ * KOFFT_ERR_UNSUPPORTED; a null pointer or context -> KOFFT_ERR_NULL.  kofft_hip_convolve_bank_f32: host pointers;
+ * kofft_hip_dev_convolve_bank_f32: device pointers, asynchronous on the context's stream; out must not overlap x or h.  Blocks 32 ..
+ * 4096 run one fused kernel (4-byte aligned x); kofft_hip_set_convolve_bank_fused(ctx, 0) sends every block of that context through
+ * the composed route instead (frames into the context's scratch and transformed once, then per filter multiply, inverse transform,
+ * gather: the same bytes; A/B measurements and tests). */
+#define KOFFT_HIP_BANK_CORRELATE 1u
+#define KOFFT_HIP_BANK_COMPLEX_TAPS 2u
+#define KOFFT_HIP_BANK_OUT_REAL 0u
+#define KOFFT_HIP_BANK_OUT_COMPLEX 4u
+#define KOFFT_HIP_BANK_OUT_MAGNITUDE 8u
+int kofft_hip_convolve_bank_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh,
+                                size_t block, unsigned flags, void *out, size_t out_first, size_t out_len);
+int kofft_hip_dev_convolve_bank_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh,
+                                    size_t block, unsigned flags, void *d_out, size_t out_first, size_t out_len);
+int kofft_hip_set_convolve_bank_fused(kofft_hip_ctx *ctx, int on);
+
 /* ---- polyphase resampling of rows (upfirdn, resample_poly) -----------------------------------
  * Sample-rate conversion by up / down of `rows` dense rows of nx f32 samples through one FIR filter of nh taps: out_len values per row
  * from up-sampled time t0 on, the decimating or interpolating filter computed directly in the time domain (with up == down == 1 a

@@ -365,6 +365,45 @@ public:
     {
         return convolve_impl(x, h, nh, out, rows, block, first, count, 1u);
     }
+    // Overlap-save FFT convolution of `rows` contiguous rows of x.size() / rows samples with every filter of a bank that the rows
+    // share (kofft_hip_convolve_bank_f32): h holds h.size() / nh filters of nh taps, float or Complex<float>; each frame is
+    // transformed once for the whole bank.  out is resized to rows * filters * count elements, [row][filter][count]: values first ..
+    // first + count of each full result of nx + nh - 1 values (count == SIZE_MAX: up to its end).  Out picks the output kind:
+    // std::vector<float> with magnitude == false the real parts, with magnitude == true the magnitudes; std::vector<Complex<float>>
+    // the complex values (with magnitude == true: InvalidValue).  correlate: the taps reversed and complex ones conjugated (numpy.correlate's "full" order).
+    // MismatchedLengths for rows that do not divide x or nh that does not divide h; then the C entry's checks in its order.
+    template <typename Tap, typename Out>
+    Result convolve_bank_rows(const std::vector<float> &x, const std::vector<Tap> &h, size_t nh, std::vector<Out> &out, size_t rows = 1,
+                              size_t block = 0, size_t first = 0, size_t count = SIZE_MAX, bool correlate = false,
+                              bool magnitude = false) const
+    {
+        static_assert(std::is_same<T, float>::value, "convolve_bank_rows is f32-only");
+        static_assert(std::is_same<Tap, float>::value || std::is_same<Tap, Complex<float>>::value, "taps: float or Complex<float>");
+        static_assert(std::is_same<Out, float>::value || std::is_same<Out, Complex<float>>::value, "out: float or Complex<float>");
+        constexpr bool complex_out = std::is_same<Out, Complex<float>>::value;
+        if (complex_out && magnitude) return Result::Err(FftError::InvalidValue);
+        if (rows == 0 || x.size() % rows != 0 || (nh != 0 && h.size() % nh != 0)) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows;
+        if (nx == 0 || nh == 0) return Result::Err(FftError::EmptyInput);
+        const size_t filters = h.size() / nh, full = nx + nh - 1;
+        if (count == SIZE_MAX) {
+            if (first > full) return Result::Err(FftError::MismatchedLengths);
+            count = full - first;
+        }
+        if (first > full || count > full - first) return Result::Err(FftError::MismatchedLengths);
+        out.resize(rows * filters * count);
+        const unsigned flags = (correlate ? KOFFT_HIP_BANK_CORRELATE : 0u) |
+                               (std::is_same<Tap, float>::value ? 0u : KOFFT_HIP_BANK_COMPLEX_TAPS) |
+                               (complex_out ? KOFFT_HIP_BANK_OUT_COMPLEX : magnitude ? KOFFT_HIP_BANK_OUT_MAGNITUDE : KOFFT_HIP_BANK_OUT_REAL);
+        Out dummy{};  // (no filters or count == 0: the C entry returns before it looks at the pointers)
+        const float none = 0.0f;
+        return st(kofft_hip_convolve_bank_f32(ctx_, x.data(), rows, nx, h.empty() ? &none : reinterpret_cast<const float *>(h.data()),
+                                              filters, nh, block, flags, out.empty() ? static_cast<void *>(&dummy) : out.data(), first,
+                                              count));
+    }
+    // false: every filter-bank convolution of this context through frames in the scratch transformed once, then per filter multiply,
+    // inverse transform, gather (the same bytes; A/B, tests)
+    Result set_convolve_bank_fused(bool on) const { return st(kofft_hip_set_convolve_bank_fused(ctx_, on ? 1 : 0)); }
     // Polyphase resampling of `rows` contiguous rows of x.size() / rows samples through the taps h (kofft_hip_resample_f32): out is
     // resized to rows * count values, output m of a row at up-sampled time t0 + m * down, in the arithmetic the C header fixes.  count
     // SIZE_MAX: every output from t0 to the end of the full result of (nx - 1) * up + h.size() values (scipy.signal.upfirdn's length at

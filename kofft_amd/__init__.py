@@ -14,7 +14,7 @@ from . import czt, goertzel  # noqa: E402  (kofft::czt::czt_f32, kofft::goertzel
 from . import hartley, window  # noqa: E402  (kofft::hartley::dht, kofft::window / window_more beyond hann)
 from . import mfcc  # noqa: E402  (kofft::cepstrum::mel_filterbank / mfcc / mfcc_batch)
 from . import spectrogram  # noqa: E402  (kofft::visual::spectrogram: magnitude_to_db, db_scale, the colour maps, log_scale_bins)
-from . import convolve  # noqa: E402  (overlap-save FFT convolution / correlation of rows: convolve, correlate, default_block)
+from . import convolve  # noqa: E402  (overlap-save FFT convolution / correlation of rows: convolve, correlate, convolve_bank, correlate_bank, default_block)
 from . import psd  # noqa: E402  (Welch power spectra and cross spectra of rows: welch, csd, segments)
 from . import resample  # noqa: E402  (polyphase resampling of rows: upfirdn, resample_poly, design_taps)
 from . import iir  # noqa: E402  (IIR filtering of rows by a cascade of biquads: sosfilt, sosfilt_zi, sosfiltfilt)

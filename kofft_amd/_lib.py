@@ -86,6 +86,9 @@ SIGNATURES = {
     "kofft_hip_dev_convolve_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_convolve_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_convolve_block": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),
+    "kofft_hip_convolve_bank_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_convolve_bank_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_convolve_bank_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_dev_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_set_resample_tiled": (C.c_int, [_ctx, C.c_int]),

@@ -71,6 +71,7 @@ struct kofft_hip_ctx {
     bool planar_fused = true; // kofft_hip_set_split_fused(ctx, 0): planar (split re / im) transforms of every length through the composed route (pack, fft_dev, unpack; A/B, tests)
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool convolve_fused = true; // kofft_hip_set_convolve_fused(ctx, 0): overlap-save convolutions of every block through the composed route (expand, fft_dev, multiply, inverse fft_dev, gather; A/B, tests)
+    bool convolve_bank_fused = true; // kofft_hip_set_convolve_bank_fused(ctx, 0): filter-bank convolutions of every block through the composed route (expand and fft_dev once, then per filter multiply, inverse fft_dev, gather; A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
     int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
     int welch_fused = 1;      // kofft_hip_set_welch_fused: 1 the measured choice (welch_use_fused), 0 every Welch / cross-spectrum call through the composed route (one-sided frames into the scratch, then the sums), 2 the fused kernel wherever it exists (A/B, tests)
@@ -799,6 +800,12 @@ int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *bl
                    const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx);
 int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
                  unsigned flags, float *d_out, size_t out_first, size_t out_len);
+// k_convolve_f32.hip: the same against a bank of filters that all rows share (convolve_bank_impl.hip.h); flags bit 0
+// correlate, bit 1 complex taps, bits 2-3 the output kind (real part, complex value, magnitude)
+int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_t *block, unsigned flags, size_t out_first, size_t out_len,
+                        const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx);
+int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
+                      unsigned flags, void *d_out, size_t out_first, size_t out_len);
 // k_resample_f32.hip: polyphase resampling of rows (resample_impl.hip.h, resample_plan.h).  resample_check: the argument
 // checks alone, in the order of include/kofft_hip.h; resample_taps: scipy.signal.resample_poly's default filter, host only
 int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, size_t t0, size_t out_len, const void *x, const void *h,

@@ -371,6 +371,21 @@ int convolve_host(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, co
                             });
 }
 
+// the same against a bank of filters (k_convolve_f32.hip): the bank is the side input, uploaded once; a row of the
+// output is filters * out_len elements of one or (complex values) two floats
+int convolve_bank_host(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh, size_t block,
+                       unsigned flags, void *out, size_t out_first, size_t out_len)
+{
+    const int rc = convolve_bank_check(rows, nx, filters, nh, &block, flags, out_first, out_len, x, h, out, ctx);
+    if (rc || rows == 0 || filters == 0 || out_len == 0) return rc;
+    if (filters > (SIZE_MAX >> 3) / nh || filters > (SIZE_MAX >> 3) / out_len) return KOFFT_ERR_UNSUPPORTED;
+    const size_t out_row = filters * out_len * (((flags >> 2) & 3u) == 1u ? 2 : 1), side_len = filters * nh * ((flags & 2u) ? 2 : 1);
+    return rows_host<float>(ctx, x, static_cast<float *>(out), rows, nx, out_row, h, side_len, true, true,
+                            [&](float *d_in, float *d_out, const float *d_h, size_t nr) {
+                                return convolve_bank_dev(ctx, d_in, nr, nx, d_h, filters, nh, block, flags, d_out, out_first, out_len);
+                            });
+}
+
 // cepstrum::mel_filterbank / mfcc on host rows of n_fft magnitudes in, num_mel energies or num_coeffs coefficients out (k_mfcc_f32.hip);
 // the edges stay on the host
 int mel_host(kofft_hip_ctx *ctx, bool mfcc, const float *mags, float *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
@@ -1023,6 +1038,22 @@ int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows
                                size_t block, unsigned flags, float *d_out, size_t out_first, size_t out_len)
 {
     return convolve_dev(ctx, d_x, rows, nx, d_h, filters, nh, block, flags, d_out, out_first, out_len);
+}
+int kofft_hip_set_convolve_bank_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->convolve_bank_fused = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_convolve_bank_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh,
+                                size_t block, unsigned flags, void *out, size_t out_first, size_t out_len)
+{
+    return convolve_bank_host(ctx, x, rows, nx, h, filters, nh, block, flags, out, out_first, out_len);
+}
+int kofft_hip_dev_convolve_bank_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh,
+                                    size_t block, unsigned flags, void *d_out, size_t out_first, size_t out_len)
+{
+    return convolve_bank_dev(ctx, d_x, rows, nx, d_h, filters, nh, block, flags, d_out, out_first, out_len);
 }
 // ---- polyphase resampling of rows (k_resample_f32.hip) -----------------------------------------------------------
 // nx samples per row go up, out_len values come down; the one filter is the side input, uploaded once

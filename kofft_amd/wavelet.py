@@ -9,7 +9,11 @@ before each level, details come finest first.  The generic functions run on the 
 module's functions, and run the reference's loop in Python around any other callable.  Lists of rows are grouped by length, one
 device call per length.  ``fft=`` names the f32 HipFftImpl to run on; without one, a context on device 0 is created at the first
 call and kept.  Errors are raised before any device is touched: a detail shorter than the approximation it is folded into raises
-FftError(MismatchedLengths) (the reference panics there); rows over 2^26 samples or more than 64 levels raise DeviceError."""
+FftError(MismatchedLengths) (the reference panics there); rows over 2^26 samples or more than 64 levels raise DeviceError.
+
+``cwt`` is the continuous counterpart (the reference has none): the scalogram of f32 rows against a bank of complex
+wavelets, one per scale, by kofft_amd.convolve.correlate_bank in "same" mode.  ``morlet_taps`` samples the Morlet wavelets on the
+host."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -22,7 +26,8 @@ __all__ = ["haar_forward", "haar_inverse", "batch_forward", "batch_inverse", "mu
            "multi_level_forward_batch", "multi_level_inverse_batch", "db2_forward", "db2_inverse", "db2_forward_batch",
            "db2_inverse_batch", "db4_forward", "db4_inverse", "sym4_forward", "sym4_inverse", "coif1_forward", "coif1_inverse",
            "haar_forward_multi", "haar_inverse_multi", "db2_forward_multi", "db2_inverse_multi", "db4_forward_multi",
-           "db4_inverse_multi", "sym4_forward_multi", "sym4_inverse_multi", "coif1_forward_multi", "coif1_inverse_multi"]
+           "db4_inverse_multi", "sym4_forward_multi", "sym4_inverse_multi", "coif1_forward_multi", "coif1_inverse_multi",
+           "morlet_taps", "cwt"]
 
 _default: Optional[HipFftImpl] = None
 
@@ -318,3 +323,33 @@ for _name in ("haar", "db2", "db4", "sym4", "coif1"):
     globals()[f"{_name}_forward_multi"].__doc__ = f"wavelet::{_name}_forward_multi: multi_level_forward with {_name}_forward."
     globals()[f"{_name}_inverse_multi"].__doc__ = f"wavelet::{_name}_inverse_multi: multi_level_inverse with {_name}_inverse."
 del _name
+
+
+# ---- continuous wavelet transform --------------------------------------------------------------------------------
+def morlet_taps(scales, w0: float = 6.0, support: float = 4.0) -> np.ndarray:
+    """complex64 [len(scales), nh] Morlet wavelets, one row per scale s (in samples), computed in float64: nh = 2 ceil(support
+    max(scales)) + 1 taps at t = i - (nh - 1) / 2 of pi^(-1/4) exp(i w0 t / s) exp(-(t / s)^2 / 2) / sqrt(s), zero where |t| >
+    ceil(support s).  Row s has its centre frequency at w0 / (2 pi s) cycles per sample."""
+    sc = np.asarray(scales, np.float64)
+    if sc.ndim != 1 or sc.size == 0:
+        raise ValueError("scales must be a non-empty 1-D sequence")
+    if not (np.isfinite(sc).all() and (sc > 0).all()) or not (np.isfinite(support) and support > 0) or not np.isfinite(w0):
+        raise ValueError("scales and support must be positive and finite, w0 finite")
+    half = int(np.ceil(support * sc.max()))
+    t = np.arange(-half, half + 1, dtype=np.float64)[None, :] / sc[:, None]
+    taps = np.pi ** -0.25 * np.exp(1j * float(w0) * t) * np.exp(-0.5 * t * t) / np.sqrt(sc)[:, None]
+    taps[np.abs(np.arange(-half, half + 1))[None, :] > np.ceil(support * sc)[:, None]] = 0.0
+    return taps.astype(np.complex64)
+
+
+def cwt(x, scales=None, w0: float = 6.0, support: float = 4.0, out: str = "magnitude", block: Optional[int] = None,
+        fft: Optional[HipFftImpl] = None, taps=None) -> np.ndarray:
+    """The scalogram of a 1-D signal or of every row of a 2-D [rows, nx] array: correlate_bank(x, morlet_taps(scales, w0, support),
+    "same", block, out), [scales, nx] or [rows, scales, nx].  ``out``: "magnitude" (float32), "complex" (complex64) or "real"
+    (float32).  ``taps=``: the caller's own [scales, nh] wavelets in place of ``scales`` (nh odd keeps them centred)."""
+    from . import convolve
+
+    if (scales is None) == (taps is None):
+        raise ValueError("pass either scales or taps=")
+    bank = morlet_taps(scales, w0, support) if taps is None else taps
+    return convolve.correlate_bank(x, bank, "same", block, out, fft)
