@@ -7,18 +7,18 @@
 // (libm_logf.hip.h).  The pointwise step is the same for every bin, so no bin position enters it.  Two routes, the same operations
 // per element:
 //  * fused (powers of two n = 32 .. 4096): cepstrum_fused_kernel<L>, one pass over HBM.  hilbert_fused_kernel's body
-//    (fused_two_transforms, hilbert_impl.hip.h) with the policy CepstrumFused: rows load as (x, +0) through one buffer
+//    (fused_two_transforms, fused_rows.hip.h) with the policy CepstrumFused: rows load as (x, +0) through one buffer
 //    descriptor per workgroup, the forward transform runs, the last pass's registers take log-magnitude + conj, one LDS exchange
 //    puts them back into pass-0 input order, the same forward transform runs again and the store writes re * scale only, 4 bytes
 //    per point;
 //  * composed (n <= 16, 8192 .. 2^26, inputs that are not 4-byte aligned, and every n after kofft_hip_set_cepstrum_fused(ctx, 0)):
 //    the output holds only n floats per row, so the context's real scratch is the workspace, in row chunks of 512 MiB at most --
-//    hilbert_expand_kernel writes (x, +0), fft_dev transforms in place, cepstrum_logmag_kernel, fft_dev(inverse) runs the
+//    expand_real_kernel writes (x, +0), fft_dev transforms in place, cepstrum_logmag_kernel, fft_dev(inverse) runs the
 //    reference's ifft in place, cepstrum_real_kernel takes the real parts into the output.
 // Both routes read all of a row before they write any of it: in == out is allowed; a partial overlap is undefined.
 #pragma once
 
-#include "hilbert_impl.hip.h"
+#include "fused_rows.hip.h"
 #include "libm_logf.hip.h"
 
 namespace kofft {
@@ -48,29 +48,29 @@ inline int cepstrum_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d
 {
     // rows per chunk as dct2_composed_dev: scratch_chunk_bytes of scratch at most
     const size_t chunk = scratch_chunk_rows(ctx->scratch_chunk_bytes, n * sizeof(cpx<float>), batch);
-    int rc = ensure(ctx, ctx->real_tmp, chunk * n * sizeof(cpx<float>));
+    const int rc = ensure(ctx, ctx->real_tmp, chunk * n * sizeof(cpx<float>));
     if (rc) return rc;
     float *zf = static_cast<float *>(ctx->real_tmp.p);
     cpx<float> *z = static_cast<cpx<float> *>(ctx->real_tmp.p);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk, total = n * nb;
-        const dim3 grid(hilbert_flat_blocks(ctx, total));
-        hipLaunchKernelGGL(hilbert_expand_kernel, grid, dim3(256), 0, ctx->stream, d_in + b0 * n, z, total);  // cepstrum.rs:20-23
+    return for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        const size_t total = n * nb;
+        const dim3 grid(flat_blocks(ctx, total, 64));
+        hipLaunchKernelGGL(expand_real_kernel, grid, dim3(256), 0, ctx->stream, d_in + b0 * n, z, total);  // cepstrum.rs:20-23
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         if (n > 1) {  // (n == 1: the transform is nothing, fft.rs:1059)
-            rc = fft_dev<float>(ctx, zf, zf, n, nb, 0);  // cepstrum.rs:25
-            if (rc) return rc;
+            const int frc = fft_dev<float>(ctx, zf, zf, n, nb, 0);  // cepstrum.rs:25
+            if (frc) return frc;
         }
         hipLaunchKernelGGL(cepstrum_logmag_kernel, grid, dim3(256), 0, ctx->stream, z, total);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         if (n > 1) {  // (n == 1: ifft returns early, fft.rs:1139)
-            rc = fft_dev<float>(ctx, zf, zf, n, nb, 1);  // cepstrum.rs:31: conj, fft, conj * (1 / n)
-            if (rc) return rc;
+            const int irc = fft_dev<float>(ctx, zf, zf, n, nb, 1);  // cepstrum.rs:31: conj, fft, conj * (1 / n)
+            if (irc) return irc;
         }
         hipLaunchKernelGGL(cepstrum_real_kernel, grid, dim3(256), 0, ctx->stream, z, d_out + b0 * n, total);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
-    }
-    return KOFFT_OK;
+        return KOFFT_OK;
+    });
 }
 
 // ---- fused route: powers of two n = 2^L, L = 5 .. 12 ------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 //  * composed (every other block up to 65536, unaligned inputs, the switch off): convolve_expand_kernel and fft_dev once per chunk of
 //    items, then per filter convolve_bank_mul_kernel into a second buffer, fft_dev(inverse) and convolve_bank_gather_kernel<Kind>.
 // The filter spectra are computed first on every call: convolve_bank_filter_kernel, then fft_dev in place, at the head of the scratch.
+// The filter and gather kernels serve the one-filter family as well.
 // x / h and out must not overlap.
 #pragma once
 
@@ -42,7 +43,8 @@ struct BankMagnitude {
 };
 
 // ---- filter spectra -------------------------------------------------------------------------------------------------------------
-// convolve_filter_kernel with complex and conjugated taps: element e is point e & (block - 1) of filter e >> lb.
+// Element e is point e & (block - 1) of filter e >> lb: real or complex taps, reversed (complex ones conjugated as well) to correlate.
+// The one-filter family's spectra too (k_convolve_f32.hip: filter_spectra), with real taps and one filter per row or one in all.
 __global__ __launch_bounds__(256) void convolve_bank_filter_kernel(const float *__restrict__ h, cpx<float> *__restrict__ H, const size_t nh,
                                                                    const int lb, const unsigned flags, const size_t total)
 {
@@ -74,7 +76,8 @@ __global__ __launch_bounds__(256) void convolve_bank_mul_kernel(const cpx<float>
         st_stream(y + e, cmul(X[e], Hf[e & mask]));  // num.rs:162-165
 }
 
-// convolve_gather_kernel for filter f of the bank: y holds ifft's results (conj and scale applied)
+// The kept part of every frame of a chunk into the window of (row, filter f): y holds ifft's results (conj and scale applied).  The
+// one-filter family's gather too: BankReal with filters = 1, f = 0 addresses out + row * out_len.
 template <class Kind>
 __global__ __launch_bounds__(256) void convolve_bank_gather_kernel(const cpx<float> *__restrict__ y, typename Kind::Out *__restrict__ out,
                                                                    const ConvShape s, const size_t filters, const size_t f,
@@ -94,49 +97,25 @@ __global__ __launch_bounds__(256) void convolve_bank_gather_kernel(const cpx<flo
 }
 
 // ---- fused route: block = 2^L, L = 5 .. 12 --------------------------------------------------------------------------------------
-// convolve_fused_kernel<L>'s geometry, item walk and per-lane row bounds.  The first transform's bins stay in 2 R registers (X) while
-// the loop over the filters multiplies, reorders through the item's exchange slot, transforms and stores: no second LDS slot, and the
-// 4096-point instance keeps its two waves per SIMD (the resource table).
+// convolve_fused_kernel<L>'s geometry, item walk and per-lane row bounds (conv_item, conv_load_frame, conv_window).  The first
+// transform's bins stay in 2 R registers (X) while the loop over the filters multiplies, reorders through the item's exchange slot,
+// transforms and stores: no second LDS slot, and the 4096-point instance keeps its two waves per SIMD (the resource
+// table).
 template <int L, class Kind>
 __global__ __launch_bounds__(256) void convolve_bank_fused_kernel(const float *__restrict__ x, const cpx<float> *__restrict__ H,
                                                                   typename Kind::Out *__restrict__ out, const cpx<float> *__restrict__ tw,
                                                                   const ConvShape s, const size_t filters, const float scale)
 {
-    using Geo = HilbertGeom<L>;
-    constexpr int N = Geo::N, R = Geo::R, TPT = Geo::TPT, XPB = Geo::XPB;
-    using G0 = WgGeom<L, Geo::RL, 0>;
+    using Geo = FusedGeom<L>;
+    constexpr int N = Geo::N, R = Geo::R, TPT = Geo::TPT;
     using GL = WgGeom<L, Geo::RL, Geo::NP - 1>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, tau = tid % TPT, slot = tid / TPT;
-    const size_t item = (size_t)blockIdx.x * XPB + slot;
-    const bool live = item < s.items;  // (the last workgroup's spare slots: zeros in, nothing out)
-    const size_t it = live ? item : 0;
-    const size_t row = s.row_of(it), b = s.b0 + (it - row * s.nbw);
-    const long long first = (long long)(b * s.hop) - (long long)(s.nh - 1);  // the sample index of frame element 0
+    const ConvItem c = conv_item<L>(s, slot);
     cpx<float> X[R];
-    {
-        // elements [lo, hi) of the frame are samples of this row (convolve_fused_kernel): no lane reads outside its row
-        const int lo = first < 0 ? (int)-first : 0;
-        const long long left = (long long)s.nx - first;
-        const int hi = !live || left <= 0 ? 0 : (left < (long long)N ? (int)left : N);
-        const float *xr = x + row * s.nx + first;
-        float raw[R];
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int i = G0::in_index(0, u) + tau;
-            raw[u] = (i >= lo && i < hi) ? xr[i] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < R; ++u) X[u] = mk<float>(raw[u], 0.0f);
-    }
-    hilbert_forward<L>(X, smem_raw, tw, tau, slot);
-    // Element k of y_f goes to full_out[b * hop + k - (nh - 1)] for k >= nh - 1; kept where that lies inside the window: k in [klo, khi)
-    const long long shift = (long long)(b * s.hop) - (long long)(s.nh - 1) - (long long)s.out_first;  // window index = k + shift
-    const long long lo64 = -shift > (long long)(s.nh - 1) ? -shift : (long long)(s.nh - 1);
-    const long long hi64 = (long long)s.out_len - shift;
-    const int klo = lo64 < (long long)N ? (int)lo64 : N;
-    const int khi = !live || hi64 <= 0 ? 0 : (hi64 < (long long)N ? (int)hi64 : N);
-    cpx<float> *buf = reinterpret_cast<cpx<float> *>(smem_raw) + (size_t)slot * lds_elems(N);
+    conv_load_frame<L>(X, x, s, c, tau);
+    fused_forward<L>(X, smem_raw, tw, tau, slot);
+    const ConvWindow w = conv_window<N>(s, c);
     for (size_t f = 0; f < filters; ++f) {  // (uniform over the workgroup: every barrier below is met by all of it)
         cpx<float> v[R];
         {   // Y = X * H_f (num.rs:162-165), then ifft's conj (fft.rs:1163-1165)
@@ -150,39 +129,16 @@ __global__ __launch_bounds__(256) void convolve_bank_fused_kernel(const float *_
                 v[u] = mk<float>(y.re, -y.im);
             }
         }
-        // last pass's output order -> pass 0's input order, through the item's exchange slot
-        __syncthreads();  // every gather of the previous transform's last exchange is done
-#pragma unroll
-        for (int u = 0; u < R; ++u) buf[lds_pad(GL::out_index(tau, u))] = v[u];
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < R; ++u) v[u] = buf[lds_pad(G0::in_index(tau, u))];
-        __syncthreads();  // (the second transform's first exchange scatters into the same cells)
-        hilbert_forward<L>(v, smem_raw, tw, tau, slot);
+        fused_reorder<L>(v, smem_raw, tau, slot);
+        fused_forward<L>(v, smem_raw, tw, tau, slot);
         // ifft's last conj and * scale (fft.rs:1168-1172)
-        typename Kind::Out *orow = out + ((row * filters + f) * s.out_len + shift);
+        typename Kind::Out *orow = out + ((c.row * filters + f) * s.out_len + w.shift);
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             const int k = GL::out_index(0, u) + tau;
-            if (k >= klo && k < khi) st_stream(orow + k, Kind::of(v[u].re * scale, (-v[u].im) * scale));
+            if (k >= w.klo && k < w.khi) st_stream(orow + k, Kind::of(v[u].re * scale, (-v[u].im) * scale));
         }
     }
-}
-
-template <int L, class Kind>
-int launch_convolve_bank_fused(kofft_hip_ctx *ctx, const float *d_x, const cpx<float> *H, void *d_out, const cpx<float> *tw,
-                               const ConvShape &s, size_t filters)
-{
-    using Geo = HilbertGeom<L>;
-    constexpr size_t lds = Geo::lds_bytes();
-    static_assert(lds <= 64 * 1024, "LDS budget");
-    const size_t blocks = (s.items + Geo::XPB - 1) / Geo::XPB;
-    if (blocks > 0x7fffffffULL) return KOFFT_ERR_UNSUPPORTED;
-    const float scale = 1.0f / (float)Geo::N;  // fft.rs:1167
-    hipLaunchKernelGGL((convolve_bank_fused_kernel<L, Kind>), dim3((unsigned)blocks), dim3(Geo::BLOCK), lds, ctx->stream, d_x, H,
-                       static_cast<typename Kind::Out *>(d_out), tw, s, filters, scale);
-    KOFFT_HIP_TRY(ctx, hipGetLastError());
-    return KOFFT_OK;
 }
 
 }  // namespace host

@@ -193,17 +193,8 @@ inline int dct2_fused_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, s
     if (rc) return rc;
     rc = dct2_table(ctx, n, &cs);
     if (rc) return rc;
-    switch (ilog2(n)) {
-    case 5: return launch_dct2_fused<5>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 6: return launch_dct2_fused<6>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 7: return launch_dct2_fused<7>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 8: return launch_dct2_fused<8>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 9: return launch_dct2_fused<9>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 10: return launch_dct2_fused<10>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 11: return launch_dct2_fused<11>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    case 12: return launch_dct2_fused<12>(ctx, d_in, d_out, tw, rtab, cs, batch);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: dct2_fused_ok)
-    }
+    // (never outside 5 .. 12: dct2_fused_ok)
+    return dispatch_log2<5, 12>(ilog2(n), [&](auto l) { return launch_dct2_fused<decltype(l)::value>(ctx, d_in, d_out, tw, rtab, cs, batch); });
 }
 
 inline int dct2_composed_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)

@@ -168,6 +168,14 @@ inline int ilog2(size_t n)
     return l;
 }
 
+// The grid of a flat grid-stride kernel of 256 threads over `total` elements: one thread per element up to per_cu workgroups per CU
+// (a tuning value of the family that calls), the kernel's stride loop takes the rest.
+inline unsigned flat_blocks(const kofft_hip_ctx *ctx, size_t total, size_t per_cu)
+{
+    const size_t want = (total + 255) / 256, cap = (size_t)ctx->num_cus * per_cu;
+    return (unsigned)(want < cap ? want : cap);
+}
+
 // The allocator of the table cache and the scratch buffers (host_cache.h).  A failed hipMalloc also leaves its error with the runtime,
 // where the next launch's hipGetLastError would find it: taken away here.
 struct HipAlloc {

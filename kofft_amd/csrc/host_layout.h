@@ -1,9 +1,12 @@
 // host_layout.h -- where the arrays of one host-pointer call lie in its staging buffer (kofft_hip.hip: stage_host), the scratch chunks
-// and their walk, and the overlap test of the device forms.  Arithmetic only, no HIP: tests/cpp/host_layout_check.cpp and
-// tests/cpp/sanitize_frame_cut.cpp include this file alone.
+// and their walk, the dispatch over a log2 and the overlap test of the device forms.  Arithmetic only, no HIP:
+// tests/cpp/host_layout_check.cpp and tests/cpp/sanitize_frame_cut.cpp include this file alone.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
+
+#include "../../include/kofft_hip.h"  // (the status codes; plain C, no HIP)
 
 namespace kofft {
 namespace host {
@@ -64,6 +67,18 @@ inline int for_chunks(size_t total, size_t chunk, Body &&body)
         if (rc) return rc;
     }
     return 0;
+}
+
+// ---- a run-time log2 to a compile-time one ----
+// f(std::integral_constant<int, L>{}) for the L in [LO, HI] that equals l; `otherwise` (KOFFT_ERR_UNSUPPORTED) for an l outside.  f is
+// a generic lambda that launches the kernel instance of 2^L points; exactly the instances LO .. HI exist.
+template <int LO, int HI, class F>
+inline int dispatch_log2(int l, F &&f, int otherwise = KOFFT_ERR_UNSUPPORTED)
+{
+    static_assert(LO <= HI, "an empty range");
+    if (l == LO) return f(std::integral_constant<int, LO>{});
+    if constexpr (LO < HI) return dispatch_log2<LO + 1, HI>(l, f, otherwise);
+    else return otherwise;
 }
 
 // ---- the overlap checks of the device forms ----

@@ -26,50 +26,41 @@ size_t convolve_default_block(size_t nx, size_t nh)
     return p < q ? p : q;
 }
 
-// The argument checks alone, in the order of include/kofft_hip.h and before the context or a device is touched.  *block: 0 on entry
-// means the default (convolve_default_block); the block in use on return.  KOFFT_OK with rows == 0 or out_len == 0: nothing to do.
-int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *block, unsigned flags, size_t out_first, size_t out_len,
-                   const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
+// The argument checks of both families, in the order of include/kofft_hip.h and before the context or a device is touched.  *block: 0
+// on entry means the default (convolve_default_block); the block in use on return.  The families differ in three predicates, which
+// the callers evaluate: `nothing` (KOFFT_OK, nothing to do), `filters_ok` and `flags_ok`.
+static int conv_check(bool nothing, bool filters_ok, bool flags_ok, size_t nx, size_t nh, size_t *block, size_t out_first, size_t out_len,
+                      const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
 {
-    if (rows == 0 || out_len == 0) return KOFFT_OK;
+    if (nothing) return KOFFT_OK;
     if (nx == 0 || nh == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (nx > (SIZE_MAX >> 2) || nh > (SIZE_MAX >> 2)) return KOFFT_ERR_UNSUPPORTED;  // (nx + nh - 1 and 2 nh stay inside size_t)
     if (*block == 0) *block = convolve_default_block(nx, nh);
     if (!is_pow2(*block)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
     if (*block < nh) return KOFFT_ERR_MISMATCHED_LENGTHS;
-    if (filters != 1 && filters != rows) return KOFFT_ERR_MISMATCHED_LENGTHS;
+    if (!filters_ok) return KOFFT_ERR_MISMATCHED_LENGTHS;
     const size_t full = nx + nh - 1;
     if (out_first > full || out_len > full - out_first) return KOFFT_ERR_MISMATCHED_LENGTHS;
-    if (flags & ~1u) return KOFFT_ERR_INVALID_VALUE;
+    if (!flags_ok) return KOFFT_ERR_INVALID_VALUE;
     if (*block > kConvolveMaxBlock) return KOFFT_ERR_UNSUPPORTED;
     if (!ctx || !x || !h || !out) return KOFFT_ERR_NULL;
     return KOFFT_OK;
 }
 
-static int convolve_composed(kofft_hip_ctx *ctx, const float *d_x, const cpx<float> *H, cpx<float> *z, size_t chunk, float *d_out,
-                             const ConvShape &s)
+// KOFFT_OK with rows == 0 or out_len == 0: nothing to do.
+int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *block, unsigned flags, size_t out_first, size_t out_len,
+                   const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
 {
-    const size_t block = size_t(1) << s.lb;
-    float *zf = reinterpret_cast<float *>(z);
-    for (size_t i0 = 0; i0 < s.items; i0 += chunk) {
-        const size_t ni = (s.items - i0 < chunk) ? s.items - i0 : chunk, total = ni * block;
-        const dim3 grid(hilbert_flat_blocks(ctx, total));
-        hipLaunchKernelGGL(convolve_expand_kernel, grid, dim3(256), 0, ctx->stream, d_x, z, s, i0, total);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-        if (block > 1) {  // (block == 1: the transform is nothing, fft.rs:1059)
-            const int rc = fft_dev<float>(ctx, zf, zf, block, ni, 0);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(convolve_mul_kernel, grid, dim3(256), 0, ctx->stream, z, H, s, i0, total);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-        if (block > 1) {  // (block == 1: ifft returns early, fft.rs:1139)
-            const int rc = fft_dev<float>(ctx, zf, zf, block, ni, 1);  // conj, fft, conj * (1 / block)
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(convolve_gather_kernel, grid, dim3(256), 0, ctx->stream, z, d_out, s, i0, total);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-    }
-    return KOFFT_OK;
+    return conv_check(rows == 0 || out_len == 0, filters == 1 || filters == rows, !(flags & ~1u), nx, nh, block, out_first, out_len, x, h, out,
+                      ctx);
+}
+
+// KOFFT_OK with rows == 0, filters == 0 or out_len == 0: nothing to do.  Any number of filters; flag bits 2-3 are the output kind.
+int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_t *block, unsigned flags, size_t out_first, size_t out_len,
+                        const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
+{
+    const bool flags_ok = !(flags >> (kBankKindShift + 2)) && ((flags >> kBankKindShift) & kBankKindMask) != 3u;
+    return conv_check(rows == 0 || filters == 0 || out_len == 0, true, flags_ok, nx, nh, block, out_first, out_len, x, h, out, ctx);
 }
 
 // The flat items of a checked call: the nbw blocks of every row that touch the window.  false: rows * nbw does not fit size_t.
@@ -90,6 +81,74 @@ static bool convolve_shape(size_t rows, size_t nx, size_t nh, size_t block, size
     return true;
 }
 
+// (the fused kernels' loads are 4 bytes wide; `enabled` is the context's switch of the family)
+static bool conv_fused_ok(bool enabled, const float *d_x, size_t block)
+{
+    return enabled && block >= 32 && block <= 4096 && (reinterpret_cast<size_t>(d_x) & 3) == 0;
+}
+
+// The scratch of a call, [filters * block spectra | `bufs` buffers of chunk * block points (composed route)], and the spectra computed
+// at its head: *H.  *chunk: the items per piece of the composed route, 0 on the fused one.  filters * block * 8 * (1 + bufs) fits
+// size_t (the callers' checks).
+static int conv_prepare(kofft_hip_ctx *ctx, const float *d_h, size_t filters, size_t nh, unsigned tap_flags, const ConvShape &s, bool fused,
+                        size_t bufs, size_t *chunk, cpx<float> **H)
+{
+    const size_t block = size_t(1) << s.lb, total = filters * block;
+    *chunk = fused ? 0 : scratch_chunk_rows(ctx->scratch_chunk_bytes, bufs * block * sizeof(cpx<float>), s.items);
+    int rc = ensure(ctx, ctx->real_tmp, (total + bufs * *chunk * block) * sizeof(cpx<float>));
+    if (rc) return rc;
+    *H = static_cast<cpx<float> *>(ctx->real_tmp.p);
+    hipLaunchKernelGGL(convolve_bank_filter_kernel, dim3(flat_blocks(ctx, total, 64)), dim3(256), 0, ctx->stream, d_h, *H, nh, s.lb, tap_flags,
+                       total);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    if (block > 1) {  // (block == 1: the transform is nothing, fft.rs:1059)
+        rc = fft_dev<float>(ctx, reinterpret_cast<float *>(*H), reinterpret_cast<float *>(*H), block, filters, 0);
+        if (rc) return rc;
+    }
+    return KOFFT_OK;
+}
+
+// The composed routes' first half for items [i0, i0 + ni): their frames as (x, +0) into X, transformed in place.
+static int conv_frames(kofft_hip_ctx *ctx, const float *d_x, cpx<float> *X, const ConvShape &s, size_t i0, size_t ni, dim3 grid)
+{
+    const size_t block = size_t(1) << s.lb;
+    hipLaunchKernelGGL(convolve_expand_kernel, grid, dim3(256), 0, ctx->stream, d_x, X, s, i0, ni * block);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    if (block == 1) return KOFFT_OK;  // (the transform is nothing, fft.rs:1059)
+    return fft_dev<float>(ctx, reinterpret_cast<float *>(X), reinterpret_cast<float *>(X), block, ni, 0);
+}
+
+// ... and their last steps for the products y of one filter: ifft in place, then the kept parts into the window of (row, filter f)
+template <class Kind>
+static int conv_finish(kofft_hip_ctx *ctx, cpx<float> *y, void *d_out, const ConvShape &s, size_t filters, size_t f, size_t i0, size_t ni,
+                       dim3 grid)
+{
+    const size_t block = size_t(1) << s.lb;
+    if (block > 1) {  // (block == 1: ifft returns early, fft.rs:1139)
+        const int rc = fft_dev<float>(ctx, reinterpret_cast<float *>(y), reinterpret_cast<float *>(y), block, ni, 1);  // conj, fft, conj * (1 / block)
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(convolve_bank_gather_kernel<Kind>, grid, dim3(256), 0, ctx->stream, y, static_cast<typename Kind::Out *>(d_out), s, filters,
+                       f, i0, ni * block);
+    KOFFT_HIP_TRY(ctx, hipGetLastError());
+    return KOFFT_OK;
+}
+
+// One chunk of flat items at a time (a seam may fall inside a row), all in one buffer z.
+static int convolve_composed(kofft_hip_ctx *ctx, const float *d_x, const cpx<float> *H, cpx<float> *z, size_t chunk, float *d_out,
+                             const ConvShape &s)
+{
+    return for_chunks(s.items, chunk, [&](size_t i0, size_t ni) {
+        const size_t total = ni << s.lb;
+        const dim3 grid(flat_blocks(ctx, total, 64));
+        const int rc = conv_frames(ctx, d_x, z, s, i0, ni, grid);
+        if (rc) return rc;
+        hipLaunchKernelGGL(convolve_mul_kernel, grid, dim3(256), 0, ctx->stream, z, H, s, i0, total);
+        KOFFT_HIP_TRY(ctx, hipGetLastError());
+        return conv_finish<BankReal>(ctx, z, d_out, s, 1, 0, i0, ni, grid);
+    });
+}
+
 int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
                  unsigned flags, float *d_out, size_t out_first, size_t out_len)
 {
@@ -98,91 +157,42 @@ int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, c
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ConvShape s{};
     if (!convolve_shape(rows, nx, nh, block, out_first, out_len, filters == rows && rows > 1, &s)) return KOFFT_ERR_UNSUPPORTED;
-    const bool fused = ctx->convolve_fused && block >= 32 && block <= 4096 && (reinterpret_cast<size_t>(d_x) & 3) == 0;
-    // scratch: [filters * block spectra | chunk * block frames (composed route)]
     if (filters > (SIZE_MAX >> 4) / block) return KOFFT_ERR_UNSUPPORTED;
-    const size_t h_bytes = filters * block * sizeof(cpx<float>);
-    const size_t chunk = fused ? 0 : scratch_chunk_rows(ctx->scratch_chunk_bytes, block * sizeof(cpx<float>), s.items);
-    int rc = ensure(ctx, ctx->real_tmp, h_bytes + chunk * block * sizeof(cpx<float>));
+    const bool fused = conv_fused_ok(ctx->convolve_fused, d_x, block);
+    size_t chunk = 0;
+    cpx<float> *H = nullptr;
+    int rc = conv_prepare(ctx, d_h, filters, nh, flags & kBankCorrelate, s, fused, 1, &chunk, &H);
     if (rc) return rc;
-    cpx<float> *H = static_cast<cpx<float> *>(ctx->real_tmp.p);
-    {
-        const size_t total = filters * block;
-        hipLaunchKernelGGL(convolve_filter_kernel, dim3(hilbert_flat_blocks(ctx, total)), dim3(256), 0, ctx->stream, d_h, H, nh, s.lb,
-                           (int)(flags & 1u), total);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-        if (block > 1) {
-            rc = fft_dev<float>(ctx, reinterpret_cast<float *>(H), reinterpret_cast<float *>(H), block, filters, 0);
-            if (rc) return rc;
-        }
-    }
     if (!fused) return convolve_composed(ctx, d_x, H, H + filters * block, chunk, d_out, s);
     const cpx<float> *tw = nullptr;
     rc = twiddle_table<float>(ctx, block, &tw);  // get_twiddles(block)
     if (rc) return rc;
-    switch (s.lb) {
-    case 5: return launch_convolve_fused<5>(ctx, d_x, H, d_out, tw, s);
-    case 6: return launch_convolve_fused<6>(ctx, d_x, H, d_out, tw, s);
-    case 7: return launch_convolve_fused<7>(ctx, d_x, H, d_out, tw, s);
-    case 8: return launch_convolve_fused<8>(ctx, d_x, H, d_out, tw, s);
-    case 9: return launch_convolve_fused<9>(ctx, d_x, H, d_out, tw, s);
-    case 10: return launch_convolve_fused<10>(ctx, d_x, H, d_out, tw, s);
-    case 11: return launch_convolve_fused<11>(ctx, d_x, H, d_out, tw, s);
-    case 12: return launch_convolve_fused<12>(ctx, d_x, H, d_out, tw, s);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: `fused`)
-    }
+    return dispatch_log2<5, 12>(s.lb, [&](auto l) {  // (never outside 5 .. 12: conv_fused_ok)
+        constexpr int L = decltype(l)::value;
+        return launch_fused_items<L>(ctx, convolve_fused_kernel<L>, s.items, d_x, H, d_out, tw, s);
+    });
 }
 
 // ---- the filter bank ---------------------------------------------------------------------------------------------
-// The argument checks alone, in the order of include/kofft_hip.h and before the context or a device is touched; *block as in
-// convolve_check.
-int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_t *block, unsigned flags, size_t out_first, size_t out_len,
-                        const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
-{
-    if (rows == 0 || filters == 0 || out_len == 0) return KOFFT_OK;
-    if (nx == 0 || nh == 0) return KOFFT_ERR_EMPTY_INPUT;
-    if (nx > (SIZE_MAX >> 2) || nh > (SIZE_MAX >> 2)) return KOFFT_ERR_UNSUPPORTED;  // (nx + nh - 1 and 2 nh stay inside size_t)
-    if (*block == 0) *block = convolve_default_block(nx, nh);
-    if (!is_pow2(*block)) return KOFFT_ERR_NON_POWER_OF_TWO_NO_STD;
-    if (*block < nh) return KOFFT_ERR_MISMATCHED_LENGTHS;
-    const size_t full = nx + nh - 1;
-    if (out_first > full || out_len > full - out_first) return KOFFT_ERR_MISMATCHED_LENGTHS;
-    if ((flags >> (kBankKindShift + 2)) || ((flags >> kBankKindShift) & kBankKindMask) == 3u) return KOFFT_ERR_INVALID_VALUE;
-    if (*block > kConvolveMaxBlock) return KOFFT_ERR_UNSUPPORTED;
-    if (!ctx || !x || !h || !out) return KOFFT_ERR_NULL;
-    return KOFFT_OK;
-}
-
 // One chunk of flat items at a time: the frames and their transforms once into X, then every filter through y.
 template <class Kind>
 static int convolve_bank_composed(kofft_hip_ctx *ctx, const float *d_x, const cpx<float> *H, cpx<float> *X, size_t chunk, void *d_out,
                                   const ConvShape &s, size_t filters)
 {
-    const size_t block = size_t(1) << s.lb;
-    cpx<float> *y = X + chunk * block;
-    float *Xf = reinterpret_cast<float *>(X), *yf = reinterpret_cast<float *>(y);
-    for (size_t i0 = 0; i0 < s.items; i0 += chunk) {
-        const size_t ni = (s.items - i0 < chunk) ? s.items - i0 : chunk, total = ni * block;
-        const dim3 grid(hilbert_flat_blocks(ctx, total));
-        hipLaunchKernelGGL(convolve_expand_kernel, grid, dim3(256), 0, ctx->stream, d_x, X, s, i0, total);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-        if (block > 1) {  // (block == 1: the transform is nothing, fft.rs:1059)
-            const int rc = fft_dev<float>(ctx, Xf, Xf, block, ni, 0);
-            if (rc) return rc;
-        }
+    cpx<float> *y = X + (chunk << s.lb);
+    return for_chunks(s.items, chunk, [&](size_t i0, size_t ni) {
+        const size_t total = ni << s.lb;
+        const dim3 grid(flat_blocks(ctx, total, 64));
+        const int rc = conv_frames(ctx, d_x, X, s, i0, ni, grid);
+        if (rc) return rc;
         for (size_t f = 0; f < filters; ++f) {
-            hipLaunchKernelGGL(convolve_bank_mul_kernel, grid, dim3(256), 0, ctx->stream, X, H + f * block, y, s.lb, total);
+            hipLaunchKernelGGL(convolve_bank_mul_kernel, grid, dim3(256), 0, ctx->stream, X, H + (f << s.lb), y, s.lb, total);
             KOFFT_HIP_TRY(ctx, hipGetLastError());
-            if (block > 1) {  // (block == 1: ifft returns early, fft.rs:1139)
-                const int rc = fft_dev<float>(ctx, yf, yf, block, ni, 1);  // conj, fft, conj * (1 / block)
-                if (rc) return rc;
-            }
-            hipLaunchKernelGGL(convolve_bank_gather_kernel<Kind>, grid, dim3(256), 0, ctx->stream, y, static_cast<typename Kind::Out *>(d_out),
-                               s, filters, f, i0, total);
-            KOFFT_HIP_TRY(ctx, hipGetLastError());
+            const int frc = conv_finish<Kind>(ctx, y, d_out, s, filters, f, i0, ni, grid);
+            if (frc) return frc;
         }
-    }
-    return KOFFT_OK;
+        return KOFFT_OK;
+    });
 }
 
 template <class Kind>
@@ -194,17 +204,11 @@ static int convolve_bank_route(kofft_hip_ctx *ctx, const float *d_x, cpx<float> 
     const cpx<float> *tw = nullptr;
     const int rc = twiddle_table<float>(ctx, block, &tw);  // get_twiddles(block)
     if (rc) return rc;
-    switch (s.lb) {
-    case 5: return launch_convolve_bank_fused<5, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 6: return launch_convolve_bank_fused<6, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 7: return launch_convolve_bank_fused<7, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 8: return launch_convolve_bank_fused<8, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 9: return launch_convolve_bank_fused<9, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 10: return launch_convolve_bank_fused<10, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 11: return launch_convolve_bank_fused<11, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    case 12: return launch_convolve_bank_fused<12, Kind>(ctx, d_x, H, d_out, tw, s, filters);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: `fused`)
-    }
+    return dispatch_log2<5, 12>(s.lb, [&](auto l) {  // (never outside 5 .. 12: conv_fused_ok)
+        constexpr int L = decltype(l)::value;
+        return launch_fused_items<L>(ctx, convolve_bank_fused_kernel<L, Kind>, s.items, d_x, H, static_cast<typename Kind::Out *>(d_out), tw, s,
+                                     filters);
+    });
 }
 
 int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
@@ -216,23 +220,12 @@ int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t 
     ConvShape s{};
     if (!convolve_shape(rows, nx, nh, block, out_first, out_len, false, &s)) return KOFFT_ERR_UNSUPPORTED;
     if (filters > (SIZE_MAX >> 5) / block || rows > (SIZE_MAX >> 3) / filters / out_len) return KOFFT_ERR_UNSUPPORTED;
-    const bool fused = ctx->convolve_bank_fused && block >= 32 && block <= 4096 && (reinterpret_cast<size_t>(d_x) & 3) == 0;
-    // scratch: [filters * block spectra | chunk * block transformed frames | chunk * block products (composed route)]
-    const size_t h_bytes = filters * block * sizeof(cpx<float>);
-    const size_t chunk = fused ? 0 : scratch_chunk_rows(ctx->scratch_chunk_bytes, 2 * block * sizeof(cpx<float>), s.items);
-    int rc = ensure(ctx, ctx->real_tmp, h_bytes + 2 * chunk * block * sizeof(cpx<float>));
+    const bool fused = conv_fused_ok(ctx->convolve_bank_fused, d_x, block);
+    size_t chunk = 0;
+    cpx<float> *H = nullptr;
+    // (two buffers per chunk on the composed route: the transformed frames, which stay for the next filter, and the products)
+    const int rc = conv_prepare(ctx, d_h, filters, nh, flags & (kBankCorrelate | kBankComplexTaps), s, fused, 2, &chunk, &H);
     if (rc) return rc;
-    cpx<float> *H = static_cast<cpx<float> *>(ctx->real_tmp.p);
-    {
-        const size_t total = filters * block;
-        hipLaunchKernelGGL(convolve_bank_filter_kernel, dim3(hilbert_flat_blocks(ctx, total)), dim3(256), 0, ctx->stream, d_h, H, nh, s.lb,
-                           flags & (kBankCorrelate | kBankComplexTaps), total);
-        KOFFT_HIP_TRY(ctx, hipGetLastError());
-        if (block > 1) {
-            rc = fft_dev<float>(ctx, reinterpret_cast<float *>(H), reinterpret_cast<float *>(H), block, filters, 0);
-            if (rc) return rc;
-        }
-    }
     switch ((flags >> kBankKindShift) & kBankKindMask) {
     case 0: return convolve_bank_route<BankReal>(ctx, d_x, H, d_out, s, filters, fused, chunk);
     case 1: return convolve_bank_route<BankComplex>(ctx, d_x, H, d_out, s, filters, fused, chunk);

@@ -92,15 +92,8 @@ static int frontend_fused(kofft_hip_ctx *ctx, const FramedSrc &s, const uint64_t
     io.nc = (int)nc;
     io.ldc = (int)direct_ldc(num_mel);
     const size_t batch = s.rows * s.frames;
-    switch (ilog2(win_len)) {
-    case 6: return launch_frontend<6, MFCC>(ctx, io, tw, batch);
-    case 7: return launch_frontend<7, MFCC>(ctx, io, tw, batch);
-    case 8: return launch_frontend<8, MFCC>(ctx, io, tw, batch);
-    case 9: return launch_frontend<9, MFCC>(ctx, io, tw, batch);
-    case 10: return launch_frontend<10, MFCC>(ctx, io, tw, batch);
-    case 11: return launch_frontend<11, MFCC>(ctx, io, tw, batch);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: frontend_fused_fits)
-    }
+    // (never outside 6 .. 11: frontend_fused_fits)
+    return dispatch_log2<6, 11>(ilog2(win_len), [&](auto l) { return launch_frontend<decltype(l)::value, MFCC>(ctx, io, tw, batch); });
 }
 
 // ---- the composed route ------------------------------------------------------------------------------------------------------------

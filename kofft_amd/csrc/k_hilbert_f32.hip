@@ -1,5 +1,7 @@
 // k_hilbert_f32.hip -- hilbert::hilbert_analytic (hilbert.rs:13-47) and cepstrum::real_cepstrum (cepstrum.rs:12-33) on float rows:
-// every kernel instance of the two families, which share the fused route's body and the composed route's expand kernel.
+// every kernel instance of the two families, which share the fused route's body and the composed route's expand kernel
+// (fused_rows.hip.h).
+#include "hilbert_impl.hip.h"
 #include "cepstrum_impl.hip.h"
 
 namespace kofft {

@@ -104,12 +104,6 @@ int mel_filterbank_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_energie
     return launch_mel(ctx, d_mags, d_energies, plan, nullptr, n_fft, num_mel, 0, rows);
 }
 
-static size_t mel_flat_blocks(const kofft_hip_ctx *ctx, size_t total)
-{
-    const size_t need = (total + 255) / 256, cap = (size_t)ctx->num_cus * 16;
-    return need < cap ? need : cap;
-}
-
 // filterbank -> log -> direct DCT-II -> the first num_coeffs columns, through the context's scratch ([energies | dct]: 2 num_mel floats
 // per row), scratch_chunk_bytes at a time
 static int mfcc_composed_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, const int *plan, size_t n_fft, size_t rows, size_t num_mel,
@@ -125,7 +119,7 @@ static int mfcc_composed_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_c
         const size_t nb = rows - r0 < chunk ? rows - r0 : chunk;
         rc = launch_mel(ctx, d_mags + r0 * n_fft, e, plan, nullptr, n_fft, num_mel, 0, nb);
         if (rc) return rc;
-        hipLaunchKernelGGL(mel_log_kernel, dim3((unsigned)mel_flat_blocks(ctx, nb * num_mel)), dim3(256), 0, ctx->stream, e, nb * num_mel);
+        hipLaunchKernelGGL(mel_log_kernel, dim3(flat_blocks(ctx, nb * num_mel, 16)), dim3(256), 0, ctx->stream, e, nb * num_mel);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         rc = direct_dev(ctx, 0, 2, e, d, num_mel, nb);  // dct::dct2 (cepstrum.rs:83)
         if (rc) return rc;

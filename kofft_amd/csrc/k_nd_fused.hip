@@ -50,16 +50,9 @@ int fft2d_fused_core(kofft_hip_ctx *ctx, cpx<float> *data, int LT)
     // (plain against streaming loads of the intermediate measured equal on 16 .. 128 MiB images, round 5; the factor path's rule)
     m.nt_load = elems * sizeof(cpx<float>) > (size_t(192) << 20);
     const size_t units = size_t(1) << (S + LC);
-    switch (LS) {
-#define KOFFT_CASE(LL) \
-    case LL: return launch_tile_persist<float, LL, AxisLastIO<float, INVERSE>>(ctx, m, tw_col, units);
-        KOFFT_CASE(8)  // LS = LT - 2, LT = 10 .. 13 (fft2d_fused_ok)
-        KOFFT_CASE(9)
-        KOFFT_CASE(10)
-        KOFFT_CASE(11)  // 8192 rows (round 6): tiles of 8 columns at 1024 threads, 64-byte runs
-#undef KOFFT_CASE
-    default: return KOFFT_ERR_UNSUPPORTED;
-    }
+    // LS = LT - 2, LT = 10 .. 13 (fft2d_fused_ok); 11, 8192 rows (round 6): tiles of 8 columns at 1024 threads, 64-byte runs
+    return dispatch_log2<8, 11>(
+        LS, [&](auto l) { return launch_tile_persist<float, decltype(l)::value, AxisLastIO<float, INVERSE>>(ctx, m, tw_col, units); });
 }
 
 bool fft2d_fused_ok(const kofft_hip_ctx *ctx, size_t rows, size_t cols)

@@ -89,18 +89,12 @@ int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins,
     return KOFFT_OK;
 }
 
-static unsigned spec_flat_blocks(const kofft_hip_ctx *ctx, size_t items)
-{
-    const size_t need = (items + 255) / 256, cap = (size_t)ctx->num_cus * 32;
-    return (unsigned)(need < cap ? need : cap);
-}
-
 int spec_db_dev(kofft_hip_ctx *ctx, int which, const float *d_mags, size_t count, const float *d_max, float level, float *d_out)
 {
     const int rc = spec_db_check(true, d_mags, count, d_max, d_out, ctx);
     if (rc) return rc;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(spec_db_kernel, dim3(spec_flat_blocks(ctx, count)), dim3(256), 0, ctx->stream, d_mags, d_out, count, d_max, level, which);
+    hipLaunchKernelGGL(spec_db_kernel, dim3(flat_blocks(ctx, count, 32)), dim3(256), 0, ctx->stream, d_mags, d_out, count, d_max, level, which);
     KOFFT_HIP_TRY(ctx, hipGetLastError());
     return KOFFT_OK;
 }
@@ -120,7 +114,7 @@ int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size
     const bool d16 = depth == 16;
     if (layout == 0) {
         auto kern = d16 ? spec_flat_kernel<true> : spec_flat_kernel<false>;
-        hipLaunchKernelGGL(kern, dim3(spec_flat_blocks(ctx, (frames * bins + 3) / 4)), dim3(256), 0, ctx->stream, d_mags, out, frames, (int)bins,
+        hipLaunchKernelGGL(kern, dim3(flat_blocks(ctx, (frames * bins + 3) / 4, 32)), dim3(256), 0, ctx->stream, d_mags, out, frames, (int)bins,
                            d_max, mode, level, cmap, start);
     } else {
         const size_t tiles_b = (bins + SPEC_TB - 1) / SPEC_TB, tiles_f = (frames + SPEC_TF - 1) / SPEC_TF;

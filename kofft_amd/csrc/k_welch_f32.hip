@@ -87,16 +87,9 @@ static int launch_fused(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float>
 template <bool CSD>
 static int launch_fused_l(kofft_hip_ctx *ctx, const WelchCall &c, const cpx<float> *tw, size_t g_first, size_t g_count, float *dst, bool final)
 {
-    switch (ilog2(c.src.win_len)) {
-    case 6: return launch_fused<6, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    case 7: return launch_fused<7, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    case 8: return launch_fused<8, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    case 9: return launch_fused<9, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    case 10: return launch_fused<10, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    case 11: return launch_fused<11, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    case 12: return launch_fused<12, CSD>(ctx, c, tw, g_first, g_count, dst, final);
-    default: return KOFFT_ERR_UNSUPPORTED;  // (never: welch_fused_fits)
-    }
+    // (never outside 6 .. 12: welch_fused_fits)
+    return dispatch_log2<6, 12>(ilog2(c.src.win_len),
+                                [&](auto l) { return launch_fused<decltype(l)::value, CSD>(ctx, c, tw, g_first, g_count, dst, final); });
 }
 
 // Rows of one group: one launch, scaled from the kernel.  Otherwise the partials of at most scratch_chunk_bytes of groups at a time,

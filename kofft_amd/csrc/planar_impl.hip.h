@@ -97,12 +97,6 @@ __global__ __launch_bounds__(256) void planar_unpack_kernel(const cpx<T> *z, T *
     }
 }
 
-inline unsigned planar_flat_blocks(const kofft_hip_ctx *ctx, size_t total)
-{
-    const size_t want = (total + 255) / 256, cap = (size_t)ctx->num_cus * 64;
-    return (unsigned)(want < cap ? want : cap);
-}
-
 template <typename T>
 int planar_composed_dev(kofft_hip_ctx *ctx, const T *re_in, const T *im_in, T *re_out, T *im_out, size_t n, size_t batch, int inverse)
 {
@@ -113,7 +107,7 @@ int planar_composed_dev(kofft_hip_ctx *ctx, const T *re_in, const T *im_in, T *r
     cpx<T> *z = static_cast<cpx<T> *>(ctx->real_tmp.p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk, total = nb * n, off = b0 * n;
-        const dim3 grid(planar_flat_blocks(ctx, total));
+        const dim3 grid(flat_blocks(ctx, total, 64));
         hipLaunchKernelGGL(planar_pack_kernel<T>, grid, dim3(256), 0, ctx->stream, re_in + off, im_in + off, z, total);
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         rc = fft_dev<T>(ctx, reinterpret_cast<T *>(z), reinterpret_cast<T *>(z), n, nb, inverse);

@@ -1,7 +1,8 @@
 // host_layout_check.cpp -- properties of the host staging layout (kofft_amd/csrc/host_layout.h) over seeded random array sets,
 // built with -fsanitize=address,undefined by tests/test_host_layout.py.  The pieces are laid into a real buffer of `total` bytes and
 // every chunk of every array is written through, so an offset or a chunk that leaves its piece is also a sanitizer report.
-// Then the scratch-chunk helper of the device routes' chunk loops (scratch_chunk_rows) and the parser of its size knob.
+// Then the scratch-chunk helper of the device routes' chunk loops (scratch_chunk_rows), the parser of its size knob and the dispatch
+// over a log2 (dispatch_log2).
 #include "../../kofft_amd/csrc/host_layout.h"
 
 #include <cstdio>
@@ -125,6 +126,28 @@ int main()
         size_t bytes = untouched;
         CHECK(!parse_scratch_chunk_mb(nullptr, &bytes) && bytes == untouched, "knob: a null string");
         CHECK(kScratchChunkDefaultBytes == (size_t)kScratchChunkMaxMb << 20, "the default is the ceiling");
+    }
+    // ---- dispatch_log2: every l of [LO, HI] reaches the instance of its own L and no other, an l outside reaches none and gives the
+    // default (KOFFT_ERR_UNSUPPORTED or the caller's); a range of one value.  (the calls stand in parentheses of their own: the comma of
+    // the template arguments would split CHECK's)
+    {
+        int calls = 0;
+        auto own = [&](auto l) { return ++calls, 1000 + decltype(l)::value; };
+        for (int l = 5; l <= 12; ++l) CHECK((dispatch_log2<5, 12>(l, own)) == 1000 + l, "dispatch_log2<5, 12>(%d)", l);
+        CHECK(calls == 8, "dispatch_log2<5, 12>: %d calls for 8 lengths", calls);
+        for (int l : {4, 13, 0, -1, 1 << 20}) {
+            CHECK((dispatch_log2<5, 12>(l, own)) == KOFFT_ERR_UNSUPPORTED, "dispatch_log2<5, 12>(%d): not the default", l);
+            CHECK((dispatch_log2<5, 12>(l, own, 77)) == 77, "dispatch_log2<5, 12>(%d): not the caller's default", l);
+        }
+        CHECK(calls == 8, "dispatch_log2<5, 12>: a call for a length outside the range");
+        CHECK((dispatch_log2<7, 7>(7, own)) == 1007 && calls == 9, "dispatch_log2<7, 7>(7)");
+        CHECK((dispatch_log2<7, 7>(6, own)) == KOFFT_ERR_UNSUPPORTED && (dispatch_log2<7, 7>(8, own, 0)) == 0 && calls == 9, "dispatch_log2<7, 7>: outside");
+        // (a body that names an instance outside [LO, HI] does not compile: the static_assert is the "nothing else" check)
+        auto only = [](auto l) {
+            static_assert(decltype(l)::value >= 6 && decltype(l)::value <= 11, "an instance outside the range");
+            return (int)decltype(l)::value;
+        };
+        for (int l = 6; l <= 11; ++l) CHECK((dispatch_log2<6, 11>(l, only)) == l, "dispatch_log2<6, 11>(%d)", l);
     }
     std::printf("%d problems\n", problems);
     return problems ? 1 : 0;

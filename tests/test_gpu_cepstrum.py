@@ -1,6 +1,6 @@
 """cepstrum::real_cepstrum (cepstrum.rs:12-33) on the device, bit for bit against tests/cepstrum_oracle.py.  Powers of two 32 .. 4096 run
 cepstrum_fused_kernel<5 .. 12> (one launch); every other length -- and every length in a context with set_cepstrum_fused(False) -- runs
-hilbert_expand_kernel -> fft_dev (in place, in the context's scratch) -> cepstrum_logmag_kernel -> fft_dev(inverse) -> cepstrum_real_kernel,
+expand_real_kernel -> fft_dev (in place, in the context's scratch) -> cepstrum_logmag_kernel -> fft_dev(inverse) -> cepstrum_real_kernel,
 whose batch ladders are there for fft_dev's routes: the one-thread kernels, the workgroup kernel, every persistent-kernel threshold of the
 n-point transform (host_common.hip.h: dispatch; the per-CU factors are restated below, as test_gpu_hilbert.py does), the register-file
 kernel at 2^15 and the factor path above.  The libm crate's logf (libm_logf.hip.h) has no entry point of its own: the cepstra of these

@@ -1,7 +1,7 @@
 """Overlap-save convolution / correlation of rows on the device, bit for bit against tests/convolve_oracle.py.  Blocks
-32 .. 4096 run convolve_fused_kernel<5 .. 12> (one launch after the filter's spectrum); every other block -- and every block in a
-context with set_convolve_fused(False) -- runs convolve_expand_kernel -> fft_dev -> convolve_mul_kernel -> fft_dev(inverse) ->
-convolve_gather_kernel through the context's scratch.  Every call runs twice and its two results are compared; the default context and
+32 .. 4096 run convolve_fused_kernel<5 .. 12> (one launch after the filter's spectrum: convolve_bank_filter_kernel with real taps,
+fft_dev); every other block -- and every block in a context with set_convolve_fused(False) -- runs convolve_expand_kernel -> fft_dev ->
+convolve_mul_kernel -> fft_dev(inverse) -> convolve_bank_gather_kernel<BankReal> (one filter) through the context's scratch.  Every call runs twice and its two results are compared; the default context and
 the composed one get the same inputs and must give the same bytes."""
 import numpy as np
 import pytest

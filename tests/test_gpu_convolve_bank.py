@@ -2,8 +2,8 @@
 bit against tests/convolve_bank_oracle.py.  Blocks 32 .. 4096 run convolve_bank_fused_kernel<5 .. 12, kind> (one launch after the
 filters' spectra: convolve_bank_filter_kernel, fft_dev); every other block -- and every block in a context with
 set_convolve_bank_fused(False), or with x off 4-byte alignment -- runs convolve_expand_kernel -> fft_dev once per chunk, then per
-filter convolve_bank_mul_kernel -> fft_dev(inverse) -> convolve_bank_gather_kernel<kind>.  Every call runs twice and its two results
-are compared; the default context and the composed one get the same inputs and must give the same bytes."""
+filter convolve_bank_mul_kernel -> fft_dev(inverse) -> convolve_bank_gather_kernel<kind>.  The filter and gather kernels are the
+one-filter family's too (test_gpu_convolve.py).  Every call runs twice and its two results are compared; the default context and the composed one get the same inputs and must give the same bytes."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """hilbert::hilbert_analytic (hilbert.rs:13-47) on the device, bit for bit against tests/hilbert_oracle.py.  Powers of two 32 .. 4096
 run hilbert_fused_kernel<5 .. 12> (one launch); every other length -- and every length in a context with set_hilbert_fused(False) --
-runs hilbert_expand_kernel -> fft_dev (in place) -> hilbert_mask_kernel -> fft_dev(inverse), whose batch ladders are there for
+runs expand_real_kernel -> fft_dev (in place) -> hilbert_mask_kernel -> fft_dev(inverse), whose batch ladders are there for
 fft_dev's routes: the one-thread kernels, the workgroup kernel, every persistent-kernel threshold of the n-point transform (host_common.hip.h:
 dispatch; the per-CU factors are restated below, as test_gpu_dct.py does), the register-file kernel at 2^15 and the factor path above."""
 import numpy as np
