@@ -12,9 +12,8 @@ namespace host {
 // large n: two factors (fft_big.hip.h)
 // ---------------------------------------------------------------------------------
 
-#ifndef KOFFT_ROWS_C32_CAP_KB
-#define KOFFT_ROWS_C32_CAP_KB 80
-#endif
+// LDS per workgroup (KiB) up to which the c32 rows kernel widens its tile (launch_rows_persist has the measurement)
+constexpr int kRowsC32CapKb = 80;
 // units (columns / rows) per CU from which the persistent factor kernels run: every resident workgroup gets several tiles
 constexpr size_t kBigPersistMinUnits = 32;
 
@@ -63,7 +62,7 @@ int launch_rows_persist(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size
     constexpr int RL = rl_for(LS);
     // (c32 rows of 2^10 points: 16-row tiles need 1024 threads at 128 registers and spill 30 of them -- measured slower
     // than 8-row tiles at 512 threads, 2^19: 0.244 vs 0.282 of the roofline)
-    constexpr int BLOCK = big_block<T, IO, LS, (sizeof(T) == 4 ? KOFFT_ROWS_C32_CAP_KB : 128) * 1024>();
+    constexpr int BLOCK = big_block<T, IO, LS, (sizeof(T) == 4 ? kRowsC32CapKb : 128) * 1024>();
     constexpr int TPT = (1 << LS) >> RL;
     constexpr int XPB = BLOCK / TPT;
     constexpr size_t lds = TileExchange<T, LS, RL, XPB, IO::kSplitLds>::bytes + (size_t)rows_tw_entries<LS, RL>() * XPB * sizeof(cpx<T>);
@@ -282,7 +281,7 @@ template <bool INV> struct rows_pair_io<BigRowsIO<float, INV, POST_NONE>> {
 };
 
 template <typename T>
-inline int big_rows_per_wg(int LB) { return LB <= 9 ? KOFFT_BIG_XPB(T) : LB == 10 ? 8 : LB == 11 ? 4 : LB == 12 ? 2 : 1; }
+inline int big_rows_per_wg(int LB) { return LB <= 9 ? big_xpb<T>() : LB == 10 ? 8 : LB == 11 ? 4 : LB == 12 ? 2 : 1; }
 
 // units (columns / rows) per tile of the two persistent factor kernels, as launch_tile_persist / launch_rows_persist compute them
 struct NoIO {};
@@ -306,7 +305,7 @@ inline int rows_persist_xpb(int LS)
 {
     switch (LS) {
 #define KOFFT_CASE(LL) \
-    case LL: return big_block<T, NoIO, LL, (sizeof(T) == 4 ? KOFFT_ROWS_C32_CAP_KB : 128) * 1024>() / ((1 << LL) >> rl_for(LL));
+    case LL: return big_block<T, NoIO, LL, (sizeof(T) == 4 ? kRowsC32CapKb : 128) * 1024>() / ((1 << LL) >> rl_for(LL));
         KOFFT_CASE(7)
         KOFFT_CASE(8)
         KOFFT_CASE(9)
@@ -448,12 +447,9 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         // Both factors on their persistent kernels (the conditions of launch_sub and of the rows branch below): the intermediate
         // is then block-interleaved -- see BigColsIO::out_lane.
         const bool rows_resident = ctx->big_persist && (nb << (L - L3)) >= persist_units && L3 >= 7 && L3 <= 10;
-        // c64 only.  On identical buffers (tools/exp_c64_blocked.py, profiles/r04_c64_blocked_ab.txt): equal where the intermediate's
+        // c64 only.  On identical buffers (profiles/r04_c64_blocked_ab.txt; its script is in git history): equal where the intermediate's
         // placement is fast, last factor 218-223 -> 203-207 us per chunk where it is slow, never slower.  c32 2^18 .. 2^20
         // lost 4-6 % in process-level A/Bs (0.324 / 0.315 / 0.284 -> 0.305 / 0.295 / 0.269) and keeps the natural layout.
-#ifndef KOFFT_BLOCKED_C32
-#define KOFFT_BLOCKED_C32 0 /* measurement builds: the block-interleaved intermediate for c32 too */
-#endif
         // c32: the last factor on PAIRS of adjacent rows (BigRowsIO<f32x2>: two Complex<f32> values as one 16-byte value through the c64
         // kernel's structure -- 16-row tiles at 512 threads, 128-byte runs on both sides) when its policy has no folded pointwise factor; the
         // first factor then interleaves the rows of a pair (blk_r = 1: 256-byte runs per wavefront store).
@@ -466,7 +462,7 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
                 a.blk_c = 0;
             }
         }
-        if ((sizeof(T) == 8 || KOFFT_BLOCKED_C32) && ctx->big_blocked && !three && ctx->big_persist && (nb << (L - L1)) >= persist_units && L1 >= 7 && L1 <= 10 && rows_resident) {
+        if (sizeof(T) == 8 && ctx->big_blocked && !three && ctx->big_persist && (nb << (L - L1)) >= persist_units && L1 >= 7 && L1 <= 10 && rows_resident) {
             a.blk_c = ilog2((size_t)tile_persist_xpb<T>(L1));
             a.blk_r = ilog2((size_t)rows_persist_xpb<T>(L3));
         }
@@ -512,11 +508,7 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         // to 2^9 points) a load is sixteen 32-byte pieces, the rest of each line is wanted by the neighbouring wavefronts a
         // moment later, and a streaming load does not keep it for them (measured, 2 GiB batches: c32 2^15..2^18 0.275-0.295 ->
         // 0.304-0.314 with plain loads, 2^22 0.190 -> 0.198; c32 2^19..2^21 and every c64 size lose 3-10 % without the hint).
-#if KOFFT_BLOCKED_C32 == 2 /* ... with streaming loads of its 512-byte runs */
-        const size_t load_piece = (size_t)(b.blk_r != 0 ? 64 : 64 / big_rows_per_wg<T>(L3)) * sizeof(cpx<T>);
-#else
         const size_t load_piece = (size_t)(64 / big_rows_per_wg<T>(L3)) * sizeof(cpx<T>);
-#endif
         b.nt_load = nb * xf_bytes > (size_t(192) << 20) && load_piece >= 64;
         rc = KOFFT_ERR_UNSUPPORTED;
         // last factor: rows resident (table entries per row tile in LDS) for batches, else one tile per workgroup (two 512-thread workgroups
@@ -537,11 +529,10 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         return rc;
     };
     if (ctx->big_tmp.bytes < need) {
-        if (ctx->big_tmp_external) return KOFFT_ERR_ALLOC;
         if (ctx->big_tmp.p) KOFFT_HIP_TRY(ctx, hipFree(ctx->big_tmp.p));
         ctx->big_tmp = DevBuf{};
         ctx->big_probe_n = 0;
-        // (Round 4, tools/exp_c64_alloc.py: a physically contiguous buffer -- hipExtMallocWithFlags(hipDeviceMallocContiguous) -- made
+        // (Round 4, a script since removed: a physically contiguous buffer -- hipExtMallocWithFlags(hipDeviceMallocContiguous) -- made
         // the last factor's reads fast on one box (188-192 us per 512 MiB chunk on 16 of 16 buffers against 217-231 us on most plain
         // ones) but not on the next (4 of 5 slow), slowed the first factor's writes by 10 % on both, and small contiguous buffers
         // returned stale data to the plain loads of the narrow-tile kernels: not used.)
@@ -564,9 +555,6 @@ int fft_big_core(kofft_hip_ctx *ctx, const cpx<T> *in_base, size_t in_row, cpx<T
         }
     }
     cpx<T> *mid0 = static_cast<cpx<T> *>(ctx->big_tmp.p);
-#ifdef KOFFT_EXP_TMP_PRINT
-    fprintf(stderr, "kofft big_tmp %p mid %p\n", ctx->big_tmp.p, (void *)mid0);
-#endif
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = (batch - b0 < chunk) ? batch - b0 : chunk;
         rc = run_chunk(in_base + b0 * in_row, out_base + b0 * out_row, mid0, nb, nullptr);
@@ -673,9 +661,7 @@ constexpr int blue_persist_wg(int L)
 }
 // from one full round of the grid on (measured: n = 1000 x 1100 0.018 -> 0.016 ms, x 2100 0.029 -> 0.023, x 4000 0.042 -> 0.037; n = 250 x 9000
 // 0.022 -> 0.018; n = 60 x 30000 0.017 -> 0.014; with a threshold of four rounds these ran the one-workgroup-per-XPB-transforms kernel)
-#ifndef KOFFT_BLUE_PERSIST_MIN_ITERS
-#define KOFFT_BLUE_PERSIST_MIN_ITERS 1
-#endif
+constexpr int kBluePersistMinIters = 1;
 template <typename T, int L>
 constexpr bool blue_persist_ok()
 {
@@ -716,7 +702,7 @@ template <typename T, int L>
 bool blue_persist_pays(const kofft_hip_ctx *ctx, size_t batch)
 {
     constexpr int XPB = blue_persist_block<T>(L) / ((1 << L) >> blue_persist_rl<T>(L));
-    return ctx->blue_persist && batch >= (size_t)ctx->num_cus * blue_persist_wg<T>(L) * XPB * KOFFT_BLUE_PERSIST_MIN_ITERS;
+    return ctx->blue_persist && batch >= (size_t)ctx->num_cus * blue_persist_wg<T>(L) * XPB * kBluePersistMinIters;
 }
 
 // STFT with a window length that is not a power of two (stft.rs:91-103 calls fft.fft(frame) for any win_len): the frames through the

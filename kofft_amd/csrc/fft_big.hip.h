@@ -440,11 +440,7 @@ __device__ __forceinline__ void wg_exchange_b128(cpx<T> *v, char *base, const in
 // which exchange a persistent factor kernel uses, and how many bytes it needs
 template <typename T, int L, int RL, int XPB, bool SPLIT>
 struct TileExchange {
-#ifdef KOFFT_TILE_SPLIT_ONLY
-    static constexpr bool kWhole = false;
-#else
     static constexpr bool kWhole = SPLIT && L == 10 && RL == 4 && XPB == 8 && sizeof(cpx<T>) == 16;
-#endif
     static constexpr size_t bytes = kWhole ? (size_t)XPB * (1 << L) * sizeof(cpx<T>) : lds_wg_bytes<T, SPLIT, true, XPB>(1 << L);
     template <int P>
     __device__ static __forceinline__ void run(cpx<T> *v, char *base, const int tau, const int slot)
@@ -675,13 +671,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 1024 ? 4 : 2)) void fft_tile_persi
     cpx<T> ra[R], rb[R];
     if (pre_resident) pre_request(tile);
     issue_loads(ra, tile, true);
-#ifdef KOFFT_TILE_NO_MEM /* measurement only: the arithmetic and the exchanges without global traffic inside the loop */
-#define KOFFT_TILE_PREFETCH(CUR, NXT)
-#define KOFFT_TILE_RUN(CUR) run_tile(ra, tile, !more)
-#else
-#define KOFFT_TILE_PREFETCH(CUR, NXT) issue_loads(NXT, ntile, more);
-#define KOFFT_TILE_RUN(CUR) run_tile(CUR, tile, true)
-#endif
 #define KOFFT_TILE_STEP(CUR, NXT)                                                                        \
     {                                                                                                    \
         const size_t ntile = next_tile(tile);                                                            \
@@ -691,9 +680,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 1024 ? 4 : 2)) void fft_tile_persi
             if constexpr (PRE_MODE == 2) pre_product(CUR, tile);                                         \
             __builtin_amdgcn_sched_barrier(0); /* the table entries are requested ahead of the prefetch */ \
         }                                                                                                \
-        KOFFT_TILE_PREFETCH(CUR, NXT)                                                                    \
+        issue_loads(NXT, ntile, more);                                                                   \
         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of the first use of CUR */         \
-        KOFFT_TILE_RUN(CUR);                                                                             \
+        run_tile(CUR, tile, true);                                                                       \
         if (!more) break;                                                                                \
         tile = ntile;                                                                                    \
         __syncthreads(); /* the last gathers of this tile are done before the next tile's first scatter */ \
@@ -708,9 +697,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 1024 ? 4 : 2)) void fft_tile_persi
             KOFFT_TILE_STEP(ra, rb)
         }
     } while (false);
-#undef KOFFT_TILE_RUN
 #undef KOFFT_TILE_STEP
-#undef KOFFT_TILE_PREFETCH
 }
 
 // ---- last factor, persistent, twiddles RESIDENT per row tile ---------------------------------------------------------
@@ -1208,14 +1195,11 @@ struct BlueStftSrc {
     }
 };
 
-#ifndef KOFFT_BLUE_CHIRP_REG
-#define KOFFT_BLUE_CHIRP_REG 1 /* 0: measurement builds -- the input product's chirp entries read per transform, as in rounds 4-5 */
-#endif
 template <typename T>
 __host__ __device__ constexpr bool bluestein_chirp_resident(int L, int wg_per_cu)
 {
     // f32, two workgroups of 256 threads per CU (256 registers each: m = 2048 / 4096 use 208 / 194 + 16)
-    return KOFFT_BLUE_CHIRP_REG && sizeof(T) == 4 && wg_per_cu <= 2 && (L == 11 || L == 12);
+    return sizeof(T) == 4 && wg_per_cu <= 2 && (L == 11 || L == 12);
 }
 template <typename T, int L, int RL, int BLOCK, int WG_PER_CU, bool INVERSE, class SRC = BlueRowsSrc<T, INVERSE>>
 __global__ __launch_bounds__(BLOCK, WG_PER_CU * BLOCK / 256 /* wavefronts per SIMD */) void bluestein_persist_kernel(const SRC src, cpx<T> *__restrict__ out,
@@ -1255,7 +1239,7 @@ __global__ __launch_bounds__(BLOCK, WG_PER_CU * BLOCK / 256 /* wavefronts per SI
     const int g2 = NP >= 3 ? lds_pad(WgGeom<L, RL, (NP >= 3 ? 2 : 0)>::in_index(tau, 0)) : 0;
     const int g3 = NP >= 4 ? lds_pad(WgGeom<L, RL, (NP >= 4 ? 3 : 0)>::in_index(tau, 0)) : 0;
     // The chirp entries of the INPUT product (R / 2 of them: the upper half of the padded input is zeros) depend on the thread only.  Read per
-    // transform at the top of its work they cost an exposed L2 round trip each time; where the register budget allows (KOFFT_BLUE_CHIRP_REG)
+    // transform at the top of its work they cost an exposed L2 round trip each time; where the register budget allows (bluestein_chirp_resident)
     // they are read once (round 6).
     constexpr bool CH_REG = bluestein_chirp_resident<T>(L, WG_PER_CU);
     cpx<T> chin[CH_REG ? R / 2 : 1];

@@ -58,19 +58,11 @@ __device__ __forceinline__ void st_stream(cpx<T> *p, cpx<T> v)
     vec2 f;
     f.x = v.re;
     f.y = v.im;
-#ifdef KOFFT_PLAIN_STORES
-    *reinterpret_cast<vec2 *>(p) = f;
-#else
     __builtin_nontemporal_store(f, reinterpret_cast<vec2 *>(p));
-#endif
 }
 __device__ __forceinline__ void st_stream(float *p, float v)
 {
-#ifdef KOFFT_PLAIN_STORES
-    *p = v;
-#else
     __builtin_nontemporal_store(v, p);
-#endif
 }
 
 // ---- buffer (SRSRC) addressing for the streaming kernels ---------------------------------------------
@@ -119,9 +111,7 @@ __device__ __forceinline__ cpx<T> buf_load_cpx(rsrc_t r, int voff, int coff)
     }
 }
 
-#ifndef KOFFT_STORE_AUX
-#define KOFFT_STORE_AUX AUX_NT  // outputs are written once and not read back by the kernel (see st_stream)
-#endif
+constexpr int kStoreAux = AUX_NT;  // outputs are written once and not read back by the kernel (see st_stream)
 // A 16-byte store of a Complex<f64> whose data registers the next f64 VALU instruction overwrites (round 6).  The compiler reuses ONE
 // register quadruple for a loop of "value * scale -> store" (ifft's scaling, the rfft post-pass, Bluestein's products):
 //     v_mul_f64 v[66:67], ..   v_mul_f64 v[68:69], ..   buffer_store_dwordx4 v[66:69], v1, s[12:15], s61 offen
@@ -130,7 +120,7 @@ __device__ __forceinline__ cpx<T> buf_load_cpx(rsrc_t r, int voff, int coff)
 // inserts `s_nop 1` -- but only when the store's soffset field is NOT an SGPR, as the SI-era documents say; every store here carries
 // its compile-time offset in an SGPR soffset (one VGPR of address for all of a thread's stores).  On gfx950 with f64 VALU
 // instructions the hazard is real with an SGPR soffset too: large c64 batches returned, in a few transforms per thousand, ONE
-// register's real part replaced by the next store's in lanes 12-15 of every row of 16 (tools/dbg_f64.py; the imaginary part, written
+// register's real part replaced by the next store's in lanes 12-15 of every row of 16 (the imaginary part, written
 // one instruction later, always arrived).  Found when tools/kernel_coverage.sh showed that the parity tests had stopped reaching
 // these kernels (the host pipeline cut their batches into eight).  The wait states are pinned to the store by an asm statement that
 // READS the stored registers: side effects keep it behind the store, the anti-dependence keeps every overwrite behind it.
@@ -155,11 +145,11 @@ __device__ __forceinline__ void buf_store_cpx(cpx<T> c, rsrc_t r, int voff, int 
     f.y = c.im;
     if constexpr (sizeof(T) == 4) {
         typedef unsigned v2u __attribute__((ext_vector_type(2)));
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, f), r, voff, coff, KOFFT_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, f), r, voff, coff, kStoreAux);
     } else {
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
         const v4u bits = __builtin_bit_cast(v4u, f);
-        __builtin_amdgcn_raw_buffer_store_b128(bits, r, voff, coff, KOFFT_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(bits, r, voff, coff, kStoreAux);
         b128_store_guard(bits);
     }
 }
@@ -195,7 +185,7 @@ __device__ __forceinline__ void buf_store_cpx_aux(cpx<T> c, rsrc_t r, int voff, 
 
 __device__ __forceinline__ void buf_store_f32(float v, rsrc_t r, int voff, int coff)
 {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, coff, KOFFT_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, coff, kStoreAux);
 }
 
 template <int AUX>
@@ -218,7 +208,7 @@ __device__ __forceinline__ cpx<T> cmul(cpx<T> a, cpx<T> b)
 // One Stockham butterfly, in place on (e, o).  fft.rs:881-893:
 //   t_re = o.re*w.re - o.im*w.im ; t_im = o.re*w.im + o.im*w.re   (4 mul, 1 sub, 1 add, un-fused)
 //   e' = e + t ; o' = e - t
-// Generic form (f64, and f32 when KOFFT_BFLY_NOASM is defined):
+// Generic form (f64):
 template <typename T>
 __device__ __forceinline__ void bfly_generic(cpx<T> &e, cpx<T> &o, const cpx<T> w)
 {
@@ -280,7 +270,6 @@ __device__ __forceinline__ v2f rfft_post_f32_pk(const v2f w, const v2f a, const 
 template <typename T, bool W_UNIFORM = false>
 __device__ __forceinline__ void bfly(cpx<T> &e, cpx<T> &o, const cpx<T> w)
 {
-#ifndef KOFFT_BFLY_NOASM
     if constexpr (sizeof(T) == 4) {
         v2f ev = {e.re, e.im}, ov = {o.re, o.im};
         const v2f wv = {w.re, w.im};
@@ -291,7 +280,6 @@ __device__ __forceinline__ void bfly(cpx<T> &e, cpx<T> &o, const cpx<T> w)
         o.im = ov.y;
         return;
     }
-#endif
     bfly_generic(e, o, w);
 }
 

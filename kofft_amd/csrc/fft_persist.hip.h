@@ -65,14 +65,11 @@ using PassGeom = WgGeom<L, RL, P>;
 // Cells between the exchange buffers of consecutive transforms.  Where one wavefront carries four transforms (n = 64, 128) a
 // ds_read_b64's 32-lane group spans TWO of them: with the buffers 16 cells (mod 32) apart the second transform's 16 cells --
 // a run in natural order (the rfft epilogue, irfft's staged row), or the first one's pattern shifted -- fall on the banks the
-// first leaves free (KOFFT_PERSIST_SLOT16; simulated tests/test_lds_layout.py-style: n = 128 63 -> 16 conflict cycles per transform).
-#ifndef KOFFT_PERSIST_SLOT16
-#define KOFFT_PERSIST_SLOT16 1
-#endif
+// first leaves free (simulated tests/test_lds_layout.py-style: n = 128 63 -> 16 conflict cycles per transform).
 __host__ __device__ constexpr int persist_slot_elems(int L)
 {
     int e = lds_elems(1 << L);
-    if (KOFFT_PERSIST_SLOT16 && L <= 7)
+    if (L <= 7)
         while ((e & 31) != 16) ++e;
     return e;
 }
@@ -80,9 +77,7 @@ __host__ __device__ constexpr int persist_slot_elems(int L)
 // The rfft epilogue of a wavefront that carries several transforms stores the group's output as ONE stream (see persist_transform).
 // Measured on one box, rfft32, fraction of the roofline: n = 256 0.63 -> 0.69, n = 512 unchanged; n = 128 0.62 -> 0.60 at
 // two workgroups per CU but 0.66 at three (PersistGrid<6>), where the row-by-row form drops to 0.61.
-#ifndef KOFFT_PERSIST_RFFT_GROUP_MIN_L
-#define KOFFT_PERSIST_RFFT_GROUP_MIN_L 6
-#endif
+constexpr int kPersistRfftGroupMinL = 6;
 
 template <typename T, int L, int RL, int P>
 __device__ __forceinline__ void persist_load_tw(cpx<T> *twr, const int tau, const cpx<T> *__restrict__ tw)
@@ -181,10 +176,7 @@ struct persist_claim<CFG, decltype((void)CFG::kClaim)> { static constexpr bool v
 // The context owns kPersistClaimMaxShards + 1 lines: the claim words first, the LAST line's word counts the workgroups that have found
 // every shard empty; the last of them stores zeros to every word the kernel uses, so that the next launch on the context's stream starts
 // from zero without any host-side reset (launch_persist; the context zeroes them once when it allocates them).
-#ifndef KOFFT_C12_CLAIM_SHARDS
-#define KOFFT_C12_CLAIM_SHARDS 2  // (A/B: 1 .. 8)
-#endif
-constexpr unsigned kPersistClaimShards = KOFFT_C12_CLAIM_SHARDS, kPersistClaimMaxShards = 8, kPersistClaimLine = 128 / sizeof(unsigned);
+constexpr unsigned kPersistClaimShards = 2, kPersistClaimMaxShards = 8, kPersistClaimLine = 128 / sizeof(unsigned);
 static_assert(kPersistClaimShards >= 1 && kPersistClaimShards <= kPersistClaimMaxShards, "claim words");
 constexpr size_t kPersistClaimBytes = (kPersistClaimMaxShards + 1) * 128;
 // (round 9) Everything above speaks of WALK indices w in [0, batch): the stride walk, split, the shards and the tickets.  The memory row
@@ -212,24 +204,6 @@ struct NoXchg {
     __device__ __forceinline__ void put() const {}
     __device__ __forceinline__ void get() const {}
 };
-
-#ifdef KOFFT_PERSIST_STAMPS /* diagnostic builds only (tools/persist_progress.py): one record per workgroup, written by lane 0 of its first wavefront */
-constexpr int kPersistStampWgs = 4096, kPersistStampWords = 16;
-static __device__ unsigned long long g_persist_stamps[kPersistStampWgs * kPersistStampWords];
-__device__ __forceinline__ unsigned long long persist_stamp()
-{
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-// the constant 100 MHz clock: the one to compare workgroups on different XCDs by
-__device__ __forceinline__ unsigned long long persist_stamp_real()
-{
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-#endif
 
 // Everything a thread keeps across transforms.
 // CFG (kofft_hip.hip: PersistCfg<L, IO>) carries the per-size, per-policy choices: BLOCK, NBUF, MINW and where the
@@ -283,10 +257,7 @@ struct persist_acc<IO, true> { using type = typename IO::Acc; };
 // first (persist_load_tw), so that the order "entries, then the part, then the butterflies" is the program's, not the scheduler's.
 // (a part at the top of the step too -- pass 0 reads its entries through scalar loads -- measured better at n = 4096, two workgroups per CU, and worse
 // at n = 8192, one: same box, three rounds, against round 5's kernels 4096 +5.4 % with, +3.8 % without; 8192 +1.5 % with, +3.6 % without)
-#ifndef KOFFT_TWG_TOP_PART
-#define KOFFT_TWG_TOP_PART -1 /* -1: by size; 0 / 1: measurement builds */
-#endif
-__host__ __device__ constexpr bool persist_twg_top_part(int L) { return KOFFT_TWG_TOP_PART < 0 ? L <= 12 : KOFFT_TWG_TOP_PART != 0; }
+__host__ __device__ constexpr bool persist_twg_top_part(int L) { return L <= 12; }
 struct NoPrefetchParts {
     __device__ __forceinline__ void operator()(int) const {}
 };
@@ -408,7 +379,7 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
             for (int u = 0; u < R; ++u) p[LastG::out_index(0, u)] = cur[u];
         }
         exchange_sync<WAVE>();
-        if constexpr (GRP > 1 && L >= KOFFT_PERSIST_RFFT_GROUP_MIN_L) {
+        if constexpr (GRP > 1 && L >= kPersistRfftGroupMinL) {
             // A wavefront holds GRP transforms whose output rows are adjacent in memory: GRP * (N + 1) values back to back.
             // The stores walk that STREAM, not the rows: lane l of store s handles stream element e = 64 s + l - a, where
             // a is the stream's offset into its 128-byte line, so every store instruction covers four whole lines and a row
@@ -525,12 +496,9 @@ __device__ __forceinline__ void persist_transform(const typename persist_raw<IO,
                 for (int u = 0; u < R; ++u) io.template store_d<AUX_DEFAULT>(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
             } else {
 #pragma unroll
-                for (int u = 0; u < R; ++u) io.template store_d<KOFFT_STORE_AUX>(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
+                for (int u = 0; u < R; ++u) io.template store_d<kStoreAux>(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off);
             }
         } else {
-#ifdef KOFFT_PERSIST_ACTIVE_BRANCH /* measurement only (tools/build_variant.sh): rounds 1-4's branch around the stores, for same-box A/Bs */
-        if (active)
-#endif
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             if constexpr (io_has_acc<IO>::value) io.store_d_acc(od, lane_bytes, LastG::out_index(0, u), cur[u], row_off, acc);
@@ -623,21 +591,6 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     const size_t step = (size_t)gridDim.x * XPB;
     size_t base = (size_t)blockIdx.x * XPB;
     constexpr bool CLAIMS = persist_claim<CFG>::value;
-#ifdef KOFFT_PERSIST_STAMPS
-    const unsigned long long stamp_entry = persist_stamp(), stamp_entry_real = persist_stamp_real();
-    unsigned long long stamp_landed = 0, stamp_landed_real = 0, stamp_rows = 0;
-#define KOFFT_PERSIST_STAMP_LANDED()                                                                                  \
-    {                                                                                                                 \
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RS) : "memory"); /* everything in front of the next row's loads */    \
-        stamp_landed = persist_stamp();                                                                               \
-        stamp_landed_real = persist_stamp_real();                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                            \
-    }
-#define KOFFT_PERSIST_STAMP_ROW() ++stamp_rows;
-#else
-#define KOFFT_PERSIST_STAMP_LANDED()
-#define KOFFT_PERSIST_STAMP_ROW()
-#endif
     // (claim hand-out) the row after `base`, and the LDS words the claims travel through
     [[maybe_unused]] size_t nbase = 0;
     [[maybe_unused]] unsigned long long *claim_word = nullptr;
@@ -753,22 +706,6 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
     auto finish = [&]() {
         if constexpr (io_has_acc<IO>::value) io.acc_finish(acc);
         if constexpr (CLAIMS) claim_leave();
-#ifdef KOFFT_PERSIST_STAMPS
-        if (tid == 0 && blockIdx.x < kPersistStampWgs) {
-            unsigned long long *rec = g_persist_stamps + (size_t)blockIdx.x * kPersistStampWords;
-            rec[0] = stamp_entry;
-            rec[1] = stamp_landed;
-            rec[2] = persist_stamp();  // the last row's stores have been issued
-            rec[3] = stamp_entry_real;
-            rec[4] = stamp_landed_real;
-            rec[5] = persist_stamp_real();
-            rec[6] = stamp_rows;
-            rec[7] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID, all 32 bits
-            rec[8] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
-            rec[9] = gridDim.x;
-            rec[10] = 1;  // record written
-        }
-#endif
     };
 
     if constexpr (CLAIMS) {
@@ -821,26 +758,20 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         __builtin_amdgcn_sched_barrier(0); /* the claim in front of the prefetch */                                  \
         issue(NXT, nbase);                                                                                           \
         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of CUR's first use */                          \
-        KOFFT_PERSIST_STEP_STAMP                                                                                     \
         const ClaimXchg xchg{claim_word, io.claim.split + (size_t)claim_shard * claim_piece, claim_len(claim_shard), &ticket, &claimed, claims, \
                              __builtin_amdgcn_readfirstlane((unsigned)(base >= io.claim.keep_from)) != 0u}; \
         persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, mem_row(base) + wslot, group_cnt(base), sub, tau, acc, NoPrefetchParts{}, xchg); \
-        KOFFT_PERSIST_STAMP_ROW()                                                                                    \
         if (!more) LEAVE;                                                                                            \
         /* (workgroup-uniform, and said so: the upper half of the word every lane has read; no row has all its bits set) */ \
         if (!walked && __builtin_amdgcn_readfirstlane((unsigned)(claimed >> 32)) == ~0u) claimed = claim_walk_on();   \
         base = nbase;                                                                                                \
         nbase = walked ? nbase + step : (size_t)claimed; /* (every shard exhausted: batch) */                        \
     }
-#define KOFFT_PERSIST_STEP_STAMP KOFFT_PERSIST_STAMP_LANDED()
         KOFFT_PERSIST_STEP_CLAIM(ra, rb, { finish(); return; })
-#undef KOFFT_PERSIST_STEP_STAMP
-#define KOFFT_PERSIST_STEP_STAMP
         for (;;) {
             KOFFT_PERSIST_STEP_CLAIM(rb, ra, break)
             KOFFT_PERSIST_STEP_CLAIM(ra, rb, break)
         }
-#undef KOFFT_PERSIST_STEP_STAMP
         finish();
 #undef KOFFT_PERSIST_STEP_CLAIM
     } else if constexpr (DEPTH == 1 && St::TWG && !(RawSel::pair || RawSel::pair_lds)) {
@@ -879,9 +810,7 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         const bool more = nbase < batch; /* workgroup-uniform */                                                     \
         issue(NXT, nbase);                                                                                           \
         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ahead of CUR's first use */                          \
-        KOFFT_PERSIST_STEP_STAMP                                                                                                     \
         persist_transform<T, L, RL, EPI, CFG>(CUR, st, io, tw, buf0, buf1, base + wslot, group_cnt(base), sub, tau, acc); \
-        KOFFT_PERSIST_STAMP_ROW()                                                                                    \
         if (!more) LEAVE;                                                                                            \
         base = nbase;                                                                                                \
     }
@@ -890,15 +819,11 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
         // With the first step inside the loop the compiler must merge the entry state (no stores yet) with the back-edge
         // state and emits vmcnt(15 - i) for both -- which, on the back edge, waits for the previous transform's STORES to
         // complete, once per two transforms.  After the peel both predecessors of the loop header look the same.
-#define KOFFT_PERSIST_STEP_STAMP KOFFT_PERSIST_STAMP_LANDED()
         KOFFT_PERSIST_STEP(ra, rb, { finish(); return; })
-#undef KOFFT_PERSIST_STEP_STAMP
-#define KOFFT_PERSIST_STEP_STAMP
         for (;;) {
             KOFFT_PERSIST_STEP(rb, ra, break)
             KOFFT_PERSIST_STEP(ra, rb, break)
         }
-#undef KOFFT_PERSIST_STEP_STAMP
         finish();
 #undef KOFFT_PERSIST_STEP
     } else {
@@ -928,8 +853,5 @@ __global__ __launch_bounds__(CFG::BLOCK, CFG::MINW) void fft_persist_kernel(cons
 #undef KOFFT_PERSIST_STEP2
     }
 }
-
-#undef KOFFT_PERSIST_STAMP_LANDED
-#undef KOFFT_PERSIST_STAMP_ROW
 
 }  // namespace kofft

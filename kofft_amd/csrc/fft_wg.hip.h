@@ -70,22 +70,13 @@ struct PlainTw {
     __device__ __forceinline__ TwPlain tw_map(size_t) const { return {}; }
 };
 
-#ifndef KOFFT_STFT_SMALL_BLOCK32
-#define KOFFT_STFT_SMALL_BLOCK32 64
-#endif
-#ifndef KOFFT_SMALL_BLOCK
-#define KOFFT_SMALL_BLOCK 256
-#endif
-#ifndef KOFFT_C64_SMALL_BLOCK
-#define KOFFT_C64_SMALL_BLOCK 64
-#endif
-#ifndef KOFFT_C_LOAD_AUX
-#define KOFFT_C_LOAD_AUX AUX_NT  // cache policy of the complex kernels' descriptor loads (A/B hook: tools/exp_inplace_ab.py)
-#endif
+// fft_small_kernel's workgroup sizes: every n, n = 32, and the policies that ask for their own (measured at the kernel, below)
+constexpr int kSmallBlock = 256, kSmallBlock32 = 64, kC64SmallBlock = 64, kStftSmallBlock32 = 64;
+constexpr int kCLoadAux = AUX_NT;  // cache policy of the complex kernels' descriptor loads
 // FftImpl::fft (fft.rs:1054) / ifft (fft.rs:1134-1174: conj, fft, conj, *scale).
 template <typename T, bool INVERSE>
 struct ComplexIO : PlainTw {
-    static constexpr int kSmallBlock16 = sizeof(T) == 8 ? KOFFT_C64_SMALL_BLOCK : KOFFT_SMALL_BLOCK;  // fft_small_kernel, n = 16
+    static constexpr int kSmallBlock16 = sizeof(T) == 8 ? kC64SmallBlock : kSmallBlock;  // fft_small_kernel, n = 16
     static constexpr bool kSplitOk = true;  // fft_split.hip.h
     static constexpr bool kStreams = true;  // descriptor loads in the generic kernels
     static constexpr bool kPersist = true;  // eligible for the persistent prefetching kernel
@@ -128,10 +119,10 @@ struct ComplexIO : PlainTw {
     }
     __device__ __forceinline__ Raw fetch_d(rsrc_t d, int lane_bytes, int iu, int row_off = 0) const
     {
-        return buf_load_cpx<T, KOFFT_C_LOAD_AUX>(d, row_off + lane_bytes, iu * (int)sizeof(cpx<T>));
+        return buf_load_cpx<T, kCLoadAux>(d, row_off + lane_bytes, iu * (int)sizeof(cpx<T>));
     }
     // (AUX: the store's cache policy, a template argument like the load helper's; the kClaim persistent kernel's kept zone alone passes another)
-    template <int AUX = KOFFT_STORE_AUX>
+    template <int AUX = kStoreAux>
     __device__ __forceinline__ void store_d(rsrc_t d, int lane_bytes, int ou, cpx<T> v, int row_off = 0) const
     {
         if (INVERSE) {
@@ -139,7 +130,7 @@ struct ComplexIO : PlainTw {
             v.re = v.re * scale;
             v.im = im * scale;
         }
-        if constexpr (AUX == KOFFT_STORE_AUX) buf_store_cpx<T>(v, d, row_off + lane_bytes, ou * (int)sizeof(cpx<T>));
+        if constexpr (AUX == kStoreAux) buf_store_cpx<T>(v, d, row_off + lane_bytes, ou * (int)sizeof(cpx<T>));
         else buf_store_cpx_aux<T, AUX>(v, d, row_off + lane_bytes, ou * (int)sizeof(cpx<T>));
     }
     __device__ __forceinline__ Inv invariant(int) const { return {}; }
@@ -164,7 +155,7 @@ struct ComplexIO : PlainTw {
 
 // stft.rs:91-103: frame f starts at start0 + f*hop; x = signal[start+i]*window[i] or 0.
 struct StftIO : PlainTw {
-    static constexpr int kSmallBlock32 = KOFFT_STFT_SMALL_BLOCK32;  // fft_small_kernel at n = 32 (StftMagIO inherits it)
+    static constexpr int kSmallBlock32 = kStftSmallBlock32;  // fft_small_kernel at n = 32 (StftMagIO inherits it)
     static constexpr bool kSplitOk = true;  // fft_split.hip.h
     static constexpr bool kStreams = true;
     static constexpr bool kPersist = true;
@@ -189,9 +180,6 @@ struct StftIO : PlainTw {
     static constexpr int kRawBytes = sizeof(float);
     __device__ __forceinline__ rsrc_t in_desc(size_t xf, bool valid) const
     {
-#ifdef KOFFT_EXP_STFT_SAMEFRAME /* measurement only (wrong results): every frame reads frame 0's samples -- the bound on what staging the samples could gain */
-        xf = 0;
-#endif
         const size_t start = start0 + xf * hop;
         const size_t avail = (valid && start < len) ? len - start : 0;
         return make_rsrc(signal + (avail ? start : 0), (unsigned)(avail < (size_t)n ? avail : (size_t)n) * 4u);
@@ -204,9 +192,6 @@ struct StftIO : PlainTw {
     __device__ __forceinline__ unsigned in_slot_bytes() const { return (unsigned)hop * 4u; }
     __device__ __forceinline__ rsrc_t in_desc_wg(size_t xf0, size_t, int) const
     {
-#ifdef KOFFT_EXP_STFT_SAMEFRAME
-        xf0 = 0;
-#endif
         const size_t start = start0 + xf0 * hop;
         size_t avail = start < len ? len - start : 0;
         if (avail > 0x3fffffffULL) avail = 0x3fffffffULL;
@@ -224,9 +209,6 @@ struct StftIO : PlainTw {
     // with the signal, so frames that run off its end read zeros (stft.rs:95-99)
     __device__ __forceinline__ rsrc_t in_desc_n(size_t xf0, int cnt) const
     {
-#ifdef KOFFT_EXP_STFT_SAMEFRAME
-        xf0 = 0;
-#endif
         const size_t start = start0 + xf0 * hop;
         size_t avail = (cnt > 0 && start < len) ? len - start : 0;
         const size_t span = cnt > 0 ? (size_t)(cnt - 1) * hop + (size_t)n : 0;
@@ -342,11 +324,7 @@ struct StftMagIO : StftIO {
             lo = __builtin_fminf(lo, s[i]);
             hi = __builtin_fmaxf(hi, s[i]);
         }
-#ifdef KOFFT_MAG_SQRTF /* measurement only (tools/build_variant.sh): round 5's roots, for same-box A/Bs */
-        const bool plain = false;
-#else
         const bool plain = lo >= 0x1p-96f && hi < __builtin_inff();  // (all NaN: false)
-#endif
         if (__builtin_amdgcn_ballot_w64(!plain) == 0) {  // wave-uniform
 #pragma unroll
             for (int i = 0; i < NK; ++i) m[i] = sqrt_cr_normal(s[i]);
@@ -593,13 +571,11 @@ struct RfftIO : PlainTw {
     // X[k] for 1 <= k < m from Y[k], Y[m-k] and W[k]  (rfft.rs:454-463)
     __device__ __forceinline__ cpx<T> post_w(cpx<T> w, cpx<T> a, cpx<T> ymk) const
     {
-#ifndef KOFFT_BFLY_NOASM
         if constexpr (sizeof(T) == 4) {
             const v2f wv = {w.re, w.im}, av = {a.re, a.im}, yv = {ymk.re, ymk.im};
             const v2f x = rfft_post_f32_pk(wv, av, yv);
             return mk<T>(x.x, x.y);
         }
-#endif
         const T half = T(0.5f);
         const cpx<T> b = mk<T>(ymk.re, -ymk.im);
         const cpx<T> sum = cadd(a, b), diff = csub(a, b);
@@ -932,9 +908,6 @@ constexpr bool wg_split_lds()
     return IO::kSplitLds || (EPI == 0 && !IO::kSlotMinor && sizeof(T) == 4 && L == 14);
 }
 
-#ifndef KOFFT_RFFT_CHUNK_STORE
-#define KOFFT_RFFT_CHUNK_STORE 1
-#endif
 template <typename T, int L, int RL, int BLOCK, int EPI, class IO>
 // (round 6: the factor policies' two-workgroups-per-CU bound -- kMinWaves = 4 in f64, i.e. 128 registers -- now holds at L = 9 only: at L = 10 / 11 the
 // c64 kernels spilled 10 .. 38 registers under it (44 .. 156 bytes of scratch per lane); they are the fallback of batches of 2 .. 7 large transforms,
@@ -1049,7 +1022,7 @@ __global__ __launch_bounds__(BLOCK, (IO::kMinWaves > 1 && BLOCK == 512 && L == 9
         __syncthreads();
         // (measured per case, same box: f64 n = 64 0.67 -> 0.80, n = 128 0.74 -> 0.79; f64 n = 256 and f32 n = 128 / 256 no change,
         // f64 n = 512 0.71 -> 0.63: only the first two take this route)
-        if constexpr (KOFFT_RFFT_CHUNK_STORE && XPB >= 4 && sizeof(T) == 8 && N <= 64 && !SPLIT) {
+        if constexpr (XPB >= 4 && sizeof(T) == 8 && N <= 64 && !SPLIT) {
             // Short rows (N + 1 <= 257 values, several transforms per workgroup): the workgroup's XPB output rows are ONE
             // contiguous piece of memory.  X goes back into the (now free) LDS rows and the piece is written in memory order
             // by all threads -- whole lines whatever the row length, instead of XPB misaligned row tails per store.
@@ -1205,24 +1178,18 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const cpx<float> *__rest
 // Tried and dropped in round 3, same box: PERSISTENT workgroups with the next block's loads prefetched into registers
 // (c32 0.69, rfft n = 64 0.60 -> 0.54, STFT n = 32 0.63 -> 0.53: 246 VGPRs, and the phases of two wavefronts per SIMD still do not
 // overlap); the 8-threads-per-transform persistent kernel (bit-equal, 0.42: its loads are 64-byte runs).
-#ifndef KOFFT_SMALL_BLOCK
-#define KOFFT_SMALL_BLOCK 256
-#endif
-#ifndef KOFFT_SMALL_BLOCK32
-#define KOFFT_SMALL_BLOCK32 64
-#endif
 // (a policy may ask for its own n = 32 workgroup: kSmallBlock32)
 template <class IO, class = void>
-struct io_small_block32 { static constexpr int value = KOFFT_SMALL_BLOCK32; };
+struct io_small_block32 { static constexpr int value = kSmallBlock32; };
 template <class IO>
 struct io_small_block32<IO, decltype((void)IO::kSmallBlock32)> { static constexpr int value = IO::kSmallBlock32; };
 // (and for n = 16: kSmallBlock16 -- c64 runs 64: 0.72 -> 0.745 on two boxes; n = 2 .. 8 at 64: -4 .. +3 %, left)
 template <class IO, class = void>
-struct io_small_block16 { static constexpr int value = KOFFT_SMALL_BLOCK; };
+struct io_small_block16 { static constexpr int value = kSmallBlock; };
 template <class IO>
 struct io_small_block16<IO, decltype((void)IO::kSmallBlock16)> { static constexpr int value = IO::kSmallBlock16; };
 template <int N, class IO>
-constexpr int small_block_threads() { return N == 32 ? io_small_block32<IO>::value : N == 16 ? io_small_block16<IO>::value : KOFFT_SMALL_BLOCK; }
+constexpr int small_block_threads() { return N == 32 ? io_small_block32<IO>::value : N == 16 ? io_small_block16<IO>::value : kSmallBlock; }
 template <typename T, int N, class IO>
 constexpr size_t small_lds_bytes() { return N == 1 ? 0 : (size_t)small_block_threads<N, IO>() * (N + 1) * sizeof(cpx<T>); }
 

@@ -131,7 +131,6 @@ struct kofft_hip_ctx {
     kofft::host::DevBuf big_tmp;
     bool big_row_pairs = true;       // KOFFT_HIP_BIG_ROW_PAIRS=0: c32 last factor one row per thread slot (8-row tiles) instead of row pairs (A/B)
     bool big_blocked = true;         // KOFFT_HIP_BIG_BLOCKED=0: natural layout of the two-factor intermediate (A/B)
-    bool big_tmp_external = false;  // KOFFT_EXP_API builds only: the intermediate belongs to the experiment script
     // placement probe of big_tmp (round 6, complex_impl.hip.h: big_probe_pick): candidates timed, figures of the last probe
     int big_probe = 5;               // KOFFT_HIP_BIG_PROBE: candidate allocations per probe (0 / 1: take what hipMalloc hands out)
     int big_probe_n = 0, big_probe_pick = -1;
@@ -273,7 +272,6 @@ inline int ensure(kofft_hip_ctx *ctx, DevBuf &buf, size_t bytes) { return ensure
 // every device scratch buffer of a context and the pinned one go (kofft_hip_destroy, kofft_hip_release_scratch)
 inline void drop_buffers(kofft_hip_ctx *ctx)
 {
-    if (ctx->big_tmp_external) ctx->big_tmp = DevBuf{};  // (KOFFT_EXP_API builds: the experiment script's own buffer)
     for (DevBuf *b : {&ctx->stage, &ctx->big_tmp, &ctx->blue_tmp, &ctx->real_tmp, &ctx->rows_tmp}) release_buf<HipAlloc>(*b);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     ctx->pinned = ctx->pinned_dev = nullptr;
@@ -283,12 +281,9 @@ inline void drop_buffers(kofft_hip_ctx *ctx)
 // ---------------------------------------------------------------------------------
 // launch geometry
 // ---------------------------------------------------------------------------------
-#ifndef KOFFT_RL_BIG
-#define KOFFT_RL_BIG 5
-#endif
 // threads per transform >= 8 (c64) / 16 (c32): every load / store instruction covers whole 128-byte lines per transform
 // (A/B on one box: n = 32 c64 0.65 -> 0.79 of the roofline, n = 64 c32 0.64 -> 0.71, n = 128 c32 0.60 -> 0.70.)
-constexpr int rl_for(int L) { return (L == 5 || L == 6) ? 2 : (L == 7 || L == 9) ? 3 : (L >= 13 ? KOFFT_RL_BIG : 4); }
+constexpr int rl_for(int L) { return (L == 5 || L == 6) ? 2 : (L == 7 || L == 9) ? 3 : (L >= 13 ? 5 : 4); }
 constexpr int block_for(int L)
 {
     const int tpt = (1 << L) >> rl_for(L);
@@ -311,7 +306,7 @@ inline int set_dyn_lds_once(kofft_hip_ctx *ctx, std::atomic<unsigned long long> 
 }
 
 // Points per thread of the one-workgroup-per-transform kernel at n = 8192 / 16384: 32 (half the threads, one exchange less)
-// or 16.  Measured per kind on one box (tools/sweep.py, KOFFT_RL_BIG=4 against 5): 16 wins for every f64 kernel of 8192
+// or 16.  Measured per kind on one box (tools/sweep.py, 4 against 5 in rl_for): 16 wins for every f64 kernel of 8192
 // points (c64 +7 %, rfft64 n = 16384 +18 %, irfft64 +8 %) and for the f32 real-input kernels (rfft32 n = 16384 +22 %,
 // 32768 +4 %); 32 wins for c32 16384 (+4 %) and STFT 16384 (+14 %); irfft32 does not care.
 template <typename T, int EPI>
@@ -320,12 +315,6 @@ constexpr int rl_for_kind(int L)
     return (L >= 13 && (sizeof(T) == 8 || EPI == EPI_RFFT)) ? 4 : rl_for(L);
 }
 
-#ifndef KOFFT_WG_MIN_BLOCK
-#define KOFFT_WG_MIN_BLOCK 256
-#endif
-#ifndef KOFFT_WG64_SMALL_FROM
-#define KOFFT_WG64_SMALL_FROM 9
-#endif
 template <typename T, int L, int EPI, class IO, int BLOCK_OVERRIDE = 0>
 int launch_wg(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch)
 {
@@ -335,7 +324,7 @@ int launch_wg(kofft_hip_ctx *ctx, const IO &io, const cpx<T> *tw, size_t batch)
     // f64 from n = 512: one transform per workgroup down to a single wavefront (round 3, same box, 256 -> 64 / 128 threads: rfft64
     // n = 2048 0.62 -> 0.71, c64 2048 0.72 -> 0.75, c64 / rfft64 512 .. 1024 +2..4 %, irfft64 2048 0.63 -> 0.64..0.66; below
     // 512 and for f32 the results are mixed (+-4 %) and the workgroups stay at 256)
-    constexpr int MINB = (sizeof(T) == 8 && L >= KOFFT_WG64_SMALL_FROM) ? 64 : KOFFT_WG_MIN_BLOCK;
+    constexpr int MINB = (sizeof(T) == 8 && L >= 9) ? 64 : 256;
     constexpr int BLOCK = BLOCK_OVERRIDE ? BLOCK_OVERRIDE : (TPT0 > MINB ? TPT0 : MINB);
     constexpr int TPT = (1 << L) >> RL;
     constexpr int XPB = BLOCK / TPT;
@@ -379,22 +368,14 @@ template <bool INV> struct PersistCfg<12, ComplexIO<double, INV>> {
     static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 2;
     static constexpr bool kInvInLds = false, kTwLastInLds = false, kTwGlobal = true;
 };
-#ifndef KOFFT_C12_DEPTH
-#define KOFFT_C12_DEPTH 1  // (round 5 A/B: two transforms ahead for the n = 4096 kernels -- three register sets, 166 VGPRs)
-#endif
-template <class IO> struct PersistCfg<12, IO> : PersistCfgBase<IO> { static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_C12_DEPTH; };
+// (DEPTH, round 5 A/B: two transforms ahead for the n = 4096 kernels -- three register sets, 166 VGPRs -- measured without gain)
+template <class IO> struct PersistCfg<12, IO> : PersistCfgBase<IO> { static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = 1; };
 // c32 n = 4096 (round 7): the last kClaimPct percent of the batch are claimed row by row instead of walked (fft_persist.hip.h,
 // PersistClaim), so that a workgroup that falls behind leaves rows to the others; the table of fractions is in DESIGN.md 5.2.
 // (round 8: 87 percent through two claim words; 25 was the largest share ONE word could hand out below its own rate)
-#ifndef KOFFT_C12_CLAIM
-#define KOFFT_C12_CLAIM true
-#endif
-#ifndef KOFFT_C12_CLAIM_PCT
-#define KOFFT_C12_CLAIM_PCT 87
-#endif
 template <bool INV> struct PersistCfg<12, ComplexIO<float, INV>> : PersistCfgBase<ComplexIO<float, INV>> {
-    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_C12_DEPTH, kClaimPct = KOFFT_C12_CLAIM_PCT;
-    static constexpr bool kClaim = KOFFT_C12_CLAIM;
+    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = 1, kClaimPct = 87;
+    static constexpr bool kClaim = true;
 };
 template <class IO> struct PersistCfg<11, IO> : PersistCfgBase<IO> { static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2; };
 template <class IO> struct PersistCfg<10, IO> : PersistCfgBase<IO> {
@@ -402,38 +383,23 @@ template <class IO> struct PersistCfg<10, IO> : PersistCfgBase<IO> {
 };
 // rfft 2048 (m = 1024, one wavefront per transform): with half the grid (PersistGrid below: fewer concurrent rows) a CU
 // runs ONE wavefront per SIMD, and one transform of work is too short for the next one's loads to land: two ahead.
-#ifndef KOFFT_RFFT10_DEPTH
-#define KOFFT_RFFT10_DEPTH 2
-#endif
 template <> struct PersistCfg<10, RfftIO<float>> : PersistCfgBase<RfftIO<float>> {
-    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_RFFT10_DEPTH;
+    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = 2;
 };
-#ifndef KOFFT_STFT10_DEPTH
-#define KOFFT_STFT10_DEPTH 1
-#endif
 template <> struct PersistCfg<10, StftIO> : PersistCfgBase<StftIO> {
-    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = KOFFT_STFT10_DEPTH;
+    static constexpr int BLOCK = 256, MINW = 2, WG_PER_CU = 2, DEPTH = 1;
 };
 // stft_magnitudes runs the n-point COMPLEX transform of each real frame (visual/spectrogram.rs:52-76): twice STFT's butterflies for half
 // its output -- compute-limited at every window; window in LDS and three workgroups per CU: n = 1024 0.210 -> 0.195 ms (config 4's stream)
 template <> struct PersistCfg<10, StftMagIO> {
     // (the last pass's twiddles from an LDS copy -- no spill at three workgroups -- measured slower: 0.205 -> 0.220 ms)
-    static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 3, WG_PER_CU = 3, DEPTH = KOFFT_STFT10_DEPTH;
+    static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 3, WG_PER_CU = 3, DEPTH = 1;
     static constexpr bool kInvInLds = true, kTwLastInLds = false;
 };
 // irfft prefetches two row elements per output: the last pass reads its twiddles from LDS to stay inside 256 VGPRs
-#ifndef KOFFT_IRFFT10_WG
-#define KOFFT_IRFFT10_WG 2
-#endif
-#ifndef KOFFT_IRFFT10_DEPTH
-#define KOFFT_IRFFT10_DEPTH 1
-#endif
-#ifndef KOFFT_IRFFT10_TWLDS
-#define KOFFT_IRFFT10_TWLDS true
-#endif
 template <> struct PersistCfg<10, IrfftIO<float>> {
-    static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = KOFFT_IRFFT10_WG, WG_PER_CU = KOFFT_IRFFT10_WG, DEPTH = KOFFT_IRFFT10_DEPTH;
-    static constexpr bool kInvInLds = true, kTwLastInLds = KOFFT_IRFFT10_TWLDS;
+    static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 2, DEPTH = 1;
+    static constexpr bool kInvInLds = true, kTwLastInLds = true;
 };
 template <> struct PersistCfg<11, IrfftIO<float>> {
     static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 2;
@@ -468,9 +434,6 @@ template <> struct PersistCfg<12, RfftIO<float>> {
     static constexpr int BLOCK = 256, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 2;
     static constexpr bool kInvInLds = false, kTwLastInLds = false;
 };
-#ifndef KOFFT_IRFFT13_TWGLOBAL
-#define KOFFT_IRFFT13_TWGLOBAL false
-#endif
 // rfft 16384 (m = 8192): one 512-thread workgroup per CU (exchange buffer 68 KiB + post-pass table 64 KiB)
 template <> struct PersistCfg<13, RfftIO<float>> {
     static constexpr int BLOCK = 512, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 1;
@@ -479,7 +442,7 @@ template <> struct PersistCfg<13, RfftIO<float>> {
 // irfft 16384 (m = 8192): the same, with the pre-pass table in LDS and every pass's twiddles from global memory
 template <> struct PersistCfg<13, IrfftIO<float>> {
     static constexpr int BLOCK = 512, NBUF = 1, RL = 4, MINW = 2, WG_PER_CU = 1;
-    static constexpr bool kInvInLds = true, kTwLastInLds = false, kTwGlobal = KOFFT_IRFFT13_TWGLOBAL;
+    static constexpr bool kInvInLds = true, kTwLastInLds = false, kTwGlobal = false;
 };
 // n = 64: 4 points per thread, 16 threads per transform, three passes of two stages
 template <class IO> struct PersistCfg<6, IO> {
@@ -509,10 +472,8 @@ template <class IO> struct PersistCfg<9, IO> {
 template <int L, class IO> struct PersistGrid {
     static int wg_per_cu(int base, size_t) { return base; }
 };
-#ifndef KOFFT_RFFT6_WG
-#define KOFFT_RFFT6_WG 3  // with the group-wide stores of round 3 (fft_persist.hip.h) three workgroups beat two by 6 %
-#endif
-template <> struct PersistGrid<6, RfftIO<float>> { static int wg_per_cu(int, size_t) { return KOFFT_RFFT6_WG; } };
+// (with the group-wide stores of round 3 (fft_persist.hip.h) three workgroups beat two by 6 %)
+template <> struct PersistGrid<6, RfftIO<float>> { static int wg_per_cu(int, size_t) { return 3; } };
 template <> struct PersistGrid<7, RfftIO<float>> { static int wg_per_cu(int base, size_t) { return base / 2; } };
 template <> struct PersistGrid<8, RfftIO<float>> { static int wg_per_cu(int base, size_t) { return base / 2; } };
 template <> struct PersistGrid<9, RfftIO<float>> { static int wg_per_cu(int base, size_t) { return base / 2; } };
@@ -665,9 +626,8 @@ int launch_small(kofft_hip_ctx *ctx, const IO &io, size_t batch, const cpx<T> *t
 
 // adjacent columns / rows per workgroup: 128-byte segments (16 x c32, 8 x c64) when the LDS budget allows
 // (measured, c32: 2^15..2^19 0.19 -> 0.225 of the roofline, 2^22..2^24 0.12 -> 0.15)
-#ifndef KOFFT_BIG_XPB
-#define KOFFT_BIG_XPB(T) (sizeof(T) == 4 ? 16 : 8)
-#endif
+template <typename T>
+constexpr int big_xpb() { return sizeof(T) == 4 ? 16 : 8; }
 // LDS_CAP: bytes of exchange buffer a workgroup may use -- 80 KiB where two workgroups share a CU (the one-tile-per-
 // workgroup kernels), 128 KiB for the persistent kernels (one workgroup per CU): c32 tiles of 2^10-point sub-transforms
 // are then 16 columns = 128-byte segments instead of 8 = 64.
@@ -675,7 +635,7 @@ template <typename T, class IO, int LS, size_t LDS_CAP = 80 * 1024>
 constexpr int big_block()
 {
     const int tpt = (1 << LS) >> rl_for(LS);
-    int xpb = KOFFT_BIG_XPB(T);
+    int xpb = big_xpb<T>();
     // (f64: at most 512 threads -- two register sets of 16 values are 128 VGPRs, a 1024-thread block has 128 in all)
     while (xpb > 1 && (xpb * tpt > (sizeof(T) == 8 ? 512 : 1024) || (size_t)xpb * (1 << LS) * 8 > LDS_CAP)) xpb /= 2;
     int block = xpb * tpt;

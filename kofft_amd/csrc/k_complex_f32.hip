@@ -13,23 +13,3 @@ template int fft_dev<float>(kofft_hip_ctx *, const float *, float *, size_t, siz
 template int fft_radix4_dev<float>(kofft_hip_ctx *, const float *, float *, size_t, size_t, int);
 }  // namespace host
 }  // namespace kofft
-
-#if defined(KOFFT_RF_STAMPS)
-// diagnostic builds only: the s_memtime stamps of fft_regfile_persist_kernel<float, ...> (this translation unit's copy)
-extern "C" int kofft_hip_exp_rf_stamps_f32(void *out, size_t bytes)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(kofft::g_rf_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-#endif
-#if defined(KOFFT_PERSIST_STAMPS)
-// diagnostic builds only: the per-workgroup records of fft_persist_kernel<float, ...> (this translation unit's copy; tools/persist_progress.py)
-extern "C" int kofft_hip_exp_persist_stamps_f32(void *out, size_t bytes)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(kofft::g_persist_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-extern "C" int kofft_hip_exp_persist_stamps_clear_f32(void)
-{
-    static const unsigned long long zeros[kofft::kPersistStampWgs * kofft::kPersistStampWords] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(kofft::g_persist_stamps), zeros, sizeof(zeros)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -13,11 +13,3 @@ template int fft_dev<double>(kofft_hip_ctx *, const double *, double *, size_t, 
 template int fft_radix4_dev<double>(kofft_hip_ctx *, const double *, double *, size_t, size_t, int);
 }  // namespace host
 }  // namespace kofft
-
-#if defined(KOFFT_RF_STAMPS)
-// diagnostic builds only: the s_memtime stamps of fft_regfile_persist_kernel<double, ...> (this translation unit's copy)
-extern "C" int kofft_hip_exp_rf_stamps_f64(void *out, size_t bytes)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(kofft::g_rf_stamps), bytes) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -23,7 +23,7 @@ int fft_axis_dev(kofft_hip_ctx *ctx, T *d_data, size_t len, size_t lines, size_t
     // 0.229 -> 0.179 ms, 2048 x 2048 0.059 -> 0.047, 8 x 2048 x 2048 0.497 -> 0.451; over 16384 adjacent lines (2048 x 256 x 64) it loses 10 %,
     // c64 (64-byte segments in the strided kernel) 3 %, and 2^10-point axes lose everywhere (tools/bench_nd.py).
     if (stride == inner && ctx->nd_two_pass && fused_len_ok<T>(len) && (len >= 4096 || (len == 2048 && sizeof(T) == 4 && inner <= 8192)) && is_pow2(inner) &&
-        inner >= (size_t)KOFFT_BIG_XPB(T) && lines % inner == 0 && (lines == inner || outer_stride == len * inner) &&
+        inner >= (size_t)big_xpb<T>() && lines % inner == 0 && (lines == inner || outer_stride == len * inner) &&
         lines * len * sizeof(cpx<T>) >= (size_t(16) << 20) && len * inner * sizeof(cpx<T>) <= (size_t(1) << 31)) {  // (32-bit buffer descriptors per block)
         return fft_axis2_dev<T>(ctx, d_data, ilog2(len), ilog2(inner), lines / inner, inverse);
     }

@@ -5,9 +5,7 @@
 namespace kofft {
 namespace host {
 
-#ifndef KOFFT_SOSFILT_MEASURE_TILE
 static_assert(kSosTile == KOFFT_HIP_SOSFILT_TILE, "include/kofft_hip.h names the tile");
-#endif
 static_assert(kSosGroup == KOFFT_HIP_SOSFILT_GROUP, "include/kofft_hip.h names the group");
 static_assert(kSosGroup == 8, "sosfilt_launch dispatches 1 .. 8 sections");
 

@@ -753,22 +753,6 @@ int kofft_hip_synchronize(kofft_hip_ctx *ctx)
     return KOFFT_OK;
 }
 
-#ifdef KOFFT_EXP_API /* measurement builds only (tools/build_variant.sh): the experiment script supplies the large-n intermediate */
-int kofft_hip_exp_set_big_tmp(kofft_hip_ctx *ctx, void *d_ptr, size_t bytes)
-{
-    if (!ctx) return KOFFT_ERR_NULL;
-    if (!ctx->big_tmp_external) release_buf<HipAlloc>(ctx->big_tmp);
-    ctx->big_tmp = DevBuf{d_ptr, bytes};
-    ctx->big_tmp_external = d_ptr != nullptr;
-    return KOFFT_OK;
-}
-int kofft_hip_exp_malloc(size_t bytes, unsigned flags, void **out)
-{
-    return hipExtMallocWithFlags(out, bytes, flags) == hipSuccess ? KOFFT_OK : KOFFT_ERR_ALLOC;
-}
-int kofft_hip_exp_free(void *p) { return hipFree(p) == hipSuccess ? KOFFT_OK : KOFFT_ERR_HIP; }
-#endif
-
 int kofft_hip_big_probe_info(kofft_hip_ctx *ctx, float *first_us, float *total_us, int cap, int *n, int *pick)
 {
     if (!ctx || !n || !pick) return KOFFT_ERR_NULL;
@@ -790,7 +774,6 @@ int kofft_hip_release_scratch(kofft_hip_ctx *ctx)
     spectral_drop(ctx);  // the chirp-Z tables (up to 4 x 128 MiB) and the Goertzel coefficient arrays: rebuilt by the next call that needs them
     mel_drop(ctx);       // the filterbank plans, likewise
     spec_drop(ctx);      // and the pixel ranges of the log-scaled spectrogram render
-    ctx->big_tmp_external = false;  // (KOFFT_EXP_API builds: the script's intermediate is forgotten, the next call allocates its own)
     ctx->big_probe_n = 0;
     ctx->big_probe_pick = -1;
     return KOFFT_OK;

@@ -26,11 +26,7 @@ __device__ __forceinline__ T ld_plane(const T *p)
 template <typename T>
 __device__ __forceinline__ void st_plane(T *p, T v)
 {
-#ifdef KOFFT_PLAIN_STORES
-    *p = v;
-#else
     __builtin_nontemporal_store(v, p);
-#endif
 }
 
 // Element i of transform xf is re_in[xf * n + i], im_in[xf * n + i]; plain per-element 4- / 8-byte accesses, coalesced over the lanes

@@ -18,16 +18,8 @@ namespace kofft {
 namespace host {
 
 constexpr unsigned kSosRows = 64;   // rows of one wavefront of the tiled kernel: one per lane
-#ifdef KOFFT_SOSFILT_MEASURE_TILE    // (a measurement build for tools/bench_sosfilt.py: another tile; the tests hold for the header's)
-constexpr unsigned kSosTile = KOFFT_SOSFILT_MEASURE_TILE;
-#else
 constexpr unsigned kSosTile = 32;   // T: samples per tile (KOFFT_HIP_SOSFILT_TILE): 16, 32 or 64
-#endif
-#ifdef KOFFT_SOSFILT_MEASURE_PREFETCH  // (a measurement build: the next tile prefetched into registers, sosfilt_impl.hip.h)
-constexpr bool kSosPrefetch = true;
-#else
-constexpr bool kSosPrefetch = false;
-#endif
+constexpr bool kSosPrefetch = false;  // the next tile prefetched into registers (sosfilt_impl.hip.h) measured no faster
 constexpr unsigned kSosGroup = 8;   // G: sections per pass (KOFFT_HIP_SOSFILT_GROUP)
 constexpr unsigned kSosPlainThreads = 256;
 

@@ -6,22 +6,11 @@ of 10 timed calls each, after 3 warm-up calls; median [min .. max] ms per call. 
 bytes per row.
 usage: bench_convolve.py [rows nx nh block ...]      (groups of four; none: the shapes of DESIGN.md 5.25)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 fused = kofft_amd.HipFftImpl(np.float32)
 composed = kofft_amd.HipFftImpl(np.float32)
 composed.set_convolve_fused(False)
-stream = torch.cuda.Stream()
-for f in (fused, composed):
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(fused, composed)
 
 
 def by_hand(x, h, z, hz, out, n, rows, nx, nh):
@@ -55,20 +44,12 @@ for rows, nx, nh, block in shapes:
     calls = {"fused": lambda: fused.convolve_dev(x.data_ptr(), rows, nx, h.data_ptr(), 1, nh, out.data_ptr(), block),
              "composed": lambda: composed.convolve_dev(x.data_ptr(), rows, nx, h.data_ptr(), 1, nh, out.data_ptr(), block),
              "by hand": lambda: by_hand(x, h, z, hz, out, n, rows, nx, nh)}
-    times = {k: [] for k in calls}
     with torch.cuda.stream(stream):
-        for c in calls.values():
-            for _ in range(3):
-                c()
-        torch.cuda.synchronize()
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c))
+        times = abtime.alternate(stream, calls, warmup=3, rounds=5, reps=10)
     frac = lambda ms: 4.0 * (nx + full) * rows / (ms * 1e-3) / 8e12
     line = f"rows {rows:8d} nx {nx:9d} nh {nh:5d} block {block:5d}:"
     for k, t in times.items():
-        md = float(np.median(t))
-        line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.3f}"
+        line += f" | {k} {abtime.cell(t)} {frac(float(np.median(t))):.3f}"
     print(line, flush=True)
     del h, out, z, hz
     torch.cuda.empty_cache()

@@ -8,22 +8,11 @@ or 8 for complex values).  The tool is one GPU step per invocation: run each sha
 usage: bench_convolve_bank.py [rows nx nh block filters taps kind ...]   (groups of seven; taps: real | complex; kind: real | complex |
        magnitude; none: the shapes of DESIGN.md 5.31)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 fused = kofft_amd.HipFftImpl(np.float32)
 composed = kofft_amd.HipFftImpl(np.float32)
 composed.set_convolve_bank_fused(False)
-stream = torch.cuda.Stream()
-for f in (fused, composed):
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(fused, composed)
 
 
 def one_by_one(x, h, one, rows, nx, nh, block, calls):
@@ -55,20 +44,13 @@ for rows, nx, nh, block, filters, taps, kind in shapes:
                                          out=kind)
     calls = {"fused": lambda: bank(fused), "composed": lambda: bank(composed),
              "one by one": lambda: one_by_one(x, h, one, rows, nx, nh, block, filters * (2 if cplx else 1))}
-    times = {k: [] for k in calls}
     with torch.cuda.stream(stream):
-        for c in calls.values():
-            for _ in range(3):
-                c()
-        torch.cuda.synchronize()
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c))
+        times = abtime.alternate(stream, calls, warmup=3, rounds=5, reps=10)
     frac = lambda ms: (4.0 * nx + elem * filters * full) * rows / (ms * 1e-3) / 8e12
     line = f"rows {rows:5d} nx {nx:8d} nh {nh:5d} block {block:5d} filters {filters:3d} taps {taps:7s} out {kind:9s}:"
     for k, t in times.items():
         md = float(np.median(t))
-        line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.3f}"
+        line += f" | {k} {abtime.cell(t)} {frac(md):.3f}"
     md = {k: float(np.median(t)) for k, t in times.items()}
     line += f" | one by one / fused {md['one by one'] / md['fused']:.2f} (bound {2 * filters / (filters + 1):.2f})"
     print(line, flush=True)

@@ -7,25 +7,15 @@ Shapes (rows, len, win_len, hop, filters, coefficients): config 4's stream, 4096
 seconds at 2048 / 512, and one shape per fused window length at 40 x 13 in two batch sizes.
 usage: bench_frontend.py [shape index | rows,len,win_len,hop,filters,coefficients ...]"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 from kofft_amd import mfcc
 SHAPES = [(1, 28_800_000, 1024, 256, 40, 13), (4096, 16000, 512, 160, 26, 13), (64, 480_000, 2048, 512, 80, 13)]
 SHAPES += [(rows, (1 << 24) // 64 * 64 // rows, w, w // 4, 40, 13) for w in (64, 128, 256, 512, 1024, 2048) for rows in (64, 1024)]
 ctx = {}
-stream = torch.cuda.Stream()
 for name, mode in (("chain", 1), ("fused", 2), ("composed", 0), ("default", 1)):
     ctx[name] = kofft_amd.HipFftImpl(np.float32)
     ctx[name].set_frontend_fused(mode)
-    ctx[name].set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(*ctx.values())
 
 
 for arg in sys.argv[1:] or range(len(SHAPES)):
@@ -55,10 +45,10 @@ for arg in sys.argv[1:] or range(len(SHAPES)):
         same = {k: torch.equal(out[k].view(torch.int32), out["chain"].view(torch.int32)) for k in calls if k != "chain"}
         for _ in range(5):
             for k, c in calls.items():
-                times[k].append(timed(c))
+                times[k].append(abtime.timed(stream, c))
     line = f"rows {rows:5d} len {length:9d} win {win_len:5d} hop {hop:4d} mel {num_mel:3d} coeffs {nc:3d} frames {rows * frames:8d} == chain: {same}:"
     for k, t in times.items():
-        line += f" | {k} {float(np.median(t)):.3f} ms [{min(t):.3f} .. {max(t):.3f}]"
+        line += f" | {k} {abtime.cell(t)}"
     print(line, flush=True)
     del x, mags, mx, out
     torch.cuda.empty_cache()

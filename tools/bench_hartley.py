@@ -9,10 +9,10 @@
     family's kernels, so the two should agree.
 usage: bench_hartley.py [first|steady ...]"""
 import sys, pathlib, time; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 
 CEIL_TERMS = 157.3e12 / 4  # one mul + one add per term
-stream = torch.cuda.Stream()
+stream = abtime.one_stream()
 
 
 def ctx(table_device=True):
@@ -20,15 +20,6 @@ def ctx(table_device=True):
     f.set_dht_table_device(table_device)
     f.set_stream(stream.cuda_stream)
     return f
-
-
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
 
 
 def first_call(n, rows, x, y, table_device):
@@ -66,7 +57,7 @@ def first_table():
             warm = ctx(True)
             for _ in range(3):
                 warm.dht_dev(x.data_ptr(), y.data_ptr(), n, rows)
-            steady = float(np.median([timed(lambda: warm.dht_dev(x.data_ptr(), y.data_ptr(), n, rows), 20) for _ in range(5)]))
+            steady = float(np.median([abtime.timed(stream, lambda: warm.dht_dev(x.data_ptr(), y.data_ptr(), n, rows), 20) for _ in range(5)]))
             warm.close()
         dh, de = [a for a, _ in t[True]], [b for _, b in t[True]]
         hh, he = [a for a, _ in t[False]], [b for _, b in t[False]]
@@ -90,17 +81,14 @@ def steady_table():
                 for _ in range(3):
                     c()
             torch.cuda.synchronize()
-            one = max(timed(c, 1) for c in calls.values())
+            one = max(abtime.timed(stream, c, 1) for c in calls.values())
             reps = max(1, min(50, int(5.0 / max(one, 1e-3))))
-            times = {k: [] for k in calls}
-            for _ in range(5):
-                for k, c in calls.items():
-                    times[k].append(timed(c, reps))
+            times = abtime.alternate(stream, calls, warmup=0, rounds=5, reps=reps)  # (warmed up above)
         line = f"steady n {n:5d} rows {rows:8d}:"
         for k, t in times.items():
             md = float(np.median(t))
             tps = terms / (md * 1e-3)
-            line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {tps / 1e12:.2f} Tterm/s valu {tps / CEIL_TERMS:.3f}"
+            line += f" | {k} {abtime.cell(t)} {tps / 1e12:.2f} Tterm/s valu {tps / CEIL_TERMS:.3f}"
         print(line, flush=True)
         del x, y
         torch.cuda.empty_cache()

@@ -6,22 +6,11 @@ calls each, after 3 warm-up calls; median [min .. max] ms per call.  Fraction of
 8 out).
 usage: bench_hilbert.py [n ...]"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 fused = kofft_amd.HipFftImpl(np.float32)
 composed = kofft_amd.HipFftImpl(np.float32)
 composed.set_hilbert_fused(False)
-stream = torch.cuda.Stream()
-for f in (fused, composed):
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(fused, composed)
 
 
 def by_hand(x, y, n, rows):
@@ -43,20 +32,13 @@ for n in [int(a) for a in sys.argv[1:]] or [8, 64, 256, 1024, 4096, 16384, 65536
     calls = {"fused": lambda: fused.hilbert_dev(x.data_ptr(), y.data_ptr(), n, rows),
              "composed": lambda: composed.hilbert_dev(x.data_ptr(), y.data_ptr(), n, rows),
              "by hand": lambda: by_hand(x, y, n, rows)}
-    times = {k: [] for k in calls}
     with torch.cuda.stream(stream):
-        for c in calls.values():
-            for _ in range(3):
-                c()
-        torch.cuda.synchronize()
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c))
+        times = abtime.alternate(stream, calls, warmup=3, rounds=5, reps=10)
     frac = lambda ms: 12 * n * rows / (ms * 1e-3) / 8e12
     line = f"n {n:6d} rows {rows:9d}:"
     for k, t in times.items():
         md = float(np.median(t))
-        line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.3f}"
+        line += f" | {k} {abtime.cell(t)} {frac(md):.3f}"
     print(line, flush=True)
     del x, y
     torch.cuda.empty_cache()

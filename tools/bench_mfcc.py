@@ -7,25 +7,14 @@ compared bit for bit at the timed size.  Five rounds of 10 timed calls each, aft
 Fraction of the roofline: 8 TB/s on rows * (n_fft + num_coeffs) * 4 bytes.
 usage: bench_mfcc.py [shape index | rows,n_fft,filters,coefficients ...]"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 from kofft_amd import mfcc
 SHAPES = [(112500, 512, 40, 13), (1 << 20, 256, 26, 13), (4096, 1024, 128, 128)]
 fused = kofft_amd.HipFftImpl(np.float32)
 fused.set_mfcc_fused(2)  # the fused kernel wherever it fits, also where the default takes the composed route
 composed = kofft_amd.HipFftImpl(np.float32)
 composed.set_mfcc_fused(0)
-stream = torch.cuda.Stream()
-for f in (fused, composed):
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(fused, composed)
 
 
 def dense(bins, n_fft, num_mel, nc):
@@ -65,12 +54,12 @@ for arg in sys.argv[1:] or range(len(SHAPES)):
         same = torch.equal(out.view(torch.int32), out2.view(torch.int32))
         for _ in range(5):
             for k, c in calls.items():
-                times[k].append(timed(c))
+                times[k].append(abtime.timed(stream, c))
     frac = lambda ms: 4 * rows * (n_fft + nc) / (ms * 1e-3) / 8e12
     line = f"rows {rows:8d} n_fft {n_fft:5d} mel {num_mel:4d} coeffs {nc:4d} fused == composed: {same}:"
     for k, t in times.items():
         md = float(np.median(t))
-        line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.3f}"
+        line += f" | {k} {abtime.cell(t)} {frac(md):.3f}"
     print(line, flush=True)
     del x, out, out2, en, w, d
     torch.cuda.empty_cache()

@@ -9,24 +9,13 @@ Shapes (rows, len, win_len, hop): config 4's stream, 64 clips of ten seconds at 
 usage: bench_picture.py [shape index | rows,len,win_len,hop ...]   (every shape in layout image and frames)"""
 import os, sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 import ctypes as C
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 SHAPES = [(1, 28_800_000, 1024, 256), (64, 480_000, 2048, 512), (1024, 16_384, 256, 64)]
-stream = torch.cuda.Stream()
 ctx = {"chain": kofft_amd.HipFftImpl(np.float32), "one": kofft_amd.HipFftImpl(np.float32)}
 os.environ["KOFFT_HIP_SCRATCH_CHUNK_MB"] = "64"
 ctx["64M"] = kofft_amd.HipFftImpl(np.float32)
 del os.environ["KOFFT_HIP_SCRATCH_CHUNK_MB"]
-for f in ctx.values():
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(*ctx.values())
 
 
 for arg in sys.argv[1:] or range(len(SHAPES)):
@@ -65,10 +54,10 @@ for arg in sys.argv[1:] or range(len(SHAPES)):
                 same[k] = torch.equal(pic["one"].view(-1)[:nb], pic["chain"].view(-1)[:nb])
             for _ in range(5):
                 for k, c in calls.items():
-                    times[k].append(timed(c))
+                    times[k].append(abtime.timed(stream, c))
         line = f"rows {rows:5d} len {length:9d} win {win_len:5d} hop {hop:4d} layout {lname:6s} frames {rows * frames:8d} == chain: {same}:"
         for k, t in times.items():
-            line += f" | {k} {float(np.median(t)):.3f} ms [{min(t):.3f} .. {max(t):.3f}]"
+            line += f" | {k} {abtime.cell(t)}"
         print(line, flush=True)
     del x, mags, mx, mo, pic
     torch.cuda.empty_cache()

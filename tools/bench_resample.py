@@ -6,24 +6,13 @@ entry point: zero-stuff the rows by `up` in torch, kofft_amd.convolve on the dev
 calls each, after 3 warm-up calls; median [min .. max] ms per call.  Fraction of the roofline: 8 TB/s on 4 nx + 4 out_len bytes per row.
 usage: bench_resample.py [rows nx up down nh ...]      (groups of five, nh 0: design_taps(up, down); none: the shapes of DESIGN.md 5.28)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 from kofft_amd import resample
 ctxs = {"tiled": kofft_amd.HipFftImpl(np.float32), "plain": kofft_amd.HipFftImpl(np.float32), "default": kofft_amd.HipFftImpl(np.float32)}
 ctxs["tiled"].set_resample_tiled(2)
 ctxs["plain"].set_resample_tiled(0)
-stream = torch.cuda.Stream()
-for f in ctxs.values():
-    f.set_stream(stream.cuda_stream)
+stream = abtime.one_stream(*ctxs.values())
 conv = ctxs["default"]
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
 
 
 def by_hand(x, h, xu, full, out, rows, nx, nh, up, down, t0, out_len):
@@ -62,20 +51,13 @@ for rows, nx, up, down, nh in shapes:
         xu = torch.empty((rows, nx * up), dtype=torch.float32, device="cuda") if up > 1 else None
         full = torch.empty((rows, nx * up + nh - 1), dtype=torch.float32, device="cuda")
         calls["by hand"] = lambda: by_hand(x, h, xu, full, out, rows, nx, nh, up, down, t0, out_len)
-    times = {k: [] for k in calls}
     with torch.cuda.stream(stream):
-        for c in calls.values():
-            for _ in range(3):
-                c()
-        torch.cuda.synchronize()
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c))
+        times = abtime.alternate(stream, calls, warmup=3, rounds=5, reps=10)
     frac = lambda ms: 4.0 * (nx + out_len) * rows / (ms * 1e-3) / 8e12
     line = f"rows {rows:8d} nx {nx:9d} {up:3d}/{down:3d} nh {nh:5d} out {out_len:9d} route {route}:"
     for k, t in times.items():
         md = float(np.median(t))
-        line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.3f}"
+        line += f" | {k} {abtime.cell(t)} {frac(md):.3f}"
     print(line, flush=True)
     del h, out, xu, full
     torch.cuda.empty_cache()

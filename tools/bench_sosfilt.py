@@ -7,7 +7,7 @@ further and its one call is what the line shows.  Fraction of the roofline: 8 TB
 written once, whatever the number of sections or passes).
 usage: bench_sosfilt.py [--skip-above S] [rows nx sections reverse ...]   (groups of four; none: the matrix of DESIGN.md 5.29)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 argv = sys.argv[1:]
 skip_above = 3.0
 if argv[:1] == ["--skip-above"]:
@@ -16,18 +16,7 @@ if argv[:1] == ["--skip-above"]:
 ctxs = {"tiled": kofft_amd.HipFftImpl(np.float32), "plain": kofft_amd.HipFftImpl(np.float32), "default": kofft_amd.HipFftImpl(np.float32)}
 ctxs["tiled"].set_sosfilt_tiled(2)
 ctxs["plain"].set_sosfilt_tiled(0)
-stream = torch.cuda.Stream()
-for f in ctxs.values():
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(*ctxs.values())
 
 
 def cascade(sections):
@@ -60,7 +49,7 @@ for rows, nx, sections, reverse in shapes:
     times, plan, note = {k: [] for k in calls}, {}, {}
     with torch.cuda.stream(stream):
         for k, c in calls.items():
-            first = timed(c, 1)
+            first = abtime.timed(stream, c, 1)
             if first > skip_above * 1e3:
                 plan[k], note[k] = (0, 0), f"one call {first:.0f} ms, not timed further"
                 continue
@@ -72,7 +61,7 @@ for rows, nx, sections, reverse in shapes:
         for rnd in range(5):
             for k, c in calls.items():
                 if rnd < plan[k][0]:
-                    times[k].append(timed(c, plan[k][1]))
+                    times[k].append(abtime.timed(stream, c, plan[k][1]))
     frac = lambda ms: 8.0 * nx * rows / (ms * 1e-3) / 8e12
     line = f"rows {rows:8d} nx {nx:9d} sections {sections:2d} {'reverse' if reverse else 'forward'}:"
     for k, t in times.items():
@@ -80,7 +69,7 @@ for rows, nx, sections, reverse in shapes:
             line += f" | {k} {note[k]}"
             continue
         md = float(np.median(t))
-        line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.4f}"
+        line += f" | {k} {abtime.cell(t)} {frac(md):.4f}"
         if plan[k] != (5, 10):
             line += f" ({plan[k][0]} x {plan[k][1]})"
     print(line, flush=True)

@@ -7,24 +7,14 @@ roofline: 8 TB/s on the bytes that candidate moves -- 8 rows nx for the baseline
 for the scan (read twice, written once); passes of a cascade of more than 8 sections are not counted.
 usage: bench_sosfilt_scan.py [--chunks a,b,..] [rows nx sections reverse ...]   (groups of four; none: the matrix of DESIGN.md 5.30)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 argv = sys.argv[1:]
 chunks = [1024, 2048, 4096, 8192, 16384]
 if argv[:1] == ["--chunks"]:
     chunks = [int(c) for c in argv[1].split(",")]
     argv = argv[2:]
 fft = kofft_amd.HipFftImpl(np.float32)
-stream = torch.cuda.Stream()
-fft.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(fft)
 
 
 def cascade(sections):
@@ -59,7 +49,7 @@ for rows, nx, sections, reverse in shapes:
     times, plan = {k: [] for k in calls}, {}
     with torch.cuda.stream(stream):
         for k, c in calls.items():
-            slow = timed(c, 1) > 200.0
+            slow = abtime.timed(stream, c, 1) > 200.0
             plan[k] = (3, 1) if slow else (5, 10)
             for _ in range(0 if slow else 2):
                 c()
@@ -67,7 +57,7 @@ for rows, nx, sections, reverse in shapes:
         for rnd in range(5):
             for k, c in calls.items():
                 if rnd < plan[k][0]:
-                    times[k].append(timed(c, plan[k][1]))
+                    times[k].append(abtime.timed(stream, c, plan[k][1]))
     print(f"rows {rows:6d} nx {nx:9d} sections {sections:2d} {'reverse' if reverse else 'forward'}: recommended chunk "
           f"{kofft_amd.iir.scan_chunk(rows, nx, sections)}", flush=True)
     for k, t in times.items():

@@ -11,9 +11,9 @@ same buffers; five rounds after 3 warm-up calls, median [min .. max] ms per call
    the kernel's 136 VGPRs): GB/s of input read, beside a device-to-device copy of the same bytes.
 usage: bench_spectral.py [table] [sum] [goertzel]"""
 import sys, pathlib, time; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 
-stream = torch.cuda.Stream()
+stream = abtime.one_stream()
 W = lambda m: np.exp(-2j * np.pi / m)
 A = np.exp(2j * np.pi * 0.1)
 
@@ -25,27 +25,15 @@ def ctx(route=0):
     return f
 
 
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
-
-
 def rounds(calls, warm=3, n=5, budget_ms=5.0):
     with torch.cuda.stream(stream):
         for c in calls.values():
             for _ in range(warm):
                 c()
         torch.cuda.synchronize()
-        one = max(timed(c, 1) for c in calls.values())
+        one = max(abtime.timed(stream, c, 1) for c in calls.values())
         reps = max(1, min(50, int(budget_ms / max(one, 1e-3))))
-        times = {k: [] for k in calls}
-        for _ in range(n):
-            for k, c in calls.items():
-                times[k].append(timed(c, reps))
+        times = abtime.alternate(stream, calls, warmup=0, rounds=n, reps=reps)  # (warmed up above)
     return {k: (float(np.median(t)), min(t), max(t)) for k, t in times.items()}
 
 
@@ -65,8 +53,8 @@ def bench_table():
             one = lambda: tab.czt_dev(x.data_ptr(), y.data_ptr(), n, m, W(m), A, 1)
             for _ in range(5):
                 tab.release_scratch()  # drops the table: the next call builds it
-                torch.cuda.synchronize(); t0 = time.perf_counter(); ev = timed(one, 1); host = (time.perf_counter() - t0) * 1e3
-                torch.cuda.synchronize(); t0 = time.perf_counter(); ev1 = timed(one, 1); host1 = (time.perf_counter() - t0) * 1e3
+                torch.cuda.synchronize(); t0 = time.perf_counter(); ev = abtime.timed(stream, one, 1); host = (time.perf_counter() - t0) * 1e3
+                torch.cuda.synchronize(); t0 = time.perf_counter(); ev1 = abtime.timed(stream, one, 1); host1 = (time.perf_counter() - t0) * 1e3
                 build_ev.append(ev - ev1); build_host.append(host - host1)
         r = rounds({"czt": lambda: tab.czt_dev(x.data_ptr(), y.data_ptr(), n, m, W(m), A, rows),
                     "dct2": lambda: dct.dct_direct_dev(2, x.data_ptr(), y.data_ptr(), n, rows)})

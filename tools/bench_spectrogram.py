@@ -7,7 +7,7 @@ calls each after 3 warm-up calls (50 timed launches per entry); median [min .. m
 per pixel (4 in, 3 out).
 usage: bench_spectrogram.py [frames [bins [rounds]]]"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 from kofft_amd import spectrogram as sp
 frames = int(sys.argv[1]) if len(sys.argv) > 1 else 112500
 bins = int(sys.argv[2]) if len(sys.argv) > 2 else 512
@@ -17,20 +17,7 @@ length = frames * hop
 lds = kofft_amd.HipFftImpl(np.float32)
 direct = kofft_amd.HipFftImpl(np.float32)
 sp.set_transpose(False, fft=direct)
-stream = torch.cuda.Stream()
-for f in (lds, direct):
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
-
-
+stream = abtime.one_stream(lds, direct)
 sig = torch.empty(length, dtype=torch.float32, device="cuda").uniform_(-1, 1)
 mags = torch.empty((frames, bins), dtype=torch.float32, device="cuda")
 d_max = torch.zeros(1, dtype=torch.float32, device="cuda")
@@ -58,7 +45,7 @@ with torch.cuda.stream(stream):
     flipped = torch.equal(outs["li"], torch.flip(outs["lf"], dims=(1,)).transpose(0, 1))
     for _ in range(rounds):
         for k, c in calls.items():
-            times[k].append(timed(c))
+            times[k].append(abtime.timed(stream, c))
 print(f"frames {frames} bins {bins}: LDS == direct: {same}; image == flipped transpose of frame-major: {flipped}; max_mag {float(d_max[0]):.4f}")
 for k, t in times.items():
     md = float(np.median(t))

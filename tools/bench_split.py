@@ -5,21 +5,12 @@ as a yardstick, with fft_dev on interleaved data of the same shape.  Five rounds
 [min .. max] ms per call.  Fraction of the roofline: 8 TB/s on 16 bytes per point (f64: 32), what the transform itself has to move.
 usage: bench_split.py [f32|f64|both] [n ...]"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 args = sys.argv[1:]
 which = args.pop(0) if args and args[0] in ("f32", "f64", "both") else "both"
 sizes = [int(a) for a in args] or [8, 64, 256, 1024, 4096, 16384]
-stream = torch.cuda.Stream()
+stream = abtime.one_stream()
 POINTS = 1 << 27
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
 
 
 for real, tdt, cdt in [(np.float32, torch.float32, torch.complex64), (np.float64, torch.float64, torch.complex128)]:
@@ -44,20 +35,13 @@ for real, tdt, cdt in [(np.float32, torch.float32, torch.complex64), (np.float64
         calls = {"fused": lambda: fused.fft_split_dev(re, im, o_re, o_im),
                  "composed": lambda: composed.fft_split_dev(re, im, o_re, o_im),
                  "interleaved": lambda: fused.fft_dev_oop(z.data_ptr(), zo.data_ptr(), n, rows)}
-        times = {k: [] for k in calls}
         with torch.cuda.stream(stream):
-            for c in calls.values():
-                for _ in range(3):
-                    c()
-            torch.cuda.synchronize()
-            for _ in range(5):
-                for k, c in calls.items():
-                    times[k].append(timed(c))
+            times = abtime.alternate(stream, calls, warmup=3, rounds=5, reps=10)
         frac = lambda ms: 4 * item * n * rows / (ms * 1e-3) / 8e12
         line = f"{np.dtype(real).name} n {n:6d} rows {rows:9d}:"
         for k, t in times.items():
             md = float(np.median(t))
-            line += f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {frac(md):.3f}"
+            line += f" | {k} {abtime.cell(t)} {frac(md):.3f}"
         print(line, flush=True)
         del re, im, o_re, o_im, z, zo
         torch.cuda.empty_cache()

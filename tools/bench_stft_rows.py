@@ -7,33 +7,20 @@ ISTFT (mode 1) inverse-transforms its frames in place, so over the repeated call
 data-dependent path and f32 denormals run at full rate here, so the times stand, but the values mean nothing.
 usage: bench_stft_rows.py [stft|mags|istft ...] [--shape ROWS,LEN,WIN,HOP ...]   (--shape replaces the built-in shapes)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 fft = kofft_amd.HipFftImpl(np.float32)
-stream = torch.cuda.Stream()
-fft.set_stream(stream.cuda_stream)
+stream = abtime.one_stream(fft)
 SHAPES = [(4096, 16000, 512, 128), (256, 480000, 1024, 256), (256, 480000, 400, 160), (8, 28800000 // 8, 1024, 256)]
 
 
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
-
-
 def run(name, calls, nbytes):
-    times = {k: [] for k in calls}
     with torch.cuda.stream(stream):
         for c in calls.values():
             for _ in range(2):
                 c()
         torch.cuda.synchronize()
-        reps = {k: max(3, int(np.ceil(30.0 / max(timed(c, 2), 1e-3)))) for k, c in calls.items()}  # windows of 30 ms and more
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c, reps[k]))
+        reps = {k: max(3, int(np.ceil(30.0 / max(abtime.timed(stream, c, 2), 1e-3)))) for k, c in calls.items()}  # windows of 30 ms and more
+        times = abtime.alternate(stream, calls, warmup=0, rounds=5, reps=reps)  # (warmed up above)
     line = name
     for k, t in times.items():
         med = float(np.median(t))

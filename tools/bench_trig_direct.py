@@ -7,10 +7,10 @@ multiply and add per term give 39.3 T terms / s) and the share of HBM (8 bytes p
 fresh context, which builds the n x n table on the host, is timed on the host (first-call ms - steady-state ms = table build).
 usage: bench_trig_direct.py [n ...]"""
 import sys, pathlib, time; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 
 CEIL_TERMS = 157.3e12 / 4  # one mul + one add per term
-stream = torch.cuda.Stream()
+stream = abtime.one_stream()
 
 
 def ctx(tiled):
@@ -18,15 +18,6 @@ def ctx(tiled):
     f.set_direct_tiled(tiled)
     f.set_stream(stream.cuda_stream)
     return f
-
-
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
 
 
 tiled, simple = ctx(True), ctx(False)
@@ -49,17 +40,14 @@ for n in [int(a) for a in sys.argv[1:]] or [32, 64, 256, 1024, 4096]:
                 for _ in range(3):
                     c()
             torch.cuda.synchronize()
-            one = max(timed(c, 1) for c in calls.values())
+            one = max(abtime.timed(stream, c, 1) for c in calls.values())
             reps = max(1, min(50, int(5.0 / max(one, 1e-3))))
-            times = {k: [] for k in calls}
-            for _ in range(5):
-                for k, c in calls.items():
-                    times[k].append(timed(c, reps))
+            times = abtime.alternate(stream, calls, warmup=0, rounds=5, reps=reps)  # (warmed up above)
         line = f"{family}{type} n {n:5d} rows {rows:8d} first-call {first_ms:8.1f} ms:"
         for k, t in times.items():
             md = float(np.median(t))
             tps = terms / (md * 1e-3)
-            line += (f" | {k} {md:.3f} ms [{min(t):.3f} .. {max(t):.3f}] {tps / 1e12:.2f} Tterm/s valu {tps / CEIL_TERMS:.3f}"
+            line += (f" | {k} {abtime.cell(t)} {tps / 1e12:.2f} Tterm/s valu {tps / CEIL_TERMS:.3f}"
                      f" hbm {8 * rows * n / (md * 1e-3) / 8e12:.3f}")
         print(line, flush=True)
     del x, y

@@ -7,9 +7,9 @@ forward (wavedec_dev) and inverse (waverec_dev).  Every call moves 64 M input fl
 input point (one read, one write), and the fused and default routes against the per-level one.
 usage: bench_wavelet.py [n ...]"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 
-stream = torch.cuda.Stream()
+stream = abtime.one_stream()
 NAMES = ("haar", "db2", "db4", "sym4", "coif1")
 
 
@@ -20,27 +20,15 @@ def ctx(mode):
     return f
 
 
-def timed(call, reps):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
-
-
 def measure(calls):
     with torch.cuda.stream(stream):
         for c in calls.values():
             for _ in range(3):
                 c()
         torch.cuda.synchronize()
-        one = max(timed(c, 1) for c in calls.values())
+        one = max(abtime.timed(stream, c, 1) for c in calls.values())
         reps = max(1, min(200, int(5.0 / max(one, 1e-3))))
-        times = {k: [] for k in calls}
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c, reps))
+        times = abtime.alternate(stream, calls, warmup=0, rounds=5, reps=reps)  # (warmed up above)
     return times
 
 
@@ -48,7 +36,7 @@ def line(head, times, nbytes, base=None):
     md = {k: float(np.median(v)) for k, v in times.items()}
     out = head
     for k, v in times.items():
-        out += f" | {k} {md[k]:.3f} ms [{min(v):.3f} .. {max(v):.3f}] {nbytes / (md[k] * 1e-3) / 8e12:.3f}"
+        out += f" | {k} {abtime.cell(v)} {nbytes / (md[k] * 1e-3) / 8e12:.3f}"
     if base:
         out += " | vs per-level:" + "".join(f" {k} {md[base] / md[k]:.2f}x" for k in md if k != base)
     return out

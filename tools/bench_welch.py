@@ -6,37 +6,19 @@ is the number of whole segments.  Three warm-up calls, then five rounds of 10 ti
 [min .. max] ms per call.  Each shape is followed by one line for the cross spectrum of two such batches (no by-hand chain).
 usage: bench_welch.py [rows len win_len hop ...]      (groups of four; none: the shapes of DESIGN.md 5.26)"""
 import sys, pathlib; sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-import numpy as np, torch, kofft_amd
+import numpy as np, torch, kofft_amd, abtime
 ctxs = {"fused": kofft_amd.HipFftImpl(np.float32), "composed": kofft_amd.HipFftImpl(np.float32), "default": kofft_amd.HipFftImpl(np.float32)}
 ctxs["fused"].set_welch_fused(2)
 ctxs["composed"].set_welch_fused(0)
-stream = torch.cuda.Stream()
-for f in ctxs.values():
-    f.set_stream(stream.cuda_stream)
-
-
-def timed(call, reps=10):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record(stream)
-    for _ in range(reps):
-        call()
-    e.record(stream); torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+stream = abtime.one_stream(*ctxs.values())
 
 
 def run(calls, head):
-    times = {k: [] for k in calls}
     with torch.cuda.stream(stream):
-        for c in calls.values():
-            for _ in range(3):
-                c()
-        torch.cuda.synchronize()
-        for _ in range(5):
-            for k, c in calls.items():
-                times[k].append(timed(c))
+        times = abtime.alternate(stream, calls, warmup=3, rounds=5, reps=10)
     line = head
     for k, t in times.items():
-        line += f" | {k} {float(np.median(t)):.3f} ms [{min(t):.3f} .. {max(t):.3f}]"
+        line += f" | {k} {abtime.cell(t)}"
     print(line, flush=True)
 
 
