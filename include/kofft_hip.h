@@ -314,6 +314,59 @@ int kofft_hip_dev_convolve_bank_f32(kofft_hip_ctx *ctx, const float *d_x, size_t
                                     size_t block, unsigned flags, void *d_out, size_t out_first, size_t out_len);
 int kofft_hip_set_convolve_bank_fused(kofft_hip_ctx *ctx, int on);
 
+/* ---- fast DCT-IV of rows, MDCT of rows of signals and IMDCT ------------------------
+ * f32 only.  The reference has no such entry point; every value is a composition of its operations, all arithmetic f32 and un-fused,
+ * met bit for bit by every route.  "fft" is the reference's fft (fft.rs:1054-1132): a length that is not a power of two goes through
+ * its Bluestein arm.
+ * Tables.  kofft_hip_dct4_table_f32(n, out), n even, M = n / 2, needs no context or device: it writes M pairs c[j] = (cos a_j, sin a_j),
+ *   a_j = -PI (4j + 1) / (4n), then M pairs d[k] = (cos b_k, sin b_k), b_k = -PI k / n (2n floats); every angle and every cos / sin is
+ *   computed in double and rounded once to f32.  n == 0 -> EMPTY_INPUT; n odd -> INVALID_VALUE; out null -> KOFFT_ERR_NULL.
+ * dct4_fast(u), N even, M = N / 2:
+ *   z[j] = (u[2j], u[N-1-2j]) * c[j] for j < M, Complex::mul (num.rs:162-165: four products, one subtract, one add);
+ *   Z = fft(z) (nothing for M == 1);  y[k] = Z[k] * d[k];  X[2k] = y[k].re and X[N-1-2k] = -y[k].im.
+ *   In exact arithmetic X[k] = sum_i u[i] cos(PI / N (i + 1/2)(k + 1/2)): dct::dct4 without its O(n^2) loop.  The two differ in the
+ *   last bits; kofft_hip_dct4_f32 stays the direct sum.
+ *   kofft_hip_dct4_fast_f32 / kofft_hip_dev_dct4_fast_f32: batch rows of n reals in, batch rows of n reals out; out may equal in, no
+ *   other overlap.  Checks, in this order and before the context or a device is touched: batch == 0 -> KOFFT_OK; n == 0 ->
+ *   EMPTY_INPUT; n odd -> INVALID_VALUE; n / 2 beyond the complex limits (2^26 for powers of two, 2^25 otherwise) or batch * n too
+ *   large -> KOFFT_ERR_UNSUPPORTED; a null pointer or context -> KOFFT_ERR_NULL.
+ * MDCT.  `rows` signals of nx samples, row r at x + r * row_stride (in floats; ignored when rows == 1), a window w of 2N values,
+ *   `frames` frames per row, `lead` < 2N virtual zeros in front of every row.  Frame f, for i < 2N:
+ *     g[i] = x[f N + i - lead] * w[i] where that sample exists in its own row, +0 elsewhere (never a sample of row r +- 1);
+ *     u[j] = (-g[3N/2-1-j]) - g[3N/2+j] for j < N/2;  u[j] = g[j-N/2] - g[3N/2-1-j] for N/2 <= j < N;
+ *   the coefficients of frame (r, f) are dct4_fast(u), dense at out[(r * frames + f) * N].  In exact arithmetic
+ *   X[k] = sum_{i < 2N} g[i] cos(PI / N (i + 1/2 + N/2)(k + 1/2)), unscaled.  out must not overlap x or w.
+ *   Checks, in this order: rows == 0 or frames == 0 -> KOFFT_OK; N == 0 -> EMPTY_INPUT; N odd -> INVALID_VALUE; N / 2 beyond the
+ *   complex limits -> KOFFT_ERR_UNSUPPORTED; nx == 0 -> EMPTY_INPUT; lead >= 2N -> INVALID_VALUE; rows > 1 and row_stride < nx ->
+ *   INVALID_VALUE; sizes that overflow -> KOFFT_ERR_UNSUPPORTED; a null pointer or context -> KOFFT_ERR_NULL.
+ * IMDCT.  coef is rows * frames * N coefficients, w a window of 2N values.  v_f = dct4_fast(X_f);
+ *     y_f[i] = v[N/2+i] for i < N/2;  -v[3N/2-1-i] for N/2 <= i < 3N/2;  -v[i-3N/2] for 3N/2 <= i < 2N.
+ *   Each row has full = (frames + 1) N samples in hop blocks b of N: where both frames exist,
+ *     full[b N + j] = (w[N+j] * y_{b-1}[N+j] + w[j] * y_b[j]) * scale, the earlier frame's term on the left;
+ *   in blocks 0 and `frames` only one term exists and the value is that product * scale.  out receives full[out_first .. out_first +
+ *   out_len) of every row, dense, out_len floats per row.  With a Princen-Bradley window (w[i]^2 + w[i+N]^2 = 1), lead = N, scale =
+ *   2 / N, out_first = N and out_len = nx the result is the signal wherever two frames cover a sample.  out must not overlap coef or w.
+ *   Checks, in this order: rows == 0, frames == 0 or out_len == 0 -> KOFFT_OK; N == 0 -> EMPTY_INPUT; N odd -> INVALID_VALUE; N / 2
+ *   beyond the complex limits or sizes that overflow -> KOFFT_ERR_UNSUPPORTED; out_first + out_len > full -> MISMATCHED_LENGTHS; a
+ *   null pointer or context -> KOFFT_ERR_NULL.
+ * The host forms stage through the context's buffers; the kofft_hip_dev_* forms take device pointers and are asynchronous on the
+ * context's stream.  N = 64 .. 8192 a power of two with 4-byte aligned inputs runs one fused kernel per DCT-IV (the MDCT's window
+ * and fold on its loads); every other N, and every N after kofft_hip_set_mdct_fused(ctx, 0), runs the composed route through the
+ * context's scratch (fold / pre-twiddle, transform, post-twiddle: the same bytes; A/B measurements and tests).  The IMDCT writes the
+ * frames' DCT-IV into scratch the context owns (until kofft_hip_release_scratch / destroy), then one unfold-window-add kernel. */
+int kofft_hip_dct4_table_f32(size_t n, float *out);
+int kofft_hip_dct4_fast_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch);
+int kofft_hip_dev_dct4_fast_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
+int kofft_hip_mdct_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, size_t row_stride, const float *window, size_t n,
+                       size_t lead, float *out, size_t frames);
+int kofft_hip_dev_mdct_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_window, size_t n,
+                           size_t lead, float *d_out, size_t frames);
+int kofft_hip_imdct_f32(kofft_hip_ctx *ctx, const float *coef, size_t rows, size_t frames, const float *window, size_t n, float scale,
+                        float *out, size_t out_first, size_t out_len);
+int kofft_hip_dev_imdct_f32(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frames, const float *d_window, size_t n, float scale,
+                            float *d_out, size_t out_first, size_t out_len);
+int kofft_hip_set_mdct_fused(kofft_hip_ctx *ctx, int on);
+
 /* ---- polyphase resampling of rows (upfirdn, resample_poly) -----------------------------------
  * Sample-rate conversion by up / down of `rows` dense rows of nx f32 samples through one FIR filter of nh taps: out_len values per row
  * from up-sampled time t0 on, the decimating or interpolating filter computed directly in the time domain (with up == down == 1 a

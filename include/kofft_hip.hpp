@@ -365,6 +365,57 @@ public:
     {
         return convolve_impl(x, h, nh, out, rows, block, first, count, 1u);
     }
+    // The fast DCT-IV, the MDCT and the IMDCT of rows (kofft_hip_dct4_fast_f32, kofft_hip_mdct_f32, kofft_hip_imdct_f32; DESIGN.md
+    // 5.32), f32 only.  dct4_fast_rows: `rows` contiguous rows of x.size() / rows reals (an even length) in x, the same shape in out.
+    // MismatchedLengths for rows that do not divide x; then the C entry's checks in its order.
+    Result dct4_fast_rows(const std::vector<float> &x, std::vector<float> &out, size_t rows = 1) const
+    {
+        static_assert(std::is_same<T, float>::value, "dct4_fast_rows is f32-only");
+        if (rows == 0 || x.size() % rows != 0) return Result::Err(FftError::MismatchedLengths);
+        out.resize(x.size());
+        return st(kofft_hip_dct4_fast_f32(ctx_, x.data(), out.data(), x.size() / rows, rows));
+    }
+    // mdct_rows: `rows` contiguous signals of x.size() / rows samples, a window of 2N values, `frames` frames per row (SIZE_MAX:
+    // ceil(nx / N) + 1) after `lead` virtual zeros (SIZE_MAX: N); out is resized to rows * frames * N unscaled coefficients.
+    // MismatchedLengths for rows that do not divide x or a window of odd length, EmptyInput for an empty window or signal.
+    Result mdct_rows(const std::vector<float> &x, const std::vector<float> &window, std::vector<float> &out, size_t rows = 1,
+                     size_t lead = SIZE_MAX, size_t frames = SIZE_MAX) const
+    {
+        static_assert(std::is_same<T, float>::value, "mdct_rows is f32-only");
+        if (rows == 0 || x.size() % rows != 0 || window.size() % 2 != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows, n = window.size() / 2;
+        if (nx == 0 || n == 0) return Result::Err(FftError::EmptyInput);
+        if (lead == SIZE_MAX) lead = n;
+        if (frames == SIZE_MAX) frames = (nx + n - 1) / n + 1;
+        out.resize(rows * frames * n);
+        float dummy = 0.0f;  // (frames == 0: the C entry returns before it looks at the pointer)
+        return st(kofft_hip_mdct_f32(ctx_, x.data(), rows, nx, nx, window.data(), n, lead, out.empty() ? &dummy : out.data(), frames));
+    }
+    // imdct_rows: coef holds rows * frames * N coefficients, N = window.size() / 2; out is resized to rows * count samples, first ..
+    // first + count of the (frames + 1) N overlap-added samples per row (count == SIZE_MAX: up to the end), each times scale (a
+    // negative scale: 2 / N).  MismatchedLengths for a window of odd length or coef that is no whole number of rows of frames.
+    Result imdct_rows(const std::vector<float> &coef, const std::vector<float> &window, std::vector<float> &out, size_t rows = 1,
+                      float scale = -1.0f, size_t first = 0, size_t count = SIZE_MAX) const
+    {
+        static_assert(std::is_same<T, float>::value, "imdct_rows is f32-only");
+        if (rows == 0 || window.size() % 2 != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t n = window.size() / 2;
+        if (n == 0) return Result::Err(FftError::EmptyInput);
+        if (coef.size() % (rows * n) != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t frames = coef.size() / (rows * n), full = (frames + 1) * n;
+        if (count == SIZE_MAX) {
+            if (first > full) return Result::Err(FftError::MismatchedLengths);
+            count = full - first;
+        }
+        if (first > full || count > full - first) return Result::Err(FftError::MismatchedLengths);
+        out.resize(rows * count);
+        float dummy = 0.0f;  // (count == 0: the C entry returns before it looks at the pointer)
+        return st(kofft_hip_imdct_f32(ctx_, coef.data(), rows, frames, window.data(), n, scale < 0.0f ? 2.0f / (float)n : scale,
+                                      out.empty() ? &dummy : out.data(), first, count));
+    }
+    // false: every fast DCT-IV, MDCT and IMDCT of this context through fold / pre-twiddle into the scratch, transform, post-twiddle
+    // (the same bytes; A/B, tests)
+    Result set_mdct_fused(bool on) const { return st(kofft_hip_set_mdct_fused(ctx_, on ? 1 : 0)); }
     // Overlap-save FFT convolution of `rows` contiguous rows of x.size() / rows samples with every filter of a bank that the rows
     // share (kofft_hip_convolve_bank_f32): h holds h.size() / nh filters of nh taps, float or Complex<float>; each frame is
     // transformed once for the whole bank.  out is resized to rows * filters * count elements, [row][filter][count]: values first ..

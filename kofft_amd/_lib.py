@@ -89,6 +89,14 @@ SIGNATURES = {
     "kofft_hip_convolve_bank_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
     "kofft_hip_dev_convolve_bank_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_uint, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_convolve_bank_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_dct4_table_f32": (C.c_int, [_sz, C.c_void_p]),
+    "kofft_hip_dct4_fast_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_dct4_fast_f32": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, _sz, _sz]),
+    "kofft_hip_mdct_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_dev_mdct_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, C.c_void_p, _sz]),
+    "kofft_hip_imdct_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_float, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_imdct_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_float, C.c_void_p, _sz, _sz]),
+    "kofft_hip_set_mdct_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_dev_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_set_resample_tiled": (C.c_int, [_ctx, C.c_int]),

@@ -33,6 +33,7 @@ enum TableKind : int {
     kTableRadix4TwF32 = 11,  // ... and every stage's (w1, w2, w3) triples, built and cached together
     kTableRadix4TwF64 = 12,
     kTableDct2 = 13,         // DctPlanner (cos, sin): n pairs, f32 only
+    kTableDct4Fast = 14,     // the fast DCT-IV's pre- and post-twiddles: n / 2 + n / 2 pairs, f32 only
     // the n x ldc tables of the direct sums: kTableDirect + 4 * family + (type - 1), family 0 = DCT, 1 = DST (direct_table_kind)
     kTableDirect = 20,
     kTableDct1Direct = kTableDirect + 4 * 0 + 0,

@@ -72,6 +72,7 @@ struct kofft_hip_ctx {
     bool cepstrum_fused = true; // kofft_hip_set_cepstrum_fused(ctx, 0): real cepstra of every length through the composed route (expand, fft_dev, log-magnitude, inverse fft_dev, real parts; A/B, tests)
     bool convolve_fused = true; // kofft_hip_set_convolve_fused(ctx, 0): overlap-save convolutions of every block through the composed route (expand, fft_dev, multiply, inverse fft_dev, gather; A/B, tests)
     bool convolve_bank_fused = true; // kofft_hip_set_convolve_bank_fused(ctx, 0): filter-bank convolutions of every block through the composed route (expand and fft_dev once, then per filter multiply, inverse fft_dev, gather; A/B, tests)
+    bool mdct_fused = true;   // kofft_hip_set_mdct_fused(ctx, 0): fast DCT-IV, MDCT and IMDCT of every length through the composed route (fold / pre-twiddle, fft_dev, post-twiddle; A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
     int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
     int welch_fused = 1;      // kofft_hip_set_welch_fused: 1 the measured choice (welch_use_fused), 0 every Welch / cross-spectrum call through the composed route (one-sided frames into the scratch, then the sums), 2 the fused kernel wherever it exists (A/B, tests)
@@ -240,6 +241,11 @@ int rfft_table(kofft_hip_ctx *ctx, size_t n, const cpx<T> **out)
 inline int dct2_table(kofft_hip_ctx *ctx, size_t n, const cpx<float> **out)
 {
     return planner_table<float>(ctx, kTableDct2, n, n, kofft_tables::dct2_table_f32, nullptr, out);
+}
+// the fast DCT-IV's twiddles of an even n: c at out[0 .. n/2), d at out[n/2 .. n)
+inline int dct4_table(kofft_hip_ctx *ctx, size_t n, const cpx<float> **out)
+{
+    return planner_table<float>(ctx, kTableDct4Fast, n, n, kofft_tables::dct4_table_f32, nullptr, out);
 }
 
 constexpr size_t kZeroCopyMax = size_t(512) << 10;  // bytes per direction up to which a host call goes zero-copy
@@ -774,6 +780,18 @@ int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_
                         const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx);
 int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
                       unsigned flags, void *d_out, size_t out_first, size_t out_len);
+// k_mdct_f32.hip: the fast DCT-IV of rows, the MDCT of rows of signals and the IMDCT with its overlap-add (mdct_impl.hip.h; DESIGN.md
+// 5.32).  The *_check functions: the argument checks alone, in the order of include/kofft_hip.h
+int dct4_fast_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
+int dct4_fast_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
+int mdct_check(size_t rows, size_t nx, size_t row_stride, size_t n, size_t lead, size_t frames, const void *x, const void *w, const void *out,
+               const kofft_hip_ctx *ctx);
+int mdct_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_w, size_t n, size_t lead,
+             float *d_out, size_t frames);
+int imdct_check(size_t rows, size_t frames, size_t n, size_t out_first, size_t out_len, const void *coef, const void *w, const void *out,
+                const kofft_hip_ctx *ctx);
+int imdct_dev(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frames, const float *d_w, size_t n, float scale, float *d_out,
+              size_t out_first, size_t out_len);
 // k_resample_f32.hip: polyphase resampling of rows (resample_impl.hip.h, resample_plan.h).  resample_check: the argument
 // checks alone, in the order of include/kofft_hip.h; resample_taps: scipy.signal.resample_poly's default filter, host only
 int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, size_t t0, size_t out_len, const void *x, const void *h,

@@ -1629,6 +1629,66 @@ int kofft_hip_set_frontend_fused(kofft_hip_ctx *ctx, int mode)
     return KOFFT_OK;
 }
 
+// ---- fast DCT-IV of rows, MDCT of rows of signals and IMDCT (k_mdct_f32.hip) ----------------------------------------
+// Whole rows per chunk of the host pipeline; the window is the side input, uploaded once.
+int kofft_hip_dct4_table_f32(size_t n, float *out)
+{
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (n & 1) return KOFFT_ERR_INVALID_VALUE;
+    if (!out) return KOFFT_ERR_NULL;
+    kofft_tables::dct4_table_f32(n, out);
+    return KOFFT_OK;
+}
+int kofft_hip_set_mdct_fused(kofft_hip_ctx *ctx, int on)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    ctx->mdct_fused = on != 0;
+    return KOFFT_OK;
+}
+int kofft_hip_dev_dct4_fast_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+{
+    return dct4_fast_dev(ctx, d_in, d_out, n, batch);
+}
+int kofft_hip_dct4_fast_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
+{
+    const int crc = dct4_fast_check(n, batch, in, out, ctx);
+    if (crc || batch == 0) return crc;
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, true,
+                            [&](float *d_in, float *d_out, const float *, size_t nb) { return dct4_fast_dev(ctx, d_in, d_out, n, nb); });
+}
+int kofft_hip_dev_mdct_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_window, size_t n,
+                           size_t lead, float *d_out, size_t frames)
+{
+    return mdct_dev(ctx, d_x, rows, nx, row_stride, d_window, n, lead, d_out, frames);
+}
+int kofft_hip_mdct_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, size_t row_stride, const float *window, size_t n, size_t lead,
+                       float *out, size_t frames)
+{
+    const int crc = mdct_check(rows, nx, row_stride, n, lead, frames, x, window, out, ctx);
+    if (crc || rows == 0 || frames == 0) return crc;
+    std::vector<float> packed;
+    const float *src = pack_rows(x, rows, nx, row_stride, packed);
+    return rows_host<float>(ctx, src, out, rows, nx, frames * n, window, 2 * n, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return mdct_dev(ctx, d_in, nb, nx, nx, d_win, n, lead, d_out, frames);
+                            });
+}
+int kofft_hip_dev_imdct_f32(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frames, const float *d_window, size_t n, float scale,
+                            float *d_out, size_t out_first, size_t out_len)
+{
+    return imdct_dev(ctx, d_coef, rows, frames, d_window, n, scale, d_out, out_first, out_len);
+}
+int kofft_hip_imdct_f32(kofft_hip_ctx *ctx, const float *coef, size_t rows, size_t frames, const float *window, size_t n, float scale, float *out,
+                        size_t out_first, size_t out_len)
+{
+    const int crc = imdct_check(rows, frames, n, out_first, out_len, coef, window, out, ctx);
+    if (crc || rows == 0 || frames == 0 || out_len == 0) return crc;
+    return rows_host<float>(ctx, coef, out, rows, frames * n, out_len, window, 2 * n, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return imdct_dev(ctx, d_in, nb, frames, d_win, n, scale, d_out, out_first, out_len);
+                            });
+}
+
 // ---- Welch power spectra and cross spectra of rows (k_welch_f32.hip) ----------------------------------------------
 // The signals go up, rows * K values come down (whole rows per chunk of the pipeline); no frame leaves the device.
 static int welch_host(kofft_hip_ctx *ctx, bool csd, const float *x, const float *y, size_t rows, size_t len, size_t row_stride,

@@ -166,6 +166,22 @@ void dct2_table_f32(size_t n, float *cs)
         cs[2 * k + 1] = sinf(a);
     }
 }
+// The fast DCT-IV's pre- and post-twiddles: no reference code to follow, so the best f32 value of each entry
+void dct4_table_f32(size_t n, float *out)
+{
+    const double pi = 3.14159265358979323846;
+    const size_t m = n / 2;
+    for (size_t j = 0; j < m; ++j) {
+        const double a = -(pi * (double)(4 * j + 1)) / (double)(4 * n);
+        out[2 * j] = (float)cos(a);
+        out[2 * j + 1] = (float)sin(a);
+    }
+    for (size_t k = 0; k < m; ++k) {
+        const double b = -(pi * (double)k) / (double)n;
+        out[2 * (m + k)] = (float)cos(b);
+        out[2 * (m + k) + 1] = (float)sin(b);
+    }
+}
 }  // namespace kofft_tables
 
 // ---- direct DCT / DST tables ---------------------------------------------------------------------------------------------------

@@ -10,6 +10,9 @@ void rfft_table_f64(size_t m, double *out);
 void hann_f32(size_t len, float *out);
 // DctPlanner (dct.rs:50-58, 89-92): n (cos, sin) pairs of a_k = (PI * k) / (2 * n), all in f32
 void dct2_table_f32(size_t n, float *cs);
+// The fast DCT-IV's two twiddle tables, n even and M = n / 2: M (cos, sin) pairs of a_j = -PI (4j + 1) / (4n), then
+// M pairs of b_k = -PI k / n; every angle and every cos / sin in double, rounded once to f32
+void dct4_table_f32(size_t n, float *out);
 // dct::dct1..dct4 (dct.rs:108-176) and dst::dst1..dst4 (dst.rs:89-146): the n x n table C[i][k] (row-major, row stride ldc >= n)
 // of the direct sums, each entry glibc cosf / sinf of the reference's angle; rows outside the kind's i range are zero, so are
 // columns n .. ldc-1.  family 0 = DCT, 1 = DST; type 1..4.  Built on up to 16 host threads.
