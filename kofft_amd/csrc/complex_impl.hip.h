@@ -3,6 +3,7 @@
 #pragma once
 
 #include "host_common.hip.h"
+#include "host_stage.hip.h"
 #include "fft_radix4.hip.h"
 
 namespace kofft {
@@ -994,6 +995,56 @@ int fft_radix4_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t
             KOFFT_HIP_TRY(ctx, hipGetLastError());
             off += len / 4;
         }
+    }
+    return KOFFT_OK;
+}
+
+// ---- the same transforms on host buffers (host_stage.hip.h) -------------------------------------------------------------------
+template <typename T>
+int fft_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inverse)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (n > (size_t(1) << (is_pow2(n) ? max_log2_big<T>() : max_log2_big<T>() - 1))) return KOFFT_ERR_UNSUPPORTED;
+    if (n == 1) return KOFFT_OK;
+    if (!ctx || !data) return KOFFT_ERR_NULL;
+    const HostArray<T> a{data, data, 2 * n};
+    return rows_host_n<T>(ctx, batch, 1, &a, nullptr, 0, is_pow2(n), true,
+                          [&](T *const *d, const T *, size_t rows) { return fft_dev<T>(ctx, d[0], d[0], n, rows, inverse); });
+}
+
+// ScalarFftImpl::fft_radix4 on a host buffer (fft_radix4.hip.h); inverse: FftPlan::ifft's loop around it (fft.rs:2040-2055)
+template <typename T>
+int fft_radix4_host(kofft_hip_ctx *ctx, T *data, size_t n, size_t batch, int inverse)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (!is_pow2(n) || (ilog2(n) & 1)) return fft_host<T>(ctx, data, n, batch, inverse);  // fft.rs:1457-1460
+    if (n > (size_t(1) << max_log2_big<T>())) return KOFFT_ERR_UNSUPPORTED;
+    if (n == 1) return KOFFT_OK;
+    if (!ctx || !data) return KOFFT_ERR_NULL;
+    const HostArray<T> a{data, data, 2 * n};
+    return stage_host<T>(ctx, batch, 1, &a, nullptr, 0, false, false,
+                         [&](T *const *d, const T *, size_t rows) { return fft_radix4_dev<T>(ctx, d[0], d[0], n, rows, inverse); });
+}
+
+// fft_strided / ifft_strided (fft.rs:1175-1199, 1236-1260): gather, transform, scatter.
+template <typename T>
+int fft_strided_host(kofft_hip_ctx *ctx, T *data, size_t data_len, size_t stride, size_t n, int inverse)
+{
+    if (stride == 0) return KOFFT_ERR_INVALID_STRIDE;  // fft.rs:1181
+    if (n == 0) return KOFFT_OK;                       // fft.rs:1185
+    if (data_len < (n - 1) * stride + 1) return KOFFT_ERR_MISMATCHED_LENGTHS;  // fft.rs:1188
+    if (!ctx || !data) return KOFFT_ERR_NULL;
+    std::vector<T> scratch(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        scratch[2 * i] = data[2 * i * stride];
+        scratch[2 * i + 1] = data[2 * i * stride + 1];
+    }
+    int rc = fft_host<T>(ctx, scratch.data(), n, 1, inverse);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        data[2 * i * stride] = scratch[2 * i];
+        data[2 * i * stride + 1] = scratch[2 * i + 1];
     }
     return KOFFT_OK;
 }

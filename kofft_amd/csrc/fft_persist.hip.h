@@ -206,7 +206,7 @@ struct NoXchg {
 };
 
 // Everything a thread keeps across transforms.
-// CFG (kofft_hip.hip: PersistCfg<L, IO>) carries the per-size, per-policy choices: BLOCK, NBUF, MINW and where the
+// CFG (host_common.hip.h: PersistCfg<L, IO>) carries the per-size, per-policy choices: BLOCK, NBUF, MINW and where the
 // thread-invariant operands live -- kInvInLds (window samples in one LDS copy per workgroup instead of R registers)
 // and kTwLastInLds (the last pass reads its twiddles from an LDS copy of the table instead of holding them in
 // registers): both trade LDS reads for the registers that decide between 2 and 3 waves per SIMD.

@@ -62,7 +62,7 @@ struct PlainTw {
     static constexpr int kPersistMaxLog2 = 13;  // largest transform the persistent kernel is built for with this policy
     // smallest one it is USED for (measured against the generic kernel, one box: complex n = 128 / 256 lose 5 %, STFT
     // gains 22 % / 6 % (n = 64: 20 %), irfft 16 % / 29 % (m = 64: 5 %), rfft n = 128 .. 512 gains 4 .. 10 % once its grid
-    // is halved -- PersistGrid in kofft_hip.hip)
+    // is halved -- PersistCfg::WG_PER_CU in host_common.hip.h)
     static constexpr int kPersistMinLog2 = 9;
     // dispatch() is reached with n = 1 (rfft of two reals, a one-sample STFT window); policies whose callers return before it say false
     static constexpr bool kLen1 = true;

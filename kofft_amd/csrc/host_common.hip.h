@@ -1,7 +1,8 @@
 // host_common.hip.h -- what every translation unit of libkofft_hip.so shares: the context, the planner-table cache,
 // launch geometry and the size dispatch.  The kernels are instantiated per family in their own translation units
-// (k_complex_*.hip, k_real_*.hip, k_stft.hip, k_nd.hip) so that the library builds in parallel; kofft_hip.hip holds the
-// host-pointer wrappers and the extern "C" ABI of include/kofft_hip.h.  gfx950 only; compiled with -ffp-contract=off.
+// (k_complex_*.hip, k_real_*.hip, k_stft.hip, k_nd.hip, ...) so that the library builds in parallel, and each of those units holds
+// its family's checks, launchers, host-pointer wrappers (host_stage.hip.h) and extern "C" entry points of include/kofft_hip.h;
+// kofft_hip.hip keeps the context's lifecycle and the host-only recipes.  gfx950 only; compiled with -ffp-contract=off.
 #pragma once
 
 #include "../../include/kofft_hip.h"
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -159,6 +161,17 @@ namespace host {
             return KOFFT_ERR_HIP;                                                             \
         }                                                                                     \
     } while (0)
+
+// The body of a route-switch setter (kofft_hip_set_*): a bool member takes value != 0, an int member the value itself, which must lie
+// in [lo, hi].
+template <class F>
+inline int set_route(kofft_hip_ctx *ctx, F kofft_hip_ctx::*member, int value, int lo = INT_MIN, int hi = INT_MAX)
+{
+    if (!ctx) return KOFFT_ERR_NULL;
+    if (value < lo || value > hi) return KOFFT_ERR_INVALID_VALUE;
+    ctx->*member = static_cast<F>(value);  // (bool: value != 0)
+    return KOFFT_OK;
+}
 
 inline bool is_pow2(size_t n) { return n != 0 && (n & (n - 1)) == 0; }
 inline int ilog2(size_t n)
@@ -749,121 +762,31 @@ inline int hann_table(kofft_hip_ctx *ctx, size_t win_len, const float **out)
     });
 }
 
-// ---- typed device-pointer entry points, one translation unit per family ---------------------------------------------
+// ---- what one translation unit defines and another calls -----------------------------------------------------------------------
+// Only that: a function that nothing outside its own unit calls is not declared here and has internal linkage there
+// (tests/test_abi_symbols.py counts the files that mention each name between the two marks).
+// [cross-unit declarations: begin]
 template <typename T>
 int fft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch, int inverse);  // k_complex_f32/f64.hip
 template <typename T>
-int fft_axis2_dev(kofft_hip_ctx *ctx, T *d_data, int LT, int I, size_t blocks, int inverse);  // k_complex_f32/f64.hip: ndfft's long axes in two passes
+int fft_axis2_dev(kofft_hip_ctx *ctx, T *d_data, int LT, int I, size_t blocks, int inverse);  // k_big_f32/f64.hip: ndfft's long axes in two passes
 bool fft2d_fused_ok(const kofft_hip_ctx *ctx, size_t rows, size_t cols);                      // k_nd_fused.hip: shapes the two-pass 2-D route takes
 int fft2d_fused_c32(kofft_hip_ctx *ctx, float *d_data, size_t rows, size_t cols, int inverse);  // ... rows + 2 column stages, then one column-tile pass
 template <typename T>
-int fft_big_windowed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, size_t m, size_t batch);  // factor path, window in the first load
-template <typename T>
-int fft_radix4_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch, int inverse);  // fft.rs:1455-1548, the reference's bytes (inverse: FftPlan::ifft's loop around it)
-template <typename T>
-int rfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, size_t n, size_t batch);  // k_real_f32/f64.hip
-template <typename T>
-int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch);
-int dct2_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_dct_f32.hip: DctPlanner::plan_dct2
-int hilbert_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: hilbert::hilbert_analytic
-int cepstrum_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);  // k_hilbert_f32.hip: cepstrum::real_cepstrum
-// k_convolve_f32.hip: overlap-save FFT convolution / correlation of rows (convolve_impl.hip.h).  convolve_check: the
-// argument checks alone, in the order of include/kofft_hip.h; *block == 0 is resolved to the default block
-size_t convolve_default_block(size_t nx, size_t nh);  // nx, nh >= 1
-int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *block, unsigned flags, size_t out_first, size_t out_len,
-                   const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx);
-int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
-                 unsigned flags, float *d_out, size_t out_first, size_t out_len);
-// k_convolve_f32.hip: the same against a bank of filters that all rows share (convolve_bank_impl.hip.h); flags bit 0
-// correlate, bit 1 complex taps, bits 2-3 the output kind (real part, complex value, magnitude)
-int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_t *block, unsigned flags, size_t out_first, size_t out_len,
-                        const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx);
-int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
-                      unsigned flags, void *d_out, size_t out_first, size_t out_len);
-// k_mdct_f32.hip: the fast DCT-IV of rows, the MDCT of rows of signals and the IMDCT with its overlap-add (mdct_impl.hip.h; DESIGN.md
-// 5.32).  The *_check functions: the argument checks alone, in the order of include/kofft_hip.h
-int dct4_fast_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
-int dct4_fast_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
-int mdct_check(size_t rows, size_t nx, size_t row_stride, size_t n, size_t lead, size_t frames, const void *x, const void *w, const void *out,
-               const kofft_hip_ctx *ctx);
-int mdct_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_w, size_t n, size_t lead,
-             float *d_out, size_t frames);
-int imdct_check(size_t rows, size_t frames, size_t n, size_t out_first, size_t out_len, const void *coef, const void *w, const void *out,
-                const kofft_hip_ctx *ctx);
-int imdct_dev(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frames, const float *d_w, size_t n, float scale, float *d_out,
-              size_t out_first, size_t out_len);
-// k_resample_f32.hip: polyphase resampling of rows (resample_impl.hip.h, resample_plan.h).  resample_check: the argument
-// checks alone, in the order of include/kofft_hip.h; resample_taps: scipy.signal.resample_poly's default filter, host only
-int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, size_t t0, size_t out_len, const void *x, const void *h,
-                   const void *out, const kofft_hip_ctx *ctx);
-int resample_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t nh, size_t up, size_t down, size_t t0,
-                 float *d_out, size_t out_len);
-int resample_taps(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh);
-// k_sosfilt_f32.hip: IIR filtering of rows by a cascade of biquads (sosfilt_impl.hip.h, sosfilt_plan.h).  sosfilt_check:
-// the argument checks alone, in the order of include/kofft_hip.h; host_sos: sos is host memory and every a0 is compared with 1.0f
-int sosfilt_check(size_t rows, size_t nx, size_t sections, unsigned flags, const void *x, const void *sos, const void *zi, const void *zf,
-                  const void *out, const kofft_hip_ctx *ctx, bool host_sos, const size_t *scan_chunk = nullptr);
-int sosfilt_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
-                float *d_zf, unsigned flags, float *d_out);
-// the scan along time: sosfilt_check with scan_chunk, rows * C chunks walked in parallel, the states in ctx->real_tmp
-int sosfilt_scan_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
-                     float *d_zf, size_t chunk, unsigned flags, float *d_out);
-// k_planar_f32/f64.hip: FftImpl::fft_split / ifft_split on planes of batch * n reals (planar_impl.hip.h); planar_check: the argument
-// checks alone, in the order of fft_dev and before the context or a device is touched
-inline int planar_check(size_t n, size_t batch, const void *p0, const void *p1, const void *p2, const void *p3, const kofft_hip_ctx *ctx)
-{
-    if (batch == 0) return KOFFT_OK;
-    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;  // fft.rs:794
-    if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
-    if (!ctx || !p0 || !p1 || !p2 || !p3) return KOFFT_ERR_NULL;
-    return KOFFT_OK;
-}
-template <typename T>
-int planar_dev(kofft_hip_ctx *ctx, const T *d_re_in, const T *d_im_in, T *d_re_out, T *d_im_out, size_t n, size_t batch, int inverse);
-// k_direct_f32.hip: dct::dct1..4 (family 0) / dst::dst1..4 (family 1), the direct sums; direct_check: the argument checks alone
+int fft_big_windowed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, size_t m, size_t batch);  // k_big_f32/f64.hip: factor path, window in the first load
+int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
+                       float *d_out, size_t count, bool *done);  // k_blue_f32.hip (complex_impl.hip.h)
+// k_direct_f32.hip: dct::dct1..4 (family 0) / dst::dst1..4 (family 1), the direct sums, with their argument checks
 constexpr size_t kDirectMaxN = 4096;  // the longest row: the n x n table is 64 MiB there
-int direct_check(int family, int type, size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
 int direct_dev(kofft_hip_ctx *ctx, int family, int type, const float *d_in, float *d_out, size_t n, size_t batch);
-// k_wavelet_f32.hip: wavelet::* (haar, db2, db4, sym4, coif1; wavelet_impl.hip.h); *_check: the argument checks alone
-constexpr size_t kWaveletMaxLen = size_t(1) << 26;  // the longest input or output row
-constexpr size_t kWaveletMaxLevels = 64;
-constexpr size_t kWaveletFusedMax = 16384;  // the longest row (forward: input, inverse: output) the fused multi-level kernels keep in LDS
-size_t wavelet_lengths(size_t len, size_t levels, size_t *lens);  // lens[0] = len, lens[l] = ceil(lens[l - 1] / 2); returns sum lens[1..]
-void wavelet_taps(int w, bool inverse, float *lo, float *hi);      // the coefficient table (8 + 8 floats, +0 past the length; haar: none)
-int dwt_check(int w, size_t len, size_t batch, size_t levels, const void *p0, const void *p1, const void *p2, const kofft_hip_ctx *ctx);
-int idwt_check(int w, size_t n, size_t batch, size_t levels, const size_t *dl, const void *p0, const void *p1, const void *p2,
-               const kofft_hip_ctx *ctx);
-int dwt_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_detail, size_t len, size_t batch);
-int idwt_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_detail, float *d_out, size_t n, size_t batch);
-int dwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_details, size_t len, size_t batch, size_t levels);
-int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_details, const size_t *detail_lens, float *d_out,
-                   size_t n, size_t batch, size_t levels);
 // k_direct_f32.hip: the +0-seeded sums out[b][k] = sum_i x[b][i] * table[i][k], i < n, k < nk, on direct_tiled_kernel<DIR_ZERO> /
 // direct_simple_kernel<DIR_ZERO> (direct_use_tiled(ctx, nk, batch)); table: n rows of direct_ldc(nk) floats
 int direct_zero_sums(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *table, size_t n, size_t nk, size_t batch);
-// k_hartley_f32.hip: hartley::dht (hartley_impl.hip.h), n <= kDirectMaxN; dht_check: the argument checks alone
-int dht_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
-int dht_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch);
-// k_spectral_f32.hip: czt::czt_f32 and goertzel::goertzel_f32 (spectral_impl.hip.h); *_check: the argument checks alone
-constexpr size_t kCztMax = 4096;                       // the longest row and the most bins: the table is 128 MiB there
-constexpr size_t kGoertzelMaxLen = size_t(1) << 26;
-constexpr size_t kGoertzelMaxFreqs = 1024;
-int czt_check(size_t n, size_t m, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx);
-int czt_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch);
-int goertzel_check(size_t n, size_t batch, float sample_rate, const void *freqs, size_t nfreq, const void *in, const void *out,
-                   const kofft_hip_ctx *ctx);
-int goertzel_launch(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *d_coeff, size_t n, size_t batch, size_t nfreq);
-int goertzel_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate, const float *target_freqs,
-                 size_t nfreq);
-void spectral_drop(kofft_hip_ctx *ctx);  // frees every slot and the coefficient buffer; the caller has synchronised the stream
-// k_mfcc_f32.hip: cepstrum::mel_filterbank / mfcc with the edges as an input (mfcc_impl.hip.h); mel_check: the argument checks alone,
-// mfcc: whether num_coeffs takes part; *_dev return before the edge sizes (num_mel == 0, num_coeffs == 0) touch anything
+void spectral_drop(kofft_hip_ctx *ctx);  // k_spectral_f32.hip: frees every chirp-Z slot and the Goertzel coefficient buffer; the caller has synchronised the stream
+// k_mfcc_f32.hip: cepstrum::mel_filterbank / mfcc with the edges as an input (mfcc_impl.hip.h), with their argument checks; they
+// return before the edge sizes (num_mel == 0, num_coeffs == 0) touch anything
 constexpr size_t kMelMaxFft = size_t(1) << 24;  // (k - a) as f32 is exact below it
 constexpr size_t kMfccFusedMaxMel = 128;        // the fused kernel's log-mel columns: 256 bytes of LDS per filter and workgroup
-constexpr size_t kMfccFusedDefaultMel = 80;     // the measured choice: the fused kernel up to 80 filters (five workgroups per CU) ...
-constexpr size_t kMfccFusedDefaultCoeffs = 16;  // ... and 16 coefficients (two passes of its DCT)
-int mel_check(bool mfcc, bool dev, const void *mags, const void *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
-              size_t num_coeffs, const kofft_hip_ctx *ctx);
 int mel_filterbank_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_energies, size_t n_fft, size_t rows, const uint64_t *bins,
                        size_t num_mel);
 int mfcc_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
@@ -871,51 +794,20 @@ int mfcc_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_
 void mel_drop(kofft_hip_ctx *ctx);  // frees every plan; the caller has synchronised the stream
 // the device plan [seg | live | w] of (bins, n_fft, num_mel) from the context's cache, built and uploaded stream-ordered on a miss
 int get_mel_plan(kofft_hip_ctx *ctx, const uint64_t *bins, size_t n_fft, size_t num_mel, const int **out);
-// k_frontend_f32.hip: rows of audio -> stft_magnitudes -> mel_filterbank (-> logf -> dct2) in one call (frontend_impl.hip.h; DESIGN.md
-// 5.23); d_window null: window::hann(win_len).  frontend_check: the argument checks alone, the STFT rows' first, then the mel ones
-int frontend_check(bool mfcc, bool dev, const void *signal, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
-                   size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, const kofft_hip_ctx *ctx);
-int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
-                 size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *d_out);
-// k_spectrogram_f32.hip: visual::spectrogram's colour helpers (spectrogram_impl.hip.h).  spec_*_check: the argument checks alone, in
-// the order of include/kofft_hip.h; pix_of_bin is a host pointer in both forms, max_mag a device pointer in the *_dev functions
+// k_spectrogram_f32.hip: visual::spectrogram's colour helpers (spectrogram_impl.hip.h)
 constexpr size_t kSpecMaxBins = size_t(1) << 24;
-int spec_db_check(bool dev, const void *mags, size_t count, const void *max_mag, const void *out, const kofft_hip_ctx *ctx);
-int spec_db_dev(kofft_hip_ctx *ctx, int which, const float *d_mags, size_t count, const float *d_max, float level, float *d_out);
-int spec_render_check(bool dev, const void *mags, size_t frames, size_t bins, const void *max_mag, int mode, int cmap, int depth, int scale,
-                      int layout, const uint32_t *pix_of_bin, const void *out, const kofft_hip_ctx *ctx);
-int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max, int mode, float level, int cmap,
-                    int depth, int scale, int layout, const uint32_t *pix_of_bin, void *d_out);
-int spec_map_color_u8(float t, int cmap, unsigned char *rgb);
 // the device ranges [start[p], start[p + 1]) of a checked log_scale_bins table, from the context's cache (uploaded stream-ordered on a miss)
 int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins, const uint32_t **out);
+void spec_drop(kofft_hip_ctx *ctx);  // frees every range table; the caller has synchronised the stream
 // k_frontend_f32.hip: magnitudes of frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_mags, no maximum; no
 // checks (framed_produce's leaf for FRAMES_MAGS)
 int mags_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_win, size_t win_len,
                size_t hop, size_t f0, size_t nf, float *d_mags);
-// k_picture_f32.hip: rows of audio -> stft_magnitudes -> the maximum (max_mode 0: of the row, 1: compute_frame's running one, 2: given)
-// -> one picture per row (picture_impl.hip.h).  picture_check: the argument checks alone, in the order of
-// include/kofft_hip.h; *empty is set where the call has no bins (win_len == 1) and only max_out is written
-int picture_check(bool dev, const void *signal, size_t rows, size_t len, size_t row_stride, const void *window, size_t win_len, size_t hop,
-                  size_t frames, int max_mode, const void *max_in, const void *max_out, int mode, int cmap, int depth, int channels, int scale,
-                  int layout, const uint32_t *pix_of_bin, const void *out, const kofft_hip_ctx *ctx, bool *empty);
-int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
-                size_t hop, size_t frames, int max_mode, const float *d_max_in, float *d_max_out, int mode, float level, int cmap, int depth,
-                int channels, int scale, int layout, const uint32_t *pix_of_bin, void *d_out);
-void spec_drop(kofft_hip_ctx *ctx);  // frees every range table; the caller has synchronised the stream
-int stft_bluestein_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t n, size_t start0, size_t hop,
-                       float *d_out, size_t count, bool *done);  // k_complex_f32.hip (complex_impl.hip.h)
-int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t start0,
-             size_t hop, float *d_out, size_t count);  // k_stft.hip
-int istft_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, const float *d_window, size_t win_len, size_t hop,
-              float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode = 1, size_t start0 = 0);
 int stft_mag_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t win_len, size_t hop, float *d_mags,
-                 size_t frames, float *d_max);
+                 size_t frames, float *d_max);  // k_stft.hip
 // k_stft_rows.hip: the three families over `rows` signals (row r at + r * row_stride, one window, `frames` frames per row).
 // *_check: the argument checks alone, before the context or a device is touched; host_form adds stft()'s frame-count check.
 int stft_rows_check(bool host_form, bool mags, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames);
-int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
-                  size_t win_len, size_t hop, float *d_out, size_t frames);
 int stft_mag_rows_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop,
                       float *d_mags, size_t frames, float *d_max);
 int istft_rows_check(size_t rows, size_t frames, size_t win_len, size_t hop, size_t out_len, size_t scratch_len, int mode);
@@ -939,6 +831,14 @@ int framed_src(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t le
 // stft_rows_composed -- into dst for FRAMES_FULL, otherwise into `spec` (nt * win_len complex, the caller's) and a per-element tail.
 enum FramedForm { FRAMES_FULL, FRAMES_HALF, FRAMES_MAGS };
 int framed_produce(kofft_hip_ctx *ctx, const FramedSrc &s, FramedForm form, size_t t0, size_t nt, void *dst, cpx<float> *spec);
+// k_stft_onesided.hip: the one-sided STFT's kernels on frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_out; no checks
+// (framed_produce's leaf for FRAMES_HALF)
+int stft_onesided_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_window,
+                        size_t win_len, size_t hop, size_t f0, size_t nf, float *d_out);
+// dst[t][k] = src[t][k] for k <= win_len/2, conj(src[t][win_len - k]) above: nt frames of win_len/2 + 1 bins -> nt frames of win_len
+int expand_half(kofft_hip_ctx *ctx, const float *d_half, float *d_full, size_t nt, size_t win_len);
+// [cross-unit declarations: end]
+
 // the input side of a StftRowsOf policy (row_stride: 0 when rows == 1)
 template <class IO>
 inline void fill_rows_io(IO &io, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
@@ -959,27 +859,6 @@ template <class IO> inline void fill_rows_io(IO &io, const FramedSrc &s)
 {
     fill_rows_io(io, s.signal, s.rows, s.len, s.row_stride, s.win, s.win_len, s.hop, s.frames);
 }
-// k_stft_onesided.hip: the STFT with bins 0 .. win_len/2 of every frame kept, rows * frames * (win_len/2 + 1) complex, bit for bit the
-// prefix of stft_rows_dev's frames, and inverse_parallel of the Hermitian completion of such frames
-int stft_onesided_check(bool host_form, size_t rows, size_t len, size_t row_stride, size_t win_len, size_t hop, size_t frames);
-int stft_onesided_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
-                      size_t win_len, size_t hop, float *d_out, size_t frames);
-int istft_onesided_dev(kofft_hip_ctx *ctx, const float *d_half, size_t rows, size_t frames, const float *d_window, size_t win_len, size_t hop,
-                       float *d_output, size_t out_len);
-// the same kernels on frames [f0, f0 + nf) of each of nrows rows (f0 != 0: one row), dense at d_out; no checks (framed_produce's leaf
-// for FRAMES_HALF)
-int stft_onesided_piece(kofft_hip_ctx *ctx, const float *d_signal, size_t nrows, size_t len, size_t row_stride, const float *d_window,
-                        size_t win_len, size_t hop, size_t f0, size_t nf, float *d_out);
-// k_welch_f32.hip: Welch power spectra (d_y null) and cross spectra of rows (welch_impl.hip.h).  welch_check: the argument
-// checks alone, in the order of include/kofft_hip.h
-int welch_check(bool csd, const void *x, const void *y, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
-                size_t win_len, size_t hop, size_t frames, int flags, const kofft_hip_ctx *ctx);
-int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
-              const float *d_window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_out);
-// dst[t][k] = src[t][k] for k <= win_len/2, conj(src[t][win_len - k]) above: nt frames of win_len/2 + 1 bins -> nt frames of win_len
-int expand_half(kofft_hip_ctx *ctx, const float *d_half, float *d_full, size_t nt, size_t win_len);
-template <typename T>
-int fft_nd_dev(kofft_hip_ctx *ctx, T *d_data, size_t depth, size_t rows, size_t cols, int inverse);  // k_nd.hip
 
 }  // namespace host
 }  // namespace kofft

@@ -1,4 +1,4 @@
-// host_layout.h -- where the arrays of one host-pointer call lie in its staging buffer (kofft_hip.hip: stage_host), the scratch chunks
+// host_layout.h -- where the arrays of one host-pointer call lie in its staging buffer (host_stage.hip.h: stage_host), the scratch chunks
 // and their walk, the dispatch over a log2 and the overlap test of the device forms.  Arithmetic only, no HIP:
 // tests/cpp/host_layout_check.cpp and tests/cpp/sanitize_frame_cut.cpp include this file alone.
 #pragma once

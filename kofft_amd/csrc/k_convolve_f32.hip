@@ -1,7 +1,8 @@
 // k_convolve_f32.hip -- overlap-save FFT convolution / correlation of float rows (convolve_impl.hip.h) and of rows
 // against a bank of filters (convolve_bank_impl.hip.h): every kernel instance of the two families and their
-// device-pointer entry points.
+// extern "C" entry points.
 #include "convolve_bank_impl.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
@@ -16,7 +17,7 @@ static size_t next_pow2(size_t v)
 // The block a call with block == 0 runs with: one block per row up to 4096 points; on longer rows the smaller of
 // 2048 and 4096 that leaves the filter half a block of new samples (measured: the 2048-point kernel, two frames per workgroup, beats
 // the 4096-point one at 64, 512, 768 and 1024 taps), then the power of two from 2 nh.  nx, nh >= 1.
-size_t convolve_default_block(size_t nx, size_t nh)
+static size_t convolve_default_block(size_t nx, size_t nh)
 {
     const size_t p = next_pow2(nx + nh - 1);
     if (p <= 4096) return p;
@@ -48,7 +49,7 @@ static int conv_check(bool nothing, bool filters_ok, bool flags_ok, size_t nx, s
 }
 
 // KOFFT_OK with rows == 0 or out_len == 0: nothing to do.
-int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *block, unsigned flags, size_t out_first, size_t out_len,
+static int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *block, unsigned flags, size_t out_first, size_t out_len,
                    const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
 {
     return conv_check(rows == 0 || out_len == 0, filters == 1 || filters == rows, !(flags & ~1u), nx, nh, block, out_first, out_len, x, h, out,
@@ -56,7 +57,7 @@ int convolve_check(size_t rows, size_t nx, size_t nh, size_t filters, size_t *bl
 }
 
 // KOFFT_OK with rows == 0, filters == 0 or out_len == 0: nothing to do.  Any number of filters; flag bits 2-3 are the output kind.
-int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_t *block, unsigned flags, size_t out_first, size_t out_len,
+static int convolve_bank_check(size_t rows, size_t nx, size_t filters, size_t nh, size_t *block, unsigned flags, size_t out_first, size_t out_len,
                         const void *x, const void *h, const void *out, const kofft_hip_ctx *ctx)
 {
     const bool flags_ok = !(flags >> (kBankKindShift + 2)) && ((flags >> kBankKindShift) & kBankKindMask) != 3u;
@@ -149,8 +150,28 @@ static int convolve_composed(kofft_hip_ctx *ctx, const float *d_x, const cpx<flo
     });
 }
 
-int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
-                 unsigned flags, float *d_out, size_t out_first, size_t out_len)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_set_convolve_fused(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::convolve_fused, on); }
+int kofft_hip_set_convolve_bank_fused(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::convolve_bank_fused, on); }
+
+int kofft_hip_convolve_block(size_t nx, size_t nh, size_t *block)
+{
+    if (nx == 0 || nh == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (nx > (SIZE_MAX >> 2) || nh > (SIZE_MAX >> 2)) return KOFFT_ERR_UNSUPPORTED;
+    if (!block) return KOFFT_ERR_NULL;
+    *block = convolve_default_block(nx, nh);
+    return KOFFT_OK;
+}
+
+int kofft_hip_dev_convolve_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh,
+                               size_t block, unsigned flags, float *d_out, size_t out_first, size_t out_len)
 {
     const int crc = convolve_check(rows, nx, nh, filters, &block, flags, out_first, out_len, d_x, d_h, d_out, ctx);
     if (crc || rows == 0 || out_len == 0) return crc;
@@ -172,6 +193,27 @@ int convolve_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, c
         return launch_fused_items<L>(ctx, convolve_fused_kernel<L>, s.items, d_x, H, d_out, tw, s);
     });
 }
+
+// On host rows: nx samples in, out_len values out.  One filter for all rows is the side input, uploaded once; one filter per row is a
+// third array, so that a pipelined chunk carries its own rows' taps
+int kofft_hip_convolve_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh, size_t block,
+                           unsigned flags, float *out, size_t out_first, size_t out_len)
+{
+    const int crc = convolve_check(rows, nx, nh, filters, &block, flags, out_first, out_len, x, h, out, ctx);
+    if (crc || rows == 0 || out_len == 0) return crc;
+    if (filters == rows && rows > 1) {
+        const HostArray<float> a[3] = {{x, nullptr, nx}, {h, nullptr, nh}, {nullptr, out, out_len}};
+        return rows_host_n<float>(ctx, rows, 3, a, nullptr, 0, true, true, [&](float *const *d, const float *, size_t nr) {
+            return kofft_hip_dev_convolve_f32(ctx, d[0], nr, nx, d[1], nr, nh, block, flags, d[2], out_first, out_len);
+        });
+    }
+    return rows_host<float>(ctx, x, out, rows, nx, out_len, h, nh, true, true,
+                            [&](float *d_in, float *d_out, const float *d_h, size_t nr) {
+                                return kofft_hip_dev_convolve_f32(ctx, d_in, nr, nx, d_h, 1, nh, block, flags, d_out, out_first, out_len);
+                            });
+}
+
+}  // extern "C"
 
 // ---- the filter bank ---------------------------------------------------------------------------------------------
 // One chunk of flat items at a time: the frames and their transforms once into X, then every filter through y.
@@ -211,8 +253,10 @@ static int convolve_bank_route(kofft_hip_ctx *ctx, const float *d_x, cpx<float> 
     });
 }
 
-int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh, size_t block,
-                      unsigned flags, void *d_out, size_t out_first, size_t out_len)
+extern "C" {
+
+int kofft_hip_dev_convolve_bank_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t filters, size_t nh,
+                                    size_t block, unsigned flags, void *d_out, size_t out_first, size_t out_len)
 {
     const int crc = convolve_bank_check(rows, nx, filters, nh, &block, flags, out_first, out_len, d_x, d_h, d_out, ctx);
     if (crc || rows == 0 || filters == 0 || out_len == 0) return crc;
@@ -233,5 +277,20 @@ int convolve_bank_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t 
     }
 }
 
-}  // namespace host
-}  // namespace kofft
+
+// On host rows: the bank is the side input, uploaded once; a row of the output is filters * out_len elements of one or (complex
+// values) two floats
+int kofft_hip_convolve_bank_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t filters, size_t nh,
+                                size_t block, unsigned flags, void *out, size_t out_first, size_t out_len)
+{
+    const int crc = convolve_bank_check(rows, nx, filters, nh, &block, flags, out_first, out_len, x, h, out, ctx);
+    if (crc || rows == 0 || filters == 0 || out_len == 0) return crc;
+    if (filters > (SIZE_MAX >> 3) / nh || filters > (SIZE_MAX >> 3) / out_len) return KOFFT_ERR_UNSUPPORTED;
+    const size_t out_row = filters * out_len * (((flags >> 2) & 3u) == 1u ? 2 : 1), side_len = filters * nh * ((flags & 2u) ? 2 : 1);
+    return rows_host<float>(ctx, x, static_cast<float *>(out), rows, nx, out_row, h, side_len, true, true,
+                            [&](float *d_in, float *d_out, const float *d_h, size_t nr) {
+                                return kofft_hip_dev_convolve_bank_f32(ctx, d_in, nr, nx, d_h, filters, nh, block, flags, d_out, out_first, out_len);
+                            });
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // k_frontend_f32.hip -- rows of audio to mel energies or MFCCs in one call (frontend_impl.hip.h): every kernel
-// instance of the family, the argument checks and the two routes.
+// instance of the family, the argument checks, the two routes and the extern "C" entry points.
 #include "frontend_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include "direct_impl.hip.h"
 
@@ -13,7 +14,7 @@ template <> struct PersistCfg<11, StftMagRowsNoMaxIO> : PersistCfg<11, StftMagIO
 template <> struct PersistCfg<12, StftMagRowsNoMaxIO> : PersistCfg<12, StftMagIO> {};
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched: the STFT rows' first, then the mel ones.
-int frontend_check(bool mfcc, bool dev, const void *signal, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
+static int frontend_check(bool mfcc, bool dev, const void *signal, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
                    size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, const kofft_hip_ctx *ctx)
 {
     const int crc = stft_rows_check(true, true, rows, len, row_stride, win_len, hop, frames);
@@ -128,7 +129,7 @@ static int frontend_composed(kofft_hip_ctx *ctx, bool mfcc, const FramedSrc &s, 
     });
 }
 
-int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+static int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
                  size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *d_out)
 {
     const int crc = frontend_check(mfcc, true, d_signal, d_window, d_out, rows, len, row_stride, win_len, hop, frames, bins, num_mel, num_coeffs, ctx);
@@ -142,5 +143,53 @@ int frontend_dev(kofft_hip_ctx *ctx, bool mfcc, const float *d_signal, size_t ro
     return frontend_composed(ctx, mfcc, s, bins, num_mel, num_coeffs, d_out);
 }
 
+// The signal goes up, the energies or coefficients come down (whole rows per chunk of the pipeline); the magnitudes stay on the device.
+static int frontend_host(kofft_hip_ctx *ctx, bool mfcc, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                         size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *out)
+{
+    const int crc = frontend_check(mfcc, false, signal, window, out, rows, len, row_stride, win_len, hop, frames, bins, num_mel, num_coeffs, ctx);
+    if (crc || rows == 0 || frames == 0 || num_mel == 0 || (mfcc && num_coeffs == 0)) return crc;
+    std::vector<float> packed;
+    const float *src = pack_rows(signal, rows, len, row_stride, packed);
+    return rows_host<float>(ctx, src, out, rows, len, frames * (mfcc ? num_coeffs : num_mel), window, window ? win_len : 0, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return frontend_dev(ctx, mfcc, d_in, nb, len, len, d_win, win_len, hop, frames, bins, num_mel, num_coeffs, d_out);
+                            });
+}
+
 }  // namespace host
 }  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_stft_mel_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                           size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, float *energies)
+{
+    return frontend_host(ctx, false, signal, rows, len, row_stride, window, win_len, hop, frames, bins, num_mel, 0, energies);
+}
+
+int kofft_hip_dev_stft_mel_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                               size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, float *d_energies)
+{
+    return frontend_dev(ctx, false, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins, num_mel, 0, d_energies);
+}
+
+int kofft_hip_stft_mfcc_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                            size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs, float *coeffs)
+{
+    return frontend_host(ctx, true, signal, rows, len, row_stride, window, win_len, hop, frames, bins, num_mel, num_coeffs, coeffs);
+}
+
+int kofft_hip_dev_stft_mfcc_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                                size_t win_len, size_t hop, size_t frames, const uint64_t *bins, size_t num_mel, size_t num_coeffs,
+                                float *d_coeffs)
+{
+    return frontend_dev(ctx, true, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, bins, num_mel, num_coeffs, d_coeffs);
+}
+
+int kofft_hip_set_frontend_fused(kofft_hip_ctx *ctx, int mode) { return set_route(ctx, &kofft_hip_ctx::frontend_fused, mode, 0, 2); }
+
+}  // extern "C"

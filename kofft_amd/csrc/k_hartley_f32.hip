@@ -1,12 +1,13 @@
 // k_hartley_f32.hip -- hartley::dht (hartley.rs:12-57) on float rows: the table kernel (hartley_impl.hip.h), the table cache and the
-// hand-over to the kernels of the direct DCT / DST.
+// hand-over to the kernels of the direct DCT / DST, and the extern "C" entry points.
 #include "hartley_impl.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
-int dht_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
+static int dht_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
 {
     if (batch == 0) return KOFFT_OK;
     if (n == 0) return KOFFT_OK;  // hartley.rs:13-14: an empty result
@@ -37,7 +38,26 @@ static int get_dht_table(kofft_hip_ctx *ctx, size_t n, const float **out)
     });
 }
 
-int dht_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_set_dht_table_device(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::dht_table_device, on); }
+
+int kofft_hip_dht_table_f32(size_t n, float *H)
+{
+    if (n == 0) return KOFFT_OK;
+    if (n > kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!H) return KOFFT_ERR_NULL;
+    kofft_tables::dht_table_f32(n, n, H);
+    return KOFFT_OK;
+}
+
+int kofft_hip_dev_dht_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     int rc = dht_check(n, batch, d_in, d_out, ctx);
     if (rc || batch == 0 || n == 0) return rc;
@@ -50,5 +70,14 @@ int dht_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_
     return direct_zero_sums(ctx, d_in, d_out, table, n, n, batch);
 }
 
-}  // namespace host
-}  // namespace kofft
+// on host rows of n reals in and out
+int kofft_hip_dht_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
+{
+    const int crc = dht_check(n, batch, in, out, ctx);
+    if (crc || batch == 0 || n == 0) return crc;
+    // No pipeline, like the direct sums: in == out works (hartley::batch is in place).
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, false,
+                            [&](float *d_in, float *d_out, const float *, size_t rows) { return kofft_hip_dev_dht_f32(ctx, d_in, d_out, n, rows); });
+}
+
+}  // extern "C"

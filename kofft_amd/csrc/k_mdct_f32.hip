@@ -1,6 +1,7 @@
 // k_mdct_f32.hip -- the fast DCT-IV of float rows, the MDCT of rows of signals and the IMDCT (mdct_impl.hip.h): every
-// kernel instance of the family and its device-pointer entry points.
+// kernel instance of the family, its argument checks and its extern "C" entry points.
 #include "mdct_impl.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
@@ -18,7 +19,7 @@ static int mdct_len_check(size_t n)
 // does a * b * 4 bytes stay well inside size_t (and a * b inside a signed 64-bit index)?
 static bool mdct_fits(size_t a, size_t b) { return a == 0 || b <= (SIZE_MAX >> 4) / a; }
 
-int dct4_fast_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
+static int dct4_fast_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
 {
     if (batch == 0) return KOFFT_OK;
     if (const int rc = mdct_len_check(n)) return rc;
@@ -27,7 +28,7 @@ int dct4_fast_check(size_t n, size_t batch, const void *in, const void *out, con
     return KOFFT_OK;
 }
 
-int mdct_check(size_t rows, size_t nx, size_t row_stride, size_t n, size_t lead, size_t frames, const void *x, const void *w, const void *out,
+static int mdct_check(size_t rows, size_t nx, size_t row_stride, size_t n, size_t lead, size_t frames, const void *x, const void *w, const void *out,
                const kofft_hip_ctx *ctx)
 {
     if (rows == 0 || frames == 0) return KOFFT_OK;
@@ -41,7 +42,7 @@ int mdct_check(size_t rows, size_t nx, size_t row_stride, size_t n, size_t lead,
     return KOFFT_OK;
 }
 
-int imdct_check(size_t rows, size_t frames, size_t n, size_t out_first, size_t out_len, const void *coef, const void *w, const void *out,
+static int imdct_check(size_t rows, size_t frames, size_t n, size_t out_first, size_t out_len, const void *coef, const void *w, const void *out,
                 const kofft_hip_ctx *ctx)
 {
     if (rows == 0 || frames == 0 || out_len == 0) return KOFFT_OK;
@@ -100,7 +101,26 @@ static int dct4_items(kofft_hip_ctx *ctx, const IO &io, size_t n, size_t items, 
     });
 }
 
-int dct4_fast_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_dct4_table_f32(size_t n, float *out)
+{
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (n & 1) return KOFFT_ERR_INVALID_VALUE;
+    if (!out) return KOFFT_ERR_NULL;
+    kofft_tables::dct4_table_f32(n, out);
+    return KOFFT_OK;
+}
+
+int kofft_hip_set_mdct_fused(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::mdct_fused, on); }
+
+int kofft_hip_dev_dct4_fast_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch)
 {
     const int crc = dct4_fast_check(n, batch, d_in, d_out, ctx);
     if (crc || batch == 0) return crc;
@@ -108,8 +128,18 @@ int dct4_fast_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n,
     return dct4_items(ctx, Dct4RowsIO{d_in, d_out, n}, n, batch, dct4_fused_ok(ctx, n, d_in, nullptr));
 }
 
-int mdct_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_w, size_t n, size_t lead,
-             float *d_out, size_t frames)
+// Whole rows per chunk of the host pipeline
+int kofft_hip_dct4_fast_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch)
+{
+    const int crc = dct4_fast_check(n, batch, in, out, ctx);
+    if (crc || batch == 0) return crc;
+    return rows_host<float>(ctx, in, out, batch, n, n, nullptr, 0, true, true, [&](float *d_in, float *d_out, const float *, size_t nb) {
+        return kofft_hip_dev_dct4_fast_f32(ctx, d_in, d_out, n, nb);
+    });
+}
+
+int kofft_hip_dev_mdct_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_w, size_t n,
+                           size_t lead, float *d_out, size_t frames)
 {
     const int crc = mdct_check(rows, nx, row_stride, n, lead, frames, d_x, d_w, d_out, ctx);
     if (crc || rows == 0 || frames == 0) return crc;
@@ -118,11 +148,25 @@ int mdct_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_
     return dct4_items(ctx, io, n, rows * frames, dct4_fused_ok(ctx, n, d_x, d_w));
 }
 
+// (the window is the side input, uploaded once)
+int kofft_hip_mdct_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, size_t row_stride, const float *window, size_t n, size_t lead,
+                       float *out, size_t frames)
+{
+    const int crc = mdct_check(rows, nx, row_stride, n, lead, frames, x, window, out, ctx);
+    if (crc || rows == 0 || frames == 0) return crc;
+    std::vector<float> packed;
+    const float *src = pack_rows(x, rows, nx, row_stride, packed);
+    return rows_host<float>(ctx, src, out, rows, nx, frames * n, window, 2 * n, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return kofft_hip_dev_mdct_f32(ctx, d_in, nb, nx, nx, d_win, n, lead, d_out, frames);
+                            });
+}
+
 // Chunks of the flat frame index t = row * frames + f.  The chunk [t0, t0 + nt) writes the hop blocks f of its frames (r, f), and
 // block `frames` of a row with the row's last frame: every sample is written once, from frames of one chunk.  Block f > 0 needs frame
 // f - 1, so a chunk that starts inside a row transforms the frame before its first as well.
-int imdct_dev(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frames, const float *d_w, size_t n, float scale, float *d_out,
-              size_t out_first, size_t out_len)
+int kofft_hip_dev_imdct_f32(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frames, const float *d_w, size_t n, float scale,
+                            float *d_out, size_t out_first, size_t out_len)
 {
     const int crc = imdct_check(rows, frames, n, out_first, out_len, d_coef, d_w, d_out, ctx);
     if (crc || rows == 0 || frames == 0 || out_len == 0) return crc;
@@ -159,5 +203,15 @@ int imdct_dev(kofft_hip_ctx *ctx, const float *d_coef, size_t rows, size_t frame
     });
 }
 
-}  // namespace host
-}  // namespace kofft
+int kofft_hip_imdct_f32(kofft_hip_ctx *ctx, const float *coef, size_t rows, size_t frames, const float *window, size_t n, float scale, float *out,
+                        size_t out_first, size_t out_len)
+{
+    const int crc = imdct_check(rows, frames, n, out_first, out_len, coef, window, out, ctx);
+    if (crc || rows == 0 || frames == 0 || out_len == 0) return crc;
+    return rows_host<float>(ctx, coef, out, rows, frames * n, out_len, window, 2 * n, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return kofft_hip_dev_imdct_f32(ctx, d_in, nb, frames, d_win, n, scale, d_out, out_first, out_len);
+                            });
+}
+
+}  // extern "C"

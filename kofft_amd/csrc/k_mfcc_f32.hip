@@ -1,14 +1,19 @@
 // k_mfcc_f32.hip -- cepstrum::mel_filterbank / mfcc (cepstrum.rs:36-85) on float rows with the filter edges as an input: every
-// kernel instance of the family (mfcc_impl.hip.h), the argument checks, the per-context plan cache and the two routes of the MFCC.
+// kernel instance of the family (mfcc_impl.hip.h), the argument checks, the per-context plan cache, the two routes of the MFCC and the
+// extern "C" entry points.
 #include "mfcc_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include <algorithm>
 
 namespace kofft {
 namespace host {
 
-// Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
-int mel_check(bool mfcc, bool dev, const void *mags, const void *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+constexpr size_t kMfccFusedDefaultMel = 80;     // the measured choice: the fused kernel up to 80 filters (five workgroups per CU) ...
+constexpr size_t kMfccFusedDefaultCoeffs = 16;  // ... and 16 coefficients (two passes of its DCT)
+
+// Checks in the order of include/kofft_hip.h, all before the context or the device is touched; mfcc: whether num_coeffs takes part.
+static int mel_check(bool mfcc, bool dev, const void *mags, const void *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
               size_t num_coeffs, const kofft_hip_ctx *ctx)
 {
     if (rows == 0) return KOFFT_OK;
@@ -159,5 +164,54 @@ int mfcc_dev(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_
     return launch_mel(ctx, d_mags, d_coeffs, plan, table, n_fft, num_mel, num_coeffs, rows);
 }
 
+// on host rows of n_fft magnitudes in, num_mel energies or num_coeffs coefficients out; the edges stay on the host
+static int mel_host(kofft_hip_ctx *ctx, bool mfcc, const float *mags, float *out, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+                    size_t num_coeffs)
+{
+    const int crc = mel_check(mfcc, false, mags, out, n_fft, rows, bins, num_mel, num_coeffs, ctx);
+    if (crc || rows == 0 || num_mel == 0 || (mfcc && num_coeffs == 0)) return crc;
+    return rows_host<float>(ctx, mags, out, rows, n_fft, mfcc ? num_coeffs : num_mel, nullptr, 0, true, true,
+                            [&](float *d_in, float *d_out, const float *, size_t nr) {
+                                return mfcc ? mfcc_dev(ctx, d_in, d_out, n_fft, nr, bins, num_mel, num_coeffs)
+                                            : mel_filterbank_dev(ctx, d_in, d_out, n_fft, nr, bins, num_mel);
+                            });
+}
+
 }  // namespace host
 }  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_set_mfcc_fused(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::mfcc_fused, on, 0, 2); }
+int kofft_hip_mel_filterbank_f32(kofft_hip_ctx *ctx, const float *mags, float *energies, size_t n_fft, size_t rows, const uint64_t *bins,
+                                 size_t num_mel)
+{
+    return mel_host(ctx, false, mags, energies, n_fft, rows, bins, num_mel, 0);
+}
+int kofft_hip_dev_mel_filterbank_f32(kofft_hip_ctx *ctx, const float *d_mags, float *d_energies, size_t n_fft, size_t rows,
+                                     const uint64_t *bins, size_t num_mel)
+{
+    return mel_filterbank_dev(ctx, d_mags, d_energies, n_fft, rows, bins, num_mel);
+}
+int kofft_hip_mfcc_f32(kofft_hip_ctx *ctx, const float *mags, float *coeffs, size_t n_fft, size_t rows, const uint64_t *bins, size_t num_mel,
+                       size_t num_coeffs)
+{
+    return mel_host(ctx, true, mags, coeffs, n_fft, rows, bins, num_mel, num_coeffs);
+}
+int kofft_hip_dev_mfcc_f32(kofft_hip_ctx *ctx, const float *d_mags, float *d_coeffs, size_t n_fft, size_t rows, const uint64_t *bins,
+                           size_t num_mel, size_t num_coeffs)
+{
+    return mfcc_dev(ctx, d_mags, d_coeffs, n_fft, rows, bins, num_mel, num_coeffs);
+}
+int kofft_hip_mel_bins_f32(float sample_rate, size_t n_fft, size_t num_filters, uint64_t *bins)
+{
+    if (num_filters > kDirectMaxN) return KOFFT_ERR_UNSUPPORTED;
+    if (!bins) return KOFFT_ERR_NULL;
+    kofft_tables::mel_bins_f32(sample_rate, n_fft, num_filters, bins);
+    return KOFFT_OK;
+}
+
+}  // extern "C"

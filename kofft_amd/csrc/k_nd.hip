@@ -1,5 +1,6 @@
-// k_nd.hip -- ndfft::fft2d_inplace / fft3d_inplace (ndfft.rs:74-155) on device pointers.
+// k_nd.hip -- ndfft::fft2d_inplace / fft3d_inplace (ndfft.rs:74-155) on device and host pointers, with their extern "C" entry points.
 #include "host_common.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
@@ -77,13 +78,21 @@ int fft_axis_dev(kofft_hip_ctx *ctx, T *d_data, size_t len, size_t lines, size_t
     return dispatch<T, EPI_STORE>(ctx, io, len, lines);
 }
 
-template <typename T>
-int fft_nd_dev(kofft_hip_ctx *ctx, T *d_data, size_t depth, size_t rows, size_t cols, int inverse)
+// the argument checks alone, before the context or a device is touched; an empty shape is KOFFT_OK with nothing to do
+static int fft_nd_check(size_t depth, size_t rows, size_t cols, const void *data, const kofft_hip_ctx *ctx)
 {
     if (depth == 0 || rows == 0 || cols == 0) return KOFFT_OK;  // ndfft.rs:84-86, 124-126
     for (size_t n : {depth, rows, cols})
         if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
-    if (!ctx || !d_data) return KOFFT_ERR_NULL;
+    if (!ctx || !data) return KOFFT_ERR_NULL;
+    return KOFFT_OK;
+}
+
+template <typename T>
+static int fft_nd_dev(kofft_hip_ctx *ctx, T *d_data, size_t depth, size_t rows, size_t cols, int inverse)
+{
+    const int crc = fft_nd_check(depth, rows, cols, d_data, ctx);
+    if (crc || depth == 0 || rows == 0 || cols == 0) return crc;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
     if (depth > 1) {  // z axis first (ndfft.rs:131-137): lines (r, c), stride rows*cols
@@ -105,9 +114,40 @@ int fft_nd_dev(kofft_hip_ctx *ctx, T *d_data, size_t depth, size_t rows, size_t 
     return fft_axis_dev<T>(ctx, d_data, rows, cols, cols, 0, cols, inverse);
 }
 
-
-template int fft_nd_dev<float>(kofft_hip_ctx *, float *, size_t, size_t, size_t, int);
-template int fft_nd_dev<double>(kofft_hip_ctx *, double *, size_t, size_t, size_t, int);
+// the same on a host array, in place: one staged array, no zero-copy and no pipeline (every axis reads the whole array)
+template <typename T>
+static int fft_nd_host(kofft_hip_ctx *ctx, T *data, size_t depth, size_t rows, size_t cols, int inverse)
+{
+    const int crc = fft_nd_check(depth, rows, cols, data, ctx);
+    if (crc || depth == 0 || rows == 0 || cols == 0) return crc;
+    const HostArray<T> a{data, data, 2 * depth * rows * cols};
+    return stage_host<T>(ctx, 1, 1, &a, nullptr, 0, false, false,
+                         [&](T *const *d, const T *, size_t) { return fft_nd_dev<T>(ctx, d[0], depth, rows, cols, inverse); });
+}
 
 }  // namespace host
 }  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_fftnd_c32(kofft_hip_ctx *ctx, float *data, size_t depth, size_t rows, size_t cols, int inverse)
+{
+    return fft_nd_host<float>(ctx, data, depth, rows, cols, inverse);
+}
+int kofft_hip_fftnd_c64(kofft_hip_ctx *ctx, double *data, size_t depth, size_t rows, size_t cols, int inverse)
+{
+    return fft_nd_host<double>(ctx, data, depth, rows, cols, inverse);
+}
+int kofft_hip_fftnd_c32_dev(kofft_hip_ctx *ctx, float *d_data, size_t depth, size_t rows, size_t cols, int inverse)
+{
+    return fft_nd_dev<float>(ctx, d_data, depth, rows, cols, inverse);
+}
+int kofft_hip_fftnd_c64_dev(kofft_hip_ctx *ctx, double *d_data, size_t depth, size_t rows, size_t cols, int inverse)
+{
+    return fft_nd_dev<double>(ctx, d_data, depth, rows, cols, inverse);
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // k_picture_f32.hip -- rows of audio to spectrogram pictures in one call (picture_impl.hip.h): every kernel instance of
 // the family, the argument checks and the routes of the three maximum modes.
 #include "picture_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include "frame_cut.h"
 
@@ -13,7 +14,7 @@ template <> struct PersistCfg<11, StftMagRowsMaxOnlyIO> : PersistCfg<11, StftMag
 template <> struct PersistCfg<12, StftMagRowsMaxOnlyIO> : PersistCfg<12, StftMagIO> {};
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
-int picture_check(bool dev, const void *signal, size_t rows, size_t len, size_t row_stride, const void *window, size_t win_len, size_t hop,
+static int picture_check(bool dev, const void *signal, size_t rows, size_t len, size_t row_stride, const void *window, size_t win_len, size_t hop,
                   size_t frames, int max_mode, const void *max_in, const void *max_out, int mode, int cmap, int depth, int channels, int scale,
                   int layout, const uint32_t *pix_of_bin, const void *out, const kofft_hip_ctx *ctx, bool *empty)
 {
@@ -151,9 +152,18 @@ static int pic_fill(kofft_hip_ctx *ctx, float *dst, size_t count, float value)
 
 static size_t pad16(size_t bytes) { return (bytes + 15) & ~size_t(15); }
 
-int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window, size_t win_len,
-                size_t hop, size_t frames, int max_mode, const float *d_max_in, float *d_max_out, int mode, float level, int cmap, int depth,
-                int channels, int scale, int layout, const uint32_t *pix_of_bin, void *d_out)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_dev_stft_picture_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                   const float *d_window, size_t win_len, size_t hop, size_t frames, int max_mode, const float *d_max_in,
+                                   float *d_max_out, int mode, float level, int cmap, int depth, int channels, int scale, int layout,
+                                   const uint32_t *pix_of_bin, void *d_out)
 {
     bool empty = false;
     int rc = picture_check(true, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, max_mode, d_max_in, d_max_out, mode, cmap, depth,
@@ -268,5 +278,38 @@ int picture_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t l
     return KOFFT_OK;
 }
 
-}  // namespace host
-}  // namespace kofft
+
+// The signal (and mode 2's maxima) go up, the pictures and the maxima come down, all as bytes, whole rows per chunk of the pipeline: a
+// row's running maximum never crosses a chunk of the pipeline.  Never zero-copy: the maxima are atomicMax targets and stay in device memory.
+int kofft_hip_stft_picture_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                               size_t win_len, size_t hop, size_t frames, int max_mode, const float *max_in, float *max_out, int mode,
+                               float level, int cmap, int depth, int channels, int scale, int layout, const uint32_t *pix_of_bin, void *out)
+{
+    bool empty = false;
+    const int crc = picture_check(false, signal, rows, len, row_stride, window, win_len, hop, frames, max_mode, max_in, max_out, mode, cmap,
+                                  depth, channels, scale, layout, pix_of_bin, out, ctx, &empty);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (empty) {
+        if (max_mode == 2 && !max_in) return KOFFT_ERR_NULL;
+        for (size_t r = 0; max_out && r < rows; ++r) max_out[r] = max_mode == 2 ? max_in[r] : (max_mode == 1 ? 1e-12f : 0.0f);
+        return KOFFT_OK;
+    }
+    typedef unsigned char byte;
+    std::vector<float> packed;
+    const float *src = pack_rows(signal, rows, len, row_stride, packed);
+    const size_t px = channels == 4 ? 4 : (depth == 16 ? 6 : 3);
+    const HostArray<byte> a[4] = {{reinterpret_cast<const byte *>(src), nullptr, len * sizeof(float)},
+                                  {nullptr, static_cast<byte *>(out), frames * (win_len / 2) * px},
+                                  {max_mode == 2 ? reinterpret_cast<const byte *>(max_in) : nullptr, nullptr, sizeof(float)},
+                                  {nullptr, reinterpret_cast<byte *>(max_out), sizeof(float)}};
+    return rows_host_n<byte>(ctx, rows, 4, a, reinterpret_cast<const byte *>(window), window ? win_len * sizeof(float) : 0, false, true,
+                             [&](byte *const *d, const byte *d_win, size_t nb) {
+                                 return kofft_hip_dev_stft_picture_f32(
+                                     ctx, reinterpret_cast<const float *>(d[0]), nb, len, len, reinterpret_cast<const float *>(d_win), win_len, hop,
+                                     frames, max_mode, max_mode == 2 ? reinterpret_cast<const float *>(d[2]) : nullptr,
+                                     max_out ? reinterpret_cast<float *>(d[3]) : nullptr, mode, level, cmap, depth, channels, scale, layout,
+                                     pix_of_bin, d[1]);
+                             });
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // k_resample_f32.hip -- polyphase resampling of float rows (resample_impl.hip.h): the two kernels, the argument
-// checks, the device-pointer entry point and the host-only tap design.
+// checks, the extern "C" entry points and the host-only tap design.
 #include "resample_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include <cmath>
 #include <new>
@@ -13,7 +14,7 @@ static_assert(kResampleTile == KOFFT_HIP_RESAMPLE_TILE, "include/kofft_hip.h nam
 
 // The argument checks alone, in the order of include/kofft_hip.h and before the context or a device is touched.  KOFFT_OK with
 // rows == 0 or out_len == 0: nothing to do.
-int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, size_t t0, size_t out_len, const void *x, const void *h,
+static int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, size_t t0, size_t out_len, const void *x, const void *h,
                    const void *out, const kofft_hip_ctx *ctx)
 {
     if (rows == 0 || out_len == 0) return KOFFT_OK;
@@ -32,8 +33,16 @@ int resample_check(size_t rows, size_t nx, size_t nh, size_t up, size_t down, si
     return KOFFT_OK;
 }
 
-int resample_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t nh, size_t up, size_t down, size_t t0,
-                 float *d_out, size_t out_len)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_dev_resample_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_h, size_t nh, size_t up,
+                               size_t down, size_t t0, float *d_out, size_t out_len)
 {
     const int crc = resample_check(rows, nx, nh, up, down, t0, out_len, d_x, d_h, d_out, ctx);
     if (crc || rows == 0 || out_len == 0) return crc;
@@ -69,6 +78,29 @@ int resample_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, c
     return KOFFT_OK;
 }
 
+// nx samples per row go up, out_len values come down; the one filter is the side input, uploaded once
+int kofft_hip_resample_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *h, size_t nh, size_t up, size_t down,
+                           size_t t0, float *out, size_t out_len)
+{
+    const int crc = resample_check(rows, nx, nh, up, down, t0, out_len, x, h, out, ctx);
+    if (crc || rows == 0 || out_len == 0) return crc;
+    return rows_host<float>(ctx, x, out, rows, nx, out_len, h, nh, true, true,
+                            [&](float *d_in, float *d_out, const float *d_h, size_t nr) {
+                                return kofft_hip_dev_resample_f32(ctx, d_in, nr, nx, d_h, nh, up, down, t0, d_out, out_len);
+                            });
+}
+
+int kofft_hip_set_resample_tiled(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::resample_tiled, on, 0, 2); }
+
+int kofft_hip_resample_route(size_t nh, size_t up, size_t down, int *route)
+{
+    if (!route) return KOFFT_ERR_NULL;
+    if (nh == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (up == 0 || down == 0) return KOFFT_ERR_INVALID_VALUE;
+    *route = resample_route(nh, up, down);
+    return KOFFT_OK;
+}
+
 // The modified Bessel function I0 by its power series sum ((x / 2)^2)^k / (k!)^2, in double, until a term no longer changes the sum.
 static double bessel_i0(double x)
 {
@@ -86,7 +118,7 @@ static double bessel_i0(double x)
 // scipy.signal.resample_poly's default filter: firwin(2 * half + 1, 1 / max(up, down), window = ("kaiser", beta)) * up with
 // half = zeros * max(up, down) -- the sinc of that cutoff under a Kaiser window, normalised to unit sum, times up; double throughout
 // and rounded to f32 once.
-int resample_taps(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh_out)
+int kofft_hip_resample_taps_f32(size_t up, size_t down, size_t zeros, double beta, float *taps, size_t *nh_out)
 {
     if (!taps && !nh_out) return KOFFT_ERR_NULL;
     if (up == 0 || down == 0 || zeros == 0 || !(beta >= 0.0)) return KOFFT_ERR_INVALID_VALUE;
@@ -118,5 +150,4 @@ int resample_taps(size_t up, size_t down, size_t zeros, double beta, float *taps
     return KOFFT_OK;
 }
 
-}  // namespace host
-}  // namespace kofft
+}  // extern "C"

@@ -1,6 +1,7 @@
 // k_sosfilt_f32.hip -- batched IIR filtering of float rows (sosfilt_impl.hip.h, sosfilt_plan.h): the two kernels'
 // instances, the argument checks and the device-pointer entry point.
 #include "sosfilt_impl.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
@@ -13,8 +14,8 @@ static_assert(kSosGroup == 8, "sosfilt_launch dispatches 1 .. 8 sections");
 // rows == 0 or nx == 0: nothing to do.  host_sos: sos is host memory, so a0 can be read.
 // scan_chunk: null for sosfilt; for sosfilt_scan the chunk, checked directly after the flags, and the bytes of its state scratch join
 // the overflow checks.
-int sosfilt_check(size_t rows, size_t nx, size_t sections, unsigned flags, const void *x, const void *sos, const void *zi, const void *zf,
-                  const void *out, const kofft_hip_ctx *ctx, bool host_sos, const size_t *scan_chunk)
+static int sosfilt_check(size_t rows, size_t nx, size_t sections, unsigned flags, const void *x, const void *sos, const void *zi, const void *zf,
+                  const void *out, const kofft_hip_ctx *ctx, bool host_sos, const size_t *scan_chunk = nullptr)
 {
     if (rows == 0 || nx == 0) return KOFFT_OK;
     if (sections == 0) return KOFFT_ERR_EMPTY_INPUT;
@@ -62,8 +63,16 @@ static void sosfilt_launch_ns(kofft_hip_ctx *ctx, bool tiled, const float *src, 
 // mode 2: the tiled kernel wherever it exists, which is everywhere; mode 1: the measured rule (sos_route); mode 0: never
 static bool sosfilt_use_tiled(const kofft_hip_ctx *ctx, size_t rows) { return ctx->sosfilt_tiled == 2 || (ctx->sosfilt_tiled == 1 && sos_route(rows) == 1); }
 
-int sosfilt_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
-                float *d_zf, unsigned flags, float *d_out)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_dev_sosfilt_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections,
+                              const float *d_zi, float *d_zf, unsigned flags, float *d_out)
 {
     const int crc = sosfilt_check(rows, nx, sections, flags, d_x, d_sos, d_zi, d_zf, d_out, ctx, false);
     if (crc || rows == 0 || nx == 0) return crc;
@@ -93,6 +102,30 @@ int sosfilt_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, co
     return KOFFT_OK;
 }
 
+// up to four row arrays: x up, out down, zi up, zf down (an absent state is an empty array and reaches the device as null); the
+// coefficients are the side input, uploaded once
+int kofft_hip_sosfilt_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *sos, size_t sections, const float *zi,
+                          float *zf, unsigned flags, float *out)
+{
+    const int crc = sosfilt_check(rows, nx, sections, flags, x, sos, zi, zf, out, ctx, true);
+    if (crc || rows == 0 || nx == 0) return crc;
+    const HostArray<float> a[4] = {{x, nullptr, nx}, {nullptr, out, nx}, {zi, nullptr, zi ? 2 * sections : 0}, {nullptr, zf, zf ? 2 * sections : 0}};
+    return rows_host_n<float>(ctx, rows, 4, a, sos, 6 * sections, true, true, [&](float *const *d, const float *d_sos, size_t nr) {
+        return kofft_hip_dev_sosfilt_f32(ctx, d[0], nr, nx, d_sos, sections, zi ? d[2] : nullptr, zf ? d[3] : nullptr, flags, d[1]);
+    });
+}
+
+int kofft_hip_sosfilt_route(size_t rows, int *route)
+{
+    if (!route) return KOFFT_ERR_NULL;
+    *route = sos_route(rows);
+    return KOFFT_OK;
+}
+
+int kofft_hip_set_sosfilt_tiled(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::sosfilt_tiled, on, 0, 2); }
+
+}  // extern "C"
+
 // ---- the scan along time ----
 template <int NS>
 static void sosfilt_scan_launch_ns(kofft_hip_ctx *ctx, const float *src, const float *d_sos, const float *d_zi, float *d_zf, float *d_out, float *st,
@@ -111,8 +144,10 @@ static void sosfilt_scan_launch_ns(kofft_hip_ctx *ctx, const float *src, const f
                        d_out, st, s);
 }
 
-int sosfilt_scan_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections, const float *d_zi,
-                     float *d_zf, size_t chunk, unsigned flags, float *d_out)
+extern "C" {
+
+int kofft_hip_dev_sosfilt_scan_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, const float *d_sos, size_t sections,
+                                   const float *d_zi, float *d_zf, size_t chunk, unsigned flags, float *d_out)
 {
     const int crc = sosfilt_check(rows, nx, sections, flags, d_x, d_sos, d_zi, d_zf, d_out, ctx, false, &chunk);
     if (crc || rows == 0 || nx == 0) return crc;
@@ -155,5 +190,24 @@ int sosfilt_scan_dev(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t n
     });
 }
 
-}  // namespace host
-}  // namespace kofft
+
+// the same staging as kofft_hip_sosfilt_f32: rows are independent
+int kofft_hip_sosfilt_scan_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, const float *sos, size_t sections, const float *zi,
+                               float *zf, size_t chunk, unsigned flags, float *out)
+{
+    const int crc = sosfilt_check(rows, nx, sections, flags, x, sos, zi, zf, out, ctx, true, &chunk);
+    if (crc || rows == 0 || nx == 0) return crc;
+    const HostArray<float> a[4] = {{x, nullptr, nx}, {nullptr, out, nx}, {zi, nullptr, zi ? 2 * sections : 0}, {nullptr, zf, zf ? 2 * sections : 0}};
+    return rows_host_n<float>(ctx, rows, 4, a, sos, 6 * sections, true, true, [&](float *const *d, const float *d_sos, size_t nr) {
+        return kofft_hip_dev_sosfilt_scan_f32(ctx, d[0], nr, nx, d_sos, sections, zi ? d[2] : nullptr, zf ? d[3] : nullptr, chunk, flags, d[1]);
+    });
+}
+
+int kofft_hip_sosfilt_scan_chunk(size_t rows, size_t nx, size_t sections, size_t *chunk)
+{
+    if (!chunk) return KOFFT_ERR_NULL;
+    *chunk = (size_t)sos_scan_chunk_rule(rows, nx, sections);
+    return KOFFT_OK;
+}
+
+}  // extern "C"

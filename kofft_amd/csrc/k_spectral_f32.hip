@@ -1,14 +1,19 @@
 // k_spectral_f32.hip -- czt::czt_f32 (czt.rs:16-54) and goertzel::goertzel_f32 (goertzel.rs:16-36) on float rows: every kernel
-// instance of the family (spectral_impl.hip.h), the table cache and the route.
+// instance of the family (spectral_impl.hip.h), the table cache, the route and the extern "C" entry points.
 #include "spectral_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include <algorithm>
 
 namespace kofft {
 namespace host {
 
+constexpr size_t kCztMax = 4096;  // the longest row and the most bins: the table is 128 MiB there
+constexpr size_t kGoertzelMaxLen = size_t(1) << 26;
+constexpr size_t kGoertzelMaxFreqs = 1024;
+
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
-int czt_check(size_t n, size_t m, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
+static int czt_check(size_t n, size_t m, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
 {
     if (batch == 0 || m == 0) return KOFFT_OK;
     if (n > kCztMax || m > kCztMax) return KOFFT_ERR_UNSUPPORTED;
@@ -16,7 +21,7 @@ int czt_check(size_t n, size_t m, size_t batch, const void *in, const void *out,
     return KOFFT_OK;
 }
 
-int goertzel_check(size_t n, size_t batch, float sample_rate, const void *freqs, size_t nfreq, const void *in, const void *out,
+static int goertzel_check(size_t n, size_t batch, float sample_rate, const void *freqs, size_t nfreq, const void *in, const void *out,
                    const kofft_hip_ctx *ctx)
 {
     if (batch == 0) return KOFFT_OK;
@@ -96,7 +101,38 @@ inline bool czt_use_table(size_t n, size_t m, size_t batch, bool cached)
     return batch >= (cached ? 2u : 8u);
 }
 
-int czt_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_set_czt_route(kofft_hip_ctx *ctx, int mode) { return set_route(ctx, &kofft_hip_ctx::czt_route, mode, 0, 2); }
+
+int kofft_hip_czt_table_f32(size_t n, size_t m, float wr, float wi, float ar, float ai, float *C)
+{
+    if (n == 0 || m == 0) return KOFFT_OK;
+    if (n > kCztMax || m > kCztMax) return KOFFT_ERR_UNSUPPORTED;
+    if (!C) return KOFFT_ERR_NULL;
+    kofft_tables::czt_table_f32(n, m, wr, wi, ar, ai, 2 * m, C);
+    return KOFFT_OK;
+}
+
+int kofft_hip_goertzel_coeff_f32(size_t n, float sample_rate, const float *target_freqs, size_t nfreq, float *coeff)
+{
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (sample_rate <= 0.0f) return KOFFT_ERR_INVALID_VALUE;
+    if (nfreq == 0) return KOFFT_OK;
+    if (n > kGoertzelMaxLen || nfreq > kGoertzelMaxFreqs) return KOFFT_ERR_UNSUPPORTED;
+    if (!target_freqs || !coeff) return KOFFT_ERR_NULL;
+    kofft_tables::goertzel_coeff_f32(n, sample_rate, target_freqs, nfreq, coeff);
+    return KOFFT_OK;
+}
+
+int kofft_hip_dev_czt_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t m, float wr, float wi, float ar, float ai,
+                          size_t batch)
 {
     int rc = czt_check(n, m, batch, d_in, d_out, ctx);
     if (rc || batch == 0 || m == 0) return rc;
@@ -147,7 +183,21 @@ int czt_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_
     return direct_zero_sums(ctx, d_in, d_out, static_cast<const float *>(slot->d_table), n, 2 * m, batch);
 }
 
-int goertzel_launch(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *d_coeff, size_t n, size_t batch, size_t nfreq)
+// on host rows: n reals in, m complex out
+int kofft_hip_czt_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t m, float wr, float wi, float ar, float ai, size_t batch)
+{
+    const int crc = czt_check(n, m, batch, in, out, ctx);
+    if (crc || batch == 0 || m == 0) return crc;
+    if (n == 0) {  // the loop body never runs: (+0, +0) in every bin
+        std::memset(out, 0, batch * 2 * m * sizeof(float));
+        return KOFFT_OK;
+    }
+    return rows_host<float>(ctx, in, out, batch, n, 2 * m, nullptr, 0, true, false, [&](float *d_in, float *d_out, const float *, size_t rows) {
+        return kofft_hip_dev_czt_f32(ctx, d_in, d_out, n, m, wr, wi, ar, ai, rows);
+    });
+}
+
+static int goertzel_launch(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const float *d_coeff, size_t n, size_t batch, size_t nfreq)
 {
     const int fpb = nfreq < 256 ? (int)nfreq : 256, rpb = 256 / fpb;
     const size_t groups = (batch + rpb - 1) / rpb;
@@ -159,8 +209,8 @@ int goertzel_launch(kofft_hip_ctx *ctx, const float *d_in, float *d_out, const f
     return KOFFT_OK;
 }
 
-int goertzel_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate, const float *target_freqs,
-                 size_t nfreq)
+int kofft_hip_dev_goertzel_f32(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, size_t batch, float sample_rate,
+                               const float *target_freqs, size_t nfreq)
 {
     int rc = goertzel_check(n, batch, sample_rate, target_freqs, nfreq, d_in, d_out, ctx);
     if (rc || batch == 0 || nfreq == 0) return rc;
@@ -188,5 +238,16 @@ int goertzel_dev(kofft_hip_ctx *ctx, const float *d_in, float *d_out, size_t n, 
     return goertzel_launch(ctx, d_in, d_out, d_coeff, n, batch, nfreq);
 }
 
-}  // namespace host
-}  // namespace kofft
+// on host rows against nfreq frequencies: the coefficients go up as the side input
+int kofft_hip_goertzel_f32(kofft_hip_ctx *ctx, const float *in, float *out, size_t n, size_t batch, float sample_rate,
+                           const float *target_freqs, size_t nfreq)
+{
+    const int crc = goertzel_check(n, batch, sample_rate, target_freqs, nfreq, in, out, ctx);
+    if (crc || batch == 0 || nfreq == 0) return crc;
+    std::vector<float> coeff(nfreq);
+    kofft_tables::goertzel_coeff_f32(n, sample_rate, target_freqs, nfreq, coeff.data());
+    return rows_host<float>(ctx, in, out, batch, n, nfreq, coeff.data(), nfreq, true, true,
+                            [&](float *d_in, float *d_out, const float *d_coeff, size_t rows) { return goertzel_launch(ctx, d_in, d_out, d_coeff, n, rows, nfreq); });
+}
+
+}  // extern "C"

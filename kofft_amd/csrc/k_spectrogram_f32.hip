@@ -1,6 +1,7 @@
 // k_spectrogram_f32.hip -- visual::spectrogram's colour helpers (spectrogram.rs:96-234) on float magnitudes: every kernel instance of
 // the family (spectrogram_impl.hip.h), the argument checks, the per-context cache of pixel ranges and the host's map_color_u8.
 #include "spectrogram_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include <algorithm>
 
@@ -8,7 +9,7 @@ namespace kofft {
 namespace host {
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
-int spec_db_check(bool dev, const void *mags, size_t count, const void *max_mag, const void *out, const kofft_hip_ctx *ctx)
+static int spec_db_check(bool dev, const void *mags, size_t count, const void *max_mag, const void *out, const kofft_hip_ctx *ctx)
 {
     if (count == 0) return KOFFT_ERR_EMPTY_INPUT;
     if (count > SIZE_MAX / sizeof(float)) return KOFFT_ERR_UNSUPPORTED;
@@ -18,7 +19,7 @@ int spec_db_check(bool dev, const void *mags, size_t count, const void *max_mag,
     return KOFFT_OK;
 }
 
-int spec_render_check(bool dev, const void *mags, size_t frames, size_t bins, const void *max_mag, int mode, int cmap, int depth, int scale,
+static int spec_render_check(bool dev, const void *mags, size_t frames, size_t bins, const void *max_mag, int mode, int cmap, int depth, int scale,
                       int layout, const uint32_t *pix_of_bin, const void *out, const kofft_hip_ctx *ctx)
 {
     if (frames == 0 || bins == 0) return KOFFT_ERR_EMPTY_INPUT;
@@ -89,7 +90,7 @@ int get_spec_ranges(kofft_hip_ctx *ctx, const uint32_t *pix_of_bin, size_t bins,
     return KOFFT_OK;
 }
 
-int spec_db_dev(kofft_hip_ctx *ctx, int which, const float *d_mags, size_t count, const float *d_max, float level, float *d_out)
+static int spec_db_dev(kofft_hip_ctx *ctx, int which, const float *d_mags, size_t count, const float *d_max, float level, float *d_out)
 {
     const int rc = spec_db_check(true, d_mags, count, d_max, d_out, ctx);
     if (rc) return rc;
@@ -99,8 +100,56 @@ int spec_db_dev(kofft_hip_ctx *ctx, int which, const float *d_mags, size_t count
     return KOFFT_OK;
 }
 
-int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max, int mode, float level, int cmap,
-                    int depth, int scale, int layout, const uint32_t *pix_of_bin, void *d_out)
+// magnitude_to_db (which == 0) / db_scale on `count` host magnitudes, max_mag a host float: one row of `count` values with max_mag as
+// the side input
+static int spec_db_host(kofft_hip_ctx *ctx, int which, const float *mags, size_t count, const float *max_mag, float level, float *out)
+{
+    const int crc = spec_db_check(false, mags, count, max_mag, out, ctx);
+    if (crc) return crc;
+    return rows_host<float>(ctx, mags, out, 1, count, count, max_mag, 1, true, true,
+                            [&](float *d_in, float *d_out, const float *d_max, size_t) { return spec_db_dev(ctx, which, d_in, count, d_max, level, d_out); });
+}
+
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_magnitude_to_db_f32(kofft_hip_ctx *ctx, const float *mags, size_t count, const float *max_mag, float floor_db, float *out)
+{
+    return spec_db_host(ctx, 0, mags, count, max_mag, floor_db, out);
+}
+int kofft_hip_dev_magnitude_to_db_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t count, const float *d_max_mag, float floor_db,
+                                      float *d_out)
+{
+    return spec_db_dev(ctx, 0, d_mags, count, d_max_mag, floor_db, d_out);
+}
+int kofft_hip_db_scale_f32(kofft_hip_ctx *ctx, const float *mags, size_t count, const float *max_mag, float dynamic_range, float *out)
+{
+    return spec_db_host(ctx, 1, mags, count, max_mag, dynamic_range, out);
+}
+int kofft_hip_dev_db_scale_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t count, const float *d_max_mag, float dynamic_range,
+                               float *d_out)
+{
+    return spec_db_dev(ctx, 1, d_mags, count, d_max_mag, dynamic_range, d_out);
+}
+
+int kofft_hip_set_spectrogram_transpose(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::spec_transpose, on); }
+
+int kofft_hip_log_bin_map(size_t bins, uint32_t *pix_of_bin)
+{
+    if (bins == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (bins > kSpecMaxBins) return KOFFT_ERR_UNSUPPORTED;
+    if (!pix_of_bin) return KOFFT_ERR_NULL;
+    kofft_tables::log_bin_map(bins, pix_of_bin);
+    return KOFFT_OK;
+}
+
+int kofft_hip_dev_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size_t bins, const float *d_max, int mode,
+                                         float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin, void *d_out)
 {
     int rc = spec_render_check(true, d_mags, frames, bins, d_max, mode, cmap, depth, scale, layout, pix_of_bin, d_out, ctx);
     if (rc) return rc;
@@ -127,7 +176,24 @@ int spec_render_dev(kofft_hip_ctx *ctx, const float *d_mags, size_t frames, size
     return KOFFT_OK;
 }
 
-int spec_map_color_u8(float t, int cmap, unsigned char *rgb)
+// the render on a host picture: the magnitudes and the picture travel as bytes (one row each), max_mag as the side input; the table
+// stays on the host
+int kofft_hip_spectrogram_render_f32(kofft_hip_ctx *ctx, const float *mags, size_t frames, size_t bins, const float *max_mag, int mode,
+                                     float level, int cmap, int depth, int scale, int layout, const uint32_t *pix_of_bin, void *out)
+{
+    const int crc = spec_render_check(false, mags, frames, bins, max_mag, mode, cmap, depth, scale, layout, pix_of_bin, out, ctx);
+    if (crc) return crc;
+    typedef unsigned char byte;
+    return rows_host<byte>(ctx, reinterpret_cast<const byte *>(mags), static_cast<byte *>(out), 1, frames * bins * sizeof(float),
+                           frames * bins * (depth == 16 ? 6 : 3), reinterpret_cast<const byte *>(max_mag), sizeof(float), true, true,
+                           [&](byte *d_in, byte *d_out, const byte *d_max, size_t) {
+                               return kofft_hip_dev_spectrogram_render_f32(ctx, reinterpret_cast<const float *>(d_in), frames, bins,
+                                                                           reinterpret_cast<const float *>(d_max), mode, level, cmap, depth, scale,
+                                                                           layout, pix_of_bin, d_out);
+                           });
+}
+
+int kofft_hip_map_color_u8(float t, int cmap, unsigned char *rgb)
 {
     if (cmap != KOFFT_CMAP_FIRE && cmap != KOFFT_CMAP_LEGACY && cmap != KOFFT_CMAP_GRAY && cmap != KOFFT_CMAP_RAINBOW) return KOFFT_ERR_INVALID_VALUE;
     if (!rgb) return KOFFT_ERR_NULL;
@@ -138,5 +204,4 @@ int spec_map_color_u8(float t, int cmap, unsigned char *rgb)
     return KOFFT_OK;
 }
 
-}  // namespace host
-}  // namespace kofft
+}  // extern "C"

@@ -1,6 +1,7 @@
 // k_stft.hip -- STFT framing kernels (stft.rs:76-105), the ISTFT overlap-add (stft.rs:117-156, 289-343, 384-399) and
-// stft_magnitudes (visual/spectrogram.rs:52-76) on device pointers.
+// stft_magnitudes (visual/spectrogram.rs:52-76) of one signal on device and host pointers, with their extern "C" entry points.
 #include "host_common.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
@@ -55,7 +56,7 @@ static int stft_composed_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t l
     return KOFFT_OK;
 }
 
-int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len,
+static int stft_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len,
              size_t start0, size_t hop, float *d_out, size_t count)
 {
     if (count == 0) return KOFFT_OK;
@@ -180,8 +181,8 @@ static int istft_fused_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, c
 
 // stft::istft (stft.rs:117-156, mode 1), stft::inverse_parallel (stft.rs:289-343, mode 2), stft::inverse_frame
 // (stft.rs:384-399, mode 0): ifft every frame in place, then the ordered overlap-add kernel -- or both in one (istft_fused_dev).
-int istft_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, const float *d_window, size_t win_len, size_t hop,
-              float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode, size_t start0)
+static int istft_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, const float *d_window, size_t win_len, size_t hop,
+              float *d_output, size_t out_len, float *d_scratch, size_t scratch_len, int mode = 1, size_t start0 = 0)
 {
     if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;                               // stft.rs:125 / 299
     if (mode == 1 && scratch_len != out_len) return KOFFT_ERR_MISMATCHED_LENGTHS;  // stft.rs:128
@@ -248,6 +249,125 @@ int stft_mag_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t 
     return KOFFT_OK;
 }
 
+// Host-pointer STFT of frames starting at start0, start0+hop, ...: uploads only the samples
+// those frames can see.
+static int stft_host(kofft_hip_ctx *ctx, const float *signal, size_t len, const float *window, size_t win_len, size_t start0, size_t hop,
+                     float *out, size_t count)
+{
+    if (count == 0) return KOFFT_OK;
+    if (win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (!complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || (!signal && len) || !window || !out) return KOFFT_ERR_NULL;
+    const size_t lo = start0 < len ? start0 : len;
+    size_t hi = start0 + (count - 1) * hop + win_len;
+    if (hi > len) hi = len;
+    if (hi < lo) hi = lo;
+    const size_t span = hi - lo;
+    const size_t out_bytes = count * win_len * 2 * sizeof(float);
+    const HostArray<float> a[2] = {{signal + lo, nullptr, span}, {nullptr, out, count * win_len * 2}};
+    // frame() / StftStream / short signals go zero-copy.  Positions are relative to `lo`; a start past the end of the signal leaves
+    // every sample zero.
+    return stage_host<float>(ctx, 1, 2, a, window, win_len, (span + win_len) * sizeof(float) + out_bytes <= kZeroCopyMax, false,
+                             [&](float *const *d, const float *d_win, size_t) {
+                                 return stft_dev(ctx, d[0], span, d_win, win_len, start0 - lo, hop, d[1], count);
+                             });
+}
+
+static int istft_host(kofft_hip_ctx *ctx, float *frames_data, size_t frames, const float *window, size_t win_len, size_t hop, float *output,
+                      size_t out_len, float *scratch, size_t scratch_len, int mode, size_t start0)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;
+    if (mode == 1 && scratch_len != out_len) return KOFFT_ERR_MISMATCHED_LENGTHS;
+    if (frames > 0 && win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (frames > 0 && !complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
+    return istft_stage(ctx, frames_data, 1, frames, window, win_len, output, out_len, scratch, mode,
+                       [&](float *d_frames, const float *d_win, float *d_out, float *d_scr) {
+                           return istft_dev(ctx, d_frames, frames, d_win, win_len, hop, d_out, out_len, d_scr, out_len, mode, start0);
+                       }, win_len);
+}
 
 }  // namespace host
 }  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_stft_f32(kofft_hip_ctx *ctx, const float *signal, size_t len, const float *window, size_t win_len, size_t hop, float *out,
+                       size_t frames)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;             // stft.rs:83
+    const size_t required = len / hop + (len % hop != 0);        // stft.rs:86
+    if (frames < required) return KOFFT_ERR_MISMATCHED_LENGTHS;  // stft.rs:87
+    return stft_host(ctx, signal, len, window, win_len, 0, hop, out, frames);
+}
+
+int kofft_hip_stft_parallel_f32(kofft_hip_ctx *ctx, const float *signal, size_t len, const float *window, size_t win_len, size_t hop,
+                                float *out, size_t frames)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;  // stft.rs:242 -- the only check parallel() makes
+    return stft_host(ctx, signal, len, window, win_len, 0, hop, out, frames);
+}
+
+int kofft_hip_stft_frame_f32(kofft_hip_ctx *ctx, const float *signal, size_t len, const float *window, size_t win_len, size_t start,
+                             float *frame_out)
+{
+    return stft_host(ctx, signal, len, window, win_len, start, 1, frame_out, 1);
+}
+
+int kofft_hip_stft_f32_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t len, const float *d_window, size_t win_len, size_t hop,
+                           float *d_out, size_t first_frame, size_t count)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;  // stft.rs:83 / 242
+    return stft_dev(ctx, d_signal, len, d_window, win_len, first_frame * hop, hop, d_out, count);
+}
+
+int kofft_hip_istft_f32_dev(kofft_hip_ctx *ctx, float *d_frames, size_t frames, const float *d_window, size_t win_len, size_t hop,
+                            float *d_output, size_t out_len, float *d_scratch, size_t scratch_len)
+{
+    return istft_dev(ctx, d_frames, frames, d_window, win_len, hop, d_output, out_len, d_scratch, scratch_len);
+}
+
+int kofft_hip_istft_f32(kofft_hip_ctx *ctx, float *frames_data, size_t frames, const float *window, size_t win_len, size_t hop,
+                        float *output, size_t out_len, float *scratch, size_t scratch_len)
+{
+    return istft_host(ctx, frames_data, frames, window, win_len, hop, output, out_len, scratch, scratch_len, 1, 0);
+}
+
+int kofft_hip_istft_parallel_f32(kofft_hip_ctx *ctx, const float *frames_data, size_t frames, const float *window, size_t win_len,
+                                 size_t hop, float *output, size_t out_len)
+{
+    // inverse_parallel clones each frame (stft.rs:310): the caller's frames are left untouched
+    return istft_host(ctx, const_cast<float *>(frames_data), frames, window, win_len, hop, output, out_len, nullptr, out_len, 2, 0);
+}
+
+int kofft_hip_istft_frame_f32(kofft_hip_ctx *ctx, float *frame, const float *window, size_t win_len, size_t start, float *output,
+                              size_t out_len)
+{
+    // inverse_frame (stft.rs:384-399): ifft(frame) in place, output[start + i] += frame[i].re * window[i], no normalisation
+    return istft_host(ctx, frame, 1, window, win_len, win_len ? win_len : 1, output, out_len, nullptr, out_len, 0, start);
+}
+
+int kofft_hip_stft_magnitudes_f32_dev(kofft_hip_ctx *ctx, const float *d_samples, size_t len, size_t win_len, size_t hop, float *d_mags,
+                                      size_t frames, float *d_max)
+{
+    return stft_mag_dev(ctx, d_samples, len, win_len, hop, d_mags, frames, d_max);
+}
+
+int kofft_hip_stft_magnitudes_f32(kofft_hip_ctx *ctx, const float *samples, size_t len, size_t win_len, size_t hop, float *mags,
+                                  size_t frames, float *max_mag)
+{
+    if (hop == 0) return KOFFT_ERR_INVALID_HOP_SIZE;
+    if (frames < len / hop + (len % hop != 0)) return KOFFT_ERR_MISMATCHED_LENGTHS;
+    if (frames > 0 && win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if (frames > 0 && !complex_len_ok(win_len)) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !max_mag || (frames && (!mags || (!samples && len)))) return KOFFT_ERR_NULL;
+    // never zero-copy: the maximum is an atomicMax target and stays in device memory
+    const HostArray<float> a[3] = {{samples, nullptr, len}, {nullptr, mags, frames * (win_len / 2)}, {nullptr, max_mag, 1}};
+    return stage_host<float>(ctx, 1, 3, a, nullptr, 0, false, false, [&](float *const *d, const float *, size_t) {
+        return stft_mag_dev(ctx, d[0], len, win_len, hop, d[1], frames, d[2]);
+    });
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // k_stft_rows.hip -- STFT (stft.rs:76-105), stft_magnitudes (visual/spectrogram.rs:52-76) and ISTFT (stft.rs:117-156, 289-343) over
-// ROWS of signals on device pointers.  Row r of every output is what k_stft.hip's single-signal entry returns for
+// ROWS of signals on device and host pointers, with their extern "C" entry points.  Row r of every output is what k_stft.hip's single-signal entry returns for
 // signal r alone; one launch chain serves all rows.  Also the framed families' shared host side: framed_src (what a framed call reads)
 // and framed_produce (frames t0 .. of the flat index densely into scratch: full, their kept bins, or their magnitudes).
 #include "host_common.hip.h"
+#include "host_stage.hip.h"
 
 #include "frame_cut.h"
 
@@ -162,7 +163,7 @@ int framed_produce(kofft_hip_ctx *ctx, const FramedSrc &s, FramedForm form, size
         KOFFT_HIP_TRY(ctx, hipGetLastError());
         return KOFFT_OK;
     }
-    if (form == FRAMES_FULL) return KOFFT_ERR_UNSUPPORTED;  // (never: the full frames of these lengths are one dispatch, stft_rows_dev)
+    if (form == FRAMES_FULL) return KOFFT_ERR_UNSUPPORTED;  // (never: the full frames of these lengths are one dispatch, kofft_hip_dev_stft_rows_f32)
     FramePiece p[3];
     const int np = frame_cut(t0, nt, s.frames, p);
     for (int k = 0; k < np; ++k) {
@@ -174,26 +175,6 @@ int framed_produce(kofft_hip_ctx *ctx, const FramedSrc &s, FramedForm form, size
         if (rc) return rc;
     }
     return KOFFT_OK;
-}
-
-int stft_rows_dev(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
-                  size_t win_len, size_t hop, float *d_out, size_t frames)
-{
-    const int crc = stft_rows_check(false, false, rows, len, row_stride, win_len, hop, frames);
-    if (crc || rows == 0 || frames == 0) return crc;
-    if (!ctx || (!d_signal && len) || !d_window || !d_out) return KOFFT_ERR_NULL;
-    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t total = rows * frames;
-    FramedSrc s;
-    (void)framed_src(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, &s);  // (the caller's window: nothing to fail)
-    if (!s.kernels)  // any other window length: composed over all rows at once (BlueStftSrc knows one signal only)
-        return for_chunks(total, composed_chunk(ctx, win_len, total), [&](size_t t0, size_t nt) {
-            return framed_produce(ctx, s, FRAMES_FULL, t0, nt, reinterpret_cast<cpx<float> *>(d_out) + t0 * win_len, nullptr);
-        });
-    StftRowsIO io{};
-    fill_rows_io(io, s);
-    io.out = reinterpret_cast<cpx<float> *>(d_out);
-    return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
 }
 
 // Frames per row from which a row alone is a persistent-kernel batch for StftMagIO; SIZE_MAX: never.  These are dispatch()'s f32
@@ -285,7 +266,7 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
     const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
     if (crc || rows == 0) return crc;
     if (!ctx || (frames && (!d_frames || !d_window)) || (out_len && (!d_output || (mode == 1 && !d_scratch)))) return KOFFT_ERR_NULL;
-    if (half && !(keep_frames && mode == 2)) return KOFFT_ERR_INVALID_VALUE;  // (never: istft_onesided_dev is the one caller)
+    if (half && !(keep_frames && mode == 2)) return KOFFT_ERR_INVALID_VALUE;  // (never: kofft_hip_dev_istft_onesided_f32 is the one caller)
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t in_frame = half ? (win_len / 2 + 1) * 2 : win_len * 2;  // floats of one frame as the caller holds it
     // keep_frames: whole rows at a time through at most scratch_chunk_bytes of the context's scratch (one row's frames where a row alone is
@@ -331,5 +312,110 @@ int istft_rows_dev(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t fram
     return KOFFT_OK;
 }
 
+// the three arrays of istft_stage over `rows` signals
+static int istft_rows_host(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len, size_t hop,
+                           float *output, size_t out_len, float *scratch, size_t scratch_len, int mode)
+{
+    const int crc = istft_rows_check(rows, frames, win_len, hop, out_len, scratch_len, mode);
+    if (crc || rows == 0) return crc;
+    return istft_stage(ctx, frames_data, rows, frames, window, win_len, output, out_len, scratch, mode,
+                       [&](float *d_frames, const float *d_win, float *d_out, float *d_scr) {
+                           return istft_rows_dev(ctx, d_frames, rows, frames, d_win, win_len, hop, d_out, out_len, d_scr, out_len, mode, false);
+                       }, win_len);
+}
+
 }  // namespace host
 }  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_dev_stft_rows_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride,
+                                const float *d_window, size_t win_len, size_t hop, float *d_out, size_t frames)
+{
+    const int crc = stft_rows_check(false, false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (!ctx || (!d_signal && len) || !d_window || !d_out) return KOFFT_ERR_NULL;
+    KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t total = rows * frames;
+    FramedSrc s;
+    (void)framed_src(ctx, d_signal, rows, len, row_stride, d_window, win_len, hop, frames, &s);  // (the caller's window: nothing to fail)
+    if (!s.kernels)  // any other window length: composed over all rows at once (BlueStftSrc knows one signal only)
+        return for_chunks(total, composed_chunk(ctx, win_len, total), [&](size_t t0, size_t nt) {
+            return framed_produce(ctx, s, FRAMES_FULL, t0, nt, reinterpret_cast<cpx<float> *>(d_out) + t0 * win_len, nullptr);
+        });
+    StftRowsIO io{};
+    fill_rows_io(io, s);
+    io.out = reinterpret_cast<cpx<float> *>(d_out);
+    return dispatch<float, EPI_STORE>(ctx, io, win_len, total);
+}
+
+// Host rows `row_stride` apart are packed (stride len) before they travel: the gaps are not the call's to read.
+int kofft_hip_stft_rows_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                            size_t win_len, size_t hop, float *out, size_t frames)
+{
+    const int crc = stft_rows_check(true, false, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0 || frames == 0) return crc;
+    if (!ctx || (!signal && len) || !window || !out) return KOFFT_ERR_NULL;
+    std::vector<float> packed;
+    const float *src = pack_rows(signal, rows, len, row_stride, packed);
+    // a chunk of the pipeline is whole rows: no seam logic on the host
+    return rows_host<float>(ctx, src, out, rows, len, frames * win_len * 2, window, win_len, true, true,
+                            [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                return kofft_hip_dev_stft_rows_f32(ctx, d_in, nb, len, len, d_win, win_len, hop, d_out, frames);
+                            });
+}
+
+int kofft_hip_dev_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *d_samples, size_t rows, size_t len, size_t row_stride,
+                                           size_t win_len, size_t hop, float *d_mags, size_t frames, float *d_max)
+{
+    return stft_mag_rows_dev(ctx, d_samples, rows, len, row_stride, win_len, hop, d_mags, frames, d_max);
+}
+
+int kofft_hip_stft_magnitudes_rows_f32(kofft_hip_ctx *ctx, const float *samples, size_t rows, size_t len, size_t row_stride, size_t win_len,
+                                       size_t hop, float *mags, size_t frames, float *max_mag)
+{
+    const int crc = stft_rows_check(true, true, rows, len, row_stride, win_len, hop, frames);
+    if (crc || rows == 0) return crc;
+    if (!ctx || !max_mag || (frames && ((!mags && win_len >= 2) || (!samples && len)))) return KOFFT_ERR_NULL;
+    if (frames == 0 || win_len < 2) {  // no magnitude bins: every maximum is its starting value
+        for (size_t r = 0; r < rows; ++r) max_mag[r] = 0.0f;
+        return KOFFT_OK;
+    }
+    std::vector<float> packed;
+    const float *src = pack_rows(samples, rows, len, row_stride, packed);
+    // never zero-copy: the maxima are atomicMax targets and stay in device memory, as in the single-signal form (k_stft.hip)
+    const HostArray<float> a[3] = {{src, nullptr, len}, {nullptr, mags, frames * (win_len / 2)}, {nullptr, max_mag, 1}};
+    return rows_host_n<float>(ctx, rows, 3, a, nullptr, 0, false, true, [&](float *const *d, const float *, size_t nb) {
+        return stft_mag_rows_dev(ctx, d[0], nb, len, len, win_len, hop, d[1], frames, d[2]);
+    });
+}
+
+int kofft_hip_dev_istft_rows_f32(kofft_hip_ctx *ctx, float *d_frames, size_t rows, size_t frames, const float *d_window, size_t win_len,
+                                 size_t hop, float *d_output, size_t out_len, float *d_scratch, size_t scratch_len)
+{
+    return istft_rows_dev(ctx, d_frames, rows, frames, d_window, win_len, hop, d_output, out_len, d_scratch, scratch_len, 1, false);
+}
+
+int kofft_hip_dev_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *d_frames, size_t rows, size_t frames, const float *d_window,
+                                          size_t win_len, size_t hop, float *d_output, size_t out_len)
+{
+    return istft_rows_dev(ctx, const_cast<float *>(d_frames), rows, frames, d_window, win_len, hop, d_output, out_len, nullptr, out_len, 2,
+                          true);
+}
+
+int kofft_hip_istft_rows_f32(kofft_hip_ctx *ctx, float *frames_data, size_t rows, size_t frames, const float *window, size_t win_len,
+                             size_t hop, float *output, size_t out_len, float *scratch, size_t scratch_len)
+{
+    return istft_rows_host(ctx, frames_data, rows, frames, window, win_len, hop, output, out_len, scratch, scratch_len, 1);
+}
+
+int kofft_hip_istft_parallel_rows_f32(kofft_hip_ctx *ctx, const float *frames_data, size_t rows, size_t frames, const float *window,
+                                      size_t win_len, size_t hop, float *output, size_t out_len)
+{
+    return istft_rows_host(ctx, const_cast<float *>(frames_data), rows, frames, window, win_len, hop, output, out_len, nullptr, out_len, 2);
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
-// k_wavelet_f32.hip -- wavelet::* (wavelet.rs) on float rows: the argument checks, the routes and every kernel instance of the
-// family (wavelet_impl.hip.h).
+// k_wavelet_f32.hip -- wavelet::* (wavelet.rs) on float rows: the argument checks, the routes, every kernel instance of the
+// family (wavelet_impl.hip.h) and the extern "C" entry points.
 #include "wavelet_impl.hip.h"
+#include "host_stage.hip.h"
 
 #include <atomic>
 #include <type_traits>
@@ -9,6 +10,10 @@ namespace kofft {
 namespace host {
 
 using namespace kofft::wav;
+
+constexpr size_t kWaveletMaxLen = size_t(1) << 26;  // the longest input or output row
+constexpr size_t kWaveletMaxLevels = 64;
+constexpr size_t kWaveletFusedMax = 16384;  // the longest row (forward: input, inverse: output) the fused multi-level kernels keep in LDS
 
 namespace {
 
@@ -147,7 +152,8 @@ bool use_fused(const kofft_hip_ctx *ctx, int w, bool inverse, size_t len, size_t
 
 }  // namespace
 
-void wavelet_taps(int w, bool inverse, float *lo, float *hi)
+// the coefficient table (8 + 8 floats, +0 past the length; haar: none)
+static void wavelet_taps(int w, bool inverse, float *lo, float *hi)
 {
     const Taps t = taps(w, inverse);
     for (int k = 0; k < 8; ++k) {
@@ -156,7 +162,8 @@ void wavelet_taps(int w, bool inverse, float *lo, float *hi)
     }
 }
 
-size_t wavelet_lengths(size_t len, size_t levels, size_t *lens)
+// lens[0] = len, lens[l] = ceil(lens[l - 1] / 2); returns sum lens[1..]
+static size_t wavelet_lengths(size_t len, size_t levels, size_t *lens)
 {
     size_t total = 0;
     lens[0] = len;
@@ -168,7 +175,7 @@ size_t wavelet_lengths(size_t len, size_t levels, size_t *lens)
 }
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched.
-int dwt_check(int w, size_t len, size_t batch, size_t levels, const void *p0, const void *p1, const void *p2, const kofft_hip_ctx *ctx)
+static int dwt_check(int w, size_t len, size_t batch, size_t levels, const void *p0, const void *p1, const void *p2, const kofft_hip_ctx *ctx)
 {
     if (w < 0 || w >= NFAM) return KOFFT_ERR_INVALID_VALUE;
     if (batch == 0 || len == 0) return KOFFT_OK;
@@ -177,7 +184,7 @@ int dwt_check(int w, size_t len, size_t batch, size_t levels, const void *p0, co
     return KOFFT_OK;
 }
 
-int idwt_check(int w, size_t n, size_t batch, size_t levels, const size_t *dl, const void *p0, const void *p1, const void *p2,
+static int idwt_check(int w, size_t n, size_t batch, size_t levels, const size_t *dl, const void *p0, const void *p1, const void *p2,
                const kofft_hip_ctx *ctx)
 {
     if (w < 0 || w >= NFAM) return KOFFT_ERR_INVALID_VALUE;
@@ -197,7 +204,34 @@ int idwt_check(int w, size_t n, size_t batch, size_t levels, const size_t *dl, c
     return KOFFT_OK;
 }
 
-int dwt_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_detail, size_t len, size_t batch)
+}  // namespace host
+}  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+using namespace kofft::wav;
+
+extern "C" {
+
+int kofft_hip_set_wavelet_fused(kofft_hip_ctx *ctx, int on) { return set_route(ctx, &kofft_hip_ctx::wavelet_fused, on, 0, 2); }
+
+int kofft_hip_wavelet_taps_f32(int wavelet, int inverse, float *lo, float *hi)
+{
+    if (wavelet < 0 || wavelet > 4) return KOFFT_ERR_INVALID_VALUE;
+    if (!lo || !hi) return KOFFT_ERR_NULL;
+    wavelet_taps(wavelet, inverse != 0, lo, hi);
+    return KOFFT_OK;
+}
+
+int kofft_hip_dwt_multi_lengths(size_t len, size_t levels, size_t *lens)
+{
+    if (levels > kWaveletMaxLevels) return KOFFT_ERR_UNSUPPORTED;
+    if (!lens) return KOFFT_ERR_NULL;
+    wavelet_lengths(len, levels, lens);
+    return KOFFT_OK;
+}
+
+int kofft_hip_dwt_f32_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_detail, size_t len, size_t batch)
 {
     int rc = dwt_check(w, len, batch, 0, d_in, d_approx, d_detail, ctx);
     if (rc || batch == 0 || len == 0) return rc;
@@ -207,7 +241,18 @@ int dwt_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float
     return dispatch(w, [&](auto W) { return launch_fwd<decltype(W)::value>(ctx, d_in, d_approx, d_detail, len, len, batch); });
 }
 
-int idwt_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_detail, float *d_out, size_t n, size_t batch)
+// wavelet::*_forward / *_inverse (one level) on host rows
+int kofft_hip_dwt_f32(kofft_hip_ctx *ctx, int w, const float *in, float *approx, float *detail, size_t len, size_t batch)
+{
+    const int crc = dwt_check(w, len, batch, 0, in, approx, detail, ctx);
+    if (crc || batch == 0 || len / 2 == 0) return crc;
+    const HostArray<float> a[3] = {{in, nullptr, len}, {nullptr, approx, len / 2}, {nullptr, detail, len / 2}};
+    return rows_host_n<float>(ctx, batch, 3, a, nullptr, 0, true, true, [&](float *const *d, const float *, size_t rows) {
+        return kofft_hip_dwt_f32_dev(ctx, w, d[0], d[1], d[2], len, rows);
+    });
+}
+
+int kofft_hip_idwt_f32_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_detail, float *d_out, size_t n, size_t batch)
 {
     const size_t one = n;
     int rc = idwt_check(w, n, batch, 1, &one, d_approx, d_detail, d_out, ctx);
@@ -218,7 +263,19 @@ int idwt_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_de
     return dispatch(w, [&](auto W) { return launch_inv<decltype(W)::value>(ctx, d_approx, d_detail, d_out, n, n, batch); });
 }
 
-int dwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_details, size_t len, size_t batch, size_t levels)
+int kofft_hip_idwt_f32(kofft_hip_ctx *ctx, int w, const float *approx, const float *detail, float *out, size_t n, size_t batch)
+{
+    const size_t one = n;
+    const int crc = idwt_check(w, n, batch, 1, &one, approx, detail, out, ctx);
+    if (crc || batch == 0 || n == 0) return crc;
+    const HostArray<float> a[3] = {{approx, nullptr, n}, {detail, nullptr, n}, {nullptr, out, 2 * n}};
+    return rows_host_n<float>(ctx, batch, 3, a, nullptr, 0, true, true, [&](float *const *d, const float *, size_t rows) {
+        return kofft_hip_idwt_f32_dev(ctx, w, d[0], d[1], d[2], n, rows);
+    });
+}
+
+int kofft_hip_dwt_multi_f32_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx, float *d_details, size_t len, size_t batch,
+                                size_t levels)
 {
     int rc = dwt_check(w, len, batch, levels, d_in, d_approx, levels ? d_details : d_approx, ctx);
     if (rc || batch == 0 || len == 0) return rc;
@@ -252,8 +309,21 @@ int dwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_in, float *d_approx,
     return KOFFT_OK;
 }
 
-int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_details, const size_t *detail_lens, float *d_out,
-                   size_t n, size_t batch, size_t levels)
+// multi_level_forward on host rows (the details are packed level after level, [batch][a_l] each: not row-contiguous, so no pipeline)
+int kofft_hip_dwt_multi_f32(kofft_hip_ctx *ctx, int w, const float *in, float *approx, float *details, size_t len, size_t batch, size_t levels)
+{
+    const int crc = dwt_check(w, len, batch, levels, in, approx, levels ? details : approx, ctx);
+    if (crc || batch == 0 || len == 0) return crc;
+    size_t lens[kWaveletMaxLevels + 1];
+    const size_t det = wavelet_lengths(len, levels, lens);
+    const HostArray<float> a[3] = {{in, nullptr, len}, {nullptr, approx, lens[levels]}, {nullptr, details, det}};
+    return rows_host_n<float>(ctx, batch, levels ? 3 : 2, a, nullptr, 0, true, false, [&](float *const *d, const float *, size_t rows) {
+        return kofft_hip_dwt_multi_f32_dev(ctx, w, d[0], d[1], levels ? d[2] : nullptr, len, rows, levels);
+    });
+}
+
+int kofft_hip_idwt_multi_f32_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float *d_details, const size_t *detail_lens,
+                                 float *d_out, size_t n, size_t batch, size_t levels)
 {
     int rc = idwt_check(w, n, batch, levels, detail_lens, d_approx, levels ? d_details : d_approx, d_out, ctx);
     if (rc || batch == 0 || n == 0) return rc;
@@ -290,5 +360,18 @@ int idwt_multi_dev(kofft_hip_ctx *ctx, int w, const float *d_approx, const float
     return KOFFT_OK;
 }
 
-}  // namespace host
-}  // namespace kofft
+// multi_level_inverse on host rows
+int kofft_hip_idwt_multi_f32(kofft_hip_ctx *ctx, int w, const float *approx, const float *details, const size_t *detail_lens, float *out,
+                             size_t n, size_t batch, size_t levels)
+{
+    const int crc = idwt_check(w, n, batch, levels, detail_lens, approx, levels ? details : approx, out, ctx);
+    if (crc || batch == 0 || n == 0) return crc;
+    size_t det = 0;
+    for (size_t l = 0; l < levels; ++l) det += detail_lens[l];
+    const HostArray<float> a[3] = {{approx, nullptr, n}, {nullptr, out, n << levels}, {details, nullptr, det}};
+    return rows_host_n<float>(ctx, batch, levels ? 3 : 2, a, nullptr, 0, true, false, [&](float *const *d, const float *, size_t rows) {
+        return kofft_hip_idwt_multi_f32_dev(ctx, w, d[0], levels ? d[2] : nullptr, detail_lens, d[1], n, rows, levels);
+    });
+}
+
+}  // extern "C"

@@ -1,13 +1,14 @@
 // k_welch_f32.hip -- Welch power spectra and cross spectra of rows (welch_impl.hip.h): every kernel instance of the
 // family, the argument checks and the two routes.
 #include "welch_impl.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
 
 // Checks in the order of include/kofft_hip.h, all before the context or the device is touched: the STFT rows' without the frame count,
 // then the flags, the pointers, the overlaps.
-int welch_check(bool csd, const void *x, const void *y, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
+static int welch_check(bool csd, const void *x, const void *y, const void *window, const void *out, size_t rows, size_t len, size_t row_stride,
                 size_t win_len, size_t hop, size_t frames, int flags, const kofft_hip_ctx *ctx)
 {
     const int crc = stft_rows_check(false, false, rows, len, row_stride, win_len, hop, frames);
@@ -162,7 +163,7 @@ static int welch_composed(kofft_hip_ctx *ctx, const WelchCall &c)
     return KOFFT_OK;
 }
 
-int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
+static int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
               const float *d_window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_out)
 {
     const int crc = welch_check(csd, d_x, d_y, d_window, d_out, rows, len, row_stride, win_len, hop, frames, flags, ctx);
@@ -184,5 +185,81 @@ int welch_dev(kofft_hip_ctx *ctx, bool csd, const float *d_x, const float *d_y, 
     return welch_composed(ctx, c);
 }
 
+// The signals go up, rows * K values come down (whole rows per chunk of the pipeline); no frame leaves the device.
+static int welch_host(kofft_hip_ctx *ctx, bool csd, const float *x, const float *y, size_t rows, size_t len, size_t row_stride,
+                      const float *window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *out)
+{
+    const int crc = welch_check(csd, x, y, window, out, rows, len, row_stride, win_len, hop, frames, flags, ctx);
+    if (crc || rows == 0 || frames == 0) return crc;
+    const size_t out_row = (win_len / 2 + 1) * (csd ? 2 : 1);
+    std::vector<float> packed_x, packed_y;
+    const float *sx = pack_rows(x, rows, len, row_stride, packed_x);
+    if (!csd)
+        return rows_host<float>(ctx, sx, out, rows, len, out_row, window, window ? win_len : 0, true, true,
+                                [&](float *d_in, float *d_out, const float *d_win, size_t nb) {
+                                    return welch_dev(ctx, false, d_in, nullptr, nb, len, len, d_win, win_len, hop, frames, scale, flags, d_out);
+                                });
+    const float *sy = pack_rows(y, rows, len, row_stride, packed_y);
+    const HostArray<float> a[3] = {{sx, nullptr, len}, {sy, nullptr, len}, {nullptr, out, out_row}};
+    return rows_host_n<float>(ctx, rows, 3, a, window, window ? win_len : 0, true, true, [&](float *const *d, const float *d_win, size_t nb) {
+        return welch_dev(ctx, true, d[0], d[1], nb, len, len, d_win, win_len, hop, frames, scale, flags, d[2]);
+    });
+}
+
 }  // namespace host
 }  // namespace kofft
+
+using namespace kofft;
+using namespace kofft::host;
+
+extern "C" {
+
+int kofft_hip_welch_f32(kofft_hip_ctx *ctx, const float *signal, size_t rows, size_t len, size_t row_stride, const float *window,
+                        size_t win_len, size_t hop, size_t frames, float scale, int flags, float *psd)
+{
+    return welch_host(ctx, false, signal, nullptr, rows, len, row_stride, window, win_len, hop, frames, scale, flags, psd);
+}
+
+int kofft_hip_dev_welch_f32(kofft_hip_ctx *ctx, const float *d_signal, size_t rows, size_t len, size_t row_stride, const float *d_window,
+                            size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_psd)
+{
+    return welch_dev(ctx, false, d_signal, nullptr, rows, len, row_stride, d_window, win_len, hop, frames, scale, flags, d_psd);
+}
+
+int kofft_hip_csd_f32(kofft_hip_ctx *ctx, const float *x, const float *y, size_t rows, size_t len, size_t row_stride, const float *window,
+                      size_t win_len, size_t hop, size_t frames, float scale, int flags, float *pxy)
+{
+    return welch_host(ctx, true, x, y, rows, len, row_stride, window, win_len, hop, frames, scale, flags, pxy);
+}
+
+int kofft_hip_dev_csd_f32(kofft_hip_ctx *ctx, const float *d_x, const float *d_y, size_t rows, size_t len, size_t row_stride,
+                          const float *d_window, size_t win_len, size_t hop, size_t frames, float scale, int flags, float *d_pxy)
+{
+    return welch_dev(ctx, true, d_x, d_y, rows, len, row_stride, d_window, win_len, hop, frames, scale, flags, d_pxy);
+}
+
+int kofft_hip_set_welch_fused(kofft_hip_ctx *ctx, int mode) { return set_route(ctx, &kofft_hip_ctx::welch_fused, mode, 0, 2); }
+
+int kofft_hip_welch_scale_f32(const float *window, size_t win_len, double fs, size_t frames, int scaling, float *scale)
+{
+    if (!scale) return KOFFT_ERR_NULL;
+    if (win_len == 0) return KOFFT_ERR_EMPTY_INPUT;
+    if ((scaling != 0 && scaling != 1) || !(fs > 0.0) || frames == 0) return KOFFT_ERR_INVALID_VALUE;
+    std::vector<float> hann;
+    if (!window) {
+        hann.resize(win_len);
+        kofft_tables::hann_f32(win_len, hann.data());
+        window = hann.data();
+    }
+    double s = 0.0;
+    for (size_t i = 0; i < win_len; ++i) {
+        const double w = (double)window[i];
+        s = s + (scaling == 0 ? w * w : w);
+    }
+    const double den = scaling == 0 ? fs * s * (double)frames : (s * s) * (double)frames;
+    if (s == 0.0 || !(den == den)) return KOFFT_ERR_INVALID_VALUE;
+    *scale = (float)(1.0 / den);
+    return KOFFT_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 #pragma once
 
 #include "host_common.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 
@@ -123,6 +124,16 @@ inline bool planar_fused_ok(const kofft_hip_ctx *ctx, size_t n)
     return ctx->planar_fused && is_pow2(n) && n >= 2 && n <= (size_t(1) << max_log2<T>());
 }
 
+// the argument checks alone, in the order of fft_dev and before the context or a device is touched
+inline int planar_check(size_t n, size_t batch, const void *p0, const void *p1, const void *p2, const void *p3, const kofft_hip_ctx *ctx)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;  // fft.rs:794
+    if (!complex_len_ok(n)) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !p0 || !p1 || !p2 || !p3) return KOFFT_ERR_NULL;
+    return KOFFT_OK;
+}
+
 template <typename T>
 int planar_dev(kofft_hip_ctx *ctx, const T *re_in, const T *im_in, T *re_out, T *im_out, size_t n, size_t batch, int inverse)
 {
@@ -142,6 +153,18 @@ int planar_dev(kofft_hip_ctx *ctx, const T *re_in, const T *im_in, T *re_out, T 
     }
     PlanarIO<T, false> io{{}, re_in, im_in, re_out, im_out, (int)n, scale};
     return dispatch<T, EPI_STORE>(ctx, io, n, batch);
+}
+
+// the same on host planes of batch * n reals each, in place
+template <typename T>
+int planar_host(kofft_hip_ctx *ctx, T *re, T *im, size_t n, size_t batch, int inverse)
+{
+    const int crc = planar_check(n, batch, re, im, re, im, ctx);
+    if (crc || batch == 0) return crc;
+    if (n == 1) return KOFFT_OK;  // the planes themselves
+    const HostArray<T> a[2] = {{re, re, n}, {im, im, n}};
+    return rows_host_n<T>(ctx, batch, 2, a, nullptr, 0, is_pow2(n), true,
+                          [&](T *const *d, const T *, size_t nb) { return planar_dev<T>(ctx, d[0], d[1], d[0], d[1], n, nb, inverse); });
 }
 
 }  // namespace host

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "host_common.hip.h"
+#include "host_stage.hip.h"
 
 namespace kofft {
 namespace host {
@@ -231,15 +232,23 @@ int irfft_composed_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, si
     return KOFFT_OK;
 }
 
+// the argument checks of rfft and irfft alone, before the context or a device is touched
+inline int real_check(size_t n, size_t batch, const void *in, const void *out, const kofft_hip_ctx *ctx)
+{
+    if (batch == 0) return KOFFT_OK;
+    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;        // rfft.rs:434, 477
+    if (n % 2 != 0) return KOFFT_ERR_INVALID_VALUE;  // rfft.rs:437, 480
+    if (!complex_len_ok(n / 2)) return KOFFT_ERR_UNSUPPORTED;
+    if (!ctx || !in || !out) return KOFFT_ERR_NULL;
+    return KOFFT_OK;
+}
+
 template <typename T>
 int rfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, size_t n, size_t batch)
 {
-    if (batch == 0) return KOFFT_OK;
-    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;   // rfft.rs:434
-    if (n % 2 != 0) return KOFFT_ERR_INVALID_VALUE;  // rfft.rs:437
+    const int crc = real_check(n, batch, d_in, d_out, ctx);
+    if (crc || batch == 0) return crc;
     const size_t m = n / 2;
-    if (!complex_len_ok(m)) return KOFFT_ERR_UNSUPPORTED;
-    if (!ctx || !d_in || !d_out) return KOFFT_ERR_NULL;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!fused_len_ok<T>(m)) return rfft_composed_dev<T>(ctx, d_in, d_out, d_window, n, batch);
     const cpx<T> *rtab = nullptr;
@@ -252,12 +261,9 @@ int rfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, const T *d_window, siz
 template <typename T>
 int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batch)
 {
-    if (batch == 0) return KOFFT_OK;
-    if (n == 0) return KOFFT_ERR_EMPTY_INPUT;   // rfft.rs:477
-    if (n % 2 != 0) return KOFFT_ERR_INVALID_VALUE;  // rfft.rs:480
+    const int crc = real_check(n, batch, d_in, d_out, ctx);
+    if (crc || batch == 0) return crc;
     const size_t m = n / 2;
-    if (!complex_len_ok(m)) return KOFFT_ERR_UNSUPPORTED;
-    if (!ctx || !d_in || !d_out) return KOFFT_ERR_NULL;
     KOFFT_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!fused_len_ok<T>(m)) return irfft_composed_dev<T>(ctx, d_in, d_out, n, batch);
     const cpx<T> *rtab = nullptr;
@@ -270,6 +276,24 @@ int irfft_dev(kofft_hip_ctx *ctx, const T *d_in, T *d_out, size_t n, size_t batc
     return dispatch<T, EPI_STORE>(ctx, io, m, batch);
 }
 
+// the same on host rows; the window is the side input, uploaded once
+template <typename T>
+int rfft_host(kofft_hip_ctx *ctx, const T *in, T *out, const T *window, size_t n, size_t batch)
+{
+    const int crc = real_check(n, batch, in, out, ctx);
+    if (crc || batch == 0) return crc;
+    return rows_host<T>(ctx, in, out, batch, n, (n / 2 + 1) * 2, window, n, true, true,
+                        [&](T *d_in, T *d_out, const T *d_win, size_t rows) { return rfft_dev<T>(ctx, d_in, d_out, d_win, n, rows); });
+}
+
+template <typename T>
+int irfft_host(kofft_hip_ctx *ctx, const T *in, T *out, size_t n, size_t batch)
+{
+    const int crc = real_check(n, batch, in, out, ctx);
+    if (crc || batch == 0) return crc;
+    return rows_host<T>(ctx, in, out, batch, (n / 2 + 1) * 2, n, nullptr, 0, true, true,
+                        [&](T *d_in, T *d_out, const T *, size_t rows) { return irfft_dev<T>(ctx, d_in, d_out, n, rows); });
+}
 
 }  // namespace host
 }  // namespace kofft

@@ -135,3 +135,28 @@ def test_every_route_switch_of_the_library_has_a_gpu_test_row():
     in_source = set(re.findall(r'getenv\("(KOFFT_HIP_[A-Z0-9_]+)"\)', src))
     in_table = {k for k, _, _ in KNOBS}
     assert in_source == in_table, (sorted(in_source - in_table), sorted(in_table - in_source))
+
+
+def test_shared_header_declares_only_what_crosses_translation_units():
+    """host_common.hip.h declares a function between its two marks only where one unit defines it and another calls it: every name
+    there is mentioned by at least two other files of kofft_amd/csrc.  A function of one unit alone stays out of the header and has
+    internal linkage in its unit."""
+    import re
+    from pathlib import Path
+
+    csrc = Path(__file__).resolve().parent.parent / "kofft_amd" / "csrc"
+    header = (csrc / "host_common.hip.h").read_text()
+    begin, end = "// [cross-unit declarations: begin]", "// [cross-unit declarations: end]"
+    assert header.count(begin) == 1 and header.count(end) == 1
+    block = header[header.index(begin) + len(begin):header.index(end)]
+    block = re.sub(r"//[^\n]*", "", block)
+    names = sorted(set(re.findall(r"^(?:const\s+)?\w+[\s\*]+(\w+)\(", block, flags=re.M)))
+    assert len(names) >= 20 and "fft_dev" in names and "framed_produce" in names, names
+    others = {p.name: p.read_text() for p in sorted(csrc.iterdir())
+              if p.is_file() and p.name != "host_common.hip.h" and p.suffix in (".hip", ".h", ".cpp")}
+    lonely = {}
+    for name in names:
+        users = [f for f, text in others.items() if re.search(r"\b%s\b" % re.escape(name), text)]
+        if len(users) < 2:
+            lonely[name] = users
+    assert not lonely, f"declared for one unit alone: {lonely}"

@@ -170,7 +170,7 @@ def test_two_contexts_in_two_threads(oracle):
 
 def test_host_pipeline_on_every_entry_point(oracle, monkeypatch):
     """The host-pointer entry points move batches of 128 MiB and more in eight chunks -- upload of chunk c + 1, kernels of chunk c and
-    download of chunk c - 1 in flight together (kofft_hip.hip: pipeline_chunks).  The session runs with the pipeline OFF (conftest.py:
+    download of chunk c - 1 in flight together (host_stage.hip.h: pipeline_chunks).  The session runs with the pipeline OFF (conftest.py:
     so that every test's batch reaches the kernel it names); here it is ON, on every entry point that has it -- complex in place
     (c32 / c64, forward and inverse), rfft with and without a row window, irfft -- with batches that do not divide by eight, EVERY row
     against the oracle, and byte for byte against the same calls with the pipeline off."""
