@@ -367,6 +367,67 @@ int kofft_hip_dev_imdct_f32(kofft_hip_ctx *ctx, const float *d_coef, size_t rows
                             float *d_out, size_t out_first, size_t out_len);
 int kofft_hip_set_mdct_fused(kofft_hip_ctx *ctx, int on);
 
+/* ---- polyphase filter bank of rows: analysis and synthesis (weighted overlap-add) -----------------
+ * A prototype filter of nh = T M taps folded onto an M-point transform: M channels, T >= 1 taps per channel, hop D >= 1, h the nh
+ * analysis taps, g the nh synthesis taps.  f32 only; one filter for all rows.  The reference has no such entry point: "fft" and "ifft"
+ * below are its own (fft.rs), exactly as kofft_hip_stft_rows_f32 and kofft_hip_istft_parallel_rows_f32 use them, the Bluestein arm for
+ * lengths that are not a power of two and ifft as conj, fft, conj, * 1 / M included.  Every route, grid and device meets the
+ * definitions bit for bit; all arithmetic is f32 and un-fused: one product, then one sum.
+ * Analysis.  `rows` signals of nx samples, row r at x + r * row_stride (in floats; ignored when rows == 1), `lead` < nh virtual zeros
+ *   in front of every row, `frames` frames per row (the caller's; frames past the end read +0).  Item (r, f), for j < M and t < T:
+ *     g_t  = h[j + tM] * x_r[fD + j + tM - lead]   where that sample exists in its own row, +0 elsewhere (never a sample of row r +- 1);
+ *     u[j] = (..((g_0 + g_1) + g_2)..) + g_{T-1}   ascending t, one accumulator started by g_0;
+ *     Z    = fft((u[j], +0))                       (nothing for M == 1);
+ *     out[(r * frames + f) * bins + k] = Z[k], k < bins: complex, dense, 8-byte aligned.
+ *   1 <= bins <= M; bins = M / 2 + 1 is the one-sided form.  Nothing of the other bins is written anywhere.  In exact arithmetic
+ *   Z[k] = sum_{i < nh} h[i] x[fD + i - lead] exp(-2 PI i k i / M).  With T = 1 and lead = 0 this is kofft_hip_stft_rows_f32 with window
+ *   h and hop D.  out must not overlap x or h.
+ *   Checks, in this order and before the context or a device is touched: rows == 0 or frames == 0 -> KOFFT_OK, nothing touched;
+ *   M == 0 or nh == 0 -> EMPTY_INPUT; nh % M != 0, or bins == 0 or bins > M -> INVALID_VALUE; M beyond the complex limits (2^26 for
+ *   powers of two, 2^25 otherwise) -> KOFFT_ERR_UNSUPPORTED; D == 0 -> INVALID_HOP_SIZE; nx == 0 -> EMPTY_INPUT; lead >= nh ->
+ *   INVALID_VALUE; rows > 1 and row_stride < nx -> INVALID_VALUE; sizes that overflow -> KOFFT_ERR_UNSUPPORTED; a null pointer or
+ *   context -> KOFFT_ERR_NULL.
+ * Synthesis.  spec is rows * frames * bins complex (8-byte aligned) and is only read.  bins == M: the frames are used as given;
+ *   bins == M / 2 + 1 with M even: completed as kofft_hip_istft_onesided_f32 does, F[k] = (half[M-k].re, -half[M-k].im) for
+ *   k >= bins, the imaginary parts of bins 0 and M / 2 used as given; any other bins -> INVALID_VALUE.  Per frame and row:
+ *     v_f = ifft(F_f);  r_f[j] = v_f[j].re;  full = (frames - 1) D + nh samples per row;
+ *     full[p] = (sum over f ascending with 0 <= p - fD < nh of g[p - fD] * r_f[(p - fD) mod M]) * scale,
+ *   the first term starting the accumulator; a sample no frame covers is +0.  out receives full[out_first .. out_first + out_len) of
+ *   every row, dense, out_len floats per row.  out must not overlap spec or g.
+ *   Checks: the analysis ones that apply, in their order -- rows == 0 or frames == 0 -> KOFFT_OK; M == 0 or nh == 0 -> EMPTY_INPUT;
+ *   nh % M != 0 or a bins that is neither form -> INVALID_VALUE; M beyond the complex limits -> KOFFT_ERR_UNSUPPORTED; D == 0 ->
+ *   INVALID_HOP_SIZE; sizes that overflow -> KOFFT_ERR_UNSUPPORTED --, then out_first + out_len > full -> MISMATCHED_LENGTHS; a null
+ *   pointer or context -> KOFFT_ERR_NULL (out may be null when out_len == 0, which writes nothing).
+ *   Reconstruction is exact when, for every p mod D, sum_f g[n_f] * h[n_f + qM] = c * delta[q] with n_f = p - fD: the round trip then
+ *   needs lead = nh - D, out_first = lead and scale = 1 / c, and returns x wherever every covering frame exists.  The sine window
+ *   with T = 1 and D = M / 2 is such a pair (c = 1); a sinc x Kaiser prototype used as h = g is not.
+ * Host helpers, no context, no device, everything in double and rounded to f32 once where the result is f32.
+ *   kofft_hip_pfb_taps_f32(M, T, beta, out) writes the nh = T M values sinc((i - (nh - 1) / 2) / M) * Kaiser_beta[i], normalised to unit
+ *   sum (sinc(t) = sin(PI t) / (PI t); Kaiser_beta[i] = I0(beta sqrt(1 - (2i / (nh - 1) - 1)^2)) / I0(beta), I0 the power series of
+ *   kofft_hip_resample_taps_f32).  M == 0 or T == 0 -> EMPTY_INPUT; beta < 0 or NaN -> INVALID_VALUE; out null -> KOFFT_ERR_NULL; more
+ *   than 2^28 taps -> KOFFT_ERR_UNSUPPORTED.
+ *   kofft_hip_pfb_reconstruction(h, g, nh, M, D, &c, &worst) evaluates the condition above in double: *c is the q = 0 sum at p = 0,
+ *   *worst the largest |sum - c * delta[q]| over all p mod D and |q| < T.  M == 0 or nh == 0 -> EMPTY_INPUT; nh % M != 0 ->
+ *   INVALID_VALUE; D == 0 -> INVALID_HOP_SIZE; a null pointer -> KOFFT_ERR_NULL.
+ * The host forms stage through the context's buffers; the kofft_hip_dev_* forms take device pointers and are asynchronous on the
+ * context's stream.  Routes, the same bytes.  The fused kernels exist for M = 32 .. 4096 a power of two with 4-byte aligned x and h: one per
+ * analysis (fold on its loads, the kept bins on its stores) and one per chunk of inverse transforms.  The composed route takes every
+ * M through scratch the context owns (fold, transform, prefix copy; completion, inverse transform, real parts).  The synthesis then
+ * runs one overlap-add kernel, one thread per sample.  kofft_hip_set_pfb_fused(ctx, on): 1, the default, the measured choice (DESIGN
+ * 5.34: the fused analysis up to M = 1024, the fused inverse wherever it exists); 0 every call of the context through the composed
+ * route; 2 the fused kernels wherever they exist (A/B measurements and tests); anything else -> INVALID_VALUE. */
+int kofft_hip_pfb_analysis_f32(kofft_hip_ctx *ctx, const float *x, size_t rows, size_t nx, size_t row_stride, const float *h, size_t nh, size_t m,
+                               size_t d, size_t lead, float *out, size_t frames, size_t bins);
+int kofft_hip_dev_pfb_analysis_f32(kofft_hip_ctx *ctx, const float *d_x, size_t rows, size_t nx, size_t row_stride, const float *d_h, size_t nh,
+                                   size_t m, size_t d, size_t lead, float *d_out, size_t frames, size_t bins);
+int kofft_hip_pfb_synthesis_f32(kofft_hip_ctx *ctx, const float *spec, size_t rows, size_t frames, size_t bins, const float *g, size_t nh, size_t m,
+                                size_t d, float scale, float *out, size_t out_first, size_t out_len);
+int kofft_hip_dev_pfb_synthesis_f32(kofft_hip_ctx *ctx, const float *d_spec, size_t rows, size_t frames, size_t bins, const float *d_g, size_t nh,
+                                    size_t m, size_t d, float scale, float *d_out, size_t out_first, size_t out_len);
+int kofft_hip_pfb_taps_f32(size_t m, size_t taps, double beta, float *out);
+int kofft_hip_pfb_reconstruction(const float *h, const float *g, size_t nh, size_t m, size_t d, double *c, double *worst);
+int kofft_hip_set_pfb_fused(kofft_hip_ctx *ctx, int on);
+
 /* ---- polyphase resampling of rows (upfirdn, resample_poly) -----------------------------------
  * Sample-rate conversion by up / down of `rows` dense rows of nx f32 samples through one FIR filter of nh taps: out_len values per row
  * from up-sampled time t0 on, the decimating or interpolating filter computed directly in the time domain (with up == down == 1 a

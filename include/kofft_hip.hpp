@@ -416,6 +416,67 @@ public:
     // false: every fast DCT-IV, MDCT and IMDCT of this context through fold / pre-twiddle into the scratch, transform, post-twiddle
     // (the same bytes; A/B, tests)
     Result set_mdct_fused(bool on) const { return st(kofft_hip_set_mdct_fused(ctx_, on ? 1 : 0)); }
+    // The polyphase filter bank of rows, analysis and synthesis (kofft_hip_pfb_analysis_f32, kofft_hip_pfb_synthesis_f32; DESIGN.md
+    // 5.34), f32 only.  pfb_analysis_rows: `rows` contiguous signals of x.size() / rows samples, taps.size() = T * channels taps, hop
+    // `hop` (0: channels), `frames` frames per row (SIZE_MAX: ceil((nx + lead) / hop), every frame that reaches a sample) after `lead`
+    // virtual zeros, `bins` bins per frame (SIZE_MAX: the one-sided channels / 2 + 1); out is resized to rows * frames * bins.
+    // MismatchedLengths for rows that do not divide x, EmptyInput for no channels, taps or samples; then the C entry's checks in its order.
+    Result pfb_analysis_rows(const std::vector<float> &x, const std::vector<float> &taps, size_t channels, std::vector<Complex<float>> &out,
+                             size_t rows = 1, size_t hop = 0, size_t lead = 0, size_t frames = SIZE_MAX, size_t bins = SIZE_MAX) const
+    {
+        static_assert(std::is_same<T, float>::value, "pfb_analysis_rows is f32-only");
+        if (rows == 0 || x.size() % rows != 0) return Result::Err(FftError::MismatchedLengths);
+        const size_t nx = x.size() / rows;
+        if (nx == 0 || channels == 0 || taps.empty()) return Result::Err(FftError::EmptyInput);
+        if (hop == 0) hop = channels;
+        if (frames == SIZE_MAX) frames = (nx + lead + hop - 1) / hop;
+        if (bins == SIZE_MAX) bins = channels / 2 + 1;
+        out.resize(rows * frames * bins);
+        Complex<float> dummy{};  // (frames == 0: the C entry returns before it looks at the pointer)
+        return st(kofft_hip_pfb_analysis_f32(ctx_, x.data(), rows, nx, nx, taps.data(), taps.size(), channels, hop, lead,
+                                             reinterpret_cast<float *>(out.empty() ? &dummy : out.data()), frames, bins));
+    }
+    // pfb_synthesis_rows: spec holds rows * frames * bins bins, bins = channels or channels / 2 + 1; out is resized to rows * count
+    // samples, first .. first + count of the (frames - 1) hop + taps.size() overlap-added samples per row (count == SIZE_MAX: up to
+    // the end), each times scale.  EmptyInput for no channels or taps, InvalidValue for a bins that is neither form, MismatchedLengths
+    // for spec that is no whole number of rows of frames or a window past the end.
+    Result pfb_synthesis_rows(const std::vector<Complex<float>> &spec, const std::vector<float> &taps, size_t channels, size_t hop, size_t bins,
+                              std::vector<float> &out, size_t rows = 1, float scale = 1.0f, size_t first = 0, size_t count = SIZE_MAX) const
+    {
+        static_assert(std::is_same<T, float>::value, "pfb_synthesis_rows is f32-only");
+        if (channels == 0 || taps.empty()) return Result::Err(FftError::EmptyInput);
+        if (bins != channels && !(channels % 2 == 0 && bins == channels / 2 + 1)) return Result::Err(FftError::InvalidValue);
+        if (rows == 0 || spec.size() % (rows * bins) != 0) return Result::Err(FftError::MismatchedLengths);
+        if (hop == 0) return Result::Err(FftError::InvalidHopSize);
+        const size_t frames = spec.size() / (rows * bins), full = frames ? (frames - 1) * hop + taps.size() : 0;
+        if (first > full) return Result::Err(FftError::MismatchedLengths);
+        if (count == SIZE_MAX) count = full - first;
+        if (count > full - first) return Result::Err(FftError::MismatchedLengths);
+        out.resize(rows * count);
+        float dummy = 0.0f;  // (count == 0: the C entry writes nothing)
+        return st(kofft_hip_pfb_synthesis_f32(ctx_, reinterpret_cast<const float *>(spec.data()), rows, frames, bins, taps.data(), taps.size(),
+                                              channels, hop, scale, out.empty() ? &dummy : out.data(), first, count));
+    }
+    // 1: the measured choice (the default); 0: every filter-bank call of this context through fold into the scratch, transform, prefix
+    // copy / completion, inverse transform, real parts; 2: the fused kernels wherever they exist (the same bytes; A/B, tests)
+    Result set_pfb_fused(int on) const { return st(kofft_hip_set_pfb_fused(ctx_, on)); }
+    // kofft_hip_pfb_taps_f32, no device: the sinc x Kaiser prototype of taps_per_channel * channels taps, normalised to unit sum
+    // (empty on an error, whose status goes to *err).
+    static std::vector<float> pfb_taps(size_t channels, size_t taps_per_channel, double beta = 5.0, int *err = nullptr)
+    {
+        std::vector<float> taps(channels * taps_per_channel);
+        float dummy = 0.0f;
+        const int rc = kofft_hip_pfb_taps_f32(channels, taps_per_channel, beta, taps.empty() ? &dummy : taps.data());
+        if (err) *err = rc;
+        if (rc != KOFFT_OK) taps.clear();
+        return taps;
+    }
+    // kofft_hip_pfb_reconstruction, no device: c and the worst deviation of the reconstruction condition of (h, g) at this hop
+    static int pfb_reconstruction(const std::vector<float> &h, const std::vector<float> &g, size_t channels, size_t hop, double &c, double &worst)
+    {
+        if (h.size() != g.size()) return KOFFT_ERR_MISMATCHED_LENGTHS;
+        return kofft_hip_pfb_reconstruction(h.data(), g.data(), h.size(), channels, hop, &c, &worst);
+    }
     // Overlap-save FFT convolution of `rows` contiguous rows of x.size() / rows samples with every filter of a bank that the rows
     // share (kofft_hip_convolve_bank_f32): h holds h.size() / nh filters of nh taps, float or Complex<float>; each frame is
     // transformed once for the whole bank.  out is resized to rows * filters * count elements, [row][filter][count]: values first ..

@@ -19,9 +19,10 @@ from . import psd  # noqa: E402  (Welch power spectra and cross spectra of rows:
 from . import resample  # noqa: E402  (polyphase resampling of rows: upfirdn, resample_poly, design_taps)
 from . import iir  # noqa: E402  (IIR filtering of rows by a cascade of biquads: sosfilt, sosfilt_zi, sosfiltfilt)
 from . import mdct  # noqa: E402  (MDCT / IMDCT of rows on a fast DCT-IV: mdct, imdct, dct4, sine_window, vorbis_window, kbd_window)
+from . import pfb  # noqa: E402  (polyphase filter bank of rows: analysis, synthesis, prototype, reconstruction)
 
 __all__ = ["DctPlanner", "DeviceError", "fft2d_inplace", "fft3d_inplace", "flatten_2d", "flatten_3d", "FftError", "FftPlan", "FftPlanner", "FftStrategy", "HipFftImpl", "HipMulti", "IstftStream", "RfftPlanner", "StftStream",
            "batch", "batch_inverse", "frame", "hann", "hilbert_analytic", "inverse_frame", "inverse_parallel", "irfft_packed", "istft", "istft_onesided", "multi_channel", "multi_channel_inverse", "new_fft_impl",
-           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_magnitudes_rows", "stft_multi", "stft_onesided", "stft_rows", "LibraryMissing", "load_library", "dct", "dst", "wavelet", "czt", "goertzel", "hartley", "window", "mfcc", "spectrogram", "convolve", "psd", "resample", "iir", "mdct",
+           "parallel", "real_cepstrum", "rfft_packed", "stft", "stft_magnitudes", "stft_magnitudes_rows", "stft_multi", "stft_onesided", "stft_rows", "LibraryMissing", "load_library", "dct", "dst", "wavelet", "czt", "goertzel", "hartley", "window", "mfcc", "spectrogram", "convolve", "psd", "resample", "iir", "mdct", "pfb",
            "ComplexVec", "SplitComplex", "fft_complex_vec", "fft_split", "fft_split_complex", "ifft_complex_vec", "ifft_split", "ifft_split_complex"]
 __version__ = "0.1.0"

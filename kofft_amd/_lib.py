@@ -97,6 +97,13 @@ SIGNATURES = {
     "kofft_hip_imdct_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_float, C.c_void_p, _sz, _sz]),
     "kofft_hip_dev_imdct_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.c_float, C.c_void_p, _sz, _sz]),
     "kofft_hip_set_mdct_fused": (C.c_int, [_ctx, C.c_int]),
+    "kofft_hip_pfb_analysis_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_pfb_analysis_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz, _sz]),
+    "kofft_hip_pfb_synthesis_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_void_p, _sz, _sz]),
+    "kofft_hip_dev_pfb_synthesis_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, _sz, C.c_void_p, _sz, _sz, _sz, C.c_float, C.c_void_p, _sz, _sz]),
+    "kofft_hip_pfb_taps_f32": (C.c_int, [_sz, _sz, C.c_double, C.c_void_p]),
+    "kofft_hip_pfb_reconstruction": (C.c_int, [C.c_void_p, C.c_void_p, _sz, _sz, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "kofft_hip_set_pfb_fused": (C.c_int, [_ctx, C.c_int]),
     "kofft_hip_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_dev_resample_f32": (C.c_int, [_ctx, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz, _sz, _sz, C.c_void_p, _sz]),
     "kofft_hip_set_resample_tiled": (C.c_int, [_ctx, C.c_int]),

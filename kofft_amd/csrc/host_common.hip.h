@@ -75,6 +75,7 @@ struct kofft_hip_ctx {
     bool convolve_fused = true; // kofft_hip_set_convolve_fused(ctx, 0): overlap-save convolutions of every block through the composed route (expand, fft_dev, multiply, inverse fft_dev, gather; A/B, tests)
     bool convolve_bank_fused = true; // kofft_hip_set_convolve_bank_fused(ctx, 0): filter-bank convolutions of every block through the composed route (expand and fft_dev once, then per filter multiply, inverse fft_dev, gather; A/B, tests)
     bool mdct_fused = true;   // kofft_hip_set_mdct_fused(ctx, 0): fast DCT-IV, MDCT and IMDCT of every length through the composed route (fold / pre-twiddle, fft_dev, post-twiddle; A/B, tests)
+    int pfb_fused = 1;        // kofft_hip_set_pfb_fused: 1 the measured choice (pfb_use_fused), 0 polyphase filter-bank analysis and synthesis of every M through the composed route (fold into the scratch, fft_dev, prefix copy / completion, inverse fft_dev, real parts), 2 the fused kernels wherever they exist (A/B, tests)
     int mfcc_fused = 1;       // kofft_hip_set_mfcc_fused: 1 the measured choice (mfcc_use_fused), 0 every MFCC through the composed route (filterbank, log, direct DCT-II, column copy), 2 the fused kernel wherever it fits (A/B, tests)
     int frontend_fused = 1;   // kofft_hip_set_frontend_fused: 1 the measured choice (frontend_use_fused), 0 every audio-to-mel / MFCC call through the composed route (magnitudes into the scratch, then the mel / MFCC path), 2 the fused kernel wherever it fits (A/B, tests)
     int welch_fused = 1;      // kofft_hip_set_welch_fused: 1 the measured choice (welch_use_fused), 0 every Welch / cross-spectrum call through the composed route (one-sided frames into the scratch, then the sums), 2 the fused kernel wherever it exists (A/B, tests)

@@ -2,6 +2,7 @@
 // checks, the extern "C" entry points and the host-only tap design.
 #include "resample_impl.hip.h"
 #include "host_stage.hip.h"
+#include "kaiser_i0.h"
 
 #include <cmath>
 #include <new>
@@ -99,20 +100,6 @@ int kofft_hip_resample_route(size_t nh, size_t up, size_t down, int *route)
     if (up == 0 || down == 0) return KOFFT_ERR_INVALID_VALUE;
     *route = resample_route(nh, up, down);
     return KOFFT_OK;
-}
-
-// The modified Bessel function I0 by its power series sum ((x / 2)^2)^k / (k!)^2, in double, until a term no longer changes the sum.
-static double bessel_i0(double x)
-{
-    const double q = (x / 2.0) * (x / 2.0);
-    double term = 1.0, sum = 1.0;
-    for (int k = 1; k < 1000; ++k) {
-        term = term * (q / ((double)k * (double)k));
-        const double next = sum + term;
-        if (next == sum) break;
-        sum = next;
-    }
-    return sum;
 }
 
 // scipy.signal.resample_poly's default filter: firwin(2 * half + 1, 1 / max(up, down), window = ("kaiser", beta)) * up with
